@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmarks of the hot path on N MI355X GPUs, one process per GPU, batch-sharded replicas (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -20,9 +20,11 @@ touches the GPU) starts N children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_
 exits with the worst child status.  Under torch.distributed.run it simply joins the job it was started in.
 
 A step = one pass of the hot path over one synthetic batch already resident in HBM.  K steps are timed between
-barrier + synchronize brackets (max over ranks); rank 0 prints ONE JSON line.  Extra objects:
+barrier + synchronize brackets (max over ranks); rank 0 prints ONE JSON line.  A plain run does only that: set-up, warm-up,
+the K timed steps, the outputs (--dump-outputs) and the line.  Extra objects:
   step_ms      - median / p10 / p90 of the per-step durations from HIP events recorded on the launch stream inside the
                  same timed region
+Only with --full (each takes runs of its own after the timed steps):
   roofline     - the dominant kernel family (the MFMA GEMMs): algorithmic FLOPs / HIP-event time per launch, measured live
                  in a second K-step pass with events on the launch stream, against the dense MFMA peak of the dtype;
                  `traffic` = HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/r0N_traffic.json,
@@ -32,6 +34,12 @@ barrier + synchronize brackets (max over ranks); rank 0 prints ONE JSON line.  E
                  taps.  Reported beside the headline, never as `value`: the headline stays the exact-fp32 MFMA path
   cpu_baseline - (N = 1, config 1 only) the same forward on the host cores: the torch-ops restatement in oracle/ (value)
                  and the plain-C OpenMP restatement beside it, best + median of 5, CPU model and core count
+
+--dump-outputs DIR writes what the last timed step computed, as the caller receives it, to DIR/<name>.npy (float32, rank 0's
+shard): tap<i> = hidden_states[i] for every tap, and for the train step also params = the flat fp32 parameters after its
+update.  Weights and images are seeded, so runs with the same arguments see the same inputs and two builds can be compared
+output for output.  An array above its share of the DUMP_BYTES budget is written as a fixed sample instead: its elements at
+the sorted distinct flat indices drawn by numpy's default_rng(0), the same for every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -57,6 +65,7 @@ CONFIGS = {
     5: dict(model="base", size=224, batch=64, dtype="f32x3", mode="forward"),
     6: dict(model="base", size=224, batch=64, dtype="f32x6", mode="forward"),
 }
+DUMP_BYTES = 60_000_000        # --dump-outputs: all files together, float32 data (headline: 4 taps of 64 x 197 x 768, sampled)
 
 
 def parse_args(argv=None):
@@ -71,10 +80,16 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default=None, choices=["f32", "bf16", "fp8", "f32x3", "f32x6"])
     ap.add_argument("--batch", type=int, default=None, help="images per GPU")
     ap.add_argument("--mode", default=None, choices=["forward", "train"])
-    ap.add_argument("--cpu-sample", type=int, default=64, help="images timed on the CPU baseline (0 = skip)")
-    ap.add_argument("--no-roofline-pass", action="store_true")
-    ap.add_argument("--no-split-fp32", action="store_true", help="skip the split-fp32 builds beside the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline pass, the split-fp32 builds and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, sampled above the size budget)")
+    ap.add_argument("--cpu-sample", type=int, default=64, help="images timed on the CPU baseline (0 = skip; --full only)")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="skip the roofline pass (--full only)")
+    ap.add_argument("--no-split-fp32", action="store_true", help="skip the split-fp32 builds beside the headline line (--full only)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     for k, v in CONFIGS[args.config].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -272,6 +287,21 @@ def percentiles(ms):
             "p90": round(float(np.percentile(a, 90)), 4), "source": "HIP events on the launch stream, one pair per step"}
 
 
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """arrays: name -> device tensor, written as outdir/<name>.npy in float32; one above DUMP_BYTES / len(arrays) becomes the
+    fixed sample described in the module docstring (a 1-D array)."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, f"{name}.npy"), t.float().cpu().numpy())
+
+
 def per_rank_report(rows):
     """rows[k] = [images/s, GEMM-family roofline fraction (nan when the roofline pass was skipped), ms per step] of rank k, each from
     that rank's OWN clock and HIP events -> the "MFMA util % at 1/2/4/8 GPU" half of BASELINE.json's metric: min / mean / max over
@@ -356,10 +386,16 @@ def run_rank(args) -> None:
         assert bool(torch.isfinite(stepper.flat_params).all())
     else:
         assert all(torch.isfinite(h).all() for h in out.hidden_states if h is not None)
+    if args.dump_outputs and r.is_main:
+        taps = out if train else [out.hidden_states[t] for t in cfg.taps]
+        arrays = {f"tap{t}": h for t, h in zip(cfg.taps, taps)}
+        if train:
+            arrays["params"] = stepper.flat_params
+        dump_outputs(args.dump_outputs, arrays)
 
     # second pass: per-kernel HIP events on the launch stream (same inputs, same K steps)
     timing: dict = {}
-    if not args.no_roofline_pass:
+    if args.full and not args.no_roofline_pass:
         with torch.no_grad():
             for _ in range(args.steps):
                 if train:
@@ -420,9 +456,9 @@ def run_rank(args) -> None:
                                 "flops_per_launch": gemm_flops // n}
             line["kernel_ms_per_step"] = {k[:-3]: round(v / args.steps, 4) for k, v in timing.items() if k.endswith("_ms")}
         line["per_rank"] = per_rank_report(per_rank)
-        if r.world == 1 and headline and not args.no_split_fp32:
+        if args.full and r.world == 1 and headline and not args.no_split_fp32:
             line["split_fp32"] = split_fp32_lines(cfg, weights, x, out, args.steps, args.warmup, dev)
-        if r.world == 1 and args.cpu_sample > 0 and headline:
+        if args.full and r.world == 1 and args.cpu_sample > 0 and headline:
             line["cpu_baseline"] = cpu_baseline(cfg, weights, x_np, min(args.cpu_sample, args.batch))
         print(json.dumps(line), flush=True)
     dp.finalize(r)

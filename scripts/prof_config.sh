@@ -6,6 +6,7 @@
 #    gpurun_out/pmc_<tag>_{sq,fetch,write,lds}/  PMC passes, each counter set in its own run (never combined with traces)
 set -o pipefail
 TAG=$1; shift
+set -- --full "$@"     # the bench line with all that --full measures; the profiled runs below switch those parts off again
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $ROOT/gpurun_out

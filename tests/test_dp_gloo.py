@@ -113,3 +113,28 @@ def test_bench_launcher_stops_all_ranks_when_one_dies_in_start_up(tmp_path):
     assert time.time() - t0 < 120
     assert "rank 1 exited with status 3" in res.stderr
     assert "fails in start-up on request" in (tmp_path / "bench_rank1.err").read_text()
+
+
+def test_bench_dump_outputs_stay_in_budget_and_repeat_exactly(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 .npy per output, small arrays whole, large ones as the same seeded sample on every
+    run, all files together under 64 MB (the headline's four 64 x 197 x 768 taps plus a train step's flat parameters)."""
+    import torch
+
+    import bench
+    assert not bench.parse_args([]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    g = torch.Generator().manual_seed(0)
+    arrays = {f"tap{t}": torch.randn((64, 197, 768), generator=g) for t in (4, 6, 8, 12)}
+    arrays["params"] = torch.randn(20_000_000, generator=g)
+    arrays["small"] = torch.arange(24, dtype=torch.bfloat16).reshape(2, 3, 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64_000_000
+    for name, t in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        if name == "small":
+            assert np.array_equal(a, t.float().numpy())
+        else:
+            assert a.ndim == 1 and 0 < a.size < t.numel() and np.isin(a[:100], t.reshape(-1).numpy()).all()
