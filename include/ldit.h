@@ -54,8 +54,21 @@ enum ldit_dtype {
                       relative L2 (LDIT_F32: 7 - 9e-7), i.e. inside the fp32 build's own parity gates (2e-5), 180x inside the north-star 1e-3.
                       The error of a dot product is 2^-17 of its TERMS: with activation outliers (LayerNorm channels x 60) the worst
                       element reaches 1.2e-3 of max(|ref|, 1) while the relative L2 stays 1.6e-5 - check parity per checkpoint. */
-    LDIT_F32X6 = 5  /* the same with THREE planes (24 significant bits) and the six plane products down to 2^-24: fp32-grade error
+    LDIT_F32X6 = 5, /* the same with THREE planes (24 significant bits) and the six plane products down to 2^-24: fp32-grade error
                       (6 - 8e-7 vs float64: under the fp32 MFMA path's on every tap, at that of ATen's CPU fp32 forward) at 6 bf16 MFMAs per product */
+    LDIT_MXFP8 = 6  /* LDIT_FP8's place without calibration: the four GEMMs of a layer on OCP MX operands - e4m3 codes with one
+                      E8M0 (power-of-two) scale per 32 consecutive K-elements of a row, applied inside the block-scaled MFMA
+                      (v_mfma_scale_f32_32x32x64_f8f6f4).  Weights are quantised by ldit_pack_weights; every activation block is
+                      scaled from its own amax where it is produced (LayerNorm, attention epilogue, GELU epilogue), so there is no
+                      scale state to set or to go stale, and a row's result does not depend on the other rows of the batch.
+                      Attention on bf16 q|k|v; residual stream / LayerNorm / softmax fp32; taps fp32.  hidden, mlp % 128 == 0.
+                      The format (everything tests against it):
+                        codes [rows, K] e4m3fn, scales [rows, K / 32] bytes, row-major, no padding;
+                        block exponent e = the smallest integer with amax <= 448 * 2^e, clamped to [-127, 127]; byte = e + 127;
+                          (amax = m 2^E, m in [0.5, 1): e = E - 9 if m <= 0.875 else E - 8) - nothing is clipped;
+                        code = e4m3_RNE(x * 2^-e); an all-zero block has byte 0 and codes 0; a block holding Inf / NaN has byte
+                          0xFF (its codes are unspecified);
+                        value = code * 2^(byte - 127). */
 };
 
 /* order of the per-layer activation scales handed to ldit_set_fp8_act_scales (scale = amax / 448) */
@@ -281,6 +294,24 @@ int ldit_linear_fp8(const void *X, int64_t lda, const void *W, const void *bias,
 /* Per-output-channel weight quantisation: scales[n] = max|W[n,:]| / 448 (never 0), codes[n,:] = fp8(W[n,:] / scales[n]).
  * W fp32 [N,K] row-major, K % 4 == 0. */
 int ldit_quant_rows_f32_fp8(const void *W, void *codes, void *scales, int64_t N, int64_t K, ldit_stream stream);
+
+/* ---- MX (block-scaled e4m3) building blocks of the mxfp8 build (LDIT_MXFP8 above: the format) ------------------------------
+ * ldit_quant_mx_f32_fp8: src fp32 [rows, K] (row stride lds elements, lds % 4 == 0, src 16-byte aligned) -> codes [rows, K]
+ * (dense, 4-byte aligned) + scales [rows, K / 32].  K % 32 == 0. */
+int ldit_quant_mx_f32_fp8(const void *src, int64_t lds, void *codes, void *scales, int64_t rows, int64_t K, ldit_stream stream);
+
+/* ldit_linear_mxfp8:  Y = epilogue(X . W^T + bias) on MX operands: X codes [M,K] (row stride lda, lda % 128 == 0) with scales Xs
+ * [M, lda / 32], W codes [N,K] with scales Ws [N, K / 32]; the block scales enter the MFMA, fp32 accumulation.  K % 128 == 0;
+ * codes 16-byte aligned, scales 4-byte aligned.  LDIT_EPI_BIAS writes bf16 Y; LDIT_EPI_BIAS_GELU writes MX Y = codes [M, ldy]
+ * + scales Ys [M, ldy / 32] of gelu(.) (N, ldy % 32 == 0); LDIT_EPI_SCALE_RESID: Y = R + lam (.) (.), fp32 (R may alias Y),
+ * and the optional fp32 copy Y2.  Ys is ignored by the other two epilogues. */
+int ldit_linear_mxfp8(const void *X, int64_t lda, const void *Xs, const void *W, const void *Ws, const void *bias, void *Y,
+                      int64_t ldy, void *Ys, int64_t M, int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2,
+                      ldit_stream stream);
+
+/* ldit_layernorm_f32's statistics and affine, the row written as MX codes Y [rows, C] + scales Ys [rows, C / 32]; C % 32 == 0. */
+int ldit_layernorm_mxfp8(const void *x, const void *gamma, const void *beta, void *Y, void *Ys, int64_t rows, int64_t C, float eps,
+                         ldit_stream stream);
 
 /* dst[i] = fp8_e4m3(src[i] * inv_scale), round to nearest even, SATURATING at +-448 (torch's cast yields NaN above
  * 464 instead); n elements, src 16-byte aligned, dst 4-byte aligned. */

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("LDIT_LIB_PATH") or os.path.join(_HERE, "libldit_hip.s
 
 LDIT_ABI_VERSION = 5
 LDIT_MAX_TAPS = 8
-DTYPE_F32, DTYPE_BF16, DTYPE_FP8, DTYPE_F32X3, DTYPE_F32X6 = 0, 1, 3, 4, 5
+DTYPE_F32, DTYPE_BF16, DTYPE_FP8, DTYPE_F32X3, DTYPE_F32X6, DTYPE_MXFP8 = 0, 1, 3, 4, 5, 6
 FP8_A_COUNT = 4
 LDIT_OK, LDIT_EINVAL, LDIT_EWORKSPACE, LDIT_EHIP, LDIT_EUNSUPPORTED = 0, -1, -2, -3, -4
 EPI_BIAS, EPI_BIAS_GELU, EPI_SCALE_RESID, EPI_F32, EPI_GELU_BWD = 0, 1, 2, 4, 5
@@ -77,6 +77,9 @@ SIGNATURES = {
     "ldit_quant_rows_f32_fp8": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "ldit_set_fp8_act_scales": (C.c_int, [C.POINTER(LditCfg), _vp, C.c_size_t, C.POINTER(C.c_float), _vp]),
     "ldit_quant_f32_fp8": (C.c_int, [_vp, _vp, _i64, _f32, _vp]),
+    "ldit_quant_mx_f32_fp8": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp]),
+    "ldit_linear_mxfp8": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "ldit_layernorm_mxfp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "ldit_amax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "ldit_preprocess_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _f32, _f32, _i32, _i32,
                                       _vp, _vp]),

@@ -199,7 +199,7 @@ int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batc
     }
 
     const float scale = 1.0f / sqrtf((float)g.D);
-    const bool bf16 = cfg->dtype == LDIT_BF16, fp8 = cfg->dtype == LDIT_FP8;
+    const bool bf16 = cfg->dtype == LDIT_BF16, fp8 = cfg->dtype == LDIT_FP8, mx = cfg->dtype == LDIT_MXFP8;
     const int S = split_planes_of(cfg->dtype);
     // split-fp32 builds: the plane products of one output element, SMALLEST FIRST (their sum is formed at its own magnitude
     // before the leading p0.q0 term arrives): bf16x3 = a1 w0 + a0 w1 + a0 w0; six products = a2 w0 + a1 w1 + a0 w2 + a1 w0 + a0 w1 + a0 w0
@@ -254,6 +254,25 @@ int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batc
                                                         nullptr, 0.f, 0.f, sc + 4, F32(pl.sw_1), sc + 6, stream));
             LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_fp8(bb, F, P + pl.w2, F32(pl.b2), h, C, M, C, F, EPI_SCALE_RESID, F32(pl.lam2), h,
                                                         tap, 0.f, 0.f, sc + 6, F32(pl.sw_2), nullptr, stream));
+        } else if (mx) {
+            // mxfp8 build: the fp8 build's dataflow on MX operands - LayerNorm, the attention epilogue and the GELU epilogue
+            // write e4m3 codes + one E8M0 scale per 32 channels, each block scaled from its own amax; no calibrated state.
+            // y: codes [M, C] then scales [M, C / 32]; big: bf16 q|k|v, later the MLP hidden's codes [M, F] then scales [M, F / 32]
+            char *y8 = ws + wm.y, *bb = ws + wm.big;
+            char *ys = y8 + (size_t)M * C, *bs = bb + (size_t)M * F;
+            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout(h, F32(pl.ln1_w), F32(pl.ln1_b), y8, ys, M, C, cfg->ln_eps, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, P + pl.wqkv, P + pl.sw_qkv, F32(pl.bqkv), bb, 3 * C, nullptr, M, 3 * C, C,
+                                                          EPI_BIAS, nullptr, nullptr, nullptr, stream));
+            LDIT_RUN(probe, LDIT_K_ATTENTION,
+                     launch_attention_bf16_mxout(bb, bb + 2 * (size_t)C, bb + 4 * (size_t)C, y8, ys, batch, g.T, g.H, g.D, 3 * C, 3 * C,
+                                                 3 * C, C, 0.0f /* q pre-scaled at pack time */, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, P + pl.wo, P + pl.sw_o, F32(pl.bo), h, C, nullptr, M, C, C,
+                                                          EPI_SCALE_RESID, F32(pl.lam1), h, nullptr, stream));
+            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout(h, F32(pl.ln2_w), F32(pl.ln2_b), y8, ys, M, C, cfg->ln_eps, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, P + pl.w1, P + pl.sw_1, F32(pl.b1), bb, F, bs, M, F, C,
+                                                          EPI_BIAS_GELU, nullptr, nullptr, nullptr, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(bb, F, bs, P + pl.w2, P + pl.sw_2, F32(pl.b2), h, C, nullptr, M, C, F,
+                                                          EPI_SCALE_RESID, F32(pl.lam2), h, tap, stream));
         } else if (!bf16) {
             // y = LN1(h)                                                               TF:426
             LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm(h, F32(pl.ln1_w), F32(pl.ln1_b), y, M, C, cfg->ln_eps, stream));
@@ -329,7 +348,7 @@ int ldit_pack_weights(const ldit_cfg *cfg, const ldit_weights *w, void *packed, 
     if (packed_bytes < pm.total) return fail(LDIT_EWORKSPACE, "packed buffer %zu bytes < required %zu", packed_bytes, pm.total);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     char *P = static_cast<char *>(packed);
-    const bool bf16 = cfg->dtype == LDIT_BF16, fp8 = cfg->dtype == LDIT_FP8;
+    const bool bf16 = cfg->dtype == LDIT_BF16, fp8 = cfg->dtype == LDIT_FP8, mx = cfg->dtype == LDIT_MXFP8;
     auto put = [&](size_t off, const void *src, size_t n, const char *what) -> int {      // fp32 copy
         if (!src) return fail(LDIT_EINVAL, "weights: %s is null", what);
         LDIT_HIP_CHECK(hipMemcpyAsync(P + off, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -348,18 +367,22 @@ int ldit_pack_weights(const ldit_cfg *cfg, const ldit_weights *w, void *packed, 
             if (!aligned16(src)) return fail(LDIT_EINVAL, "weights: %s must be 16-byte aligned", what);
             return launch_split_planes(static_cast<const float *>(src), (int)cols, P + off + elt_off * 2 * Sp, (int)rows, (int)cols, Sp, stream, mul);
         }
-        if (!bf16 && !fp8) return put(off + elt_off * 4, src, rows * cols, what);
+        if (!bf16 && !fp8 && !mx) return put(off + elt_off * 4, src, rows * cols, what);
         if (!aligned16(src)) return fail(LDIT_EINVAL, "weights: %s must be 16-byte aligned", what);
+        // mxfp8: codes + block scales of the rows; `mul` goes into the values before they are quantised (no per-row float scale)
+        if (mx)
+            return launch_quant_mx(static_cast<const float *>(src), (int64_t)cols, P + off + elt_off, P + sw_off + row0 * (cols / 32),
+                                   (int64_t)rows, (int)cols, mul, stream);
         if (fp8)
             return launch_quant_rows_fp8(static_cast<const float *>(src), P + off + elt_off,
                                          reinterpret_cast<float *>(P + sw_off) + row0, (int)rows, (int)cols, stream, mul);
         return launch_cvt_bf16(static_cast<const float *>(src), P + off + elt_off * 2, rows * cols, stream, mul);
     };
     // (the split-fp32 builds too: their attention runs on bf16-plane operands with exp2-domain scores, attention_planes.hip)
-    const float qfold = (bf16 || fp8 || split_planes_of(cfg->dtype)) ? (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f : 1.0f;
+    const float qfold = (bf16 || fp8 || mx || split_planes_of(cfg->dtype)) ? (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f : 1.0f;
     const size_t C = g.C, F = g.F;
     LDIT_TRY(put(pm.patch_w, w->patch_w, C * g.Kp, "patch_w"));
-    if (bf16 || fp8) {
+    if (bf16 || fp8 || mx) {
         if (!aligned16(w->patch_w)) return fail(LDIT_EINVAL, "weights: patch_w must be 16-byte aligned");
         LDIT_TRY(launch_cvt_bf16(static_cast<const float *>(w->patch_w), P + pm.patch_w16, C * g.Kp, stream));
     } else if (const int Sp = split_planes_of(cfg->dtype)) {
@@ -669,6 +692,43 @@ int ldit_quant_rows_f32_fp8(const void *W, void *codes, void *scales, int64_t N,
     if (!codes || (reinterpret_cast<uintptr_t>(codes) & 3u)) return fail(LDIT_EINVAL, "quant_rows_fp8: codes null or misaligned");
     return launch_quant_rows_fp8(static_cast<const float *>(W), codes, static_cast<float *>(scales), (int)N, (int)K,
                                  static_cast<hipStream_t>(stream));
+}
+
+int ldit_quant_mx_f32_fp8(const void *src, int64_t lds, void *codes, void *scales, int64_t rows, int64_t K, ldit_stream stream)
+{
+    if (rows <= 0 || K <= 0 || K >= (1ll << 31) || rows * (lds > K ? lds : K) >= (1ll << 40)) return fail(LDIT_EINVAL, "quant_mx: bad shape");
+    if (K % 32 || lds < K || lds % 4) return fail(LDIT_EINVAL, "quant_mx: K %% 32 == 0 and lds >= K, lds %% 4 == 0 required");
+    if (!src || !codes || !scales) return fail(LDIT_EINVAL, "quant_mx: null operand");
+    if (!aligned16(src) || (reinterpret_cast<uintptr_t>(codes) & 3u)) return fail(LDIT_EINVAL, "quant_mx: misaligned operand");
+    return launch_quant_mx(static_cast<const float *>(src), lds, codes, scales, rows, (int)K, 1.0f, static_cast<hipStream_t>(stream));
+}
+
+int ldit_linear_mxfp8(const void *X, int64_t lda, const void *Xs, const void *W, const void *Ws, const void *bias, void *Y,
+                      int64_t ldy, void *Ys, int64_t M, int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2,
+                      ldit_stream stream)
+{
+    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_mxfp8: empty problem");
+    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_mxfp8: operand exceeds 2^31 elements");
+    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear_mxfp8: bad leading dimension");
+    if (K % 128 || lda % 128) return fail(LDIT_EUNSUPPORTED, "linear_mxfp8: K and lda must be multiples of 128");
+    if (!X || !W || !Xs || !Ws) return fail(LDIT_EINVAL, "linear_mxfp8: null operand");
+    if (!aligned16(X) || !aligned16(W) || (reinterpret_cast<uintptr_t>(Xs) & 3u) || (reinterpret_cast<uintptr_t>(Ws) & 3u))
+        return fail(LDIT_EINVAL, "linear_mxfp8: codes must be 16-byte aligned, scales 4-byte aligned");
+    if (!Y || (reinterpret_cast<uintptr_t>(Y) & 15u) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear_mxfp8: output null or misaligned");
+    if (epilogue < LDIT_EPI_BIAS || epilogue > LDIT_EPI_SCALE_RESID) return fail(LDIT_EINVAL, "linear_mxfp8: unknown epilogue %d", epilogue);
+    if (epilogue == LDIT_EPI_BIAS_GELU && (!Ys || N % 32 || ldy % 32))
+        return fail(LDIT_EINVAL, "linear_mxfp8: the GELU epilogue writes MX: Ys needed, N and ldy multiples of 32");
+    return launch_gemm_mxfp8(X, (int)lda, Xs, W, Ws, static_cast<const float *>(bias), Y, (int)ldy, Ys, (int)M, (int)N, (int)K, epilogue,
+                             static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2),
+                             static_cast<hipStream_t>(stream));
+}
+
+int ldit_layernorm_mxfp8(const void *x, const void *gamma, const void *beta, void *Y, void *Ys, int64_t rows, int64_t C, float eps,
+                         ldit_stream stream)
+{
+    if (C > 4096 || C % 32) return fail(LDIT_EINVAL, "layernorm_mxfp8: C must be a multiple of 32, at most 4096");
+    return launch_layernorm_mxout(static_cast<const float *>(x), static_cast<const float *>(gamma), static_cast<const float *>(beta), Y,
+                                  Ys, rows, (int)C, eps, static_cast<hipStream_t>(stream));
 }
 
 int ldit_quant_f32_fp8(const void *src, void *dst, int64_t n, float inv_scale, ldit_stream stream)

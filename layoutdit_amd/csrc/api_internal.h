@@ -22,8 +22,9 @@ inline int split_planes_of(int dtype) { return dtype == LDIT_F32X3 ? 2 : dtype =
 inline int geometry(const ldit_cfg *cfg, Geo &g)
 {
     if (!cfg) return fail(LDIT_EINVAL, "cfg is null");
-    if (cfg->dtype != LDIT_F32 && cfg->dtype != LDIT_BF16 && cfg->dtype != LDIT_FP8 && !split_planes_of(cfg->dtype))
-        return fail(LDIT_EUNSUPPORTED, "dtype %d: only fp32 (0), bf16 (1), fp8 e4m3 (3) and split fp32 (4, 5) are implemented", cfg->dtype);
+    if (cfg->dtype != LDIT_F32 && cfg->dtype != LDIT_BF16 && cfg->dtype != LDIT_FP8 && cfg->dtype != LDIT_MXFP8 && !split_planes_of(cfg->dtype))
+        return fail(LDIT_EUNSUPPORTED, "dtype %d: only fp32 (0), bf16 (1), fp8 e4m3 (3), split fp32 (4, 5) and MX fp8 (6) are implemented",
+                    cfg->dtype);
     g.C = cfg->hidden; g.L = cfg->layers; g.H = cfg->heads; g.F = cfg->mlp; g.p = cfg->patch; g.in_ch = cfg->in_ch;
     if (g.C <= 0 || g.L < 0 || g.H <= 0 || g.F <= 0 || g.p <= 0 || g.in_ch <= 0) return fail(LDIT_EINVAL, "cfg: non-positive dimension");
     if (g.C % g.H) return fail(LDIT_EINVAL, "cfg: hidden %d not divisible by heads %d", g.C, g.H);
@@ -33,6 +34,7 @@ inline int geometry(const ldit_cfg *cfg, Geo &g)
     if ((cfg->dtype == LDIT_BF16 || split_planes_of(cfg->dtype)) && (g.C % 64 || g.F % 64))
         return fail(LDIT_EUNSUPPORTED, "cfg: bf16 needs hidden and mlp multiples of 64");
     if (cfg->dtype == LDIT_FP8 && (g.C % 128 || g.F % 128)) return fail(LDIT_EUNSUPPORTED, "cfg: fp8 needs hidden and mlp multiples of 128");
+    if (cfg->dtype == LDIT_MXFP8 && (g.C % 128 || g.F % 128)) return fail(LDIT_EUNSUPPORTED, "cfg: mxfp8 needs hidden and mlp multiples of 128");
     if (cfg->img_h <= 0 || cfg->img_w <= 0 || cfg->img_h % g.p || cfg->img_w % g.p)
         return fail(LDIT_EINVAL, "cfg: image %dx%d is not a multiple of patch %d", cfg->img_h, cfg->img_w, g.p);
     g.gh = cfg->img_h / g.p; g.gw = cfg->img_w / g.p; g.P = g.gh * g.gw; g.T = g.P + 1;
@@ -48,7 +50,8 @@ inline int geometry(const ldit_cfg *cfg, Geo &g)
 // big matrices of a layer (fused q|k|v, o_proj, fc1, fc2) are stored as bf16, in the fp8 build as e4m3 codes; everything
 // else stays fp32.  fp8 adds, per layer, one fp32 scale per output channel of each matrix (sw_*: measured and applied by
 // ldit_pack_weights) and a block of 8 floats whose slots 0, 2, 4, 6 hold the activation scales a_ln1, a_attn, a_ln2,
-// a_gelu (ldit_set_fp8_act_scales; the odd slots are spare).
+// a_gelu (ldit_set_fp8_act_scales; the odd slots are spare).  The mxfp8 build stores the matrices as e4m3 codes too, and in
+// sw_* the E8M0 block scales of each matrix ([rows, cols / 32] bytes); it has no activation scales.
 struct PackedLayer { size_t ln1_w, ln1_b, wqkv, bqkv, wo, bo, lam1, ln2_w, ln2_b, w1, b1, w2, b2, lam2, scales, sw_qkv, sw_o, sw_1, sw_2; };
 struct PackedMap {
     size_t patch_w, patch_b, cls, pos, total;
@@ -60,7 +63,7 @@ inline PackedMap packed_map(const Geo &g, int dtype)
 {
     PackedMap m;
     size_t o = 0;
-    const size_t mat = dtype == LDIT_FP8 ? 1 : dtype == LDIT_BF16 ? 2 : split_planes_of(dtype) ? 2 * (size_t)split_planes_of(dtype) : 4;
+    const size_t mat = dtype == LDIT_FP8 || dtype == LDIT_MXFP8 ? 1 : dtype == LDIT_BF16 ? 2 : split_planes_of(dtype) ? 2 * (size_t)split_planes_of(dtype) : 4;
     auto take = [&](size_t n, size_t elt) { size_t at = o; o += up(n * elt, 16); return at; };
     m.patch_w = take((size_t)g.C * g.Kp, 4);
     m.patch_b = take(g.C, 4);
@@ -82,6 +85,12 @@ inline PackedMap packed_map(const Geo &g, int dtype)
         pl.sw_o = dtype == LDIT_FP8 ? take(g.C, 4) : 0;
         pl.sw_1 = dtype == LDIT_FP8 ? take(g.F, 4) : 0;
         pl.sw_2 = dtype == LDIT_FP8 ? take(g.C, 4) : 0;
+        if (dtype == LDIT_MXFP8) {
+            pl.sw_qkv = take((size_t)3 * g.C * (g.C / 32), 1);
+            pl.sw_o = take((size_t)g.C * (g.C / 32), 1);
+            pl.sw_1 = take((size_t)g.F * (g.C / 32), 1);
+            pl.sw_2 = take((size_t)g.C * (g.F / 32), 1);
+        }
     }
     m.total = o;
     return m;
@@ -93,7 +102,9 @@ inline Workspace workspace_map(const Geo &g, int batch, int dtype)
 {
     const size_t M = (size_t)batch * g.T;
     const size_t wide = (size_t)(3 * g.C > g.F ? 3 * g.C : g.F);
-    const size_t act = dtype == LDIT_F32 ? 4 : 2;   // fp8 build: sized for its bf16 q|k|v; the fp8 buffers need less
+    // fp8 / mxfp8 builds: sized for their bf16 q|k|v; the fp8 buffers need less (mxfp8: codes [M, K] followed by their block
+    // scales [M, K / 32] - 33/32 bytes per element)
+    const size_t act = dtype == LDIT_F32 ? 4 : 2;
     Workspace w;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o += up(bytes, 256); return at; };

@@ -69,12 +69,14 @@ __device__ __forceinline__ void glds16_sbase(const void *ubase, unsigned voff_by
 // two bf16 so that 2^-17 |m| is all it loses) initialises the S^T accumulators with -m_run.  p = exp2(S') then needs no
 // per-element FMA: 32 of the ~180 VALU instructions of a chunk, on a kernel whose four waves per SIMD saturate instruction
 // issue (PMC: SQ_ACTIVE_INST_ANY x 4 waves = 1.07 of the SIMD's cycles; MFMA pipe 32 % busy).
-template <int KT, int NW, bool OUT_FP8, bool PRE>
+// OUT_MX (with OUT_FP8): MX codes + E8M0 block scales Os [rows, ldo / 32] (ldit.h, LDIT_MXFP8): a lane holds 16 columns of each
+// 32-column block dt of its query row, lane l ^ 32 the other 16 - one exchange gives the block amax.
+template <int KT, int NW, bool OUT_FP8, bool PRE, bool OUT_MX = false>
 __global__ void __launch_bounds__(NW * 64, KT == 2 ? 4 : 2) attention_bf16(const bf16_t *__restrict__ Q, const bf16_t *__restrict__ K,
                                                              const bf16_t *__restrict__ V, void *__restrict__ Ov,
                                                              int N, int H, int ldq, int ldk, int ldv, int ldo,
                                                              float scale, int nqg, const float *__restrict__ qscale,
-                                                             float *__restrict__ lse)
+                                                             float *__restrict__ lse, unsigned char *__restrict__ Os)
 {
     constexpr int KC = KT * 32, HALF = KC * KROWB, STAGE = 2 * HALF;     // keys per chunk; K image, then V image
     constexpr int PIECES = KC / 8, PPW = PIECES / NW;                    // 1-KB DMA pieces (8 keys) per operand, per wave
@@ -344,12 +346,33 @@ __global__ void __launch_bounds__(NW * 64, KT == 2 ? 4 : 2) attention_bf16(const
 #endif
     if (!active) return;
     const float l = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = OUT_FP8 ? 1.0f / (l * qscale[0]) : 1.0f / l;
+    const float inv = OUT_FP8 && !OUT_MX ? 1.0f / (l * qscale[0]) : 1.0f / l;
     const int qrow = qt * 32 + c32;
     // train step: log2-domain log-sum-exp of the scaled scores, L2 = log2 sum_k exp2(c s_k) = m c + log2 l, so that the
     // backward recomputes p = exp2(c s - L2) with no row maximum (layout [B, H, N])
     if (lse && h == 0 && qrow < N) lse[((size_t)b * H + head) * N + qrow] = (PRE ? m_run : m_run * c) + __builtin_amdgcn_logf(l);
-    if (OUT_FP8) {
+    if (OUT_MX) {
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+            unsigned amax = 0;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                o[dt][e] *= inv;
+                amax = umax32(amax, __float_as_uint(o[dt][e]) & 0x7fffffffu);
+            }
+            amax = umax32(amax, (unsigned)__shfl_xor((int)amax, 32, 64));
+            const unsigned sb = mx_scale_byte(amax);
+            const float qi = mx_inv_scale(sb);
+            if (qrow < N) {
+                unsigned char *op = static_cast<unsigned char *>(Ov) + (tok0 + qrow) * ldo + head * 64 + dt * 32 + 4 * h;
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<unsigned *>(op + 8 * g) =
+                        pack_fp8x4(o[dt][4 * g + 0] * qi, o[dt][4 * g + 1] * qi, o[dt][4 * g + 2] * qi, o[dt][4 * g + 3] * qi);
+                if (h == 0) Os[(tok0 + qrow) * (ldo >> 5) + ((head * 64 + dt * 32) >> 5)] = (unsigned char)sb;
+            }
+        }
+    } else if (OUT_FP8) {
         if (qrow < N) {
             unsigned char *op = static_cast<unsigned char *>(Ov) + (tok0 + qrow) * ldo + head * 64 + 4 * h;
 #pragma unroll
@@ -374,9 +397,9 @@ __global__ void __launch_bounds__(NW * 64, KT == 2 ? 4 : 2) attention_bf16(const
 
 }  // namespace
 
-template <bool OUT_FP8>
+template <bool OUT_FP8, bool OUT_MX = false>
 static int launch_attn(const void *Q, const void *K, const void *V, void *O, int B, int N, int H, int D, int ldq, int ldk, int ldv,
-                       int ldo, float scale, const float *qscale, float *lse, hipStream_t stream)
+                       int ldo, float scale, const float *qscale, float *lse, hipStream_t stream, unsigned char *Os = nullptr)
 {
     if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_bf16: empty problem");
     if (D != 64) return fail(LDIT_EUNSUPPORTED, "attention_bf16: head_dim=%d, only 64 is implemented", D);
@@ -392,7 +415,7 @@ static int launch_attn(const void *Q, const void *K, const void *V, void *O, int
         const int nqg = (nqt + nw - 1) / nw;
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * H * nqg)), dim3(nw * 64), lds, stream, static_cast<const bf16_t *>(Q),
                            static_cast<const bf16_t *>(K), static_cast<const bf16_t *>(V), O, N, H, ldq, ldk, ldv, ldo, scale, nqg,
-                           qscale, lse);
+                           qscale, lse, Os);
         return LDIT_OK;
     };
     auto go = [&](auto kern, int lds, std::atomic<unsigned long long> &attr_done) -> int { return go_nw(kern, NW, lds, attr_done); };
@@ -408,11 +431,11 @@ static int launch_attn(const void *Q, const void *K, const void *V, void *O, int
     static std::atomic<unsigned long long> set2p8{0}, set28{0};
     const int force_nw = diag().attn_bf16_nw;
     const bool wide = force_nw == 8 || (force_nw != 4 && nqt > 4 && nqt <= 8);
-    if (scale == 0.0f && wide) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, true>, 8, 2 * 2 * 2 * 32 * KROWB, set2p8));
-    else if (scale == 0.0f) LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, true>, 2 * 2 * 2 * 32 * KROWB, set2p));
-    else if (wide && !kt4) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, false>, 8, 2 * 2 * 2 * 32 * KROWB, set28));
-    else if (kt4) LDIT_TRY_RC(go(attention_bf16<4, NW, OUT_FP8, false>, 2 * 2 * 4 * 32 * KROWB, set4));
-    else LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, false>, 2 * 2 * 2 * 32 * KROWB, set2));
+    if (scale == 0.0f && wide) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, true, OUT_MX>, 8, 2 * 2 * 2 * 32 * KROWB, set2p8));
+    else if (scale == 0.0f) LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, true, OUT_MX>, 2 * 2 * 2 * 32 * KROWB, set2p));
+    else if (wide && !kt4) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, false, OUT_MX>, 8, 2 * 2 * 2 * 32 * KROWB, set28));
+    else if (kt4) LDIT_TRY_RC(go(attention_bf16<4, NW, OUT_FP8, false, OUT_MX>, 2 * 2 * 4 * 32 * KROWB, set4));
+    else LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, false, OUT_MX>, 2 * 2 * 2 * 32 * KROWB, set2));
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
 }
@@ -436,6 +459,14 @@ int launch_attention_bf16_fp8out(const void *Q, const void *K, const void *V, vo
 {
     if (!qscale) return fail(LDIT_EINVAL, "attention_bf16: fp8 output needs a scale");
     return launch_attn<true>(Q, K, V, O, B, N, H, D, ldq, ldk, ldv, ldo, scale, qscale, nullptr, stream);
+}
+
+int launch_attention_bf16_mxout(const void *Q, const void *K, const void *V, void *O, void *Os, int B, int N, int H, int D, int ldq,
+                                int ldk, int ldv, int ldo, float scale, hipStream_t stream)
+{
+    if (!Os || (ldo & 31)) return fail(LDIT_EINVAL, "attention_bf16: MX output needs block scales and ldo %% 32 == 0");
+    return launch_attn<true, true>(Q, K, V, O, B, N, H, D, ldq, ldk, ldv, ldo, scale, nullptr, nullptr, stream,
+                                   static_cast<unsigned char *>(Os));
 }
 
 }  // namespace ldit

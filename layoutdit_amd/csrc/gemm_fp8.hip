@@ -8,6 +8,7 @@
 // The non-scaled fp8 MFMA issues at the bf16 rate; what fp8 buys here is half the DMA / LDS bytes per FLOP.
 // Epilogues: bias -> bf16 ; bias + erf-GELU -> fp8 (times out_inv_scale, saturated to +-448) ; R + lam (.) (.) -> fp32.
 #include <cstdlib>
+#include <type_traits>
 
 #include "ldit_common.h"
 #include "epilogue_rows.h"
@@ -39,12 +40,18 @@ struct GemmArgs8 {
     const float *d_act, *d_out;   // device-resident sa / so: override the two host values when non-null
     const float *d_wrow;          // optional per-output-channel weight scales [N] (multiplied onto the per-tensor part)
     int direct_epi;               // LDIT_GEMM_DIRECT_EPILOGUE=1: interior tiles stored straight from the accumulators
+    // MX instantiations only (block scales, ldit.h LDIT_MXFP8): E8M0 bytes [rows, ld / 32] beside A, W and the MX output of
+    // BIAS_GELU; row strides in bytes (= elements / 32).  Appended last: the per-tensor instantiations read the fields above
+    // at the offsets they always had.
+    const unsigned char *As, *Ws;
+    unsigned char *Ys;
+    int ldas, ldws, ldys;
 };
 
 // MODE 0: tile inside the matrix, 16-B / 8-B accesses unchecked; MODE 1: columns inside, rows past M skipped (the ragged
 // last row tile keeps its vector accesses - a lane owns a row, so the element-wise path does not coalesce and cost ~20 us);
 // MODE 2: element-wise with checks.
-template <int TM, int TN, int EPI, int MODE>
+template <int TM, int TN, int EPI, int MODE, bool MX = false>
 __device__ __forceinline__ void store_q(const GemmArgs8 &p, const f32x16 (&acc)[TM][TN], int mw, int nw, int lane)
 {
     const int c32 = lane & 31, h = lane >> 5;
@@ -68,6 +75,32 @@ __device__ __forceinline__ void store_q(const GemmArgs8 &p, const f32x16 (&acc)[
         for (int i = 0; i < TM; ++i) {
             const int m = mw + i * 32 + c32;
             if (MODE != 0 && m >= p.M) continue;
+            if constexpr (MX && EPI == EPI_BIAS_GELU) {
+                // MX output: the row's 32-column block j is split between this lane (columns 8 g + 4 h + e) and lane l ^ 32 -
+                // one exchange completes its amax (N % 32 == 0: a block is wholly inside or wholly outside the matrix)
+                f32x4 v[4];
+                unsigned amax = 0;
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[g][e] = gelu_lp(__builtin_fmaf(acc[i][j][4 * g + e], abq[g][e], bias[g][e]));
+                        amax = umax32(amax, __float_as_uint(v[g][e]) & 0x7fffffffu);
+                    }
+                amax = umax32(amax, (unsigned)__shfl_xor((int)amax, 32, 64));
+                const unsigned sb = mx_scale_byte(amax);
+                const float inv = mx_inv_scale(sb);
+                const int nb = nw + j * 32;
+                if (MODE == 2 && nb >= p.N) continue;
+                unsigned char *y = static_cast<unsigned char *>(p.Y);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const unsigned o = (unsigned)m * (unsigned)p.ldy + (unsigned)(nb + 8 * g + 4 * h);
+                    *reinterpret_cast<unsigned *>(y + o) = pack_fp8x4(v[g][0] * inv, v[g][1] * inv, v[g][2] * inv, v[g][3] * inv);
+                }
+                if (h == 0) p.Ys[(unsigned)m * (unsigned)p.ldys + (unsigned)(nb >> 5)] = (unsigned char)sb;
+                continue;
+            }
             f32x4 res[4];
             if (EPI == EPI_SCALE_RESID) {
 #pragma unroll
@@ -130,7 +163,14 @@ __device__ __forceinline__ void store_q(const GemmArgs8 &p, const f32x16 (&acc)[
 // K64 = false: v_mfma_f32_32x32x16_fp8_fp8 (bf16 rate), two per b128 fragment read, four chunk steps per k-tile.
 // K64 = true : v_mfma_f32_32x32x64_f8f6f4 with e4m3 operands and unit block scales (2x the bf16 rate): a lane's operand is
 //              32 consecutive fp8 of its row (two b128 reads), two chunk steps per k-tile.
-template <int WM, int WN, int TM, int TN, int EPI, bool K64>
+// MX = true (K64 only): the same MFMA with VGPR block scales (v_mfma_scale_f32_32x32x64_f8f6f4 ..., vS, vT).  The instruction's
+//              scale block b of a 64-deep step is the b-th 16 bytes of BOTH lane halves, and lane half b supplies its scale: a lane
+//              therefore takes 16-B chunks h and 2 + h of the step (not 2 h, 2 h + 1), block b is then the row's 32 consecutive
+//              bytes 64 c + 32 b, and lane half h's scale is byte 2 c + h of the row's k-tile dword - the dword shifted right by
+//              8 h, op_sel 2 c (pinned exactly by tests/test_gpu_mxfp8.py).  A k-tile's dwords are fetched behind the hand-over
+//              barrier one iteration ahead (asm loads in front of that iteration's DMA pieces, so that the counted wait at the end
+//              of the iteration lets the DMA stay in flight), the per-tensor instantiations are unchanged.
+template <int WM, int WN, int TM, int TN, int EPI, bool K64, bool MX = false>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(const GemmArgs8 p)
 {
     constexpr int NWAVES = WM * WN;
@@ -244,13 +284,54 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
             __builtin_amdgcn_sched_barrier(0);
         }
     } else {
-        auto mfma_chunk = [&](const i32x8(&xa)[TM], const i32x8(&wb)[TN]) {
+        // MX: sx / sw = the scale dwords of tile kt (shifted: byte 0 = block h, byte 2 = block 2 + h), nx / nw_ = tile kt + 1 in flight
+        unsigned xo[MX ? TM : 1], wo[MX ? TN : 1], sx[MX ? TM : 1], sw_[MX ? TN : 1], nx[MX ? TM : 1], nw_[MX ? TN : 1];
+        const unsigned sh = 8u * (unsigned)h;
+        if constexpr (MX) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const int r = m0 + wm * TM * 32 + i * 32 + c32;
+                xo[i] = (unsigned)(r < p.M ? r : p.M - 1) * (unsigned)p.ldas;
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int r = n0 + wn * TN * 32 + j * 32 + c32;
+                wo[j] = (unsigned)(r < p.N ? r : p.N - 1) * (unsigned)p.ldws;
+            }
+        }
+        // (hand-counted like the DMA: hipcc cannot see these loads, the registers are read only behind an explicit vmcnt wait
+        //  that names them - `landed`)
+        auto fetch_scales = [&](unsigned(&dx)[MX ? TM : 1], unsigned(&dw)[MX ? TN : 1], int kt) {
+            if constexpr (MX) {
+                const unsigned char *xb = p.As + 4 * kt, *wbs = p.Ws + 4 * kt;
+#pragma unroll
+                for (int i = 0; i < TM; ++i) asm volatile("global_load_dword %0, %1, %2" : "=v"(dx[i]) : "v"(xo[i]), "s"(xb) : "memory");
+#pragma unroll
+                for (int j = 0; j < TN; ++j) asm volatile("global_load_dword %0, %1, %2" : "=v"(dw[j]) : "v"(wo[j]), "s"(wbs) : "memory");
+            }
+        };
+        auto landed = [&](unsigned(&dx)[MX ? TM : 1], unsigned(&dw)[MX ? TN : 1]) {   // behind a vmcnt that covers them
+            if constexpr (MX) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) { asm volatile("" : "+v"(dx[i])); sx[i] = dx[i] >> sh; }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) { asm volatile("" : "+v"(dw[j])); sw_[j] = dw[j] >> sh; }
+            }
+        };
+        auto mfma_chunk = [&](const i32x8(&xa)[TM], const i32x8(&wb)[TN], auto chunk) {
+            constexpr int OPS = 2 * decltype(chunk)::value;
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, 0, 0, 0);
+                for (int j = 0; j < TN; ++j) {
+                    if constexpr (MX)
+                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, OPS, (int)sw_[j], OPS, (int)sx[i]);
+                    else
+                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, 0, 0, 0);
+                }
         };
+        const std::integral_constant<int, 0> chunk0{};
+        const std::integral_constant<int, 1> chunk1{};
         i32x8 xa0[TM], wb0[TN], xa1[TM], wb1[TN];
         // Round 3: the DMA of tile kt+2 is issued right BEHIND the hand-over barrier of iteration kt (stage `cur` is free there:
         // every wave's last fragments of tile kt are in registers) and waited for at the NEXT hand-over - a whole k-tile of MFMA
@@ -265,12 +346,16 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
         constexpr bool PIN = TM < 5;
         // fragment of rows r: chunks (4 c + 2 h) ^ sw and (4 c + 2 h + 1) ^ sw of the 128-byte row - the chunk index is an XOR of
         // address bits 6 (c) and 4 (second half); every other term is a multiple of 128 bytes (aligned(128) stage memory)
+        // MX: the fragment of chunk c is 16-B chunks (4 c + h) ^ sw and (4 c + 2 + h) ^ sw instead - the instruction's block b of a
+        // 64-deep step is the b-th 16 bytes of BOTH lane halves, so that block b = the row's 32 consecutive bytes 64 c + 32 b
         const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)smem);
-        const unsigned fa0 = lds0 + a_row + (((2 * h) ^ sw) << 4), fb0 = lds0 + b_row + (((2 * h) ^ sw) << 4);
+        constexpr unsigned HI = MX ? 32u : 16u;
+        const int hc = MX ? h : 2 * h;
+        const unsigned fa0 = lds0 + a_row + ((hc ^ sw) << 4), fb0 = lds0 + b_row + ((hc ^ sw) << 4);
         auto load_frags = [&](int stage, int c, i32x8(&xa)[TM], i32x8(&wb)[TN]) {
             if constexpr (PIN) {
                 const unsigned so = (unsigned)(stage * (ROWS * ROW8));
-                const unsigned a_lo = (fa0 + so) ^ (unsigned)(c << 6), a_hi = a_lo ^ 16u, b_lo = (fb0 + so) ^ (unsigned)(c << 6), b_hi = b_lo ^ 16u;
+                const unsigned a_lo = (fa0 + so) ^ (unsigned)(c << 6), a_hi = a_lo ^ HI, b_lo = (fb0 + so) ^ (unsigned)(c << 6), b_hi = b_lo ^ HI;
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     union { i32x4 v[2]; i32x8 f; } u;
@@ -287,7 +372,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
                 }
             } else {
                 const char *base = smem + stage * (ROWS * ROW8);
-                const int o0 = ((4 * c + 2 * h) ^ sw) * 16, o1 = ((4 * c + 2 * h + 1) ^ sw) * 16;
+                const int o0 = MX ? ((4 * c + h) ^ sw) * 16 : ((4 * c + 2 * h) ^ sw) * 16;
+                const int o1 = MX ? ((4 * c + 2 + h) ^ sw) * 16 : ((4 * c + 2 * h + 1) ^ sw) * 16;
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     const i32x4 lo = *reinterpret_cast<const i32x4 *>(base + a_row + i * 32 * ROW8 + o0);
@@ -305,9 +391,11 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
         // (PIN: every group below is fenced; else the fences and hand waits for the reads drop out and hipcc orders / waits as before)
         auto fence = [&]() { if constexpr (PIN) __builtin_amdgcn_sched_barrier(0); };
         auto reads_done = [&]() { if constexpr (PIN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
+        if constexpr (MX) fetch_scales(nx, nw_, 0);
         issue(0, 0);
         issue(1, (nk > 1 ? 1 : 0) * BKE);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");      // tile 0 landed; tile 1's NLD pieces stay in flight
+        landed(nx, nw_);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         load_frags(0, 0, xa0, wb0);
@@ -318,7 +406,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
             const int k2 = (kt + 2 < nk ? kt + 2 : nk - 1) * BKE;
             load_frags(cur, 1, xa1, wb1);
             fence();
-            mfma_chunk(xa0, wb0);
+            mfma_chunk(xa0, wb0, chunk0);
             fence();
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // tile kt+1 landed; own reads of stage cur retired
             __builtin_amdgcn_s_barrier();   // hand-over: tile kt+1 visible to every wave, stage cur released
@@ -327,14 +415,20 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
             if constexpr (PIN) {
                 load_frags(cur ^ 1, 0, xa0, wb0);
                 fence();
+                if constexpr (MX) fetch_scales(nx, nw_, kt + 1 < nk ? kt + 1 : nk - 1);
                 issue(cur, k2);             // tile kt+2 -> stage cur (a clamped re-fetch on the last two iterations, never read)
             } else {
+                if constexpr (MX) fetch_scales(nx, nw_, kt + 1 < nk ? kt + 1 : nk - 1);
                 issue(cur, k2);
                 load_frags(cur ^ 1, 0, xa0, wb0);
             }
-            mfma_chunk(xa1, wb1);
+            mfma_chunk(xa1, wb1, chunk1);
             fence();
             reads_done();
+            if constexpr (MX) {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");   // tile kt+1's scales; tile kt+2's pieces stay in flight
+                landed(nx, nw_);
+            }
             fence();
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-fetches must not outlive the LDS allocation
@@ -343,24 +437,24 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
     const bool cols_in = (n0 + BN <= p.N) && ((p.ldy & 3) == 0);
     const int mw = m0 + wm * TM * 32, nw = n0 + wn * TN * 32;
     // (the slab path stores eight bf16 columns per lane - EPI_BIAS, the q|k|v output -: ldy a multiple of 8 then)
-    if (cols_in && (EPI != EPI_BIAS || (p.ldy & 7) == 0) && m0 + BM <= p.M && !p.direct_epi) {
+    if (cols_in && (EPI != EPI_BIAS || (p.ldy & 7) == 0) && m0 + BM <= p.M && !p.direct_epi && !(MX && EPI == EPI_BIAS_GELU)) {
         __syncthreads();     // every wave is out of the k-loop (and its DMA drained): the stage memory becomes slab buffers
         const float ab = p.d_act ? p.d_act[0] : p.ab_scale;
         const float oinv = (EPI == EPI_BIAS_GELU && p.d_out) ? 1.0f / p.d_out[0] : p.out_inv_scale;
         store_rows_via_lds<TM, TN, EPI, EPI == EPI_SCALE_RESID ? EPI_OUT_F32 : EPI == EPI_BIAS_GELU ? EPI_OUT_FP8 : EPI_OUT_BF16>(
             acc, smem + wave * EPI_WAVE_BYTES, p.Y, p.Y2, p.R, p.bias, p.lam, p.d_wrow, p.ldy, mw, nw, lane, ab, oinv);
-    } else if (cols_in && m0 + BM <= p.M) store_q<TM, TN, EPI, 0>(p, acc, mw, nw, lane);
-    else if (cols_in) store_q<TM, TN, EPI, 1>(p, acc, mw, nw, lane);
-    else store_q<TM, TN, EPI, 2>(p, acc, mw, nw, lane);
+    } else if (cols_in && m0 + BM <= p.M) store_q<TM, TN, EPI, 0, MX>(p, acc, mw, nw, lane);
+    else if (cols_in) store_q<TM, TN, EPI, 1, MX>(p, acc, mw, nw, lane);
+    else store_q<TM, TN, EPI, 2, MX>(p, acc, mw, nw, lane);
 }
 
-template <int WM, int WN, int TM, int TN, int EPI, bool K64>
+template <int WM, int WN, int TM, int TN, int EPI, bool K64, bool MX = false>
 int launch_q(const GemmArgs8 &a, hipStream_t stream)
 {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int lds = 2 * (BM + BN) * ROW8;
     const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    auto kern = gemm_fp8_mfma<WM, WN, TM, TN, EPI, K64>;
+    auto kern = gemm_fp8_mfma<WM, WN, TM, TN, EPI, K64, MX>;
     LDIT_DYN_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(64 * WM * WN), lds, stream, a);
     LDIT_HIP_CHECK(hipGetLastError());
@@ -372,8 +466,8 @@ int launch_q(const GemmArgs8 &a, hipStream_t stream)
 // kernel's own instruction - v_mfma_f32_32x32x64_f8f6f4, a lane's operand = 32 consecutive fp8 of its row at k = 64 s + 32 h -
 // so a peeled row gets the bits a 256 x 256 tile would have given it (the round-2 split-K kernel summed eight K slices of
 // v_mfma_f32_32x32x16_fp8_fp8 products: another order AND another instruction).  Fragments straight from global memory,
-// two register sets of four 64-deep steps.
-template <int EPI>
+// two register sets of four 64-deep steps.  MX: the lane's operand of step s is block 2 s + h of its row - one scale byte each.
+template <int EPI, bool MX = false>
 __global__ void __launch_bounds__(64) gemm_fp8_tail(const GemmArgs8 p)
 {
     constexpr int D = 4;
@@ -381,54 +475,75 @@ __global__ void __launch_bounds__(64) gemm_fp8_tail(const GemmArgs8 p)
     const int nct = (p.N + 31) / 32;
     const int n0 = (blockIdx.x % nct) * 32, m0 = (blockIdx.x / nct) * 32;
     const int ra = m0 + c32 < p.M ? m0 + c32 : p.M - 1, rw = n0 + c32 < p.N ? n0 + c32 : p.N - 1;
-    const unsigned char *ap = p.A + (size_t)ra * p.lda + 32 * h, *wp = p.W + (size_t)rw * p.K + 32 * h;
+    // (MX: the two 16-byte halves of a lane's operand are bytes 16 h and 32 + 16 h of the step - see gemm_fp8_mfma)
+    constexpr int HO = MX ? 32 : 16;
+    const unsigned char *ap = p.A + (size_t)ra * p.lda + (MX ? 16 : 32) * h, *wp = p.W + (size_t)rw * p.K + (MX ? 16 : 32) * h;
     const int nsteps = p.K / 64;
     f32x16 acc[1][1];
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[0][0][e] = 0.0f;
     i32x8 xa0[D], wb0[D], xa1[D], wb1[D];
+    int sa0[D], sb0[D], sa1[D], sb1[D];
+    const unsigned char *asp = MX ? p.As + (size_t)ra * p.ldas + h : nullptr, *wsp = MX ? p.Ws + (size_t)rw * p.ldws + h : nullptr;
+    auto lds_ = [&](int(&sa)[D], int(&sb)[D], int s0) {
+        if constexpr (MX)
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                const int s = s0 + u < nsteps ? s0 + u : nsteps - 1;
+                sa[u] = asp[2 * s];
+                sb[u] = wsp[2 * s];
+            }
+    };
     auto ld = [&](i32x8(&xa)[D], i32x8(&wb)[D], int s0) {
 #pragma unroll
         for (int u = 0; u < D; ++u) {
             const int s = s0 + u < nsteps ? s0 + u : nsteps - 1;
-            const i32x4 al = *reinterpret_cast<const i32x4 *>(ap + 64 * s), ah = *reinterpret_cast<const i32x4 *>(ap + 64 * s + 16);
-            const i32x4 wl = *reinterpret_cast<const i32x4 *>(wp + 64 * s), wh = *reinterpret_cast<const i32x4 *>(wp + 64 * s + 16);
+            const i32x4 al = *reinterpret_cast<const i32x4 *>(ap + 64 * s), ah = *reinterpret_cast<const i32x4 *>(ap + 64 * s + HO);
+            const i32x4 wl = *reinterpret_cast<const i32x4 *>(wp + 64 * s), wh = *reinterpret_cast<const i32x4 *>(wp + 64 * s + HO);
             xa[u] = i32x8{al[0], al[1], al[2], al[3], ah[0], ah[1], ah[2], ah[3]};
             wb[u] = i32x8{wl[0], wl[1], wl[2], wl[3], wh[0], wh[1], wh[2], wh[3]};
         }
     };
-    auto mm = [&](const i32x8(&xa)[D], const i32x8(&wb)[D], int s0) {
+    auto mm = [&](const i32x8(&xa)[D], const i32x8(&wb)[D], const int(&sa)[D], const int(&sb)[D], int s0) {
 #pragma unroll
         for (int u = 0; u < D; ++u)
-            if (s0 + u < nsteps)
-                acc[0][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[u], xa[u], acc[0][0], 0, 0, 0, 0, 0, 0);
+            if (s0 + u < nsteps) {
+                if constexpr (MX)
+                    acc[0][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[u], xa[u], acc[0][0], 0, 0, 0, sb[u], 0, sa[u]);
+                else
+                    acc[0][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[u], xa[u], acc[0][0], 0, 0, 0, 0, 0, 0);
+            }
     };
     ld(xa0, wb0, 0);
+    lds_(sa0, sb0, 0);
     for (int s0 = 0; s0 < nsteps; s0 += 2 * D) {
         ld(xa1, wb1, s0 + D);
-        mm(xa0, wb0, s0);
+        lds_(sa1, sb1, s0 + D);
+        mm(xa0, wb0, sa0, sb0, s0);
         ld(xa0, wb0, s0 + 2 * D);
-        mm(xa1, wb1, s0 + D);
+        lds_(sa0, sb0, s0 + 2 * D);
+        mm(xa1, wb1, sa1, sb1, s0 + D);
     }
-    if ((n0 + 32 <= p.N) && ((p.ldy & 3) == 0)) store_q<1, 1, EPI, 1>(p, acc, m0, n0, lane);
-    else store_q<1, 1, EPI, 2>(p, acc, m0, n0, lane);
+    if ((n0 + 32 <= p.N) && ((p.ldy & 3) == 0)) store_q<1, 1, EPI, 1, MX>(p, acc, m0, n0, lane);
+    else store_q<1, 1, EPI, 2, MX>(p, acc, m0, n0, lane);
 }
 
-template <int EPI>
+template <int EPI, bool MX = false>
 int launch_qtail(const GemmArgs8 &a, hipStream_t stream)
 {
     const unsigned blocks = (unsigned)(((a.N + 31) / 32) * ((a.M + 31) / 32));
-    hipLaunchKernelGGL(gemm_fp8_tail<EPI>, dim3(blocks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL((gemm_fp8_tail<EPI, MX>), dim3(blocks), dim3(64), 0, stream, a);
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
 }
 
-template <int EPI>
+template <int EPI, bool MX = false>
 int launch_q_tiled(const GemmArgs8 &a, hipStream_t stream)
 {
     // LDIT_GEMM_FP8_K16=1 selects the K = 16 MFMA, LDIT_GEMM_FP8_TILE=0..2 forces a tile (both for experiments / tests)
-    const bool k16 = diag().fp8_k16, noskinny = diag().fp8_noskinny;
-    if (a.M <= 64 && !noskinny && !k16) return launch_qtail<EPI>(a, stream);     // peeled tail / tiny batch (bit-identical to the K = 64 tiles)
+    // (MX: the K = 16 MFMA has no block scales - the switch does not apply)
+    const bool k16 = !MX && diag().fp8_k16, noskinny = diag().fp8_noskinny;
+    if (a.M <= 64 && !noskinny && !k16) return launch_qtail<EPI, MX>(a, stream);     // peeled tail / tiny batch (bit-identical to the K = 64 tiles)
     // Time model fitted to scripts/gemm_fp8_bench.py on ViT-B / ViT-L shapes, M = 3 k .. 25 k (profiles/README.md), in us:
     //   256 x 256 (one workgroup per CU):  strict rounds of 256 tiles, each  a[epi] + 11.3e-3 K
     //   128 x 128 (two per CU, they overlap each other's prologue / epilogue):  rounds of 256 tiles, each  r[epi] + 4.25e-3 K,
@@ -450,10 +565,15 @@ int launch_q_tiled(const GemmArgs8 &a, hipStream_t stream)
     }
     if (const int force = diag().fp8_tile; force >= 0 && force <= 4) pick = force;
     if (k16 && pick > 2) pick = 0;
-    if (pick == 3) return launch_q<2, 4, 3, 2, EPI, true>(a, stream);      // 192 x 256
+    if (pick == 3) return launch_q<2, 4, 3, 2, EPI, true, MX>(a, stream);      // 192 x 256
     if (pick == 4 && EPI == EPI_SCALE_RESID) pick = 0;
     if constexpr (EPI != EPI_SCALE_RESID)
-        if (pick == 4) return launch_q<2, 4, 5, 2, EPI, true>(a, stream);  // 320 x 256
+        if (pick == 4) return launch_q<2, 4, 5, 2, EPI, true, MX>(a, stream);  // 320 x 256
+    if constexpr (MX) {
+        if (pick == 0) return launch_q<2, 4, 4, 2, EPI, true, true>(a, stream);
+        if (pick == 1) return launch_q<2, 2, 4, 2, EPI, true, true>(a, stream);
+        return launch_q<2, 2, 2, 2, EPI, true, true>(a, stream);
+    }
     if (k16) {
         if (pick == 0) return launch_q<2, 4, 4, 2, EPI, false>(a, stream);
         if (pick == 1) return launch_q<2, 2, 4, 2, EPI, false>(a, stream);
@@ -522,6 +642,33 @@ __global__ void __launch_bounds__(256) quant_rows_fp8(const float *__restrict__ 
     }
 }
 
+// MX quantisation (ldit.h, LDIT_MXFP8): eight consecutive lanes own one 32-element block of a row (4 elements each), three
+// exchanges give its amax.  codes [rows, K] (dense), scales [rows, K / 32]; `mul` is folded into the values first (W_q at pack time).
+__global__ void __launch_bounds__(256) quant_mx(const float *__restrict__ src, int64_t lds, unsigned char *__restrict__ codes,
+                                                unsigned char *__restrict__ scales, int64_t rows, int K, float mul)
+{
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, blk = gid >> 3;
+    const int nb = K >> 5, q = (int)(gid & 7);
+    const bool ok = blk < rows * nb;
+    const int64_t b = ok ? blk : rows * nb - 1;
+    const int64_t row = b / nb;
+    const int col = (int)(b - row * nb) * 32 + 4 * q;
+    f32x4 v = *reinterpret_cast<const f32x4 *>(src + row * lds + col);
+    unsigned amax = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v[e] *= mul;
+        amax = umax32(amax, __float_as_uint(v[e]) & 0x7fffffffu);
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) amax = umax32(amax, (unsigned)__shfl_xor((int)amax, o, 64));
+    const unsigned sb = mx_scale_byte(amax);
+    const float inv = mx_inv_scale(sb);
+    if (!ok) return;
+    *reinterpret_cast<unsigned *>(codes + row * K + col) = pack_fp8x4(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv);
+    if (q == 0) scales[row * nb + (col >> 5)] = (unsigned char)sb;
+}
+
 __global__ void amax_to_scale(float *p, int n)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -576,6 +723,67 @@ static int launch_gemm_fp8_one(const void *A, int lda, const void *W, const floa
             return launch_q_tiled<EPI_SCALE_RESID>(a, stream);
         default: return fail(LDIT_EINVAL, "gemm_fp8: unknown epilogue %d", epi);
     }
+}
+
+static int launch_gemm_mxfp8_one(const void *A, int lda, const void *As, const void *W, const void *Ws, const float *bias, void *Y,
+                                 int ldy, void *Ys, int M, int N, int K, int epi, const float *lam, const float *R, float *Y2,
+                                 hipStream_t stream)
+{
+    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "gemm_mxfp8: empty problem");
+    if (K % BKE) return fail(LDIT_EUNSUPPORTED, "gemm_mxfp8: K=%d must be a multiple of %d", K, BKE);
+    if (!A || !W || !Y || !As || !Ws || (epi == EPI_BIAS_GELU && !Ys)) return fail(LDIT_EINVAL, "gemm_mxfp8: null operand");
+    if (!aligned16(A) || !aligned16(W) || (lda % BKE) || (reinterpret_cast<uintptr_t>(As) & 3u) || (reinterpret_cast<uintptr_t>(Ws) & 3u))
+        return fail(LDIT_EINVAL, "gemm_mxfp8: operands must be 16-byte aligned (scales 4-byte), lda a multiple of %d", BKE);
+    if (epi == EPI_BIAS_GELU && ((N & 31) || (ldy & 31) || (reinterpret_cast<uintptr_t>(Y) & 3u)))
+        return fail(LDIT_EINVAL, "gemm_mxfp8: the MX output needs N and ldy multiples of 32");
+    GemmArgs8 a{};
+    a.A = static_cast<const unsigned char *>(A); a.W = static_cast<const unsigned char *>(W); a.Y = Y; a.Y2 = Y2;
+    a.bias = bias; a.lam = lam; a.R = R; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldy = ldy;
+    a.ab_scale = 1.0f; a.out_inv_scale = 1.0f;     // every scale is a block scale inside the MFMA
+    a.direct_epi = diag().direct_epi ? 1 : 0;
+    a.As = static_cast<const unsigned char *>(As); a.Ws = static_cast<const unsigned char *>(Ws); a.Ys = static_cast<unsigned char *>(Ys);
+    a.ldas = lda / 32; a.ldws = K / 32; a.ldys = ldy / 32;
+    switch (epi) {
+        case EPI_BIAS: return launch_q_tiled<EPI_BIAS, true>(a, stream);
+        case EPI_BIAS_GELU: return launch_q_tiled<EPI_BIAS_GELU, true>(a, stream);
+        case EPI_SCALE_RESID:
+            if (!lam || !R) return fail(LDIT_EINVAL, "gemm_mxfp8: scale+residual epilogue needs lam and R");
+            return launch_q_tiled<EPI_SCALE_RESID, true>(a, stream);
+        default: return fail(LDIT_EINVAL, "gemm_mxfp8: unknown epilogue %d", epi);
+    }
+}
+
+// launch_gemm_fp8's peeling of a ragged tail of up to 64 rows, on MX operands (the scale rows move with the code rows)
+int launch_gemm_mxfp8(const void *A, int lda, const void *As, const void *W, const void *Ws, const float *bias, void *Y, int ldy,
+                      void *Ys, int M, int N, int K, int epi, const float *lam, const float *R, float *Y2, hipStream_t stream)
+{
+    const int rem = M % 256;
+    const long nbn = (N + 255) / 256, full = ((long)M / 256 + 1) * nbn, mainp = ((long)M / 256) * nbn;
+    if (rem != 0 && rem <= 64 && M > 256 && (full + 255) / 256 > (mainp + 255) / 256) {
+        const int main_rows = M - rem;
+        const size_t out_elt = epi == EPI_SCALE_RESID ? 4 : epi == EPI_BIAS_GELU ? 1 : 2;
+        int rc = launch_gemm_mxfp8_one(A, lda, As, W, Ws, bias, Y, ldy, Ys, main_rows, N, K, epi, lam, R, Y2, stream);
+        if (rc != LDIT_OK) return rc;
+        const char *At = static_cast<const char *>(A) + (size_t)main_rows * lda;
+        const char *Ast = static_cast<const char *>(As) + (size_t)main_rows * (lda / 32);
+        char *Yt = static_cast<char *>(Y) + (size_t)main_rows * ldy * out_elt;
+        char *Yst = Ys ? static_cast<char *>(Ys) + (size_t)main_rows * (ldy / 32) : nullptr;
+        return launch_gemm_mxfp8_one(At, lda, Ast, W, Ws, bias, Yt, ldy, Yst, rem, N, K, epi, lam, R ? R + (size_t)main_rows * ldy : nullptr,
+                                     Y2 ? Y2 + (size_t)main_rows * ldy : nullptr, stream);
+    }
+    return launch_gemm_mxfp8_one(A, lda, As, W, Ws, bias, Y, ldy, Ys, M, N, K, epi, lam, R, Y2, stream);
+}
+
+int launch_quant_mx(const float *src, int64_t lds, void *codes, void *scales, int64_t rows, int K, float mul, hipStream_t stream)
+{
+    if (rows <= 0 || K <= 0 || (K & 31) || lds < K || (lds & 3)) return fail(LDIT_EINVAL, "quant_mx: bad shape %lld x %d (ld %lld)", (long long)rows, K, (long long)lds);
+    if (!src || !codes || !scales || !aligned16(src) || (reinterpret_cast<uintptr_t>(codes) & 3u))
+        return fail(LDIT_EINVAL, "quant_mx: null or misaligned operand");
+    const int64_t threads = rows * (K / 32) * 8;
+    hipLaunchKernelGGL(quant_mx, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, src, lds,
+                       static_cast<unsigned char *>(codes), static_cast<unsigned char *>(scales), rows, K, mul);
+    LDIT_HIP_CHECK(hipGetLastError());
+    return LDIT_OK;
 }
 
 int launch_quant_fp8(const float *src, void *dst, size_t n, float inv_scale, const float *d_scale, hipStream_t stream)

@@ -133,6 +133,23 @@ __device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float 
     return (unsigned)w;
 }
 
+__device__ __forceinline__ unsigned umax32(unsigned a, unsigned b) { return a > b ? a : b; }
+
+// MX block scale (ldit.h, LDIT_MXFP8) of a block whose largest |x| has the bit pattern `amax` (sign cleared; an integer maximum of
+// such patterns also catches NaN): the smallest e with amax <= 448 2^e, clamped to [-127, 127], as the E8M0 byte e + 127.  With
+// amax = 1.f 2^(x - 127): e = x - 135, one more when 1.f > 1.75 (448 = 1.75 2^8).  All-zero block: 0; Inf / NaN: 0xFF.
+__device__ __forceinline__ unsigned mx_scale_byte(unsigned amax)
+{
+    if (amax >= 0x7f800000u) return 0xFFu;
+    if (amax == 0u) return 0u;
+    int e = (int)(amax >> 23) - 135 + ((amax & 0x7fffffu) > 0x600000u ? 1 : 0);
+    e = e < -127 ? -127 : (e > 127 ? 127 : e);
+    return (unsigned)(e + 127);
+}
+
+// 2^-e for the scale byte b = e + 127: an exact power of two (b <= 253 for every finite fp32 amax); 1 for the NaN byte
+__device__ __forceinline__ float mx_inv_scale(unsigned b) { return b >= 254u ? 1.0f : __uint_as_float((254u - b) << 23); }
+
 // ---- GEMM ----------------------------------------------------------------------------------------------------
 enum AMode { A_ROWMAJOR = 0, A_PATCH = 1,
              A_CONV3 = 2 };   // fp32 general kernel only: implicit im2col of a 3x3 / pad 1 convolution over an NHWC map
@@ -263,6 +280,14 @@ int launch_layernorm_splitout(const float *X, const float *g, const float *b, vo
 int launch_gemm_fp8(const void *A, int lda, const void *W, const float *bias, void *Y, int ldy, int M, int N, int K, int epi,
                     const float *lam, const float *R, float *Y2, float ab_scale, float out_inv_scale, const float *d_act,
                     const float *d_wrow, const float *d_out, hipStream_t stream);
+// MX (block-scaled) fp8 - ldit.h, LDIT_MXFP8: codes [rows, K] e4m3 + E8M0 scales [rows, K / 32], scale rows ld / 32 bytes
+int launch_gemm_mxfp8(const void *A, int lda, const void *As, const void *W, const void *Ws, const float *bias, void *Y, int ldy,
+                      void *Ys, int M, int N, int K, int epi, const float *lam, const float *R, float *Y2, hipStream_t stream);
+int launch_quant_mx(const float *src, int64_t lds, void *codes, void *scales, int64_t rows, int K, float mul, hipStream_t stream);
+int launch_layernorm_mxout(const float *X, const float *g, const float *b, void *Y, void *Ys, int64_t rows, int C, float eps,
+                           hipStream_t stream);
+int launch_attention_bf16_mxout(const void *Q, const void *K, const void *V, void *O, void *Os, int B, int N, int H, int D, int ldq,
+                                int ldk, int ldv, int ldo, float scale, hipStream_t stream);
 int launch_quant_rows_fp8(const float *W, void *dst, float *scales, int N, int K, hipStream_t stream, float mul = 1.0f);
 int launch_quant_fp8(const float *src, void *dst, size_t n, float inv_scale, const float *d_scale, hipStream_t stream);
 int launch_amax_f32(const float *src, size_t n, float *out, bool accumulate, hipStream_t stream);

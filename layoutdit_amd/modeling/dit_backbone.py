@@ -27,8 +27,9 @@ class DiTBackbone(nn.Module):
                  checkpoint: Optional[str] = None, compute_dtype: str = "f32"):
         """``pretrained=True`` in the reference means a hub download; offline it must come with a local
         ``checkpoint`` path (a ``state_dict`` in any of the accepted BEiT key layouts, loaded with
-        ``weights_only=True``).  ``compute_dtype`` selects the encoder build (``"f32"``, ``"bf16"``, ``"fp8"`` - the
-        last needs ``self.dit.calibrate_fp8(sample)`` once); the returned maps are fp32 in every build."""
+        ``weights_only=True``).  ``compute_dtype`` selects the encoder build (``"f32"``, ``"bf16"``, ``"fp8"`` - which
+        needs ``self.dit.calibrate_fp8(sample)`` once -, ``"mxfp8"`` - block-scaled, no calibration); the returned maps are fp32
+        in every build."""
         super().__init__()
         self.dit = DiTEncoder(config, compute_dtype=compute_dtype)
         if pretrained and checkpoint is None:

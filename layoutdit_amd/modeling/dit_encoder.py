@@ -49,7 +49,8 @@ class _Affine(nn.Module):
             self.register_parameter("bias", None)
 
 
-_DTYPES = {"f32": _lib.DTYPE_F32, "bf16": _lib.DTYPE_BF16, "fp8": _lib.DTYPE_FP8, "f32x3": _lib.DTYPE_F32X3, "f32x6": _lib.DTYPE_F32X6}
+_DTYPES = {"f32": _lib.DTYPE_F32, "bf16": _lib.DTYPE_BF16, "fp8": _lib.DTYPE_FP8, "f32x3": _lib.DTYPE_F32X3, "f32x6": _lib.DTYPE_F32X6,
+           "mxfp8": _lib.DTYPE_MXFP8}
 
 
 class _Holder(nn.Module):
@@ -70,7 +71,10 @@ class DiTEncoder(nn.Module):
         """``compute_dtype``: arithmetic of the INFERENCE forward - ``"f32"`` (exact-fp32 MFMA, the parity path), ``"bf16"``
         (bf16 GEMM / attention operands with fp32 accumulation, residual stream, LayerNorm and softmax; parameters and
         returned taps stay fp32) or ``"fp8"`` (the four GEMMs of a layer on fp8 e4m3 operands with per-tensor scales,
-        attention on bf16; needs one ``calibrate_fp8(sample_batch)`` call before the first forward).
+        attention on bf16; needs one ``calibrate_fp8(sample_batch)`` call before the first forward) or ``"mxfp8"`` (the same
+        GEMMs on OCP MX operands - e4m3 with one power-of-two scale per 32 elements of a row, each activation block scaled from
+        its own amax where it is produced: no calibration, nothing to go stale after a weight update, and each image's result
+        independent of the rest of the batch; include/ldit.h, LDIT_MXFP8).
         ``"f32x3"`` / ``"f32x6"``: the fp32 forward with every GEMM operand held as two / three bf16 planes and every product
         formed from three / six plane products on the bf16 MFMA (16x the fp32 matrix rate) with fp32 accumulation; LayerNorm,
         softmax, erf-GELU and the residual stream exactly as ``"f32"``.  ``"f32x6"`` has the error of fp32 arithmetic (6-8e-7 vs
@@ -82,7 +86,7 @@ class DiTEncoder(nn.Module):
         gradients / master parameters - what the reference's CUDA branch does with fp16 autocast + GradScaler
         (trainer.py:168,177-180; bf16 needs no loss scaling, a scaled loss passes through unharmed) and within the
         bf16 gate of its fp32 CPU branch (trainer.py:171-172; gradients rel-L2 <= 3e-2 per tensor, measured <= 1e-2:
-        tests/test_gpu_train.py).  The ``"fp8"`` build is inference only.
+        tests/test_gpu_train.py).  The ``"fp8"`` and ``"mxfp8"`` builds are inference only.
 
         ACTIVATION: HF's ``hidden_act="gelu"`` is the exact erf-GELU.  The ``"f32"`` / ``"f32x3"`` / ``"f32x6"`` inference forwards
         evaluate it (< 1 ulp); the bf16 / fp8 inference forwards and EVERY training forward evaluate its logistic form
@@ -91,7 +95,7 @@ class DiTEncoder(nn.Module):
         operands, than its eval forward computes - inside the stated gates, documented here and in INTEGRATION.md."""
         super().__init__()
         if compute_dtype not in _DTYPES:
-            raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'f32', 'f32x3', 'f32x6', 'bf16' or 'fp8'")
+            raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'f32', 'f32x3', 'f32x6', 'bf16', 'fp8' or 'mxfp8'")
         self.compute_dtype = compute_dtype
         self.config = config or DiTConfig()
         cfg = self.config
@@ -282,6 +286,9 @@ class DiTEncoder(nn.Module):
         outliers exceed what e4m3's range covers."""
         from .. import ops
         cfg = self.config
+        if self.compute_dtype == "mxfp8":
+            raise RuntimeError("calibrate_fp8 is not needed by the 'mxfp8' build: its block scales are measured from every "
+                               "activation block as it is produced - run the forward directly")
         if not pixel_values.is_cuda:
             raise RuntimeError("calibrate_fp8 runs on the GPU kernels: move the sample batch to a HIP device")
         x = pixel_values.detach().to(torch.float32).contiguous()
@@ -346,8 +353,8 @@ class DiTEncoder(nn.Module):
         ``layoutdit_amd.training`` (C ABI: ldit_vit_forward_train / ldit_vit_backward).  bf16 build only."""
         from .. import training
         cfg = self.config
-        if self.compute_dtype == "fp8":
-            raise NotImplementedError("the fp8 build is inference only: train a DiTEncoder(..., compute_dtype='bf16' or 'f32') "
+        if self.compute_dtype in ("fp8", "mxfp8"):
+            raise NotImplementedError(f"the {self.compute_dtype} build is inference only: train a DiTEncoder(..., compute_dtype='bf16' or 'f32') "
                                       "(both train on bf16 MFMA operands with fp32 master parameters), or call .eval()")
         x = self._pixels_f32(pixel_values)
         L = cfg.num_hidden_layers
@@ -376,8 +383,8 @@ class DiTEncoder(nn.Module):
         cfg = self.config
         if cfg.drop_path_rate <= 0.0 or cfg.num_hidden_layers < 2:
             return False
-        if self.compute_dtype == "fp8":
-            raise NotImplementedError("train mode with stochastic depth on the fp8 (inference-only) build: call .eval()")
+        if self.compute_dtype in ("fp8", "mxfp8"):
+            raise NotImplementedError(f"train mode with stochastic depth on the {self.compute_dtype} (inference-only) build: call .eval()")
         return True
 
     # ---- forward -------------------------------------------------------------------------------------------------

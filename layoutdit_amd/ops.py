@@ -382,6 +382,66 @@ def linear_fp8(x: torch.Tensor, weight: torch.Tensor, ab_scale: float, bias: Opt
     return out
 
 
+def quant_mxfp8(x: torch.Tensor):
+    """fp32 [rows, K] -> MX operand ``(codes [rows, K] float8_e4m3fn, scales [rows, K / 32] uint8)``: one E8M0 scale per 32
+    consecutive elements of a row, ``x ~= codes * 2^(scales - 127)`` (the format: ``include/ldit.h``, ``LDIT_MXFP8``).
+    ``x`` may be a row slice with unit column stride (its row stride a multiple of 4)."""
+    lib = _lib.load()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("x: expected a 2-d float32 GPU tensor with unit column stride")
+    rows, K = x.shape
+    codes = torch.empty((rows, K), device=x.device, dtype=torch.float8_e4m3fn)
+    scales = torch.empty((rows, K // 32), device=x.device, dtype=torch.uint8)
+    _launch(_device(x), lib.ldit_quant_mx_f32_fp8, _ptr(x), x.stride(0), _ptr(codes), _ptr(scales), rows, K)
+    return codes, scales
+
+
+def layernorm_mxfp8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-12):
+    """LayerNorm over the last axis written as an MX operand ``(codes float8_e4m3fn, scales uint8 [rows, C / 32])``."""
+    lib = _lib.load()
+    x, gamma, beta = _req(x, "x"), _req(gamma, "gamma"), _req(beta, "beta")
+    C = x.shape[-1]
+    rows = x.numel() // C
+    codes = torch.empty((rows, C), device=x.device, dtype=torch.float8_e4m3fn)
+    scales = torch.empty((rows, C // 32), device=x.device, dtype=torch.uint8)
+    _launch(_device(x, gamma, beta), lib.ldit_layernorm_mxfp8, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(codes), _ptr(scales), rows, C,
+            float(eps))
+    return codes, scales
+
+
+def linear_mxfp8(x, weight, bias: Optional[torch.Tensor] = None, epilogue: int = _lib.EPI_BIAS,
+                 lam: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None):
+    """Block-scaled MX GEMM (``v_mfma_scale_f32_32x32x64_f8f6f4``): ``x`` = (codes [M, K], scales [M, K / 32]) and ``weight`` =
+    (codes [N, K], scales [N, K / 32]) as :func:`quant_mxfp8` returns them; ``epilogue(x . weight^T + bias)`` with fp32
+    accumulation.  bf16 result for the bias epilogue, an MX pair ``(codes [M, N], scales [M, N / 32])`` of ``gelu(.)`` for the
+    GELU epilogue, fp32 for the scale+residual epilogue (``out`` may be ``residual``)."""
+    lib = _lib.load()
+    (xc, xs), (wc, ws) = x, weight
+    for t, n in ((xc, "x codes"), (wc, "weight codes")):
+        if not t.is_cuda or t.dtype != torch.float8_e4m3fn or not t.is_contiguous():
+            raise ValueError(f"{n}: expected a contiguous float8_e4m3fn GPU tensor")
+    M, K = xc.shape
+    N = wc.shape[0]
+    for t, n, shape in ((xs, "x scales", (M, K // 32)), (ws, "weight scales", (N, K // 32))):
+        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{n}: expected a contiguous uint8 GPU tensor of shape {shape}")
+    ys = None
+    if epilogue == _lib.EPI_BIAS_GELU:
+        if out is None:
+            out = (torch.empty((M, N), device=xc.device, dtype=torch.float8_e4m3fn),
+                   torch.empty((M, N // 32), device=xc.device, dtype=torch.uint8))
+        out, ys = out
+    elif out is None:
+        out = torch.empty((M, N), device=xc.device, dtype=torch.bfloat16 if epilogue == _lib.EPI_BIAS else torch.float32)
+    for t, n in ((bias, "bias"), (lam, "lam"), (residual, "residual"), (out2, "out2")):
+        if t is not None:
+            _req(t, n)
+    _launch(_device(xc, xs, wc, ws, bias, lam, residual, out, ys, out2), lib.ldit_linear_mxfp8, _ptr(xc), K, _ptr(xs), _ptr(wc),
+            _ptr(ws), _ptr(bias), _ptr(out), N, _ptr(ys), M, N, K, epilogue, _ptr(lam), _ptr(residual), _ptr(out2))
+    return (out, ys) if ys is not None else out
+
+
 def attention_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None,
                    prescaled: bool = False) -> torch.Tensor:
     """bf16 fused attention; ``q, k, v``: bf16 [B, N, H*D] token-major (column slices of a fused tensor are fine)."""

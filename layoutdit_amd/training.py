@@ -339,8 +339,8 @@ class TrainStep:
                  dtaps: Optional[Sequence[torch.Tensor]] = None, drop_path_rate: Optional[float] = None,
                  img_size: Optional[Tuple[int, int]] = None, force_comm: bool = False):
         cfg = encoder.config
-        if encoder.compute_dtype == "fp8":
-            raise NotImplementedError("the fp8 build is inference only; the train step runs the 'bf16' and 'f32' builds on bf16 "
+        if encoder.compute_dtype in ("fp8", "mxfp8"):
+            raise NotImplementedError(f"the {encoder.compute_dtype} build is inference only; the train step runs the 'bf16' and 'f32' builds on bf16 "
                                       "MFMA operands with fp32 master parameters (BASELINE configs[2])")
         h, w = img_size or (cfg.image_size, cfg.image_size)
         self.encoder, self.rank = encoder, rank
