@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define LDIT_ABI_VERSION 5
+#define LDIT_ABI_VERSION 6
 #define LDIT_MAX_TAPS 8
 
 enum ldit_status {
@@ -377,7 +377,18 @@ int ldit_colamax_f32(const void *x, int64_t M, int64_t N, int64_t ldx, void *out
  * Replaces, for the encoder, what the reference's loop runs through torch.autograd and torch.optim:
  *     loss_dict = self.model(images, targets) ; loss.backward() ; optimizer.step()     ref trainer.py:169-180
  *     optimizer = AdamW(params, lr = 1e-4, weight_decay = 0)                           ref trainer.py:62-68
- * bf16 build only (cfg.dtype = LDIT_BF16; BASELINE asks bf16 where the reference uses fp16 autocast + GradScaler).
+ * bf16 build (cfg.dtype = LDIT_BF16; BASELINE asks bf16 where the reference uses fp16 autocast + GradScaler), and the mxfp8 build
+ * (cfg.dtype = LDIT_MXFP8, hidden and mlp multiples of 128) as QUANTISATION-AWARE training:
+ *   - the training forward IS the mxfp8 inference forward (same kernels, same tiles, same bits; extra outputs are side stores);
+ *   - the backward is that forward's gradient with every MX quantiser Q taken as the identity (straight-through), computed on
+ *     the bf16 backward kernels with the operands the forward multiplied: the wgrads read the dequantised activations Q(y1), Q(o),
+ *     Q(y2), Q(g), the dgrads the dequantised weights Q(W).  EXACTNESS RULE: an e4m3 code has at most 4 significant bits and bf16
+ *     has 8, so code 2^e is exact in bf16 for every block exponent -124 <= e <= 119 (every finite block with amax between ~2^-115
+ *     and ~2^127); the dequantised operands are those values, held as bf16;
+ *   - the q fold of the packed builds (W_q' = Q(qfold W_q), b_q' = qfold b_q, qfold = D^-1/2 log2 e - not a power of two, so it
+ *     stays inside the quantiser): the attention backward runs in the folded convention and the W_q / b_q gradients are qfold
+ *     times those of the folded tensors; the GELU derivative is that of the function the MX GELU epilogue computes;
+ *   - parameter gradients and master weights stay fp32; no atomics.
  *
  * Parameters, gradients and the two AdamW moments are FLAT fp32 device blocks of ldit_flat_param_bytes(cfg) bytes, laid out
  * like the fp32 packed block: patch_w, patch_b, cls, pos, then per layer ln1_w, ln1_b, wqkv [3C,C] = [Wq;Wk;Wv],
@@ -400,6 +411,15 @@ size_t ldit_train_workspace_bytes(const ldit_cfg *cfg, int32_t batch);
  * current by itself when handed the mirror. */
 size_t ldit_train_mirror_bytes(const ldit_cfg *cfg);
 int ldit_pack_train(const ldit_cfg *cfg, const void *flat_params, void *mirror, size_t mirror_bytes, ldit_stream stream);
+/* LDIT_MXFP8 mirror, ldit_train_mirror_bytes = A + packed_bytes(LDIT_MXFP8), A = flat_bytes / 2 rounded up to 256:
+ *   [0, flat_bytes / 2)  the bf16 part as above, except that the four matrices of every layer hold their DEQUANTISED MX codes
+ *                        (the q third of wqkv folded: Q(qfold W_q)) - the dgrads' operand at the same offsets;
+ *   [A, ...)             the MX section, laid out as ldit_pack_weights' LDIT_MXFP8 block: codes and block scales of the four
+ *                        matrices and the folded q|k|v bias [qfold bq; 0; bv], bit-identical to what ldit_pack_weights(LDIT_MXFP8)
+ *                        makes from the same fp32 values (its other slots are unused).
+ * ldit_pack_train builds both parts; ldit_adamw_step_mxfp8 keeps them current.
+ * ldit_train_saved_bytes(LDIT_MXFP8) = the bf16 layout plus, per layer, M C bf16 (the dequantised attention output), and two
+ * transient MX operands, M (C + C / 32) and M (F + F / 32) bytes (M = batch tokens, each region rounded up to 256 bytes). */
 
 /* Training forward: as ldit_vit_forward, and keeps in `saved` what the backward needs (LayerNorm inputs and outputs, q|k|v,
  * the attention output and its log-sum-exp, the pre-LayerScale branch outputs, the MLP hidden after GELU and the GELU derivative at its pre-activation).
@@ -430,6 +450,30 @@ int ldit_vit_backward(const ldit_cfg *cfg, const void *flat_params, const void *
 int ldit_adamw_step(void *params, const void *grads, void *exp_avg, void *exp_avg_sq, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *bf16_mirror,
                     ldit_stream stream);
+
+/* mxfp8 build: ldit_adamw_step's update of the whole flat block (same bits for master and moments), fused per layer with the
+ * re-quantisation of the forward's operands: afterwards `mirror` (ldit_train_mirror_bytes(cfg) bytes) equals ldit_pack_train of
+ * the updated master bit for bit.  cfg->dtype == LDIT_MXFP8. */
+int ldit_adamw_step_mxfp8(const ldit_cfg *cfg, void *params, const void *grads, void *exp_avg, void *exp_avg_sq, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *mirror, size_t mirror_bytes,
+                          ldit_stream stream);
+
+/* ---- the train variants of the mxfp8 forward's kernels, one entry point each (unit parity tests) ----
+ * ldit_layernorm_mxfp8 that also writes Yd bf16 [rows, C] = the dequantised codes (8-byte aligned). */
+int ldit_layernorm_mxfp8_train(const void *x, const void *gamma, const void *beta, void *Y, void *Ys, void *Yd, int64_t rows, int64_t C,
+                               float eps, ldit_stream stream);
+/* The bf16 attention with MX output O codes [rows, ldo] + Os [rows, ldo / 32] (ldo % 32 == 0), plus lse (fp32 [B, H, N], the
+ * convention of ldit_attention_fwd_lse_bf16), Ob = bf16 O before quantisation and Od = bf16 dequantised codes (both [rows, ldo]).
+ * scale == 0: Q pre-multiplied by D^-1/2 log2 e (the packed builds' fold) - lse is then log2 sum_k exp2(q'.k). */
+int ldit_attention_mxfp8_train(const void *Q, const void *K, const void *V, void *O, void *Os, void *lse, void *Ob, void *Od, int64_t B,
+                               int64_t N, int64_t H, int64_t D, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale,
+                               ldit_stream stream);
+/* ldit_linear_mxfp8 with the train step's side outputs (row stride ldy, bf16, 8-byte aligned); Y is bit-identical to ldit_linear_mxfp8's.
+ * LDIT_EPI_SCALE_RESID: Ypre (optional) = the branch output before LayerScale, rowscale (optional, fp32 [M]) multiplies lam per row;
+ * LDIT_EPI_BIAS_GELU: Ypre = gelu'(pre-activation), Yd = the dequantised MX output (both required). */
+int ldit_linear_mxfp8_train(const void *X, int64_t lda, const void *Xs, const void *W, const void *Ws, const void *bias, void *Y,
+                            int64_t ldy, void *Ys, int64_t M, int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R,
+                            void *Y2, void *Ypre, const void *rowscale, void *Yd, ldit_stream stream);
 
 /* ---- the kernels of the backward, one entry point each (unit parity tests) ---- */
 /* ldit_attention_bf16 that also writes lse[b][h][q] = log2 sum_k exp2(scale log2(e) q.k)  (fp32 [B, H, N]) */

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # scripts/build_alt.sh - instead of the shipped one.  Still the HIP library or nothing: there is no other implementation.
 LIB_PATH = os.environ.get("LDIT_LIB_PATH") or os.path.join(_HERE, "libldit_hip.so")
 
-LDIT_ABI_VERSION = 5
+LDIT_ABI_VERSION = 6
 LDIT_MAX_TAPS = 8
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8, DTYPE_F32X3, DTYPE_F32X6, DTYPE_MXFP8 = 0, 1, 3, 4, 5, 6
 FP8_A_COUNT = 4
@@ -106,6 +106,10 @@ SIGNATURES = {
     "ldit_vit_backward": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _vp, _i32, C.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, _vp, _sz,
                                     _i32, _i32, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ldit_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
+    "ldit_adamw_step_mxfp8": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _sz, _vp]),
+    "ldit_layernorm_mxfp8_train": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp]),
+    "ldit_attention_mxfp8_train": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp]),
+    "ldit_linear_mxfp8_train": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldit_attention_fwd_lse_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp]),
     "ldit_attention_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                           _i64, _f32, _vp]),

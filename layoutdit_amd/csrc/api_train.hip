@@ -23,16 +23,20 @@
 namespace ldit {
 namespace {
 
-struct SavedLayer { size_t h_in, y1, qkv, lse, o, z1, h_mid, y2, a1, g, z2; };
+// mxfp8 build (quantisation-aware training, ldit.h): y1, y2, g hold the DEQUANTISED MX operands Q(.) the forward multiplied (bf16,
+// exact), o the bf16 attention output before quantisation (attention backward) and od its dequantised codes (o_proj wgrad);
+// mx_c / mx_f are the forward's transient MX operands (codes [M, C] / [M, F], then their scales [M, C / 32] / [M, F / 32]).
+struct SavedLayer { size_t h_in, y1, qkv, lse, o, z1, h_mid, y2, a1, g, z2, od; };
 struct SavedMap {
     std::vector<SavedLayer> layer;
     size_t rowscale, h_final, total;
     size_t patches;    // bf16 im2col of the batch [B P, 3 p p]: operand of the patch-embedding GEMM (forward) and of its wgrad
+    size_t mx_c = 0, mx_f = 0;
 };
 
 inline int pad64(int v) { return (v + 63) / 64 * 64; }
 
-SavedMap saved_map(const Geo &g, int batch)
+SavedMap saved_map(const Geo &g, int batch, int dtype)
 {
     SavedMap m;
     const size_t M = (size_t)batch * g.T, C = g.C, F = g.F;
@@ -52,10 +56,15 @@ SavedMap saved_map(const Geo &g, int batch)
         s.a1 = take(M * F * 2);
         s.g = take(M * F * 2);
         s.z2 = take(M * C * 2);
+        s.od = dtype == LDIT_MXFP8 ? take(M * C * 2) : s.o;
     }
     m.rowscale = take((size_t)2 * (g.L > 0 ? g.L : 1) * M * 4);
     m.h_final = take(M * C * 4);
     m.patches = take((size_t)batch * g.P * g.Kp * 2);
+    if (dtype == LDIT_MXFP8) {
+        m.mx_c = take(M * C + M * C / 32);
+        m.mx_f = take(M * F + M * F / 32);
+    }
     m.total = o;
     return m;
 }
@@ -120,8 +129,42 @@ TrainWs train_ws_map(const Geo &g, int batch)
 
 int train_geometry(const ldit_cfg *cfg, Geo &g)
 {
-    LDIT_TRY(geometry(cfg, g));
-    if (cfg->dtype != LDIT_BF16) return fail(LDIT_EUNSUPPORTED, "train step: only the bf16 build (cfg.dtype = LDIT_BF16) is implemented");
+    if (cfg && cfg->dtype != LDIT_BF16 && cfg->dtype != LDIT_MXFP8)
+        return fail(LDIT_EUNSUPPORTED, "train step: only the bf16 (LDIT_BF16) and mxfp8 (LDIT_MXFP8, quantisation-aware) builds are implemented");
+    LDIT_TRY(geometry(cfg, g));     // (mxfp8: hidden and mlp multiples of 128)
+    return LDIT_OK;
+}
+
+// q fold of the packed builds (api.hip, ldit_pack_weights): q' = (D^-1/2 log2 e) q
+inline float qfold_of(const Geo &g) { return (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f; }
+
+// Train mirror (ldit_train_mirror_bytes): the bf16 part - element i of the flat block at byte 2 i (bf16 of the master; in the mxfp8
+// build the four matrices of a layer hold their dequantised MX codes instead, the q third folded) - then, mxfp8 only, at byte
+// mirror_mx_offset the MX section laid out as packed_map(g, LDIT_MXFP8): the matrices' codes and scales and the folded q|k|v bias.
+inline size_t mirror_mx_offset(const Geo &g) { return up(packed_map(g, LDIT_F32).total / 2, 256); }
+inline size_t mirror_bytes(const Geo &g, int dtype)
+{
+    return dtype == LDIT_MXFP8 ? mirror_mx_offset(g) + packed_map(g, LDIT_MXFP8).total : packed_map(g, LDIT_F32).total / 2;
+}
+
+// mxfp8 mirror from the flat block, per layer (one launch each): update = true fuses the AdamW step on that range (adamw_kernel's
+// arithmetic); the embeddings' range is left to the caller
+int mx_layers(const Geo &g, float *p, const float *gr, float *m, float *v, bool update, float lr, float b1, float b2, float eps, float wd,
+              int step, float grad_scale, void *mirror, hipStream_t stream)
+{
+    const PackedMap fm = packed_map(g, LDIT_F32), xm = packed_map(g, LDIT_MXFP8);
+    char *mx = static_cast<char *>(mirror) + mirror_mx_offset(g);
+    const int64_t C = g.C, F = g.F;
+    for (int l = 0; l < g.L; ++l) {
+        const PackedLayer &f = fm.layer[l], &x = xm.layer[l];
+        const int64_t e0 = (int64_t)(f.ln1_w / 4), e1 = (int64_t)((l + 1 < g.L ? fm.layer[l + 1].ln1_w : fm.total) / 4);
+        const MxRequantSeg segs[4] = {{(int64_t)(f.wqkv / 4), 3 * C * C, (int)C, (int)C, (int64_t)x.wqkv, (int64_t)x.sw_qkv},
+                                      {(int64_t)(f.wo / 4), C * C, (int)C, 0, (int64_t)x.wo, (int64_t)x.sw_o},
+                                      {(int64_t)(f.w1 / 4), F * C, (int)C, 0, (int64_t)x.w1, (int64_t)x.sw_1},
+                                      {(int64_t)(f.w2 / 4), C * F, (int)F, 0, (int64_t)x.w2, (int64_t)x.sw_2}};
+        LDIT_TRY(launch_adamw_mx(p, gr, m, v, e0, e1, update, lr, b1, b2, eps, wd, step, grad_scale, mirror, mx, segs, 4,
+                                 (int64_t)(f.bqkv / 4), (int64_t)x.bqkv, g.C, qfold_of(g), stream));
+    }
     return LDIT_OK;
 }
 
@@ -153,7 +196,7 @@ int forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_para
         if (!tap_out[i] || !aligned16(tap_out[i])) return fail(LDIT_EINVAL, "tap_out[%d] is null or misaligned", i);
     if ((int64_t)batch * g.T * (int64_t)(g.F > 3 * g.C ? g.F : 3 * g.C) >= (1ll << 31))
         return fail(LDIT_EUNSUPPORTED, "batch %d: activation index space exceeds 2^31 elements, split the batch", batch);
-    const SavedMap sm = saved_map(g, batch);
+    const SavedMap sm = saved_map(g, batch, cfg->dtype);
     if (saved_bytes < sm.total) return fail(LDIT_EWORKSPACE, "saved-activation block %zu bytes < required %zu", saved_bytes, sm.total);
     // `packed` is the bf16 MIRROR of the flat fp32 block (element i of the mirror = bf16 of element i of the master): a matrix
     // sits at half its fp32 byte offset.  Every fp32 vector (and the fp32 patch projection) is read from the master itself.
@@ -198,6 +241,38 @@ int forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_para
         LDIT_TRY(copy_taps(0, h_of(0), nullptr));
     }
     const float scale = 1.0f / sqrtf((float)g.D);
+    if (cfg->dtype == LDIT_MXFP8) {
+        // mxfp8 (quantisation-aware training): the inference forward of api.hip's mxfp8 branch, launch for launch and tile for tile,
+        // on the mirror's MX section; the train variants of its kernels add side stores only - the dequantised MX operands, the
+        // pre-quantisation attention output, lse, the pre-LayerScale branch outputs, gelu' - and the stochastic-depth row factors
+        const PackedMap xm = packed_map(g, LDIT_MXFP8);
+        const char *X = P + mirror_mx_offset(g);
+        char *y8 = S + sm.mx_c, *ys = y8 + (size_t)M * C, *b8 = S + sm.mx_f, *bs = b8 + (size_t)M * F;
+        for (int l = 0; l < g.L; ++l) {
+            const PackedLayer &pl = pm.layer[l], &xl = xm.layer[l];
+            const SavedLayer &sl = sm.layer[l];
+            float *h_in = h_of(l), *h_mid = reinterpret_cast<float *>(S + sl.h_mid), *h_out = h_of(l + 1);
+            float *tap = tap_of(cfg, tap_out, l + 1);
+            const float *rs1 = rowscale ? rowscale + (size_t)(2 * l) * M : nullptr, *rs2 = rowscale ? rowscale + (size_t)(2 * l + 1) * M : nullptr;
+            char *qkv = S + sl.qkv;
+            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout_train(h_in, F32(pl.ln1_w), F32(pl.ln1_b), y8, ys, S + sl.y1, M, C, cfg->ln_eps, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, X + xl.wqkv, X + xl.sw_qkv, reinterpret_cast<const float *>(X + xl.bqkv), qkv,
+                                                          3 * C, nullptr, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, stream));
+            LDIT_RUN(probe, LDIT_K_ATTENTION,
+                     launch_attention_bf16_mxout_train(qkv, qkv + 2 * (size_t)C, qkv + 4 * (size_t)C, y8, ys, reinterpret_cast<float *>(S + sl.lse),
+                                                       S + sl.o, S + sl.od, batch, g.T, g.H, g.D, 3 * C, 3 * C, 3 * C, C,
+                                                       0.0f /* q folded */, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8_train(y8, C, ys, X + xl.wo, X + xl.sw_o, F32(pl.bo), h_mid, C, nullptr, M, C, C,
+                                                                EPI_SCALE_RESID, F32(pl.lam1), h_in, nullptr, S + sl.z1, rs1, nullptr, stream));
+            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout_train(h_mid, F32(pl.ln2_w), F32(pl.ln2_b), y8, ys, S + sl.y2, M, C, cfg->ln_eps, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8_train(y8, C, ys, X + xl.w1, X + xl.sw_1, F32(pl.b1), b8, F, bs, M, F, C,
+                                                                EPI_BIAS_GELU, nullptr, nullptr, nullptr, S + sl.a1, nullptr, S + sl.g, stream));
+            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8_train(b8, F, bs, X + xl.w2, X + xl.sw_2, F32(pl.b2), h_out, C, nullptr, M, C, F,
+                                                                EPI_SCALE_RESID, F32(pl.lam2), h_mid, tap, S + sl.z2, rs2, nullptr, stream));
+            if (tap) LDIT_TRY(copy_taps(l + 1, h_out, tap));
+        }
+        return LDIT_OK;
+    }
     for (int l = 0; l < g.L; ++l) {
         const PackedLayer &pl = pm.layer[l];
         const SavedLayer &sl = sm.layer[l];
@@ -259,7 +334,7 @@ int backward(const ldit_cfg *cfg, const void *flat_params, const void *packed, c
     if (!aligned16(flat_params) || !aligned16(packed) || !aligned16(x) || !aligned16(saved) || !aligned16(grads) || !aligned16(workspace))
         return fail(LDIT_EINVAL, "backward: pointers must be 16-byte aligned");
     if (stage_hi > g.L || stage_lo < 0 || stage_lo > stage_hi) return fail(LDIT_EINVAL, "backward: stages [%d, %d] outside [0, %d]", stage_lo, stage_hi, g.L);
-    const SavedMap sm = saved_map(g, batch);
+    const SavedMap sm = saved_map(g, batch, cfg->dtype);
     if (saved_bytes < sm.total) return fail(LDIT_EWORKSPACE, "saved-activation block %zu bytes < required %zu", saved_bytes, sm.total);
     const TrainWs wm = train_ws_map(g, batch);
     if (ws_bytes < wm.total) return fail(LDIT_EWORKSPACE, "workspace %zu bytes < required %zu", ws_bytes, wm.total);
@@ -281,7 +356,11 @@ int backward(const ldit_cfg *cfg, const void *flat_params, const void *packed, c
     LDIT_HIP_CHECK(hipMemsetAsync(ws + wm.zeros, 0, 256, stream));
     // stochastic depth: the forward left the per-row factors (expanded from drop_scales) in the saved block
     const float *rowscale = drop_scales ? reinterpret_cast<const float *>(S + sm.rowscale) : nullptr;
-    const float scale = 1.0f / sqrtf((float)g.D);
+    // mxfp8 (straight-through backward): the forward's q was folded, q' = qfold q, and its scores are exp2-domain exponents - the
+    // attention backward runs in that convention (scale ln 2: c = scale log2 e = 1), and the q rows / q bias of the fused
+    // gradient come out per folded parameter: times qfold afterwards (chain rule of W_q' = qfold W_q, b_q' = qfold b_q)
+    const bool mx = cfg->dtype == LDIT_MXFP8;
+    const float scale = mx ? 0.693147180559945309f : 1.0f / sqrtf((float)g.D);
     const int rows_tile = (int)wm.part_rows_tile, rows_ln = (int)wm.part_rows_ln;
     const int rows_lnr = C <= 1024 ? layernorm_bwd_resid_blocks((int64_t)M) : rows_ln;     // partial rows of the fused LayerNorm + LayerScale backward
     ReduceJobs jobs;
@@ -324,7 +403,7 @@ int backward(const ldit_cfg *cfg, const void *flat_params, const void *packed, c
         LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_bwd_resid(dy, reinterpret_cast<const float *>(S + sl.h_mid), F32(pl.ln2_w), dh, M, C,
                                                                     cfg->ln_eps, PART(3), PART(4), S + sl.z1, F32(pl.lam1), rs1, dz, PART(5),
                                                                     PART(6), stream));
-        LDIT_TRY(wgrad(probe, jobs, dz, C, S + sl.o, C, GR(gl.wo), reinterpret_cast<float *>(ws + wm.slab[2]), C, C, M, zeros, stream));
+        LDIT_TRY(wgrad(probe, jobs, dz, C, S + sl.od, C, GR(gl.wo), reinterpret_cast<float *>(ws + wm.slab[2]), C, C, M, zeros, stream));
         LDIT_TRY(dgrad(probe, dz, C, W16 + gl.wo / 2, dob, M, C, EPI_BIAS, nullptr, zeros, stream));
         {
             const char *qkv = S + sl.qkv;
@@ -360,6 +439,10 @@ int backward(const ldit_cfg *cfg, const void *flat_params, const void *packed, c
         jobs.add(PART(8), GR(gl.ln1_w), C, rows_ln, C);
         jobs.add(PART(9), GR(gl.ln1_b), C, rows_ln, C);
         LDIT_RUN(probe, LDIT_K_OTHER, launch_reduce_jobs(jobs, stream));
+        if (mx) {
+            LDIT_RUN(probe, LDIT_K_OTHER, launch_scale_inplace(GR(gl.wqkv), (size_t)C * C, qfold_of(g), stream));
+            LDIT_RUN(probe, LDIT_K_OTHER, launch_scale_inplace(GR(gl.bqkv), (size_t)C, qfold_of(g), stream));
+        }
     }
     if (stage_lo == 0) {
         // ---- embeddings: h0[b, 0] = cls + pos[0];  h0[b, 1 + i] = patch_i . Wp^T + bp + pos[1 + i]  (TF:81-90, 168-172) ------
@@ -416,7 +499,7 @@ size_t ldit_train_saved_bytes(const ldit_cfg *cfg, int32_t batch)
 {
     Geo g;
     if (batch <= 0 || train_geometry(cfg, g) != LDIT_OK) return 0;
-    return saved_map(g, batch).total;
+    return saved_map(g, batch, cfg->dtype).total;
 }
 
 size_t ldit_train_workspace_bytes(const ldit_cfg *cfg, int32_t batch)
@@ -430,7 +513,7 @@ size_t ldit_train_mirror_bytes(const ldit_cfg *cfg)
 {
     Geo g;
     if (train_geometry(cfg, g) != LDIT_OK) return 0;
-    return packed_map(g, LDIT_F32).total / 2;
+    return mirror_bytes(g, cfg->dtype);
 }
 
 int ldit_pack_train(const ldit_cfg *cfg, const void *flat_params, void *mirror, size_t mirror_bytes, ldit_stream stream)
@@ -440,10 +523,38 @@ int ldit_pack_train(const ldit_cfg *cfg, const void *flat_params, void *mirror, 
     if (!flat_params || !mirror) return fail(LDIT_EINVAL, "pack_train: null pointer");
     if (!aligned16(flat_params) || !aligned16(mirror)) return fail(LDIT_EINVAL, "pack_train: pointers must be 16-byte aligned");
     const size_t n = packed_map(g, LDIT_F32).total / 4;
-    if (mirror_bytes < 2 * n) return fail(LDIT_EWORKSPACE, "bf16 mirror %zu bytes < required %zu", mirror_bytes, 2 * n);
+    if (mirror_bytes < ldit::mirror_bytes(g, cfg->dtype))
+        return fail(LDIT_EWORKSPACE, "train mirror %zu bytes < required %zu", mirror_bytes, ldit::mirror_bytes(g, cfg->dtype));
     // one pass: the whole flat block rounded to bf16, same element layout (matrices stay in nn.Linear's [out, in] layout: the
     // forward reads them K-contiguous, the dgrad reads the SAME copy reduction-major, the wgrad needs no weight)
-    return launch_cvt_bf16(static_cast<const float *>(flat_params), mirror, n, static_cast<hipStream_t>(stream));
+    LDIT_TRY(launch_cvt_bf16(static_cast<const float *>(flat_params), mirror, n, static_cast<hipStream_t>(stream)));
+    if (cfg->dtype != LDIT_MXFP8) return LDIT_OK;
+    // mxfp8: each layer's matrices re-made as ldit_pack_weights(LDIT_MXFP8) makes them (codes + scales, q third folded) with their
+    // dequantised codes in the bf16 part, and the folded q|k|v bias - the AdamW-MX pass without the update
+    return mx_layers(g, const_cast<float *>(static_cast<const float *>(flat_params)), nullptr, nullptr, nullptr, false, 0.f, 0.f, 0.f,
+                     0.f, 0.f, 0, 1.0f, mirror, static_cast<hipStream_t>(stream));
+}
+
+int ldit_adamw_step_mxfp8(const ldit_cfg *cfg, void *params, const void *grads, void *exp_avg, void *exp_avg_sq, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *mirror, size_t mirror_bytes,
+                          ldit_stream stream_)
+{
+    Geo g;
+    LDIT_TRY(train_geometry(cfg, g));
+    if (cfg->dtype != LDIT_MXFP8) return fail(LDIT_EINVAL, "adamw_step_mxfp8: cfg.dtype must be LDIT_MXFP8");
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !mirror) return fail(LDIT_EINVAL, "adamw_step_mxfp8: null pointer");
+    if (!aligned16(params) || !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) || !aligned16(mirror))
+        return fail(LDIT_EINVAL, "adamw_step_mxfp8: pointers must be 16-byte aligned");
+    if (step < 1) return fail(LDIT_EINVAL, "adamw_step_mxfp8: step counts from 1");
+    if (mirror_bytes < ldit::mirror_bytes(g, LDIT_MXFP8))
+        return fail(LDIT_EWORKSPACE, "train mirror %zu bytes < required %zu", mirror_bytes, ldit::mirror_bytes(g, LDIT_MXFP8));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    float *p = static_cast<float *>(params), *m = static_cast<float *>(exp_avg), *v = static_cast<float *>(exp_avg_sq);
+    const float *gr = static_cast<const float *>(grads);
+    // ldit_adamw_step over the whole block (its bf16 mirror = the embeddings' operands), then every layer's matrices re-quantised
+    // from the updated master: the codes, scales, folded bias and dequantised copies a fresh ldit_pack_train would make
+    LDIT_TRY(launch_adamw(p, gr, m, v, packed_map(g, LDIT_F32).total / 4, lr, beta1, beta2, eps, weight_decay, step, grad_scale, mirror, stream));
+    return mx_layers(g, p, nullptr, nullptr, nullptr, false, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 1.0f, mirror, stream);
 }
 
 int ldit_vit_forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_params, const void *x, int32_t batch,
@@ -482,6 +593,51 @@ int ldit_adamw_step(void *params, const void *grads, void *exp_avg, void *exp_av
 }
 
 // ---- single kernels of the backward (unit parity tests) -------------------------------------------------------------------
+// ---- single kernels of the mxfp8 train forward (unit parity tests) ------------------------------------------------------
+int ldit_layernorm_mxfp8_train(const void *x, const void *gamma, const void *beta, void *Y, void *Ys, void *Yd, int64_t rows, int64_t C,
+                               float eps, ldit_stream stream)
+{
+    if (rows <= 0 || C <= 0 || C > 4096 || C % 32) return fail(LDIT_EINVAL, "layernorm_mxfp8_train: bad shape");
+    return launch_layernorm_mxout_train(static_cast<const float *>(x), static_cast<const float *>(gamma), static_cast<const float *>(beta),
+                                        Y, Ys, Yd, rows, (int)C, eps, static_cast<hipStream_t>(stream));
+}
+
+int ldit_attention_mxfp8_train(const void *Q, const void *K, const void *V, void *O, void *Os, void *lse, void *Ob, void *Od, int64_t B,
+                               int64_t N, int64_t H, int64_t D, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale,
+                               ldit_stream stream)
+{
+    if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_mxfp8_train: empty problem");
+    if (B * N * (ldq > ldo ? ldq : ldo) >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "attention_mxfp8_train: operand exceeds 2^31 elements");
+    return launch_attention_bf16_mxout_train(Q, K, V, O, Os, static_cast<float *>(lse), Ob, Od, (int)B, (int)N, (int)H, (int)D, (int)ldq,
+                                             (int)ldk, (int)ldv, (int)ldo, scale, static_cast<hipStream_t>(stream));
+}
+
+int ldit_linear_mxfp8_train(const void *X, int64_t lda, const void *Xs, const void *W, const void *Ws, const void *bias, void *Y,
+                            int64_t ldy, void *Ys, int64_t M, int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R,
+                            void *Y2, void *Ypre, const void *rowscale, void *Yd, ldit_stream stream)
+{
+    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_mxfp8_train: empty problem");
+    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_mxfp8_train: operand exceeds 2^31 elements");
+    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear_mxfp8_train: bad leading dimension");
+    if (K % 128 || lda % 128) return fail(LDIT_EUNSUPPORTED, "linear_mxfp8_train: K and lda must be multiples of 128");
+    if (!X || !W || !Xs || !Ws || !Y) return fail(LDIT_EINVAL, "linear_mxfp8_train: null operand");
+    if (!aligned16(X) || !aligned16(W) || (reinterpret_cast<uintptr_t>(Y) & 15u) || (Y2 && !aligned16(Y2)))
+        return fail(LDIT_EINVAL, "linear_mxfp8_train: misaligned operand");
+    int epi;
+    if (epilogue == LDIT_EPI_SCALE_RESID) {
+        if (!lam || !R) return fail(LDIT_EINVAL, "linear_mxfp8_train: the scale + residual epilogue needs lam and R");
+        epi = EPI_SCALE_RESID;
+    } else if (epilogue == LDIT_EPI_BIAS_GELU) {
+        if (!Ys || N % 32 || ldy % 32) return fail(LDIT_EINVAL, "linear_mxfp8_train: the GELU epilogue writes MX: Ys needed, N and ldy multiples of 32");
+        epi = EPI_BIAS_GELU;
+    } else {
+        return fail(LDIT_EINVAL, "linear_mxfp8_train: epilogue %d not available (scale + residual or bias + GELU)", epilogue);
+    }
+    return launch_gemm_mxfp8_train(X, (int)lda, Xs, W, Ws, static_cast<const float *>(bias), Y, (int)ldy, Ys, (int)M, (int)N, (int)K, epi,
+                                   static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), Ypre,
+                                   static_cast<const float *>(rowscale), Yd, static_cast<hipStream_t>(stream));
+}
+
 int ldit_attention_fwd_lse_bf16(const void *Q, const void *K, const void *V, void *O, void *lse, int64_t B, int64_t N, int64_t H,
                                 int64_t D, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, ldit_stream stream)
 {

@@ -71,12 +71,15 @@ __device__ __forceinline__ void glds16_sbase(const void *ubase, unsigned voff_by
 // issue (PMC: SQ_ACTIVE_INST_ANY x 4 waves = 1.07 of the SIMD's cycles; MFMA pipe 32 % busy).
 // OUT_MX (with OUT_FP8): MX codes + E8M0 block scales Os [rows, ldo / 32] (ldit.h, LDIT_MXFP8): a lane holds 16 columns of each
 // 32-column block dt of its query row, lane l ^ 32 the other 16 - one exchange gives the block amax.
-template <int KT, int NW, bool OUT_FP8, bool PRE, bool OUT_MX = false>
+// TR (with OUT_MX; mxfp8 train step): also Ob, the bf16 O before quantisation (what the bf16 kernel writes: the backward's
+// rowsum(dO o O) operand), and Od, the bf16 dequantised codes (the o_proj wgrad's operand); lse as the bf16 train kernel.
+template <int KT, int NW, bool OUT_FP8, bool PRE, bool OUT_MX = false, bool TR = false>
 __global__ void __launch_bounds__(NW * 64, KT == 2 ? 4 : 2) attention_bf16(const bf16_t *__restrict__ Q, const bf16_t *__restrict__ K,
                                                              const bf16_t *__restrict__ V, void *__restrict__ Ov,
                                                              int N, int H, int ldq, int ldk, int ldv, int ldo,
                                                              float scale, int nqg, const float *__restrict__ qscale,
-                                                             float *__restrict__ lse, unsigned char *__restrict__ Os)
+                                                             float *__restrict__ lse, unsigned char *__restrict__ Os,
+                                                             bf16_t *__restrict__ Ob, bf16_t *__restrict__ Od)
 {
     constexpr int KC = KT * 32, HALF = KC * KROWB, STAGE = 2 * HALF;     // keys per chunk; K image, then V image
     constexpr int PIECES = KC / 8, PPW = PIECES / NW;                    // 1-KB DMA pieces (8 keys) per operand, per wave
@@ -360,15 +363,24 @@ __global__ void __launch_bounds__(NW * 64, KT == 2 ? 4 : 2) attention_bf16(const
                 o[dt][e] *= inv;
                 amax = umax32(amax, __float_as_uint(o[dt][e]) & 0x7fffffffu);
             }
+            if (TR && qrow < N) {
+                bf16_t *ob = Ob + (tok0 + qrow) * ldo + head * 64 + dt * 32 + 4 * h;
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<bf16x4 *>(ob + 8 * g) = bf16x4{(bf16_t)o[dt][4 * g + 0], (bf16_t)o[dt][4 * g + 1],
+                                                                     (bf16_t)o[dt][4 * g + 2], (bf16_t)o[dt][4 * g + 3]};
+            }
             amax = umax32(amax, (unsigned)__shfl_xor((int)amax, 32, 64));
             const unsigned sb = mx_scale_byte(amax);
             const float qi = mx_inv_scale(sb);
             if (qrow < N) {
                 unsigned char *op = static_cast<unsigned char *>(Ov) + (tok0 + qrow) * ldo + head * 64 + dt * 32 + 4 * h;
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<unsigned *>(op + 8 * g) =
-                        pack_fp8x4(o[dt][4 * g + 0] * qi, o[dt][4 * g + 1] * qi, o[dt][4 * g + 2] * qi, o[dt][4 * g + 3] * qi);
+                for (int g = 0; g < 4; ++g) {
+                    const unsigned pk = pack_fp8x4(o[dt][4 * g + 0] * qi, o[dt][4 * g + 1] * qi, o[dt][4 * g + 2] * qi, o[dt][4 * g + 3] * qi);
+                    *reinterpret_cast<unsigned *>(op + 8 * g) = pk;
+                    if (TR) *reinterpret_cast<mx_bf16x4 *>(Od + (tok0 + qrow) * ldo + head * 64 + dt * 32 + 4 * h + 8 * g) = mx_dequant_bf16x4(pk, sb);
+                }
                 if (h == 0) Os[(tok0 + qrow) * (ldo >> 5) + ((head * 64 + dt * 32) >> 5)] = (unsigned char)sb;
             }
         }
@@ -397,9 +409,10 @@ __global__ void __launch_bounds__(NW * 64, KT == 2 ? 4 : 2) attention_bf16(const
 
 }  // namespace
 
-template <bool OUT_FP8, bool OUT_MX = false>
+template <bool OUT_FP8, bool OUT_MX = false, bool TR = false>
 static int launch_attn(const void *Q, const void *K, const void *V, void *O, int B, int N, int H, int D, int ldq, int ldk, int ldv,
-                       int ldo, float scale, const float *qscale, float *lse, hipStream_t stream, unsigned char *Os = nullptr)
+                       int ldo, float scale, const float *qscale, float *lse, hipStream_t stream, unsigned char *Os = nullptr,
+                       void *Ob = nullptr, void *Od = nullptr)
 {
     if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_bf16: empty problem");
     if (D != 64) return fail(LDIT_EUNSUPPORTED, "attention_bf16: head_dim=%d, only 64 is implemented", D);
@@ -415,7 +428,7 @@ static int launch_attn(const void *Q, const void *K, const void *V, void *O, int
         const int nqg = (nqt + nw - 1) / nw;
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * H * nqg)), dim3(nw * 64), lds, stream, static_cast<const bf16_t *>(Q),
                            static_cast<const bf16_t *>(K), static_cast<const bf16_t *>(V), O, N, H, ldq, ldk, ldv, ldo, scale, nqg,
-                           qscale, lse, Os);
+                           qscale, lse, Os, static_cast<bf16_t *>(Ob), static_cast<bf16_t *>(Od));
         return LDIT_OK;
     };
     auto go = [&](auto kern, int lds, std::atomic<unsigned long long> &attr_done) -> int { return go_nw(kern, NW, lds, attr_done); };
@@ -431,11 +444,11 @@ static int launch_attn(const void *Q, const void *K, const void *V, void *O, int
     static std::atomic<unsigned long long> set2p8{0}, set28{0};
     const int force_nw = diag().attn_bf16_nw;
     const bool wide = force_nw == 8 || (force_nw != 4 && nqt > 4 && nqt <= 8);
-    if (scale == 0.0f && wide) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, true, OUT_MX>, 8, 2 * 2 * 2 * 32 * KROWB, set2p8));
-    else if (scale == 0.0f) LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, true, OUT_MX>, 2 * 2 * 2 * 32 * KROWB, set2p));
-    else if (wide && !kt4) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, false, OUT_MX>, 8, 2 * 2 * 2 * 32 * KROWB, set28));
-    else if (kt4) LDIT_TRY_RC(go(attention_bf16<4, NW, OUT_FP8, false, OUT_MX>, 2 * 2 * 4 * 32 * KROWB, set4));
-    else LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, false, OUT_MX>, 2 * 2 * 2 * 32 * KROWB, set2));
+    if (scale == 0.0f && wide) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, true, OUT_MX, TR>, 8, 2 * 2 * 2 * 32 * KROWB, set2p8));
+    else if (scale == 0.0f) LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, true, OUT_MX, TR>, 2 * 2 * 2 * 32 * KROWB, set2p));
+    else if (wide && !kt4) LDIT_TRY_RC(go_nw(attention_bf16<2, 8, OUT_FP8, false, OUT_MX, TR>, 8, 2 * 2 * 2 * 32 * KROWB, set28));
+    else if (kt4) LDIT_TRY_RC(go(attention_bf16<4, NW, OUT_FP8, false, OUT_MX, TR>, 2 * 2 * 4 * 32 * KROWB, set4));
+    else LDIT_TRY_RC(go(attention_bf16<2, NW, OUT_FP8, false, OUT_MX, TR>, 2 * 2 * 2 * 32 * KROWB, set2));
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
 }
@@ -467,6 +480,17 @@ int launch_attention_bf16_mxout(const void *Q, const void *K, const void *V, voi
     if (!Os || (ldo & 31)) return fail(LDIT_EINVAL, "attention_bf16: MX output needs block scales and ldo %% 32 == 0");
     return launch_attn<true, true>(Q, K, V, O, B, N, H, D, ldq, ldk, ldv, ldo, scale, nullptr, nullptr, stream,
                                    static_cast<unsigned char *>(Os));
+}
+
+// mxfp8 train step: the MX output of launch_attention_bf16_mxout plus lse, the pre-quantisation bf16 O (Ob) and the dequantised
+// codes (Od), both bf16 [rows, ldo]
+int launch_attention_bf16_mxout_train(const void *Q, const void *K, const void *V, void *O, void *Os, float *lse, void *Ob, void *Od,
+                                      int B, int N, int H, int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t stream)
+{
+    if (!Os || !lse || !Ob || !Od || (ldo & 31)) return fail(LDIT_EINVAL, "attention_bf16: MX train output needs Os, lse, Ob, Od and ldo %% 32 == 0");
+    if ((reinterpret_cast<uintptr_t>(Ob) | reinterpret_cast<uintptr_t>(Od)) & 7u) return fail(LDIT_EINVAL, "attention_bf16: Ob / Od must be 8-byte aligned");
+    return launch_attn<true, true, true>(Q, K, V, O, B, N, H, D, ldq, ldk, ldv, ldo, scale, nullptr, lse, stream,
+                                         static_cast<unsigned char *>(Os), Ob, Od);
 }
 
 }  // namespace ldit

@@ -23,12 +23,13 @@ typedef __bf16 ln_bf16x4 __attribute__((ext_vector_type(4)));
 // y / *qscale (operand of the fp8 GEMMs, saturating); OUT = 3 / 4: written as 2 / 3 bf16 planes y ~= p0 + p1 (+ p2) side by
 // side in a row of 2 C / 3 C elements (operand of the split-fp32 GEMMs); OUT = 5: MX codes + E8M0 block scales Ys [rows, C / 32]
 // (ldit.h, LDIT_MXFP8; C % 32 == 0) - a 32-channel block is 8 consecutive lanes of one u, three exchanges give its amax;
-// statistics and affine stay fp32.
+// statistics and affine stay fp32.  OUT = 6 (mxfp8 train step): OUT = 5 plus Yd, the bf16 row of the dequantised codes
+// code 2^e (exact in bf16, ldit.h) - the operand of the wgrad that the straight-through backward multiplies.
 template <int VPL, int OUT, int RPW>
 __global__ void __launch_bounds__(256) layernorm_rows(const float *__restrict__ X, const float *__restrict__ g,
                                                       const float *__restrict__ b, void *__restrict__ Yv, int64_t rows,
                                                       int C, float eps, const float *__restrict__ qscale,
-                                                      unsigned char *__restrict__ Ys)
+                                                      unsigned char *__restrict__ Ys, __bf16 *__restrict__ Yd)
 {
     // RPW rows per wave, their loads all issued before the first reduction (round 3: with one 4-KB row per wave the kernel
     // sat at 4.8 TB/s - four 16-B loads in flight per lane; two rows double the bytes in flight per CU)
@@ -95,7 +96,7 @@ __global__ void __launch_bounds__(256) layernorm_rows(const float *__restrict__ 
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] -= (float)pk[e];
                     }
-                } else if (OUT == 5) {
+                } else if (OUT == 5 || OUT == 6) {
                     unsigned amax = 0;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) amax = umax32(amax, __float_as_uint(o[e]) & 0x7fffffffu);
@@ -103,9 +104,10 @@ __global__ void __launch_bounds__(256) layernorm_rows(const float *__restrict__ 
                     for (int sh = 1; sh < 8; sh <<= 1) amax = umax32(amax, (unsigned)__shfl_xor((int)amax, sh, 64));
                     const unsigned sb = mx_scale_byte(amax);
                     const float qi = mx_inv_scale(sb);
-                    reinterpret_cast<unsigned *>(static_cast<unsigned char *>(Yv) + row * C)[idx] =
-                        pack_fp8x4(o[0] * qi, o[1] * qi, o[2] * qi, o[3] * qi);
+                    const unsigned pk = pack_fp8x4(o[0] * qi, o[1] * qi, o[2] * qi, o[3] * qi);
+                    reinterpret_cast<unsigned *>(static_cast<unsigned char *>(Yv) + row * C)[idx] = pk;
                     if ((lane & 7) == 0) Ys[row * (C >> 5) + (idx >> 3)] = (unsigned char)sb;
+                    if (OUT == 6) reinterpret_cast<ln_bf16x4 *>(Yd + row * C)[idx] = mx_dequant_bf16x4(pk, sb);
                 } else if (OUT == 2) {
                     const float qi = 1.0f / qscale[0];
                     reinterpret_cast<unsigned *>(static_cast<unsigned char *>(Yv) + row * C)[idx] =
@@ -125,7 +127,7 @@ __global__ void __launch_bounds__(256) layernorm_rows(const float *__restrict__ 
 
 template <int OUT>
 static int launch_ln(const float *X, const float *g, const float *b, void *Y, int64_t rows, int C, float eps,
-                     const float *qscale, hipStream_t stream, unsigned char *Ys = nullptr)
+                     const float *qscale, hipStream_t stream, unsigned char *Ys = nullptr, __bf16 *Yd = nullptr)
 {
     if (rows <= 0 || C <= 0) return fail(LDIT_EINVAL, "layernorm: empty problem");
     if (!X || !g || !b || !Y) return fail(LDIT_EINVAL, "layernorm: null operand");
@@ -136,10 +138,10 @@ static int launch_ln(const float *X, const float *g, const float *b, void *Y, in
     const dim3 grid1((unsigned)((rows + 3) / 4)), grid2((unsigned)((rows + 7) / 8));
     // two rows per wave once there are enough rows to fill the machine twice over (serving sizes keep one row per wave)
     const bool two = rows >= 2 * 256 * 16;
-    if (C <= 256) hipLaunchKernelGGL((layernorm_rows<1, OUT, 1>), grid1, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys);
-    else if (C <= 1024 && two) hipLaunchKernelGGL((layernorm_rows<4, OUT, 2>), grid2, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys);
-    else if (C <= 1024) hipLaunchKernelGGL((layernorm_rows<4, OUT, 1>), grid1, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys);
-    else hipLaunchKernelGGL((layernorm_rows<16, OUT, 1>), grid1, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys);
+    if (C <= 256) hipLaunchKernelGGL((layernorm_rows<1, OUT, 1>), grid1, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys, Yd);
+    else if (C <= 1024 && two) hipLaunchKernelGGL((layernorm_rows<4, OUT, 2>), grid2, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys, Yd);
+    else if (C <= 1024) hipLaunchKernelGGL((layernorm_rows<4, OUT, 1>), grid1, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys, Yd);
+    else hipLaunchKernelGGL((layernorm_rows<16, OUT, 1>), grid1, block, 0, stream, X, g, b, Y, rows, C, eps, qscale, Ys, Yd);
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
 }
@@ -176,6 +178,14 @@ int launch_layernorm_mxout(const float *X, const float *g, const float *b, void 
 {
     if (!Ys || (C & 31)) return fail(LDIT_EINVAL, "layernorm: MX output needs block scales and C %% 32 == 0");
     return launch_ln<5>(X, g, b, Y, rows, C, eps, nullptr, stream, static_cast<unsigned char *>(Ys));
+}
+
+int launch_layernorm_mxout_train(const float *X, const float *g, const float *b, void *Y, void *Ys, void *Yd, int64_t rows, int C,
+                                 float eps, hipStream_t stream)
+{
+    if (!Ys || !Yd || (C & 31)) return fail(LDIT_EINVAL, "layernorm: MX output needs block scales, a bf16 copy and C %% 32 == 0");
+    if (reinterpret_cast<uintptr_t>(Yd) & 7u) return fail(LDIT_EINVAL, "layernorm: bf16 copy must be 8-byte aligned");
+    return launch_ln<6>(X, g, b, Y, rows, C, eps, nullptr, stream, static_cast<unsigned char *>(Ys), static_cast<__bf16 *>(Yd));
 }
 
 }  // namespace ldit

@@ -150,6 +150,23 @@ __device__ __forceinline__ unsigned mx_scale_byte(unsigned amax)
 // 2^-e for the scale byte b = e + 127: an exact power of two (b <= 253 for every finite fp32 amax); 1 for the NaN byte
 __device__ __forceinline__ float mx_inv_scale(unsigned b) { return b >= 254u ? 1.0f : __uint_as_float((254u - b) << 23); }
 
+// 2^e for the scale byte b = e + 127 (b = 0: 2^-127, a denormal; the NaN byte: NaN)
+__device__ __forceinline__ float mx_scale_value(unsigned b)
+{
+    return b == 0u ? __uint_as_float(0x00400000u) : (b == 255u ? __uint_as_float(0x7fc00000u) : __uint_as_float(b << 23));
+}
+
+typedef __bf16 mx_bf16x4 __attribute__((ext_vector_type(4)));
+
+// Dequantised MX values of the four e4m3 codes packed in `pk` (pack_fp8x4's layout) under scale byte b, as bf16: code 2^e is
+// exact in bf16 for every block exponent -124 <= e <= 119 (ldit.h, LDIT_MXFP8) - the operands of the straight-through backward.
+__device__ __forceinline__ mx_bf16x4 mx_dequant_bf16x4(unsigned pk, unsigned b)
+{
+    const float s = mx_scale_value(b);
+    return mx_bf16x4{(__bf16)(__builtin_amdgcn_cvt_f32_fp8((int)pk, 0) * s), (__bf16)(__builtin_amdgcn_cvt_f32_fp8((int)pk, 1) * s),
+                     (__bf16)(__builtin_amdgcn_cvt_f32_fp8((int)pk, 2) * s), (__bf16)(__builtin_amdgcn_cvt_f32_fp8((int)pk, 3) * s)};
+}
+
 // ---- GEMM ----------------------------------------------------------------------------------------------------
 enum AMode { A_ROWMAJOR = 0, A_PATCH = 1,
              A_CONV3 = 2 };   // fp32 general kernel only: implicit im2col of a 3x3 / pad 1 convolution over an NHWC map
@@ -284,6 +301,18 @@ int launch_gemm_fp8(const void *A, int lda, const void *W, const float *bias, vo
 int launch_gemm_mxfp8(const void *A, int lda, const void *As, const void *W, const void *Ws, const float *bias, void *Y, int ldy,
                       void *Ys, int M, int N, int K, int epi, const float *lam, const float *R, float *Y2, hipStream_t stream);
 int launch_quant_mx(const float *src, int64_t lds, void *codes, void *scales, int64_t rows, int K, float mul, hipStream_t stream);
+int launch_layernorm_mxout_train(const float *X, const float *g, const float *b, void *Y, void *Ys, void *Yd, int64_t rows, int C,
+                                 float eps, hipStream_t stream);
+int launch_attention_bf16_mxout_train(const void *Q, const void *K, const void *V, void *O, void *Os, float *lse, void *Ob, void *Od,
+                                      int B, int N, int H, int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t stream);
+int launch_gemm_mxfp8_train(const void *A, int lda, const void *As, const void *W, const void *Ws, const float *bias, void *Y, int ldy,
+                            void *Ys, int M, int N, int K, int epi, const float *lam, const float *R, float *Y2, void *Ypre,
+                            const float *rowscale, void *Yd, hipStream_t stream);
+int launch_scale_inplace(float *x, size_t n, float mul, hipStream_t stream);
+struct MxRequantSeg { int64_t start, n; int cols; int fold_rows; int64_t codes, scales; };
+int launch_adamw_mx(float *p, const float *g, float *m, float *v, int64_t e0, int64_t e1, bool update, float lr, float b1, float b2,
+                    float eps, float wd, int step, float grad_scale, void *mirror16, void *mx, const MxRequantSeg *segs, int nseg,
+                    int64_t bias_start, int64_t bias_dst, int C, float fold, hipStream_t stream);
 int launch_layernorm_mxout(const float *X, const float *g, const float *b, void *Y, void *Ys, int64_t rows, int C, float eps,
                            hipStream_t stream);
 int launch_attention_bf16_mxout(const void *Q, const void *K, const void *V, void *O, void *Os, int B, int N, int H, int D, int ldq,

@@ -67,7 +67,7 @@ class DiTEncoderOutput:
 
 
 class DiTEncoder(nn.Module):
-    def __init__(self, config: Optional[DiTConfig] = None, compute_dtype: str = "f32"):
+    def __init__(self, config: Optional[DiTConfig] = None, compute_dtype: str = "f32", qat: bool = False):
         """``compute_dtype``: arithmetic of the INFERENCE forward - ``"f32"`` (exact-fp32 MFMA, the parity path), ``"bf16"``
         (bf16 GEMM / attention operands with fp32 accumulation, residual stream, LayerNorm and softmax; parameters and
         returned taps stay fp32) or ``"fp8"`` (the four GEMMs of a layer on fp8 e4m3 operands with per-tensor scales,
@@ -86,7 +86,13 @@ class DiTEncoder(nn.Module):
         gradients / master parameters - what the reference's CUDA branch does with fp16 autocast + GradScaler
         (trainer.py:168,177-180; bf16 needs no loss scaling, a scaled loss passes through unharmed) and within the
         bf16 gate of its fp32 CPU branch (trainer.py:171-172; gradients rel-L2 <= 3e-2 per tensor, measured <= 1e-2:
-        tests/test_gpu_train.py).  The ``"fp8"`` and ``"mxfp8"`` builds are inference only.
+        tests/test_gpu_train.py).  The ``"fp8"`` and ``"mxfp8"`` builds are inference only, unless ``qat=True``.
+
+        ``qat=True`` (``"mxfp8"`` only): QUANTISATION-AWARE training of the mxfp8 build.  The training forward is the mxfp8
+        inference forward bit for bit (same kernels and tiles, on MX codes re-made from the fp32 master after every update); the
+        backward is its straight-through gradient (every MX quantiser taken as the identity) on the bf16 backward kernels, fed
+        the dequantised operands the forward multiplied (exact in bf16); master weights and gradients stay fp32 (include/ldit.h,
+        DESIGN.md section 16).  ``.eval()`` of such a model is the ordinary mxfp8 inference path.
 
         ACTIVATION: HF's ``hidden_act="gelu"`` is the exact erf-GELU.  The ``"f32"`` / ``"f32x3"`` / ``"f32x6"`` inference forwards
         evaluate it (< 1 ulp); the bf16 / fp8 inference forwards and EVERY training forward evaluate its logistic form
@@ -96,7 +102,11 @@ class DiTEncoder(nn.Module):
         super().__init__()
         if compute_dtype not in _DTYPES:
             raise ValueError(f"compute_dtype {compute_dtype!r}: expected 'f32', 'f32x3', 'f32x6', 'bf16', 'fp8' or 'mxfp8'")
+        if qat and compute_dtype != "mxfp8":
+            raise ValueError(f"qat=True is the quantisation-aware training of the 'mxfp8' build; compute_dtype {compute_dtype!r} has none "
+                             "(the 'fp8' build's calibrated scales would go stale after a weight update)")
         self.compute_dtype = compute_dtype
+        self.qat = bool(qat)
         self.config = config or DiTConfig()
         cfg = self.config
         Cc, Fm, p, ch = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size, cfg.num_channels
@@ -353,9 +363,10 @@ class DiTEncoder(nn.Module):
         ``layoutdit_amd.training`` (C ABI: ldit_vit_forward_train / ldit_vit_backward).  bf16 build only."""
         from .. import training
         cfg = self.config
-        if self.compute_dtype in ("fp8", "mxfp8"):
+        if self.compute_dtype in ("fp8", "mxfp8") and not self.qat:
             raise NotImplementedError(f"the {self.compute_dtype} build is inference only: train a DiTEncoder(..., compute_dtype='bf16' or 'f32') "
-                                      "(both train on bf16 MFMA operands with fp32 master parameters), or call .eval()")
+                                      "(both train on bf16 MFMA operands with fp32 master parameters), build the mxfp8 encoder with "
+                                      "qat=True (quantisation-aware training), or call .eval()")
         x = self._pixels_f32(pixel_values)
         L = cfg.num_hidden_layers
         drop = None
@@ -383,8 +394,9 @@ class DiTEncoder(nn.Module):
         cfg = self.config
         if cfg.drop_path_rate <= 0.0 or cfg.num_hidden_layers < 2:
             return False
-        if self.compute_dtype in ("fp8", "mxfp8"):
-            raise NotImplementedError(f"train mode with stochastic depth on the {self.compute_dtype} (inference-only) build: call .eval()")
+        if self.compute_dtype in ("fp8", "mxfp8") and not self.qat:
+            raise NotImplementedError(f"train mode with stochastic depth on the {self.compute_dtype} (inference-only) build: call .eval()"
+                                      + (" or build it with qat=True" if self.compute_dtype == "mxfp8" else ""))
         return True
 
     # ---- forward -------------------------------------------------------------------------------------------------

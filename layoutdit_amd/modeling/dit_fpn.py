@@ -161,9 +161,9 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 
 class DiTWithFPN(nn.Module):
     def __init__(self, pretrained: bool = False, config: Optional[DiTConfig] = None, checkpoint: Optional[str] = None,
-                 compute_dtype: str = "f32"):
+                 compute_dtype: str = "f32", qat: bool = False):
         super().__init__()
-        self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype)
+        self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype, qat=qat)
         self.fpn = _FPNParams([self.backbone.hidden_size] * 4, 256)
         self.out_channels = 256
         self._cache: Dict[int, tuple] = {}

@@ -442,6 +442,68 @@ def linear_mxfp8(x, weight, bias: Optional[torch.Tensor] = None, epilogue: int =
     return (out, ys) if ys is not None else out
 
 
+# ---- train variants of the mxfp8 forward's kernels (quantisation-aware training, DiTEncoder(qat=True)) ----------------------
+def layernorm_mxfp8_train(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-12):
+    """:func:`layernorm_mxfp8` plus the bf16 row of the dequantised codes: ``(codes, scales, dequantised bf16 [rows, C])``."""
+    lib = _lib.load()
+    x, gamma, beta = _req(x, "x"), _req(gamma, "gamma"), _req(beta, "beta")
+    C = x.shape[-1]
+    rows = x.numel() // C
+    codes = torch.empty((rows, C), device=x.device, dtype=torch.float8_e4m3fn)
+    scales = torch.empty((rows, C // 32), device=x.device, dtype=torch.uint8)
+    deq = torch.empty((rows, C), device=x.device, dtype=torch.bfloat16)
+    _launch(_device(x, gamma, beta), lib.ldit_layernorm_mxfp8_train, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(codes), _ptr(scales),
+            _ptr(deq), rows, C, float(eps))
+    return codes, scales, deq
+
+
+def linear_mxfp8_train(x, weight, bias: Optional[torch.Tensor] = None, epilogue: int = _lib.EPI_SCALE_RESID,
+                       lam: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                       rowscale: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None):
+    """:func:`linear_mxfp8` with the train step's side outputs.  Scale+residual: ``(Y fp32, Ypre bf16)`` - the branch output
+    before LayerScale; ``rowscale`` (fp32 [M]) multiplies ``lam`` per row.  GELU: ``((codes, scales), gelu' bf16, dequantised
+    output bf16)``."""
+    lib = _lib.load()
+    (xc, xs), (wc, ws) = x, weight
+    M, K = xc.shape
+    N = wc.shape[0]
+    for t, n in ((bias, "bias"), (lam, "lam"), (residual, "residual"), (rowscale, "rowscale"), (out2, "out2")):
+        if t is not None:
+            _req(t, n)
+    ypre = torch.empty((M, N), device=xc.device, dtype=torch.bfloat16)
+    ys = yd = None
+    if epilogue == _lib.EPI_BIAS_GELU:
+        out = torch.empty((M, N), device=xc.device, dtype=torch.float8_e4m3fn)
+        ys = torch.empty((M, N // 32), device=xc.device, dtype=torch.uint8)
+        yd = torch.empty((M, N), device=xc.device, dtype=torch.bfloat16)
+    else:
+        out = torch.empty((M, N), device=xc.device, dtype=torch.float32)
+    _launch(_device(xc, xs, wc, ws, bias, lam, residual, out2), lib.ldit_linear_mxfp8_train, _ptr(xc), K, _ptr(xs), _ptr(wc), _ptr(ws),
+            _ptr(bias), _ptr(out), N, _ptr(ys), M, N, K, epilogue, _ptr(lam), _ptr(residual), _ptr(out2), _ptr(ypre), _ptr(rowscale),
+            _ptr(yd))
+    return ((out, ys), ypre, yd) if ys is not None else (out, ypre)
+
+
+def attention_mxfp8_train(qkv: torch.Tensor, heads: int, scale: float = 0.0):
+    """Attention over a fused bf16 ``q|k|v`` [B, N, 3C] with the MX output of the mxfp8 build plus the train step's side outputs:
+    ``((codes, scales), lse fp32 [B, H, N], O bf16 before quantisation, dequantised O bf16)``.  ``scale == 0``: q arrives
+    pre-multiplied by ``D^-1/2 log2 e`` (the packed builds' fold)."""
+    lib = _lib.load()
+    if not isinstance(qkv, torch.Tensor) or not qkv.is_cuda or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous() or qkv.dim() != 3:
+        raise ValueError("qkv: expected a contiguous bf16 [B, N, 3C] GPU tensor")
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    codes = torch.empty((B * N, C), device=qkv.device, dtype=torch.float8_e4m3fn)
+    scales = torch.empty((B * N, C // 32), device=qkv.device, dtype=torch.uint8)
+    lse = torch.empty((B, heads, N), device=qkv.device, dtype=torch.float32)
+    ob = torch.empty((B * N, C), device=qkv.device, dtype=torch.bfloat16)
+    od = torch.empty((B * N, C), device=qkv.device, dtype=torch.bfloat16)
+    base = _ptr(qkv)
+    _launch(_device(qkv), lib.ldit_attention_mxfp8_train, base, base + 2 * C, base + 4 * C, _ptr(codes), _ptr(scales), _ptr(lse),
+            _ptr(ob), _ptr(od), B, N, heads, C // heads, 3 * C, 3 * C, 3 * C, C, float(scale))
+    return (codes, scales), lse, ob, od
+
+
 def attention_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: Optional[float] = None,
                    prescaled: bool = False) -> torch.Tensor:
     """bf16 fused attention; ``q, k, v``: bf16 [B, N, H*D] token-major (column slices of a fused tensor are fine)."""

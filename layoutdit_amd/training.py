@@ -58,7 +58,9 @@ class FlatState:
         self.encoder_ref = encoder
         lib = _lib.load()
         self.lcfg = encoder._lcfg(img_h, img_w, cfg.taps)
-        self.lcfg.dtype = _lib.DTYPE_BF16
+        # the bf16 build's train step, or the mxfp8 build's quantisation-aware one (DiTEncoder(qat=True))
+        self.mx = encoder.compute_dtype == "mxfp8" and getattr(encoder, "qat", False)
+        self.lcfg.dtype = _lib.DTYPE_MXFP8 if self.mx else _lib.DTYPE_BF16
         L, Cc = cfg.num_hidden_layers, cfg.hidden_size
         n_off = 4 + 14 * L + 1
         offs = (C.c_int64 * n_off)()
@@ -113,7 +115,11 @@ class FlatState:
                 view.copy_(p.data)
                 p.data = view
         # scratch of the library, sized once per batch size
-        self.packed = torch.empty(lib.ldit_train_mirror_bytes(C.byref(self.lcfg)), dtype=torch.uint8, device=self.device)   # bf16 mirror
+        # bf16 mirror (mxfp8: followed by the MX operands of the forward, include/ldit.h)
+        mirror = lib.ldit_train_mirror_bytes(C.byref(self.lcfg))
+        if mirror == 0:
+            raise _lib.LditError(_lib.LDIT_EUNSUPPORTED, lib.ldit_last_error().decode())
+        self.packed = torch.empty(mirror, dtype=torch.uint8, device=self.device)
         self._packed_version = None
         self._dirty = True
         self._ws: Dict[int, torch.Tensor] = {}
@@ -339,9 +345,10 @@ class TrainStep:
                  dtaps: Optional[Sequence[torch.Tensor]] = None, drop_path_rate: Optional[float] = None,
                  img_size: Optional[Tuple[int, int]] = None, force_comm: bool = False):
         cfg = encoder.config
-        if encoder.compute_dtype in ("fp8", "mxfp8"):
+        if encoder.compute_dtype == "fp8" or (encoder.compute_dtype == "mxfp8" and not getattr(encoder, "qat", False)):
             raise NotImplementedError(f"the {encoder.compute_dtype} build is inference only; the train step runs the 'bf16' and 'f32' builds on bf16 "
-                                      "MFMA operands with fp32 master parameters (BASELINE configs[2])")
+                                      "MFMA operands with fp32 master parameters (BASELINE configs[2]), and the 'mxfp8' build built with "
+                                      "qat=True (quantisation-aware training)")
         h, w = img_size or (cfg.image_size, cfg.image_size)
         self.encoder, self.rank = encoder, rank
         self.state = flat_state(encoder, h, w)
@@ -432,10 +439,16 @@ class TrainStep:
             mark("backward_done", 0)
         self.steps += 1
         with torch.cuda.device(st.device):
-            _lib.check(_lib.load().ldit_adamw_step(st.params.data_ptr(), st.grads.data_ptr(), self.exp_avg.data_ptr(),
-                                                   self.exp_avg_sq.data_ptr(), st.numel, self.lr, self.betas[0], self.betas[1],
-                                                   self.eps, self.wd, self.steps, 1.0 / self.world, st.packed.data_ptr(),
-                                                   torch.cuda.current_stream(st.device).cuda_stream))
+            stream = torch.cuda.current_stream(st.device).cuda_stream
+            if st.mx:       # the update fused with the re-quantisation of the forward's MX operands (the mirror = a fresh pack)
+                _lib.check(_lib.load().ldit_adamw_step_mxfp8(C.byref(st.lcfg), st.params.data_ptr(), st.grads.data_ptr(), self.exp_avg.data_ptr(),
+                                                             self.exp_avg_sq.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                                                             self.wd, self.steps, 1.0 / self.world, st.packed.data_ptr(), st.packed.numel(),
+                                                             stream))
+            else:
+                _lib.check(_lib.load().ldit_adamw_step(st.params.data_ptr(), st.grads.data_ptr(), self.exp_avg.data_ptr(),
+                                                       self.exp_avg_sq.data_ptr(), st.numel, self.lr, self.betas[0], self.betas[1],
+                                                       self.eps, self.wd, self.steps, 1.0 / self.world, st.packed.data_ptr(), stream))
         mark("adamw_done", None)
         st._packed_version = st.version()     # the update refreshed the bf16 mirror itself
         st._dirty = False
