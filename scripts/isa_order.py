@@ -8,12 +8,12 @@ import re
 import sys
 
 
-def kernels(asm_text):
-    """{mangled name: [instruction lines]} of a device-assembly file."""
+def kernels(asm_text, end="s_endpgm"):
+    """{mangled name: [instruction lines]} of a device-assembly file, each up to its first `end` (".Lfunc_end": the whole function)."""
     out = {}
     for f in re.split(r"\n(?=_Z\w+:)", asm_text)[1:]:
         name = f.split(":")[0]
-        lines = [re.sub(r"\s+", " ", l.split(";")[0]).strip() for l in f.split("s_endpgm")[0].splitlines()]
+        lines = [re.sub(r"\s+", " ", l.split(";")[0]).strip() for l in f.split(end)[0].splitlines()]
         out[name] = [l for l in lines if l and (not l.startswith(".") or l.startswith(".L"))]
     return out
 

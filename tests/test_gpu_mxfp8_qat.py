@@ -164,6 +164,43 @@ def test_linear_mxfp8_train_epilogues(M, N, K):
     assert np.abs(gp.float().cpu().numpy() - _gelu_grad_ref(acc)).max() < 2e-2
 
 
+@pytest.mark.parametrize("M,N,K", [(700, 768, 256), (600, 544, 384)])
+def test_linear_mxfp8_train_is_the_same_on_every_tile(M, N, K):
+    """The train GEMM on each forced tile (LDIT_GEMM_FP8_TILE = 0..4: 256 x 256, 256 x 128, 128 x 128, 192 x 256, 320 x 256; M ragged
+    for all of them, N = 544 also ragged in the columns): every tile walks K in the same order with the same instruction, so Y and the
+    side outputs (gelu', the dequantised output, Ypre) are bit-equal across tiles, and Y is bit-equal to the inference epilogue's."""
+    g = torch.Generator().manual_seed(M + N)
+    x = _mx_pair(torch.randn(M, K, generator=g).to(DEV))
+    w = _mx_pair((torch.randn(N, K, generator=g) / K ** 0.5).to(DEV))
+    bias = (0.1 * torch.randn(N, generator=g)).to(DEV)
+    lam = (0.5 + torch.rand(N, generator=g)).to(DEV)
+    R = torch.randn(M, N, generator=g).to(DEV)
+    rs = (torch.rand(M, generator=g) < 0.7).float().to(DEV) / 0.7
+    acc = _deq(x) @ _deq(w).T + bias.cpu().numpy().astype(np.float64)
+    c0, s0 = ops.linear_mxfp8(x, w, bias, _lib.EPI_BIAS_GELU)
+    y0 = ops.linear_mxfp8(x, w, bias, _lib.EPI_SCALE_RESID, lam=lam, residual=R)
+    first = None
+    try:
+        for tile in ("0", "1", "2", "3", "4"):
+            _lib.set_switch("LDIT_GEMM_FP8_TILE", tile)
+            (c1, s1), gp, yd = ops.linear_mxfp8_train(x, w, bias, _lib.EPI_BIAS_GELU)
+            y1, pre = ops.linear_mxfp8_train(x, w, bias, _lib.EPI_SCALE_RESID, lam=lam, residual=R)      # (tile 4: runs as 256 x 256)
+            y2, pre2 = ops.linear_mxfp8_train(x, w, bias, _lib.EPI_SCALE_RESID, lam=lam, residual=R, rowscale=rs)
+            assert torch.equal(c0.view(torch.uint8), c1.view(torch.uint8)) and torch.equal(s0, s1), tile
+            assert torch.equal(y0, y1) and torch.equal(pre, pre2), tile
+            assert np.array_equal(yd.float().cpu().numpy().astype(np.float64), _deq((c1, s1))), tile
+            got = [t.clone() for t in (gp, yd, pre, y2)]
+            if first is None:
+                first = got
+                assert np.abs(gp.float().cpu().numpy() - _gelu_grad_ref(acc)).max() < 2e-2
+                assert np.abs(pre.float().cpu().numpy() - acc).max() <= 1e-2 * max(1.0, np.abs(acc).max())
+            for name, t0, t1 in zip(("gelu'", "Yd", "Ypre", "Y with rowscale"), first, got):
+                bits = torch.int16 if t0.dtype == torch.bfloat16 else torch.int32
+                assert torch.equal(t0.view(bits), t1.view(bits)), (tile, name)
+    finally:
+        _lib.set_switch("LDIT_GEMM_FP8_TILE", None)
+
+
 @pytest.mark.parametrize("B,N,H", [(2, 197, 2), (1, 290, 12), (3, 17, 2)])
 def test_attention_mxfp8_train_outputs(B, N, H):
     C = 64 * H

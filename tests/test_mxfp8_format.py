@@ -180,6 +180,7 @@ def _kernels(asm: str):
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc (cross-compiles without a GPU)")
 def test_mx_gemm_instantiations_issue_the_vgpr_scaled_mfma(tmp_path):
+    """Every MX instantiation of the fp8 GEMM, inference and train step, issues the VGPR-scaled MFMA and uses no scratch memory."""
     out = os.path.join(str(tmp_path), "gemm_fp8.s")
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-Wno-unused-function",
                         "-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "layoutdit_amd", "csrc", "gemm_fp8.hip")],
@@ -187,13 +188,18 @@ def test_mx_gemm_instantiations_issue_the_vgpr_scaled_mfma(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     ks = _kernels(open(out).read())
     vgpr_scaled = re.compile(r"v_mfma_scale_f32_32x32x64_f8f6f4\s+\S+,\s*\S+,\s*\S+,\s*\S+,\s*v\d+,\s*v\d+")
-    mx = {n: t for n, t in ks.items() if re.search(r"gemm_fp8_(mfma|tail)I.*ELb1EEEv", n)}
-    plain = {n: t for n, t in ks.items() if re.search(r"gemm_fp8_(mfma|tail)I.*ELb0EEEv", n)}
+    # template arguments end in <MX, TR>; a TR (mxfp8 train step) instantiation is an MX one with its own argument struct
+    mx = {n: t for n, t in ks.items() if re.search(r"gemm_fp8_(mfma|tail)I.*ELb1ELb0EEEv", n)}
+    plain = {n: t for n, t in ks.items() if re.search(r"gemm_fp8_(mfma|tail)I.*ELb0ELb0EEEv", n)}
+    train = {n: t for n, t in ks.items() if re.search(r"gemm_fp8_(mfma|tail)I.*ELb1ELb1EEEv", n)}
+    assert len(mx) + len(plain) + len(train) == sum("gemm_fp8_" in n for n in ks), sorted(ks)
     # three epilogues x (five tiles + the tail)
     assert len(mx) == 3 * 6 - 1, sorted(mx)        # (the scale+residual epilogue has no 320-row tile)
     assert len(plain) >= 3 * 9 - 1, sorted(plain)
-    for n, t in mx.items():
-        assert vgpr_scaled.search(t), n
-        assert re.search(r"ScratchSize:\s*0\b", t), n
+    # the two train epilogues x (five tiles + the tail), no 320-row scale+residual tile
+    assert len(train) == 2 * 6 - 1, sorted(train)
     for n, t in plain.items():
         assert not vgpr_scaled.search(t), n
+    for n, t in {**mx, **train}.items():
+        assert vgpr_scaled.search(t), n
+        assert re.search(r"ScratchSize:\s*0\b", t), (n, re.search(r"ScratchSize:\s*\d+", t).group(0))
