@@ -506,6 +506,42 @@ int ldit_linear_bf16_tr(const void *A, int64_t lda, int32_t a_reduction_major, c
                         int64_t M, int64_t N, int64_t K, int32_t epilogue, const void *aux, int32_t splits, const void *zeros,
                         ldit_stream stream);
 
+/* ==== region proposals (torchvision RegionProposalNetwork in eval mode, which the reference runs inside FasterRCNN(...,
+ * rpn_anchor_generator = AnchorGenerator(...)), ref src/layoutdit/modeling/model.py:40-55): per-level top-k on the objectness
+ * logits, box decoding, clipping and the small-box filter, batched NMS, top-N per image - as three launches with fixed-size,
+ * padded results: no device-to-host synchronisation, no data-dependent shape, capturable.  Inference only.  The batched NMS keyed
+ * by class is also what the box head's postprocess_detections needs.  Additive to ABI 6.
+ *
+ * ldit_rpn_topk_f32: logits fp32 [B, Ntot], Ntot = sum of level_sizes (HOST int64[L], L <= 8, each 1 .. 16384; larger:
+ *   LDIT_EUNSUPPORTED).  For every image and level l, columns [Koff_l, Koff_l + k_l) of idx_out (int32 [B, Ksum], k_l = min(k, N_l),
+ *   Ksum = sum k_l) receive the positions on the concatenated axis of the level's k_l largest logits, in DESCENDING logit order, ties
+ *   by ASCENDING index; -inf sorts last and NaN after -inf (a total order: the result is unique).  One workgroup per (level, image).
+ * ldit_rpn_decode_f32: for each idx[b, j] gathers anchors [Ntot, 4] (x1, y1, x2, y2), deltas [B, Ntot, 4] (dx, dy, dw, dh) and the
+ *   logit, and decodes like BoxCoder(weights = (1, 1, 1, 1)):  w = x2 - x1, cx = x1 + w / 2;  dw, dh = min(., log(1000 / 16));
+ *   pcx = dx w + cx, pw = exp(dw) w;  box = pc -+ p / 2 (y alike), clamped to [0, img_w] x [0, img_h];  score = sigmoid(logit).
+ *   A candidate whose clamped width or height is not >= min_size, or whose score is not >= score_thresh, gets score -inf (its box is
+ *   still written), and so does an index outside [0, Ntot) (box 0).  boxes_out fp32 [B, Ksum, 4], scores_out fp32 [B, Ksum].
+ * ldit_nms_batched_f32: P independent problems, boxes fp32 [P, N, 4], scores fp32 [P, N], groups int32 [P, N] or NULL (one group);
+ *   N <= 8192 (larger: LDIT_EUNSUPPORTED).  The semantics of torchvision batched_nms(boxes, scores, groups, iou_thr)[:max_out]:
+ *     1. candidates whose score is -inf or NaN are dropped: never kept, never suppressing;
+ *     2. the others are ordered by descending score, ties by ascending input index;
+ *     3. greedily, a candidate is kept unless an ALREADY KEPT candidate of the SAME group has IoU > iou_thr with it;
+ *     4. keep (int32 [P, max_out]) = the first max_out kept input indices in that order, padded with -1; count (int32 [P]) = how many
+ *        (at most max_out); out_boxes [P, max_out, 4] / out_scores [P, max_out] (each optional) = the kept rows, padding rows zero.
+ *   IoU in fp32, exactly:  area = (x2 - x1) * (y2 - y1);  iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih alike;  inter = iw * ih;
+ *   iou = inter / ((areaA + areaB) - inter), no contraction, correctly rounded division;  suppressed iff iou > iou_thr.  Box
+ *   coordinates are expected finite.  One workgroup per problem, no atomics: bit-reproducible.
+ *   workspace: ldit_nms_workspace_bytes(P, N) bytes (currently 0: the kernel keeps its state in registers and LDS; NULL is then fine);
+ *   a shorter buffer is refused with LDIT_EWORKSPACE. */
+int ldit_rpn_topk_f32(const void *logits, const int64_t *level_sizes, int32_t L, int32_t B, int32_t k, void *idx_out, ldit_stream stream);
+int ldit_rpn_decode_f32(const void *logits, const void *deltas, const void *anchors, const void *idx, int32_t B, int64_t Ntot, int64_t Ksum,
+                        float img_h, float img_w, float min_size, float score_thresh, void *boxes_out, void *scores_out,
+                        ldit_stream stream);
+size_t ldit_nms_workspace_bytes(int64_t P, int64_t N);
+int ldit_nms_batched_f32(const void *boxes, const void *scores, const void *groups, int32_t P, int64_t N, float iou_thr, int32_t max_out,
+                         void *keep, void *count, void *out_boxes, void *out_scores, void *workspace, size_t workspace_bytes,
+                         ldit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,11 @@ SIGNATURES = {
                                       _i32, _vp]),
     "ldit_reduce_slabs_f32": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "ldit_linear_bf16_tr": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i32, _vp, _vp]),
+    # region proposals
+    "ldit_rpn_topk_f32": (C.c_int, [_vp, C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp]),
+    "ldit_rpn_decode_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    "ldit_nms_workspace_bytes": (_sz, [_i64, _i64]),
+    "ldit_nms_batched_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
@@ -156,6 +161,11 @@ def set_switch(name: str, value) -> None:
     else:
         os.environ[name] = str(value)
     load().ldit_debug_reload_env()
+
+
+def nms_workspace_bytes(problems: int, n: int) -> int:
+    """Scratch bytes ``ldit_nms_batched_f32`` wants for ``problems`` x ``n`` candidates (host arithmetic, no launch)."""
+    return int(load().ldit_nms_workspace_bytes(problems, n))
 
 
 def check(rc: int) -> None:

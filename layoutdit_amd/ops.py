@@ -650,3 +650,91 @@ def wgrad_bf16(a: torch.Tensor, w: torch.Tensor, K: int, w_row_offset: int = 0) 
     out = torch.empty((M, N), device=dev, dtype=torch.float32)
     _launch(_device(slabs), lib.ldit_reduce_slabs_f32, slabs.data_ptr(), out.data_ptr(), M * N, splits)
     return out
+
+
+# ---- region proposals (include/ldit.h "region proposals"; csrc/proposals.hip) ------------------------------------------------
+def _req_i32(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous int32 tensor on the GPU")
+    return t
+
+
+def rpn_topk(logits: torch.Tensor, level_sizes: Sequence[int], k: int) -> torch.Tensor:
+    """Per-level top-k of the objectness logits.  ``logits``: [B, Ntot] with the levels concatenated (``sum(level_sizes) ==
+    Ntot``).  Returns int32 [B, sum(min(k, n_l))]: for each level the positions on the concatenated axis of its largest logits,
+    descending, ties by ascending index.  No synchronisation."""
+    lib = _lib.load()
+    logits = _req(logits, "logits")
+    sizes = [int(n) for n in level_sizes]
+    if logits.dim() != 2 or sum(sizes) != logits.shape[1] or not sizes:
+        raise ValueError(f"logits {tuple(logits.shape)} is not [B, sum(level_sizes) = {sum(sizes)}]")
+    if k <= 0:
+        raise ValueError("k must be positive")
+    B = logits.shape[0]
+    idx = torch.empty((B, sum(min(k, n) for n in sizes)), device=logits.device, dtype=torch.int32)
+    _launch(_device(logits), lib.ldit_rpn_topk_f32, _ptr(logits), (C.c_int64 * len(sizes))(*sizes), len(sizes), B, int(k), _ptr(idx))
+    return idx
+
+
+def rpn_decode(logits: torch.Tensor, deltas: torch.Tensor, anchors: torch.Tensor, idx: torch.Tensor, image_size,
+               min_size: float = 1e-3, score_thresh: float = 0.0):
+    """Gather + ``BoxCoder(1, 1, 1, 1).decode`` + clip to ``image_size = (h, w)`` + sigmoid for the candidates ``idx`` [B, K] of
+    :func:`rpn_topk`.  ``logits`` [B, Ntot], ``deltas`` [B, Ntot, 4], ``anchors`` [Ntot, 4].  Returns ``boxes`` [B, K, 4] and
+    ``scores`` [B, K]; a candidate that is too small or scores below the threshold has score ``-inf``.  No synchronisation."""
+    lib = _lib.load()
+    logits, deltas, anchors, idx = _req(logits, "logits"), _req(deltas, "deltas"), _req(anchors, "anchors"), _req_i32(idx, "idx")
+    B, Ntot = logits.shape
+    if tuple(deltas.shape) != (B, Ntot, 4) or tuple(anchors.shape) != (Ntot, 4) or idx.dim() != 2 or idx.shape[0] != B:
+        raise ValueError(f"rpn_decode: logits {tuple(logits.shape)}, deltas {tuple(deltas.shape)}, anchors {tuple(anchors.shape)}, "
+                         f"idx {tuple(idx.shape)} do not fit together")
+    K = idx.shape[1]
+    boxes = torch.empty((B, K, 4), device=logits.device, dtype=torch.float32)
+    scores = torch.empty((B, K), device=logits.device, dtype=torch.float32)
+    _launch(_device(logits, deltas, anchors, idx), lib.ldit_rpn_decode_f32, _ptr(logits), _ptr(deltas), _ptr(anchors), _ptr(idx), B, Ntot, K,
+            float(image_size[0]), float(image_size[1]), float(min_size), float(score_thresh), _ptr(boxes), _ptr(scores))
+    return boxes, scores
+
+
+def batched_nms_padded(boxes: torch.Tensor, scores: torch.Tensor, groups: Optional[torch.Tensor], iou_threshold: float, max_out: int,
+                       gather: bool = True):
+    """``P`` independent NMS problems with fixed-size results.  ``boxes`` [P, N, 4], ``scores`` [P, N], ``groups`` int32 [P, N] or
+    None.  Returns ``(keep, count, out_boxes, out_scores)``: ``keep`` int32 [P, max_out] = the kept input indices in descending
+    score order padded with -1, ``count`` int32 [P], and (``gather``) the kept rows [P, max_out, 4] / [P, max_out] with zero
+    padding (else None).  Candidates with score ``-inf`` / NaN take no part.  No synchronisation."""
+    lib = _lib.load()
+    boxes, scores = _req(boxes, "boxes"), _req(scores, "scores")
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or tuple(scores.shape) != tuple(boxes.shape[:2]):
+        raise ValueError(f"batched_nms_padded: boxes {tuple(boxes.shape)} / scores {tuple(scores.shape)} are not [P, N, 4] / [P, N]")
+    if groups is not None and tuple(_req_i32(groups, "groups").shape) != tuple(scores.shape):
+        raise ValueError(f"groups {tuple(groups.shape)} does not match scores {tuple(scores.shape)}")
+    P, N = scores.shape
+    if P == 0 or N == 0 or max_out <= 0:
+        raise ValueError("batched_nms_padded: empty problem")
+    dev = boxes.device
+    keep = torch.empty((P, max_out), device=dev, dtype=torch.int32)
+    count = torch.empty((P,), device=dev, dtype=torch.int32)
+    out_boxes = torch.empty((P, max_out, 4), device=dev, dtype=torch.float32) if gather else None
+    out_scores = torch.empty((P, max_out), device=dev, dtype=torch.float32) if gather else None
+    need = _lib.nms_workspace_bytes(P, N)
+    ws = torch.empty(need, device=dev, dtype=torch.uint8) if need else None
+    _launch(_device(boxes, scores, groups), lib.ldit_nms_batched_f32, _ptr(boxes), _ptr(scores), _ptr(groups), P, N, float(iou_threshold),
+            int(max_out), _ptr(keep), _ptr(count), _ptr(out_boxes), _ptr(out_scores), _ptr(ws), need)
+    return keep, count, out_boxes, out_scores
+
+
+def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    """torchvision ``batched_nms``: ``boxes`` [N, 4], ``scores`` [N], ``idxs`` [N] (any integer type).  int64 indices of the kept
+    boxes, descending score.  Slices by the kept count, so it synchronises."""
+    if boxes.dim() != 2 or boxes.shape[0] == 0:
+        if boxes.dim() == 2:
+            return torch.empty((0,), dtype=torch.int64, device=boxes.device)
+        raise ValueError(f"boxes {tuple(boxes.shape)} is not [N, 4]")
+    N = boxes.shape[0]
+    groups = None if idxs is None else idxs.to(torch.int32).contiguous()[None]
+    keep, count, _, _ = batched_nms_padded(boxes[None], scores[None], groups, iou_threshold, N, gather=False)
+    return keep[0, :int(count[0])].to(torch.int64)
+
+
+def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    """torchvision ``nms``.  Synchronises (see :func:`batched_nms`)."""
+    return batched_nms(boxes, scores, None, iou_threshold)
