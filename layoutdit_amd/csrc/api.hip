@@ -83,8 +83,6 @@ DiagSwitches &switches()
 const DiagSwitches &diag() { return switches(); }
 void reload_diag() { switches() = read_switches(); }
 
-namespace {
-
 int embed(const Geo &g, const float *x, const float *pw, const float *pb, const float *cls, const float *pos, float *out,
           int batch, int img_h, int img_w, hipStream_t stream, Probe &probe)
 {
@@ -99,87 +97,212 @@ int embed(const Geo &g, const float *x, const float *pw, const float *pb, const 
     return LDIT_OK;
 }
 
-int linear(const float *X, int lda, const float *W, const float *bias, float *Y, int ldy, int M, int N, int K, int epi,
-           const float *lam, const float *R, float *Y2, hipStream_t stream, Probe &probe)
+// One HBM-bound pass rounds the batch to a bf16 im2col matrix `patches` [B P, planes Kp] (split-fp32 builds: the bf16 planes of the
+// pixels, the GEMM walks the plane products) and the bf16 MFMA GEMM multiplies it - 16x the fp32 matrix rate for 1.8 - 4.5 % of those
+// steps (the fp32 kernel took 266 us of the 14.6 ms ViT-L/512 step, 60 us of the 1.6 ms fp8 step).
+int embed_bf16(const Geo &g, const float *x, const ImgSrc *imgs, int planes, void *patches, const void *w16, const float *pb,
+               const float *cls, const float *pos, float *out, int batch, int img_h, int img_w, hipStream_t stream, Probe &probe)
 {
-    GemmArgs a{};
-    a.A = X; a.W = W; a.Y = Y; a.Y2 = Y2; a.bias = bias; a.lam = lam; a.R = R;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldy = ldy;
-    LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm(a, epi, A_ROWMAJOR, stream));
+    if (imgs)       // normalise + bilinear resize of the ragged list INSIDE this pass - no fp32 batch in between
+        LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows_images(imgs->images, imgs->half_in, imgs->heights, imgs->widths, batch, g.in_ch,
+                                                                imgs->mean, imgs->std, img_h, img_w, g.p, patches, stream, planes));
+    else
+        LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows(x, patches, batch, g.in_ch, img_h, img_w, g.p, stream, planes));
+    GemmExtra xe = split_segments(planes);
+    xe.pos = pos; xe.patches = g.P;
+    LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(patches, planes * g.Kp, w16, pb, out, g.C, batch * g.P, g.C, g.Kp, EPI_EMBED, nullptr,
+                                                    nullptr, nullptr, xe, stream));
+    LDIT_RUN(probe, LDIT_K_OTHER, launch_cls_rows(cls, pos, out, batch, g.T, g.C, stream));
     return LDIT_OK;
 }
 
-// the pixels as the detector holds them before its input transform: a ragged list of [in_ch, h_i, w_i] images in [0, 1]
-// (ldit_vit_forward_images: the transform is evaluated by the kernel that produces the patch-embedding operand)
-struct ImgSrc {
-    const void *const *images;
-    const int32_t *heights, *widths;
-    bool half_in;
-    float mean, std;
-};
+// LayerNorm of the fp32 residual stream into the build's operand format (Yd: mxfp8 training, the dequantised copy)
+int layernorm(Build b, const float *X, const float *gamma, const float *beta, const Operand &Y, void *Yd, int64_t rows, int C, float eps, hipStream_t stream)
+{
+    switch (b.dtype) {
+        case LDIT_F32: return launch_layernorm(X, gamma, beta, static_cast<float *>(Y.p), rows, C, eps, stream);
+        case LDIT_BF16: return launch_layernorm_bf16out(X, gamma, beta, Y.p, rows, C, eps, stream);
+        case LDIT_FP8: return launch_layernorm_fp8out(X, gamma, beta, Y.p, rows, C, eps, static_cast<const float *>(Y.s), stream);
+        case LDIT_MXFP8:
+            return b.train ? launch_layernorm_mxout_train(X, gamma, beta, Y.p, Y.s, Yd, rows, C, eps, stream)
+                           : launch_layernorm_mxout(X, gamma, beta, Y.p, Y.s, rows, C, eps, stream);
+        case LDIT_F32X3: case LDIT_F32X6: return launch_layernorm_splitout(X, gamma, beta, Y.p, rows, C, eps, Y.planes, stream);
+        default: return fail(LDIT_EUNSUPPORTED, "layernorm: no kernel for dtype %d", b.dtype);
+    }
+}
+
+// Y = epi(A . W^T + bias) on the build's operand format.  Y is an operand of the build when the next launch multiplies it (q|k|v, the
+// MLP hidden), else the fp32 residual stream.  ab_scale / out_inv_scale: host scales of ldit_linear_fp8 (the fp8 build reads A.s, Y.s).
+int linear(Build b, const Operand &A, const void *W, const void *Ws, const float *bias, const Operand &Y, int M, int N, int K, int epi,
+           const float *lam, const float *R, float *Y2, const Side &t, hipStream_t stream, float ab_scale, float out_inv_scale)
+{
+    switch (b.dtype) {
+        case LDIT_F32: {
+            GemmArgs a{};
+            a.A = static_cast<const float *>(A.p); a.W = static_cast<const float *>(W); a.Y = static_cast<float *>(Y.p); a.Y2 = Y2;
+            a.bias = bias; a.lam = lam; a.R = R;
+            a.M = M; a.N = N; a.K = K; a.lda = A.ld; a.ldy = Y.ld;
+            return launch_gemm(a, epi, A_ROWMAJOR, stream);
+        }
+        case LDIT_BF16: case LDIT_F32X3: case LDIT_F32X6: {
+            // split-fp32 builds: the bf16 MFMA over the plane products of the operands, fp32 accumulation; an output that is an operand
+            // leaves as planes [M, S N] (q pre-multiplied by scale log2 e at pack time: attention_planes.hip runs on the plane products too)
+            GemmExtra x = split_segments(A.planes);
+            x.Ypre = t.Ypre; x.rowscale = t.rowscale;
+            if (Y.planes) { x.nsplit_out = Y.planes; epi = epi == EPI_BIAS_GELU ? EPI_GELU_SPLIT : EPI_BIAS_SPLIT; }
+            return launch_gemm_bf16_ex(A.p, A.ld, W, bias, Y.p, Y.ld, M, N, K, epi, lam, R, Y2, x, stream);
+        }
+        case LDIT_FP8:
+            return launch_gemm_fp8(A.p, A.ld, W, bias, Y.p, Y.ld, M, N, K, epi, lam, R, Y2, ab_scale, out_inv_scale,
+                                   static_cast<const float *>(A.s), static_cast<const float *>(Ws), static_cast<const float *>(Y.s), stream);
+        case LDIT_MXFP8:
+            // the train kernel exists for the two epilogues that have side stores; q|k|v has none
+            if (b.train && epi != EPI_BIAS)
+                return launch_gemm_mxfp8_train(A.p, A.ld, A.s, W, Ws, bias, Y.p, Y.ld, Y.s, M, N, K, epi, lam, R, Y2, t.Ypre, t.rowscale, t.Yd, stream);
+            return launch_gemm_mxfp8(A.p, A.ld, A.s, W, Ws, bias, Y.p, Y.ld, Y.s, M, N, K, epi, lam, R, Y2, stream);
+        default: return fail(LDIT_EUNSUPPORTED, "linear: no kernel for dtype %d", b.dtype);
+    }
+}
+
+// O = softmax(Q K^T) V per head, heads merged token-major, into the build's operand format.  Split builds: ldq = row stride of the
+// q|k|v planes, plane_in = distance between a row's planes.  Training: lse, and (mxfp8) Ob / Od, the bf16 output and its dequantised codes.
+int attention(Build b, const void *Q, const void *K, const void *V, int ldq, int ldk, int ldv, const Operand &O, int B, int N, int H, int D,
+              float scale, hipStream_t stream, float *lse, void *Ob, void *Od, int plane_in)
+{
+    switch (b.dtype) {
+        case LDIT_F32:
+            return launch_attention(static_cast<const float *>(Q), static_cast<const float *>(K), static_cast<const float *>(V),
+                                    static_cast<float *>(O.p), B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream);
+        case LDIT_BF16:
+            return b.train ? launch_attention_bf16_lse(Q, K, V, O.p, lse, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream)
+                           : launch_attention_bf16(Q, K, V, O.p, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream);
+        case LDIT_FP8:
+            return launch_attention_bf16_fp8out(Q, K, V, O.p, B, N, H, D, ldq, ldk, ldv, O.ld, scale, static_cast<const float *>(O.s), stream);
+        case LDIT_MXFP8:
+            return b.train ? launch_attention_bf16_mxout_train(Q, K, V, O.p, O.s, lse, Ob, Od, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream)
+                           : launch_attention_bf16_mxout(Q, K, V, O.p, O.s, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream);
+        case LDIT_F32X3: case LDIT_F32X6:
+            return (O.planes == 2 ? launch_attention_planes2 : launch_attention_planes3)(Q, K, V, O.p, B, N, H, D, ldq, plane_in, O.ld, stream);
+        default: return fail(LDIT_EUNSUPPORTED, "attention: no kernel for dtype %d", b.dtype);
+    }
+}
+
+// The seven launches of one encoder layer.  The residual stream, LayerNorm statistics, softmax and every accumulation are fp32 in
+// every build; what the build decides is the format of the four GEMM operands and of q|k|v (Operand), behind the three dispatchers.
+int run_layer(Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe)
+{
+    const int M = batch * g.T, C = g.C, F = g.F;
+    const char *q = static_cast<const char *>(d.qkv.p), *k = q + d.qk_bytes, *v = k + d.qk_bytes;
+    const Operand mid = operand(d.h_mid, nullptr, C), out = operand(d.h_out, nullptr, C);
+    const PackedLayer &pv = *d.v, &pw = *d.w;
+    // y1 = LN1(h_in)                                                            TF:426
+    LDIT_RUN(probe, LDIT_K_LAYERNORM, layernorm(b, d.h_in, d.vec(pv.ln1_w), d.vec(pv.ln1_b), d.y1, d.y1d, M, C, eps, stream));
+    // qkv[:, 0:3C] = y1 . [Wq;Wk;Wv]^T + [bq;0;bv]                              TF:319-321
+    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.y1, d.mat(pw.wqkv), d.W + pw.sw_qkv, d.bqkv, d.qkv, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, Side{}, stream));
+    // o = softmax(q k^T / sqrt(D)) v, heads merged token-major                  TF:323-338
+    LDIT_RUN(probe, LDIT_K_ATTENTION, attention(b, q, k, v, d.qkv.ld, d.qkv.ld, d.qkv.ld, d.o, batch, g.T, g.H, g.D, d.scale, stream, d.lse, d.ob, d.od,
+                                                d.qkv.planes ? d.qkv.ld / d.qkv.planes : 0));
+    // h_mid = h_in + lam1 (.) (o . Wo^T + bo)                                   TF:339, 432-434
+    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.o, d.mat(pw.wo), d.W + pw.sw_o, d.vec(pv.bo), mid, M, C, C, EPI_SCALE_RESID, d.vec(pv.lam1), d.h_in, nullptr, d.s_o, stream));
+    // y2 = LN2(h_mid)                                                           TF:438
+    LDIT_RUN(probe, LDIT_K_LAYERNORM, layernorm(b, d.h_mid, d.vec(pv.ln2_w), d.vec(pv.ln2_b), d.y2, d.y2d, M, C, eps, stream));
+    // hid[:, 0:F] = gelu(y2 . W1^T + b1)                                        TF:353-354
+    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.y2, d.mat(pw.w1), d.W + pw.sw_1, d.vec(pv.b1), d.hid, M, F, C, EPI_BIAS_GELU, nullptr, nullptr, nullptr, d.s_fc1, stream));
+    // h_out = h_mid + lam2 (.) (hid . W2^T + b2)  (+ tap copy of the new hidden state)   TF:355, 440-442
+    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.hid, d.mat(pw.w2), d.W + pw.sw_2, d.vec(pv.b2), out, M, C, F, EPI_SCALE_RESID, d.vec(pv.lam2), d.h_mid, d.tap, d.s_fc2, stream));
+    return LDIT_OK;
+}
+
+namespace {
+
+// geometry of the stand-alone embedding entries (the caller has checked the divisions)
+Geo embed_geo(int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C)
+{
+    Geo g{};
+    g.C = (int)C; g.p = (int)p; g.in_ch = (int)in_ch; g.gh = (int)(img_h / p); g.gw = (int)(img_w / p);
+    g.P = g.gh * g.gw; g.T = g.P + 1; g.Kp = (int)(in_ch * p * p);
+    return g;
+}
+
+// ldit_embed_bf16 (the fp32 batch `x`) and ldit_embed_bf16_images (the image list `imgs`)
+int embed_bf16_entry(const char *name, const void *x, const ImgSrc *imgs, const void *patch_w_bf16, const void *patch_b, const void *cls,
+                     const void *pos, void *out, void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C,
+                     ldit_stream stream)
+{
+    if (B <= 0 || (imgs && B > 65535) || in_ch <= 0 || img_h <= 0 || img_w <= 0 || p <= 0 || C <= 0) return fail(LDIT_EINVAL, "%s: empty problem", name);
+    if (img_h % p || img_w % p)
+        return fail(LDIT_EINVAL, "%s: %s %lldx%lld is not a multiple of patch %lld", name, imgs ? "target" : "image", (long long)img_h, (long long)img_w, (long long)p);
+    if ((imgs ? !imgs->images || !imgs->heights || !imgs->widths : !x) || !patch_w_bf16 || !patch_b || !cls || !pos || !out || !scratch)
+        return fail(LDIT_EINVAL, "%s: null operand", name);
+    if (imgs && !(imgs->std > 0.0f)) return fail(LDIT_EINVAL, "%s: std must be positive", name);
+    if (!aligned16(out) || !aligned16(pos) || !aligned16(scratch) || !aligned16(patch_w_bf16) || (C & 3))
+        return fail(LDIT_EINVAL, "%s: out / pos / scratch / patch_w must be 16-byte aligned, C a multiple of 4", name);
+    const int64_t P = (img_h / p) * (img_w / p), Kp = in_ch * p * p;
+    if (Kp % 64) return fail(LDIT_EUNSUPPORTED, "%s: in_ch*p*p = %lld must be a multiple of 64", name, (long long)Kp);
+    if (B * in_ch * img_h * img_w >= (1ll << 31) || B * (P + 1) * C >= (1ll << 31) || B * P * Kp >= (1ll << 31))
+        return fail(LDIT_EUNSUPPORTED, "%s: operand exceeds 2^31 elements", name);
+    Probe probe;
+    return embed_bf16(embed_geo(in_ch, img_h, img_w, p, C), static_cast<const float *>(x), imgs, 1, scratch, patch_w_bf16,
+                      static_cast<const float *>(patch_b), static_cast<const float *>(cls), static_cast<const float *>(pos), static_cast<float *>(out),
+                      (int)B, (int)img_h, (int)img_w, static_cast<hipStream_t>(stream), probe);
+}
+
+// ldit_linear_f32 / ldit_linear_bf16
+int linear_entry(const char *name, int dtype, const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M, int64_t N,
+                 int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, ldit_stream stream)
+{
+    LDIT_TRY(check_linear(name, M, N, K, lda, ldy, Y, Y2, epilogue));
+    return linear(Build{dtype, false}, operand(X, nullptr, lda), W, nullptr, static_cast<const float *>(bias), operand(Y, nullptr, ldy), (int)M, (int)N,
+                  (int)K, epilogue, static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), Side{},
+                  static_cast<hipStream_t>(stream));
+}
+
+// ldit_attention_f32 / ldit_attention_bf16; qtile: query rows per workgroup of the kernel
+int attention_entry(const char *name, int dtype, int64_t qtile, const void *Q, const void *K, const void *V, void *O, int64_t B, int64_t N, int64_t H,
+                    int64_t D, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, ldit_stream stream)
+{
+    if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "%s: empty problem", name);
+    const int64_t ldmax = ldq > ldk ? (ldq > ldv ? ldq : ldv) : (ldk > ldv ? ldk : ldv);
+    if (B * N * (ldmax > ldo ? ldmax : ldo) >= (1ll << 31) || B * H * ((N + qtile - 1) / qtile) >= (1ll << 31))
+        return fail(LDIT_EUNSUPPORTED, "%s: operand exceeds 2^31 elements", name);
+    if (ldq < H * D || ldk < H * D || ldv < H * D || ldo < H * D) return fail(LDIT_EINVAL, "%s: row stride smaller than H*D", name);
+    return attention(Build{dtype, false}, Q, K, V, (int)ldq, (int)ldk, (int)ldv, operand(O, nullptr, ldo), (int)B, (int)N, (int)H, (int)D, scale,
+                     static_cast<hipStream_t>(stream));
+}
+
+int preprocess(bool half_in, const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch, float mean,
+               float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
+{
+    if (!images || !heights || !widths || !out) return fail(LDIT_EINVAL, "preprocess: null argument");
+    if (B <= 0 || B > 65535 || in_ch <= 0 || out_h <= 0 || out_w <= 0) return fail(LDIT_EINVAL, "preprocess: bad geometry");
+    if (!(std > 0.0f)) return fail(LDIT_EINVAL, "preprocess: std must be positive");
+    if ((int64_t)B * in_ch * out_h * out_w >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "preprocess: batch exceeds 2^31 elements");
+    return launch_preprocess(images, half_in, heights, widths, B, in_ch, mean, std, out_h, out_w, static_cast<float *>(out),
+                             static_cast<hipStream_t>(stream));
+}
 
 int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batch, void *const *tap_out, void *workspace,
             size_t ws_bytes, hipStream_t stream, Probe &probe, const ImgSrc *imgs = nullptr)
 {
     Geo g;
     LDIT_TRY(geometry(cfg, g));
-    if (batch <= 0) return fail(LDIT_EINVAL, "batch %d must be positive", batch);
-    if (!packed || (!x && !imgs) || !workspace) return fail(LDIT_EINVAL, "null packed / x / workspace pointer");
-    if (!aligned16(packed) || (x && !aligned16(x)) || !aligned16(workspace)) return fail(LDIT_EINVAL, "pointers must be 16-byte aligned");
-    if (imgs && (!imgs->images || !imgs->heights || !imgs->widths || !(imgs->std > 0.0f) || batch > 65535))
-        return fail(LDIT_EINVAL, "image list: null array, non-positive std or more than 65535 images");
-    if (cfg->n_taps && !tap_out) return fail(LDIT_EINVAL, "tap_out is null");
-    for (int i = 0; i < cfg->n_taps; ++i)
-        if (!tap_out[i] || !aligned16(tap_out[i])) return fail(LDIT_EINVAL, "tap_out[%d] is null or misaligned", i);
-    if ((int64_t)batch * g.T * (int64_t)(g.F > 3 * g.C ? g.F : 3 * g.C) >= (1ll << 31))
-        return fail(LDIT_EUNSUPPORTED, "batch %d: activation index space exceeds 2^31 elements, split the batch", batch);
-    const Workspace wm = workspace_map(g, batch, cfg->dtype);
+    LDIT_TRY(check_forward_args(cfg, g, batch, {packed, imgs ? packed : x, workspace}, "packed / x / workspace", imgs, tap_out));
+    const int dt = cfg->dtype, S = split_planes_of(dt);
+    const Workspace wm = workspace_map(g, batch, dt);
     if (ws_bytes < wm.total) return fail(LDIT_EWORKSPACE, "workspace %zu bytes < required %zu", ws_bytes, wm.total);
-    const PackedMap pm = packed_map(g, cfg->dtype);
+    const PackedMap pm = packed_map(g, dt);
     const char *P = static_cast<const char *>(packed);
     auto F32 = [&](size_t off) { return reinterpret_cast<const float *>(P + off); };
-    char *ws = static_cast<char *>(workspace);
+    char *ws = static_cast<char *>(workspace), *yb = ws + wm.y, *bb = ws + wm.big;
     float *h = reinterpret_cast<float *>(ws + wm.h);
-    float *y = reinterpret_cast<float *>(ws + wm.y);
-    float *big = reinterpret_cast<float *>(ws + wm.big);
     const int M = batch * g.T, C = g.C, F = g.F;
     const size_t act_bytes = (size_t)M * C * 4;
 
-    auto tap_for = [&](int hidden_idx) -> float * {
-        for (int i = 0; i < cfg->n_taps; ++i)
-            if (cfg->taps[i] == hidden_idx) return static_cast<float *>(tap_out[i]);
-        return nullptr;
-    };
-    auto extra_taps = [&](int hidden_idx, const float *src, float *first) -> int {
-        // the same hidden state requested more than once: copy to the remaining destinations
-        for (int i = 0; i < cfg->n_taps; ++i)
-            if (cfg->taps[i] == hidden_idx && tap_out[i] != first)
-                LDIT_HIP_CHECK(hipMemcpyAsync(tap_out[i], src, act_bytes, hipMemcpyDeviceToDevice, stream));
-        return LDIT_OK;
-    };
-
-    // embeddings (TF:153-176).  fp32 build: the fp32 GEMM gathers the NCHW pixels itself (LDS-DMA source addresses).  bf16 / fp8
-    // builds: one HBM-bound pass rounds the batch to a bf16 im2col matrix [B P, 3 p p] (into `big`, free until layer 0) and the
-    // bf16 MFMA GEMM multiplies it - 16x the fp32 matrix rate for 1.8 - 4.5 % of those steps (the fp32 kernel took 266 us of
-    // the 14.6 ms ViT-L/512 step, 60 us of the 1.6 ms fp8 step).
-    if (cfg->dtype != LDIT_F32 && g.Kp % 64 == 0) {
-        // (split-fp32 builds: the im2col rows hold the bf16 planes of the pixels, the GEMM walks the plane products)
-        const int Se = split_planes_of(cfg->dtype) ? split_planes_of(cfg->dtype) : 1;
-        char *patches = ws + wm.big;
-        if (imgs)       // normalise + bilinear resize of the ragged list INSIDE this pass - no fp32 batch in between
-            LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows_images(imgs->images, imgs->half_in, imgs->heights, imgs->widths, batch, g.in_ch,
-                                                                    imgs->mean, imgs->std, cfg->img_h, cfg->img_w, g.p, patches, stream, Se));
-        else
-            LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows(static_cast<const float *>(x), patches, batch, g.in_ch, cfg->img_h, cfg->img_w,
-                                                             g.p, stream, Se));
-        GemmExtra xe{};
-        xe.pos = F32(pm.pos); xe.patches = g.P;
-        if (Se == 2) { xe.nseg = 3; xe.seg_a = 0x001u; xe.seg_w = 0x010u; }
-        if (Se == 3) { xe.nseg = 6; xe.seg_a = 0x001012u; xe.seg_w = 0x010210u; }
-        xe.seg_inner = 1;
-        LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(patches, Se * g.Kp, P + pm.patch_w16, F32(pm.patch_b), h, C, batch * g.P, C, g.Kp,
-                                                        EPI_EMBED, nullptr, nullptr, nullptr, xe, stream));
-        LDIT_RUN(probe, LDIT_K_OTHER, launch_cls_rows(F32(pm.cls), F32(pm.pos), h, batch, g.T, C, stream));
+    // embeddings (TF:153-176).  fp32 build: the fp32 GEMM gathers the NCHW pixels itself (LDS-DMA source addresses).  Every other
+    // build: the bf16 GEMM on the im2col of the batch (into `big`, free until layer 0).
+    if (dt != LDIT_F32 && g.Kp % 64 == 0) {
+        LDIT_TRY(embed_bf16(g, static_cast<const float *>(x), imgs, S ? S : 1, bb, P + pm.patch_w16, F32(pm.patch_b), F32(pm.cls), F32(pm.pos), h,
+                            batch, cfg->img_h, cfg->img_w, stream, probe));
     } else {
         const float *xp = static_cast<const float *>(x);
         if (imgs) {
@@ -187,127 +310,37 @@ int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batc
             // first (same statement, image_blend.h), into `big` - free until layer 0
             const size_t pix = (size_t)batch * g.in_ch * cfg->img_h * cfg->img_w * 4;
             if (wm.total - wm.big < pix) return fail(LDIT_EUNSUPPORTED, "image list: the pixel batch does not fit the workspace of this geometry");
+            xp = reinterpret_cast<const float *>(bb);
             LDIT_RUN(probe, LDIT_K_OTHER, launch_preprocess(imgs->images, imgs->half_in, imgs->heights, imgs->widths, batch, g.in_ch, imgs->mean,
-                                                           imgs->std, cfg->img_h, cfg->img_w, big, stream));
-            xp = big;
+                                                           imgs->std, cfg->img_h, cfg->img_w, reinterpret_cast<float *>(bb), stream));
         }
         LDIT_TRY(embed(g, xp, F32(pm.patch_w), F32(pm.patch_b), F32(pm.cls), F32(pm.pos), h, batch, cfg->img_h, cfg->img_w, stream, probe));
     }
-    if (float *t0 = tap_for(0)) {
-        LDIT_HIP_CHECK(hipMemcpyAsync(t0, h, act_bytes, hipMemcpyDeviceToDevice, stream));
-        LDIT_TRY(extra_taps(0, h, t0));
-    }
+    LDIT_TRY(copy_taps(cfg, tap_out, 0, h, nullptr, act_bytes, stream));
 
-    const float scale = 1.0f / sqrtf((float)g.D);
-    const bool bf16 = cfg->dtype == LDIT_BF16, fp8 = cfg->dtype == LDIT_FP8, mx = cfg->dtype == LDIT_MXFP8;
-    const int S = split_planes_of(cfg->dtype);
-    // split-fp32 builds: the plane products of one output element, SMALLEST FIRST (their sum is formed at its own magnitude
-    // before the leading p0.q0 term arrives): bf16x3 = a1 w0 + a0 w1 + a0 w0; six products = a2 w0 + a1 w1 + a0 w2 + a1 w0 + a0 w1 + a0 w0
-    GemmExtra xs{};
-    if (S == 2) { xs.nseg = 3; xs.seg_a = 0x001u; xs.seg_w = 0x010u; }
-    if (S == 3) { xs.nseg = 6; xs.seg_a = 0x001012u; xs.seg_w = 0x010210u; }
-    // per 64-deep k-tile (k-tile outermost): the operand tiles one product has just pulled through L2 serve the next one - 1-5 % on the
-    // q|k|v and fc1 GEMMs against whole-K segments (profiles/r03_planes_segment_order.txt), never slower
-    xs.seg_inner = 1;
+    // The buffers in the build's format.  y: LayerNorm output, then attention output; big: q|k|v, later the MLP hidden (never live together).
+    // bf16, fp8, mxfp8: q|k|v bf16 for the bf16 attention kernel, whose epilogue - like LayerNorm's and the GELU's - writes bf16, e4m3 codes on
+    // the calibrated per-tensor scales, or e4m3 codes [M, K] then one E8M0 scale per 32 channels [M, K / 32].  Split fp32: S bf16 planes per row.
+    const bool mx = dt == LDIT_MXFP8;
+    const int Sp = S ? S : 1;
+    Layer d{};
+    d.h_in = d.h_mid = d.h_out = h;
+    d.V = d.W = P; d.div = 1;
+    d.y1 = d.o = d.y2 = operand(yb, mx ? yb + (size_t)M * C : nullptr, Sp * C, S);
+    d.qkv = operand(bb, nullptr, Sp * 3 * C, S);
+    d.hid = operand(bb, mx ? bb + (size_t)M * F : nullptr, Sp * F, S);
+    d.qk_bytes = (size_t)(dt == LDIT_F32 ? 4 : 2) * C;
+    d.scale = dt == LDIT_F32 ? 1.0f / sqrtf((float)g.D) : 0.0f /* q pre-scaled at pack time */;
     for (int l = 0; l < g.L; ++l) {
         const PackedLayer &pl = pm.layer[l];
-        float *tap = tap_for(l + 1);
-        if (S) {
-            // fp32 forward on split operands (ldit.h, LDIT_F32X3 / LDIT_F32X6): every GEMM on the bf16 MFMA over the plane products of
-            // its operands, fp32 accumulation; LayerNorm, attention (the fp32 kernel), erf-GELU, LayerScale + residual in fp32.
-            char *ys = ws + wm.y, *bb = ws + wm.big;
-            GemmExtra xg = xs;
-            xg.nsplit_out = S;
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_splitout(h, F32(pl.ln1_w), F32(pl.ln1_b), ys, M, C, cfg->ln_eps, S, stream));
-            {
-                // q|k|v leave their GEMM as bf16 planes [M, S * 3C] (q pre-multiplied by scale log2 e at pack time) and the attention
-                // runs on the plane products too (attention_planes.hip: 3 products for two planes, 6 for three)
-                const __bf16 *qp = reinterpret_cast<const __bf16 *>(bb);
-                LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(ys, S * C, P + pl.wqkv, F32(pl.bqkv), bb, S * 3 * C, M, 3 * C, C, EPI_BIAS_SPLIT,
-                                                                nullptr, nullptr, nullptr, xg, stream));
-                LDIT_RUN(probe, LDIT_K_ATTENTION,
-                         (S == 2 ? launch_attention_planes2 : launch_attention_planes3)(qp, qp + C, qp + 2 * C, ys, batch, g.T, g.H, g.D,
-                                                                                        S * 3 * C, 3 * C, S * C, stream));
-            }
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(ys, S * C, P + pl.wo, F32(pl.bo), h, C, M, C, C, EPI_SCALE_RESID, F32(pl.lam1), h,
-                                                            nullptr, xs, stream));
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_splitout(h, F32(pl.ln2_w), F32(pl.ln2_b), ys, M, C, cfg->ln_eps, S, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(ys, S * C, P + pl.w1, F32(pl.b1), bb, S * F, M, F, C, EPI_GELU_SPLIT, nullptr, nullptr,
-                                                            nullptr, xg, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(bb, S * F, P + pl.w2, F32(pl.b2), h, C, M, C, F, EPI_SCALE_RESID, F32(pl.lam2), h,
-                                                            tap, xs, stream));
-        } else if (fp8) {
-            // fp8 build: LayerNorm, the attention epilogue and the GELU epilogue quantise straight to e4m3 with the
-            // calibrated per-tensor scales; q|k|v leave their GEMM as bf16 for the bf16 attention kernel.
-            char *y8 = ws + wm.y, *bb = ws + wm.big;
+        d.v = d.w = &pl; d.bqkv = F32(pl.bqkv);
+        if (dt == LDIT_FP8) {     // slots 0, 2, 4, 6 of the layer's scale block
             const float *sc = F32(pl.scales);
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_fp8out(h, F32(pl.ln1_w), F32(pl.ln1_b), y8, M, C, cfg->ln_eps, sc + 0, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_fp8(y8, C, P + pl.wqkv, F32(pl.bqkv), bb, 3 * C, M, 3 * C, C, EPI_BIAS, nullptr,
-                                                        nullptr, nullptr, 0.f, 0.f, sc + 0, F32(pl.sw_qkv), nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_ATTENTION,
-                     launch_attention_bf16_fp8out(bb, bb + 2 * (size_t)C, bb + 4 * (size_t)C, y8, batch, g.T, g.H, g.D, 3 * C, 3 * C,
-                                                  3 * C, C, 0.0f /* q pre-scaled at pack time */, sc + 2, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_fp8(y8, C, P + pl.wo, F32(pl.bo), h, C, M, C, C, EPI_SCALE_RESID, F32(pl.lam1), h,
-                                                        nullptr, 0.f, 0.f, sc + 2, F32(pl.sw_o), nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_fp8out(h, F32(pl.ln2_w), F32(pl.ln2_b), y8, M, C, cfg->ln_eps, sc + 4, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_fp8(y8, C, P + pl.w1, F32(pl.b1), bb, F, M, F, C, EPI_BIAS_GELU, nullptr, nullptr,
-                                                        nullptr, 0.f, 0.f, sc + 4, F32(pl.sw_1), sc + 6, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_fp8(bb, F, P + pl.w2, F32(pl.b2), h, C, M, C, F, EPI_SCALE_RESID, F32(pl.lam2), h,
-                                                        tap, 0.f, 0.f, sc + 6, F32(pl.sw_2), nullptr, stream));
-        } else if (mx) {
-            // mxfp8 build: the fp8 build's dataflow on MX operands - LayerNorm, the attention epilogue and the GELU epilogue
-            // write e4m3 codes + one E8M0 scale per 32 channels, each block scaled from its own amax; no calibrated state.
-            // y: codes [M, C] then scales [M, C / 32]; big: bf16 q|k|v, later the MLP hidden's codes [M, F] then scales [M, F / 32]
-            char *y8 = ws + wm.y, *bb = ws + wm.big;
-            char *ys = y8 + (size_t)M * C, *bs = bb + (size_t)M * F;
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout(h, F32(pl.ln1_w), F32(pl.ln1_b), y8, ys, M, C, cfg->ln_eps, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, P + pl.wqkv, P + pl.sw_qkv, F32(pl.bqkv), bb, 3 * C, nullptr, M, 3 * C, C,
-                                                          EPI_BIAS, nullptr, nullptr, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_ATTENTION,
-                     launch_attention_bf16_mxout(bb, bb + 2 * (size_t)C, bb + 4 * (size_t)C, y8, ys, batch, g.T, g.H, g.D, 3 * C, 3 * C,
-                                                 3 * C, C, 0.0f /* q pre-scaled at pack time */, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, P + pl.wo, P + pl.sw_o, F32(pl.bo), h, C, nullptr, M, C, C,
-                                                          EPI_SCALE_RESID, F32(pl.lam1), h, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout(h, F32(pl.ln2_w), F32(pl.ln2_b), y8, ys, M, C, cfg->ln_eps, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, P + pl.w1, P + pl.sw_1, F32(pl.b1), bb, F, bs, M, F, C,
-                                                          EPI_BIAS_GELU, nullptr, nullptr, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(bb, F, bs, P + pl.w2, P + pl.sw_2, F32(pl.b2), h, C, nullptr, M, C, F,
-                                                          EPI_SCALE_RESID, F32(pl.lam2), h, tap, stream));
-        } else if (!bf16) {
-            // y = LN1(h)                                                               TF:426
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm(h, F32(pl.ln1_w), F32(pl.ln1_b), y, M, C, cfg->ln_eps, stream));
-            // big[:, 0:3C] = y . [Wq;Wk;Wv]^T + [bq;0;bv]                               TF:319-321
-            LDIT_TRY(linear(y, C, F32(pl.wqkv), F32(pl.bqkv), big, 3 * C, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, stream, probe));
-            // y = softmax(q k^T / sqrt(D)) v, heads merged token-major                 TF:323-338
-            LDIT_RUN(probe, LDIT_K_ATTENTION,
-                     launch_attention(big, big + C, big + 2 * C, y, batch, g.T, g.H, g.D, 3 * C, 3 * C, 3 * C, C, scale, stream));
-            // h += lam1 (.) (y . Wo^T + bo)                                             TF:339, 432-434
-            LDIT_TRY(linear(y, C, F32(pl.wo), F32(pl.bo), h, C, M, C, C, EPI_SCALE_RESID, F32(pl.lam1), h, nullptr, stream, probe));
-            // y = LN2(h)                                                               TF:438
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm(h, F32(pl.ln2_w), F32(pl.ln2_b), y, M, C, cfg->ln_eps, stream));
-            // big[:, 0:F] = gelu(y . W1^T + b1)                                         TF:353-354
-            LDIT_TRY(linear(y, C, F32(pl.w1), F32(pl.b1), big, F, M, F, C, EPI_BIAS_GELU, nullptr, nullptr, nullptr, stream, probe));
-            // h += lam2 (.) (big . W2^T + b2)  (+ tap copy of the new hidden state)      TF:355, 440-442
-            LDIT_TRY(linear(big, F, F32(pl.w2), F32(pl.b2), h, C, M, C, F, EPI_SCALE_RESID, F32(pl.lam2), h, tap, stream, probe));
-        } else {
-            // bf16 build: residual stream h, LayerNorm statistics, softmax and every accumulation stay fp32; the GEMM /
-            // attention operands (LN output, q|k|v, attention output, MLP hidden, the four weight matrices) are bf16.
-            char *yb = ws + wm.y, *bb = ws + wm.big;                 // bf16 buffers
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_bf16out(h, F32(pl.ln1_w), F32(pl.ln1_b), yb, M, C, cfg->ln_eps, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16(yb, C, P + pl.wqkv, F32(pl.bqkv), bb, 3 * C, M, 3 * C, C, EPI_BIAS,
-                                                         nullptr, nullptr, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_ATTENTION,
-                     launch_attention_bf16(bb, bb + 2 * (size_t)C, bb + 4 * (size_t)C, yb, batch, g.T, g.H, g.D, 3 * C, 3 * C, 3 * C,
-                                           C, 0.0f /* q pre-scaled at pack time */, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16(yb, C, P + pl.wo, F32(pl.bo), h, C, M, C, C, EPI_SCALE_RESID, F32(pl.lam1),
-                                                         h, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_bf16out(h, F32(pl.ln2_w), F32(pl.ln2_b), yb, M, C, cfg->ln_eps, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16(yb, C, P + pl.w1, F32(pl.b1), bb, F, M, F, C, EPI_BIAS_GELU, nullptr,
-                                                         nullptr, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16(bb, F, P + pl.w2, F32(pl.b2), h, C, M, C, F, EPI_SCALE_RESID, F32(pl.lam2),
-                                                         h, tap, stream));
+            d.y1.s = const_cast<float *>(sc); d.o.s = const_cast<float *>(sc + 2); d.y2.s = const_cast<float *>(sc + 4); d.hid.s = const_cast<float *>(sc + 6);
         }
-        if (tap) LDIT_TRY(extra_taps(l + 1, h, tap));
+        d.tap = tap_of(cfg, tap_out, l + 1);
+        LDIT_TRY(run_layer(Build{dt, false}, g, batch, cfg->ln_eps, d, stream, probe));
+        if (d.tap) LDIT_TRY(copy_taps(cfg, tap_out, l + 1, h, d.tap, act_bytes, stream));
     }
     return LDIT_OK;
 }
@@ -379,7 +412,7 @@ int ldit_pack_weights(const ldit_cfg *cfg, const ldit_weights *w, void *packed, 
         return launch_cvt_bf16(static_cast<const float *>(src), P + off + elt_off * 2, rows * cols, stream, mul);
     };
     // (the split-fp32 builds too: their attention runs on bf16-plane operands with exp2-domain scores, attention_planes.hip)
-    const float qfold = (bf16 || fp8 || mx || split_planes_of(cfg->dtype)) ? (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f : 1.0f;
+    const float qfold = cfg->dtype != LDIT_F32 ? qfold_of(g) : 1.0f;
     const size_t C = g.C, F = g.F;
     LDIT_TRY(put(pm.patch_w, w->patch_w, C * g.Kp, "patch_w"));
     if (bf16 || fp8 || mx) {
@@ -477,15 +510,7 @@ int ldit_vit_forward_timed(const ldit_cfg *cfg, const void *packed, const void *
 int ldit_linear_f32(const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M,
                     int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, ldit_stream stream)
 {
-    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear: empty problem");
-    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear: operand exceeds 2^31 elements");
-    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear: bad leading dimension");
-    if (!Y || !aligned16(Y) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear: output null or misaligned");
-    if (epilogue < LDIT_EPI_BIAS || epilogue > LDIT_EPI_SCALE_RESID) return fail(LDIT_EINVAL, "linear: unknown epilogue %d", epilogue);
-    Probe probe;
-    return linear(static_cast<const float *>(X), (int)lda, static_cast<const float *>(W), static_cast<const float *>(bias),
-                  static_cast<float *>(Y), (int)ldy, (int)M, (int)N, (int)K, epilogue, static_cast<const float *>(lam),
-                  static_cast<const float *>(R), static_cast<float *>(Y2), static_cast<hipStream_t>(stream), probe);
+    return linear_entry("linear", LDIT_F32, X, lda, W, bias, Y, ldy, M, N, K, epilogue, lam, R, Y2, stream);
 }
 
 int ldit_layernorm_f32(const void *X, const void *gamma, const void *beta, void *Y, int64_t rows, int64_t C, float eps,
@@ -499,14 +524,7 @@ int ldit_layernorm_f32(const void *X, const void *gamma, const void *beta, void 
 int ldit_attention_f32(const void *Q, const void *K, const void *V, void *O, int64_t B, int64_t N, int64_t H, int64_t D,
                        int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, ldit_stream stream)
 {
-    if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention: empty problem");
-    const int64_t ldmax = ldq > ldk ? (ldq > ldv ? ldq : ldv) : (ldk > ldv ? ldk : ldv);
-    if (B * N * (ldmax > ldo ? ldmax : ldo) >= (1ll << 31) || B * H * ((N + 127) / 128) >= (1ll << 31))
-        return fail(LDIT_EUNSUPPORTED, "attention: operand exceeds 2^31 elements");
-    if (ldq < H * D || ldk < H * D || ldv < H * D || ldo < H * D) return fail(LDIT_EINVAL, "attention: row stride smaller than H*D");
-    return launch_attention(static_cast<const float *>(Q), static_cast<const float *>(K), static_cast<const float *>(V),
-                            static_cast<float *>(O), (int)B, (int)N, (int)H, (int)D, (int)ldq, (int)ldk, (int)ldv, (int)ldo,
-                            scale, static_cast<hipStream_t>(stream));
+    return attention_entry("attention", LDIT_F32, 128, Q, K, V, O, B, N, H, D, ldq, ldk, ldv, ldo, scale, stream);
 }
 
 int ldit_embed_f32(const void *x, const void *patch_w, const void *patch_b, const void *cls, const void *pos, void *out,
@@ -516,9 +534,7 @@ int ldit_embed_f32(const void *x, const void *patch_w, const void *patch_b, cons
     if (img_h % p || img_w % p) return fail(LDIT_EINVAL, "embed: image %lldx%lld is not a multiple of patch %lld", (long long)img_h, (long long)img_w, (long long)p);
     if (!x || !patch_w || !patch_b || !cls || !pos || !out) return fail(LDIT_EINVAL, "embed: null operand");
     if (!aligned16(out) || !aligned16(pos) || (C & 3)) return fail(LDIT_EINVAL, "embed: out / pos must be 16-byte aligned, C a multiple of 4");
-    Geo g{};
-    g.C = (int)C; g.p = (int)p; g.in_ch = (int)in_ch; g.gh = (int)(img_h / p); g.gw = (int)(img_w / p);
-    g.P = g.gh * g.gw; g.T = g.P + 1; g.Kp = (int)(in_ch * p * p);
+    const Geo g = embed_geo(in_ch, img_h, img_w, p, C);
     if (B * in_ch * img_h * img_w >= (1ll << 31) || B * g.T * C >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "embed: operand exceeds 2^31 elements");
     Probe probe;
     return embed(g, static_cast<const float *>(x), static_cast<const float *>(patch_w), static_cast<const float *>(patch_b),
@@ -533,8 +549,8 @@ int ldit_attention_planes(const void *Q, const void *K, const void *V, void *O, 
     if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_planes: empty problem");
     if (B * N * (ld_in > ldo ? ld_in : ldo) >= (1ll << 31) || B * H * ((N + 127) / 128) >= (1ll << 31))
         return fail(LDIT_EUNSUPPORTED, "attention_planes: operand exceeds 2^31 elements");
-    return (planes == 2 ? launch_attention_planes2 : launch_attention_planes3)(Q, K, V, O, (int)B, (int)N, (int)H, (int)D, (int)ld_in,
-                                                                              (int)plane_in, (int)ldo, static_cast<hipStream_t>(stream));
+    return attention(Build{LDIT_F32X3, false}, Q, K, V, (int)ld_in, (int)ld_in, (int)ld_in, operand(O, nullptr, ldo, planes), (int)B, (int)N, (int)H,
+                     (int)D, 0.0f, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, (int)plane_in);
 }
 
 int ldit_split_f32_planes(const void *src, int64_t lds, void *dst, int64_t rows, int64_t cols, int32_t planes, ldit_stream stream)
@@ -547,22 +563,16 @@ int ldit_layernorm_f32_planes(const void *X, const void *gamma, const void *beta
                               int32_t planes, ldit_stream stream)
 {
     if (C > (1 << 20)) return fail(LDIT_EINVAL, "layernorm: C out of range");
-    return launch_layernorm_splitout(static_cast<const float *>(X), static_cast<const float *>(gamma), static_cast<const float *>(beta), Y,
-                                     rows, (int)C, eps, planes, static_cast<hipStream_t>(stream));
+    return layernorm(Build{LDIT_F32X3, false}, static_cast<const float *>(X), static_cast<const float *>(gamma), static_cast<const float *>(beta),
+                     operand(Y, nullptr, planes * C, planes), nullptr, rows, (int)C, eps, static_cast<hipStream_t>(stream));
 }
 
 int ldit_linear_planes(const void *Xp, int64_t lda, const void *Wp, const void *bias, void *Y, int64_t ldy, int64_t M, int64_t N,
                        int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, int32_t planes, ldit_stream stream)
 {
-    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_planes: empty problem");
     if (planes != 2 && planes != 3) return fail(LDIT_EINVAL, "linear_planes: %d planes (2 or 3)", planes);
-    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K * planes >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_planes: operand exceeds 2^31 elements");
-    if (lda < planes * K) return fail(LDIT_EINVAL, "linear_planes: bad leading dimension");
-    if (!Y || !aligned16(Y) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear_planes: output null or misaligned");
-    GemmExtra x{};
-    if (planes == 2) { x.nseg = 3; x.seg_a = 0x001u; x.seg_w = 0x010u; }
-    else { x.nseg = 6; x.seg_a = 0x001012u; x.seg_w = 0x010210u; }
-    x.seg_inner = 1;
+    LDIT_TRY(check_linear("linear_planes", M, N, K, lda, ldy, Y, Y2, LDIT_EPI_BIAS, planes));
+    GemmExtra x = split_segments(planes);
     int epi;
     if (epilogue == LDIT_EPI_BIAS) epi = EPI_F32;
     else if (epilogue == LDIT_EPI_SCALE_RESID) epi = EPI_SCALE_RESID;
@@ -575,50 +585,17 @@ int ldit_linear_planes(const void *Xp, int64_t lda, const void *Wp, const void *
 }
 
 int ldit_embed_bf16(const void *x, const void *patch_w_bf16, const void *patch_b, const void *cls, const void *pos, void *out,
-                    void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream_)
+                    void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream)
 {
-    if (B <= 0 || in_ch <= 0 || img_h <= 0 || img_w <= 0 || p <= 0 || C <= 0) return fail(LDIT_EINVAL, "embed_bf16: empty problem");
-    if (img_h % p || img_w % p) return fail(LDIT_EINVAL, "embed_bf16: image %lldx%lld is not a multiple of patch %lld", (long long)img_h, (long long)img_w, (long long)p);
-    if (!x || !patch_w_bf16 || !patch_b || !cls || !pos || !out || !scratch) return fail(LDIT_EINVAL, "embed_bf16: null operand");
-    if (!aligned16(out) || !aligned16(pos) || !aligned16(scratch) || !aligned16(patch_w_bf16) || (C & 3))
-        return fail(LDIT_EINVAL, "embed_bf16: out / pos / scratch / patch_w must be 16-byte aligned, C a multiple of 4");
-    const int64_t P = (img_h / p) * (img_w / p), Kp = in_ch * p * p;
-    if (Kp % 64) return fail(LDIT_EUNSUPPORTED, "embed_bf16: in_ch*p*p = %lld must be a multiple of 64", (long long)Kp);
-    if (B * in_ch * img_h * img_w >= (1ll << 31) || B * (P + 1) * C >= (1ll << 31) || B * P * Kp >= (1ll << 31))
-        return fail(LDIT_EUNSUPPORTED, "embed_bf16: operand exceeds 2^31 elements");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    LDIT_TRY(launch_patches_rows(static_cast<const float *>(x), scratch, (int)B, (int)in_ch, (int)img_h, (int)img_w, (int)p, stream));
-    GemmExtra xe{};
-    xe.pos = static_cast<const float *>(pos); xe.patches = (int)P;
-    LDIT_TRY(launch_gemm_bf16_ex(scratch, (int)Kp, patch_w_bf16, static_cast<const float *>(patch_b), out, (int)C, (int)(B * P), (int)C, (int)Kp,
-                                 EPI_EMBED, nullptr, nullptr, nullptr, xe, stream));
-    return launch_cls_rows(static_cast<const float *>(cls), static_cast<const float *>(pos), static_cast<float *>(out), (int)B, (int)(P + 1),
-                           (int)C, stream);
+    return embed_bf16_entry("embed_bf16", x, nullptr, patch_w_bf16, patch_b, cls, pos, out, scratch, B, in_ch, img_h, img_w, p, C, stream);
 }
 
 int ldit_embed_bf16_images(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t half_in, float mean,
                            float std, const void *patch_w_bf16, const void *patch_b, const void *cls, const void *pos, void *out,
-                           void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream_)
+                           void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream)
 {
-    if (B <= 0 || B > 65535 || in_ch <= 0 || img_h <= 0 || img_w <= 0 || p <= 0 || C <= 0) return fail(LDIT_EINVAL, "embed_bf16_images: empty problem");
-    if (img_h % p || img_w % p) return fail(LDIT_EINVAL, "embed_bf16_images: target %lldx%lld is not a multiple of patch %lld", (long long)img_h, (long long)img_w, (long long)p);
-    if (!images || !heights || !widths || !patch_w_bf16 || !patch_b || !cls || !pos || !out || !scratch) return fail(LDIT_EINVAL, "embed_bf16_images: null operand");
-    if (!(std > 0.0f)) return fail(LDIT_EINVAL, "embed_bf16_images: std must be positive");
-    if (!aligned16(out) || !aligned16(pos) || !aligned16(scratch) || !aligned16(patch_w_bf16) || (C & 3))
-        return fail(LDIT_EINVAL, "embed_bf16_images: out / pos / scratch / patch_w must be 16-byte aligned, C a multiple of 4");
-    const int64_t P = (img_h / p) * (img_w / p), Kp = in_ch * p * p;
-    if (Kp % 64) return fail(LDIT_EUNSUPPORTED, "embed_bf16_images: in_ch*p*p = %lld must be a multiple of 64", (long long)Kp);
-    if (B * in_ch * img_h * img_w >= (1ll << 31) || B * (P + 1) * C >= (1ll << 31) || B * P * Kp >= (1ll << 31))
-        return fail(LDIT_EUNSUPPORTED, "embed_bf16_images: operand exceeds 2^31 elements");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    LDIT_TRY(launch_patches_rows_images(images, half_in != 0, heights, widths, (int)B, (int)in_ch, mean, std, (int)img_h, (int)img_w, (int)p,
-                                        scratch, stream));
-    GemmExtra xe{};
-    xe.pos = static_cast<const float *>(pos); xe.patches = (int)P;
-    LDIT_TRY(launch_gemm_bf16_ex(scratch, (int)Kp, patch_w_bf16, static_cast<const float *>(patch_b), out, (int)C, (int)(B * P), (int)C, (int)Kp,
-                                 EPI_EMBED, nullptr, nullptr, nullptr, xe, stream));
-    return launch_cls_rows(static_cast<const float *>(cls), static_cast<const float *>(pos), static_cast<float *>(out), (int)B, (int)(P + 1),
-                           (int)C, stream);
+    const ImgSrc src{images, heights, widths, half_in != 0, mean, std};
+    return embed_bf16_entry("embed_bf16_images", nullptr, &src, patch_w_bf16, patch_b, cls, pos, out, scratch, B, in_ch, img_h, img_w, p, C, stream);
 }
 
 int ldit_tap_to_map_f32(const void *tap, void *out, int64_t B, int64_t Gh, int64_t Gw, int64_t C, float scale,
@@ -641,26 +618,13 @@ int ldit_tap_to_map_bwd_f32(const void *dmap, void *dtap, int64_t B, int64_t Gh,
 int ldit_linear_bf16(const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M,
                      int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, ldit_stream stream)
 {
-    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_bf16: empty problem");
-    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_bf16: operand exceeds 2^31 elements");
-    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear_bf16: bad leading dimension");
-    if (!Y || !aligned16(Y) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear_bf16: output null or misaligned");
-    if (epilogue < LDIT_EPI_BIAS || epilogue > LDIT_EPI_SCALE_RESID) return fail(LDIT_EINVAL, "linear_bf16: unknown epilogue %d", epilogue);
-    return launch_gemm_bf16(X, (int)lda, W, static_cast<const float *>(bias), Y, (int)ldy, (int)M, (int)N, (int)K, epilogue,
-                            static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2),
-                            static_cast<hipStream_t>(stream));
+    return linear_entry("linear_bf16", LDIT_BF16, X, lda, W, bias, Y, ldy, M, N, K, epilogue, lam, R, Y2, stream);
 }
 
 int ldit_attention_bf16(const void *Q, const void *K, const void *V, void *O, int64_t B, int64_t N, int64_t H, int64_t D,
                         int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, ldit_stream stream)
 {
-    if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_bf16: empty problem");
-    const int64_t ldmax = ldq > ldk ? (ldq > ldv ? ldq : ldv) : (ldk > ldv ? ldk : ldv);
-    if (B * N * (ldmax > ldo ? ldmax : ldo) >= (1ll << 31) || B * H * ((N + 255) / 256) >= (1ll << 31))
-        return fail(LDIT_EUNSUPPORTED, "attention_bf16: operand exceeds 2^31 elements");
-    if (ldq < H * D || ldk < H * D || ldv < H * D || ldo < H * D) return fail(LDIT_EINVAL, "attention_bf16: row stride smaller than H*D");
-    return launch_attention_bf16(Q, K, V, O, (int)B, (int)N, (int)H, (int)D, (int)ldq, (int)ldk, (int)ldv, (int)ldo, scale,
-                                 static_cast<hipStream_t>(stream));
+    return attention_entry("attention_bf16", LDIT_BF16, 256, Q, K, V, O, B, N, H, D, ldq, ldk, ldv, ldo, scale, stream);
 }
 
 int ldit_cast_f32_bf16(const void *src, void *dst, int64_t n, ldit_stream stream)
@@ -674,16 +638,12 @@ int ldit_linear_fp8(const void *X, int64_t lda, const void *W, const void *bias,
                     int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, float ab_scale, float out_inv_scale,
                     const void *w_scales, ldit_stream stream)
 {
-    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_fp8: empty problem");
+    LDIT_TRY(check_linear("linear_fp8", M, N, K, lda, ldy, Y, Y2, epilogue));
     if (w_scales && !aligned16(w_scales)) return fail(LDIT_EINVAL, "linear_fp8: w_scales must be 16-byte aligned");
-    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_fp8: operand exceeds 2^31 elements");
-    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear_fp8: bad leading dimension");
-    if (!Y || (reinterpret_cast<uintptr_t>(Y) & 15u) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear_fp8: output null or misaligned");
-    if (epilogue < LDIT_EPI_BIAS || epilogue > LDIT_EPI_SCALE_RESID) return fail(LDIT_EINVAL, "linear_fp8: unknown epilogue %d", epilogue);
     if (!(ab_scale > 0.0f) || (epilogue == LDIT_EPI_BIAS_GELU && !(out_inv_scale > 0.0f))) return fail(LDIT_EINVAL, "linear_fp8: scales must be positive");
-    return launch_gemm_fp8(X, (int)lda, W, static_cast<const float *>(bias), Y, (int)ldy, (int)M, (int)N, (int)K, epilogue,
-                           static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), ab_scale,
-                           out_inv_scale, nullptr, static_cast<const float *>(w_scales), nullptr, static_cast<hipStream_t>(stream));
+    return linear(Build{LDIT_FP8, false}, operand(X, nullptr, lda), W, w_scales, static_cast<const float *>(bias), operand(Y, nullptr, ldy), (int)M,
+                  (int)N, (int)K, epilogue, static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), Side{},
+                  static_cast<hipStream_t>(stream), ab_scale, out_inv_scale);
 }
 
 int ldit_quant_rows_f32_fp8(const void *W, void *codes, void *scales, int64_t N, int64_t K, ldit_stream stream)
@@ -707,28 +667,24 @@ int ldit_linear_mxfp8(const void *X, int64_t lda, const void *Xs, const void *W,
                       int64_t ldy, void *Ys, int64_t M, int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2,
                       ldit_stream stream)
 {
-    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_mxfp8: empty problem");
-    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_mxfp8: operand exceeds 2^31 elements");
-    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear_mxfp8: bad leading dimension");
+    LDIT_TRY(check_linear("linear_mxfp8", M, N, K, lda, ldy, Y, Y2, epilogue));
     if (K % 128 || lda % 128) return fail(LDIT_EUNSUPPORTED, "linear_mxfp8: K and lda must be multiples of 128");
     if (!X || !W || !Xs || !Ws) return fail(LDIT_EINVAL, "linear_mxfp8: null operand");
     if (!aligned16(X) || !aligned16(W) || (reinterpret_cast<uintptr_t>(Xs) & 3u) || (reinterpret_cast<uintptr_t>(Ws) & 3u))
         return fail(LDIT_EINVAL, "linear_mxfp8: codes must be 16-byte aligned, scales 4-byte aligned");
-    if (!Y || (reinterpret_cast<uintptr_t>(Y) & 15u) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear_mxfp8: output null or misaligned");
-    if (epilogue < LDIT_EPI_BIAS || epilogue > LDIT_EPI_SCALE_RESID) return fail(LDIT_EINVAL, "linear_mxfp8: unknown epilogue %d", epilogue);
     if (epilogue == LDIT_EPI_BIAS_GELU && (!Ys || N % 32 || ldy % 32))
         return fail(LDIT_EINVAL, "linear_mxfp8: the GELU epilogue writes MX: Ys needed, N and ldy multiples of 32");
-    return launch_gemm_mxfp8(X, (int)lda, Xs, W, Ws, static_cast<const float *>(bias), Y, (int)ldy, Ys, (int)M, (int)N, (int)K, epilogue,
-                             static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2),
-                             static_cast<hipStream_t>(stream));
+    return linear(Build{LDIT_MXFP8, false}, operand(X, Xs, lda), W, Ws, static_cast<const float *>(bias), operand(Y, Ys, ldy), (int)M, (int)N, (int)K,
+                  epilogue, static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), Side{},
+                  static_cast<hipStream_t>(stream));
 }
 
 int ldit_layernorm_mxfp8(const void *x, const void *gamma, const void *beta, void *Y, void *Ys, int64_t rows, int64_t C, float eps,
                          ldit_stream stream)
 {
     if (C > 4096 || C % 32) return fail(LDIT_EINVAL, "layernorm_mxfp8: C must be a multiple of 32, at most 4096");
-    return launch_layernorm_mxout(static_cast<const float *>(x), static_cast<const float *>(gamma), static_cast<const float *>(beta), Y,
-                                  Ys, rows, (int)C, eps, static_cast<hipStream_t>(stream));
+    return layernorm(Build{LDIT_MXFP8, false}, static_cast<const float *>(x), static_cast<const float *>(gamma), static_cast<const float *>(beta),
+                     operand(Y, Ys, C), nullptr, rows, (int)C, eps, static_cast<hipStream_t>(stream));
 }
 
 int ldit_quant_f32_fp8(const void *src, void *dst, int64_t n, float inv_scale, ldit_stream stream)
@@ -748,23 +704,13 @@ int ldit_amax_f32(const void *src, int64_t n, void *out, ldit_stream stream)
 int ldit_preprocess_f32(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch,
                         float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
 {
-    if (!images || !heights || !widths || !out) return fail(LDIT_EINVAL, "preprocess: null argument");
-    if (B <= 0 || B > 65535 || in_ch <= 0 || out_h <= 0 || out_w <= 0) return fail(LDIT_EINVAL, "preprocess: bad geometry");
-    if (!(std > 0.0f)) return fail(LDIT_EINVAL, "preprocess: std must be positive");
-    if ((int64_t)B * in_ch * out_h * out_w >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "preprocess: batch exceeds 2^31 elements");
-    return launch_preprocess(images, false, heights, widths, B, in_ch, mean, std, out_h, out_w, static_cast<float *>(out),
-                             static_cast<hipStream_t>(stream));
+    return preprocess(false, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
 }
 
 int ldit_preprocess_f16(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch,
                         float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
 {
-    if (!images || !heights || !widths || !out) return fail(LDIT_EINVAL, "preprocess: null argument");
-    if (B <= 0 || B > 65535 || in_ch <= 0 || out_h <= 0 || out_w <= 0) return fail(LDIT_EINVAL, "preprocess: bad geometry");
-    if (!(std > 0.0f)) return fail(LDIT_EINVAL, "preprocess: std must be positive");
-    if ((int64_t)B * in_ch * out_h * out_w >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "preprocess: batch exceeds 2^31 elements");
-    return launch_preprocess(images, true, heights, widths, B, in_ch, mean, std, out_h, out_w, static_cast<float *>(out),
-                             static_cast<hipStream_t>(stream));
+    return preprocess(true, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
 }
 
 int ldit_fpn_merge_f32(const void *lat, const void *top, void *out, int64_t B, int64_t Gh, int64_t Gw, int64_t Ch, float scale,

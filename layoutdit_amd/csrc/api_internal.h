@@ -2,6 +2,7 @@
 // byte layout of the packed parameter block and of the inference workspace, per-launch HIP-event bracketing.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -181,5 +182,124 @@ struct Probe {
         LDIT_TRY((probe).end());       \
     } while (0)
 
+// q fold of the packed builds (ldit_pack_weights; the mxfp8 train mirror): q' = (D^-1/2 log2 e) q - exp2-domain scores (attention_bf16.hip, PRE)
+inline float qfold_of(const Geo &g) { return (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f; }
+
+// split-fp32 builds: the plane products of one output element, SMALLEST FIRST (their sum is formed at its own magnitude
+// before the leading p0.q0 term arrives): bf16x3 = a1 w0 + a0 w1 + a0 w0; six products = a2 w0 + a1 w1 + a0 w2 + a1 w0 + a0 w1 + a0 w0.
+// Walked per 64-deep k-tile (k-tile outermost): the operand tiles one product has just pulled through L2 serve the next one - 1-5 % on
+// the q|k|v and fc1 GEMMs against whole-K segments (profiles/r03_planes_segment_order.txt), never slower.  planes < 2: an ordinary GEMM.
+inline GemmExtra split_segments(int planes)
+{
+    GemmExtra x{};
+    if (planes == 2) { x.nseg = 3; x.seg_a = 0x001u; x.seg_w = 0x010u; }
+    if (planes == 3) { x.nseg = 6; x.seg_a = 0x001012u; x.seg_w = 0x010210u; }
+    x.seg_inner = x.nseg != 0;
+    return x;
+}
+
+// the pixels as the detector holds them before its input transform: a ragged list of [in_ch, h_i, w_i] images in [0, 1]
+// (ldit_vit_forward_images: the transform is evaluated by the kernel that produces the patch-embedding operand)
+struct ImgSrc {
+    const void *const *images;
+    const int32_t *heights, *widths;
+    bool half_in;
+    float mean, std;
+};
+
+// the first destination that asked for hidden state `hidden_idx` (the fc2 epilogue writes it), or null
+inline float *tap_of(const ldit_cfg *cfg, void *const *taps, int hidden_idx)
+{
+    for (int i = 0; taps && i < cfg->n_taps; ++i)
+        if (cfg->taps[i] == hidden_idx && taps[i]) return static_cast<float *>(taps[i]);
+    return nullptr;
+}
+
+// hidden state `hidden_idx` to every destination that asked for it, except the one already written
+inline int copy_taps(const ldit_cfg *cfg, void *const *taps, int hidden_idx, const float *src, const float *already, size_t bytes, hipStream_t stream)
+{
+    for (int i = 0; i < cfg->n_taps; ++i)
+        if (cfg->taps[i] == hidden_idx && taps[i] != already)
+            LDIT_HIP_CHECK(hipMemcpyAsync(taps[i], src, bytes, hipMemcpyDeviceToDevice, stream));
+    return LDIT_OK;
+}
+
+// shared preamble of forward() and forward_train(): `ptrs` are the blocks named in `names` (an image list stands in for x)
+inline int check_forward_args(const ldit_cfg *cfg, const Geo &g, int batch, std::initializer_list<const void *> ptrs, const char *names,
+                              const ImgSrc *imgs, void *const *tap_out)
+{
+    if (batch <= 0) return fail(LDIT_EINVAL, "batch %d must be positive", batch);
+    for (const void *p : ptrs)
+        if (!p) return fail(LDIT_EINVAL, "null %s pointer", names);
+    for (const void *p : ptrs)
+        if (!aligned16(p)) return fail(LDIT_EINVAL, "pointers must be 16-byte aligned");
+    if (imgs && (!imgs->images || !imgs->heights || !imgs->widths || !(imgs->std > 0.0f) || batch > 65535))
+        return fail(LDIT_EINVAL, "image list: null array, non-positive std or more than 65535 images");
+    if (cfg->n_taps && !tap_out) return fail(LDIT_EINVAL, "tap_out is null");
+    for (int i = 0; i < cfg->n_taps; ++i)
+        if (!tap_out[i] || !aligned16(tap_out[i])) return fail(LDIT_EINVAL, "tap_out[%d] is null or misaligned", i);
+    if ((int64_t)batch * g.T * (int64_t)(g.F > 3 * g.C ? g.F : 3 * g.C) >= (1ll << 31))
+        return fail(LDIT_EUNSUPPORTED, "batch %d: activation index space exceeds 2^31 elements, split the batch", batch);
+    return LDIT_OK;
+}
+
+// shared preamble of the ldit_linear_* entries.  planes > 1 (ldit_linear_planes): operand rows hold that many bf16 planes and the entry
+// checks its output stride itself.  Entries that map their epilogue themselves leave `epilogue` out.
+inline int check_linear(const char *name, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldy, const void *Y, const void *Y2,
+                        int epilogue = LDIT_EPI_BIAS, int64_t planes = 1)
+{
+    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "%s: empty problem", name);
+    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K * planes >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "%s: operand exceeds 2^31 elements", name);
+    if ((planes == 1 && ldy < N) || lda < planes * K) return fail(LDIT_EINVAL, "%s: bad leading dimension", name);
+    if (!Y || !aligned16(Y) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "%s: output null or misaligned", name);
+    if (epilogue < LDIT_EPI_BIAS || epilogue > LDIT_EPI_SCALE_RESID) return fail(LDIT_EINVAL, "%s: unknown epilogue %d", name, epilogue);
+    return LDIT_OK;
+}
+
+// ---- the encoder layer, written once (api.hip: run_layer) for every build and for inference and training ------------------------
+struct Build { int dtype; bool train; };     // train: the kernels that also store what the backward reads
+
+// An activation operand in the build's format: fp32 or bf16 values, the bf16 planes of the split builds side by side, or e4m3 codes
+struct Operand {
+    void *p = nullptr;
+    void *s = nullptr;     // mxfp8: its E8M0 block scales [rows, ld / 32]; fp8: its calibrated fp32 scale (device, read only); else null
+    int ld = 0;            // row stride in elements, every plane counted
+    int planes = 0;        // split builds: bf16 planes per value
+};
+inline Operand operand(const void *p, const void *s, int64_t ld, int planes = 0) { return {const_cast<void *>(p), const_cast<void *>(s), (int)ld, planes}; }
+
+// side stores of one training GEMM: Ypre = the branch output before LayerScale (EPI_SCALE_RESID) or gelu' (EPI_BIAS_GELU), rowscale = the
+// stochastic-depth row factors on lam, Yd (mxfp8) = the dequantised MX output
+struct Side { void *Ypre = nullptr; const float *rowscale = nullptr; void *Yd = nullptr; };
+
+// One layer as the schedule sees it.  Inference: h_in = h_mid = h_out and one buffer serves y1, o and y2 in turn, another q|k|v and
+// then the MLP hidden; training: every tensor in its own slot of the saved block.
+struct Layer {
+    const float *h_in; float *h_mid, *h_out;   // residual stream before the layer, after the attention branch, after the MLP branch
+    Operand y1, qkv, o, y2, hid;       // LN1 output, q|k|v, attention output, LN2 output, MLP hidden
+    size_t qk_bytes;                   // from a row's q to its k, and from its k to its v
+    float scale;                       // score scale; 0: q was folded when the weights were packed
+    // parameters: fp32 vectors at V + v->*; matrices in the build's format at W + w->* / div (div = 2: the bf16 mirror of the flat fp32
+    // block) and their scales at W + w->sw_* (fp8: fp32 per row, mxfp8: E8M0 blocks); bqkv apart (mxfp8 training reads the folded copy)
+    const char *V, *W; const PackedLayer *v, *w; size_t div; const float *bqkv;
+    const float *vec(size_t off) const { return reinterpret_cast<const float *>(V + off); }
+    const void *mat(size_t off) const { return W + off / div; }
+    float *tap;                        // second copy of h_out, or null
+    // training only
+    Side s_o, s_fc1, s_fc2;            // z1 + rs1; a1 (+ g dequantised, mxfp8); z2 + rs2
+    float *lse; void *y1d, *y2d, *ob, *od;   // mxfp8: dequantised y1, y2; the bf16 attention output before quantisation, its dequantised codes
+};
+
+// the three places that choose a kernel by build (api.hip); everything else sees operands
+int layernorm(Build b, const float *X, const float *gamma, const float *beta, const Operand &Y, void *Yd, int64_t rows, int C, float eps, hipStream_t stream);
+int linear(Build b, const Operand &A, const void *W, const void *Ws, const float *bias, const Operand &Y, int M, int N, int K, int epi, const float *lam,
+           const float *R, float *Y2, const Side &t, hipStream_t stream, float ab_scale = 0.f, float out_inv_scale = 0.f);
+int attention(Build b, const void *Q, const void *K, const void *V, int ldq, int ldk, int ldv, const Operand &O, int B, int N, int H, int D, float scale,
+              hipStream_t stream, float *lse = nullptr, void *Ob = nullptr, void *Od = nullptr, int plane_in = 0);
+int run_layer(Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe);
+// patch embedding + CLS rows into `out`: on the fp32 GEMM straight from the NCHW batch, or on the bf16 GEMM from an im2col pass
+int embed(const Geo &g, const float *x, const float *pw, const float *pb, const float *cls, const float *pos, float *out, int batch, int img_h, int img_w, hipStream_t stream, Probe &probe);
+int embed_bf16(const Geo &g, const float *x, const ImgSrc *imgs, int planes, void *patches, const void *w16, const float *pb, const float *cls,
+               const float *pos, float *out, int batch, int img_h, int img_w, hipStream_t stream, Probe &probe);
 
 }  // namespace ldit

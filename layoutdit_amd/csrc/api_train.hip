@@ -119,8 +119,6 @@ TrainWs train_ws_map(const Geo &g, int batch)
     w.part_rows_tile = Mp / 64;
     w.part_rows_ln = (size_t)layernorm_bwd_blocks((int64_t)M);
     const size_t widths[10] = {C, C, F, C, C, C, C, 3 * C, C, C};
-    const bool ln[10] = {false, false, false, true, true, false, false, false, true, true};
-    (void)ln;
     const size_t part_rows = std::max(std::max(w.part_rows_ln, w.part_rows_tile), (size_t)layernorm_bwd_resid_blocks((int64_t)M));     // every buffer fits any producer
     for (int i = 0; i < 10; ++i) w.part[i] = take(part_rows * widths[i] * 4);
     w.total = o;
@@ -134,9 +132,6 @@ int train_geometry(const ldit_cfg *cfg, Geo &g)
     LDIT_TRY(geometry(cfg, g));     // (mxfp8: hidden and mlp multiples of 128)
     return LDIT_OK;
 }
-
-// q fold of the packed builds (api.hip, ldit_pack_weights): q' = (D^-1/2 log2 e) q
-inline float qfold_of(const Geo &g) { return (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f; }
 
 // Train mirror (ldit_train_mirror_bytes): the bf16 part - element i of the flat block at byte 2 i (bf16 of the master; in the mxfp8
 // build the four matrices of a layer hold their dequantised MX codes instead, the q third folded) - then, mxfp8 only, at byte
@@ -168,34 +163,12 @@ int mx_layers(const Geo &g, float *p, const float *gr, float *m, float *v, bool 
     return LDIT_OK;
 }
 
-int gemm(Probe &probe, const void *A, int lda, const void *W, const float *bias, void *Y, int ldy, int M, int N, int K, int epi,
-         const float *lam, const float *R, float *Y2, const GemmExtra &x, hipStream_t stream)
-{
-    LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_bf16_ex(A, lda, W, bias, Y, ldy, M, N, K, epi, lam, R, Y2, x, stream));
-    return LDIT_OK;
-}
-
-float *tap_of(const ldit_cfg *cfg, void *const *taps, int hidden_idx)
-{
-    if (!taps) return nullptr;
-    for (int i = 0; i < cfg->n_taps; ++i)
-        if (cfg->taps[i] == hidden_idx && taps[i]) return static_cast<float *>(taps[i]);
-    return nullptr;
-}
-
 int forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_params, const void *x, int32_t batch,
                   void *const *tap_out, const void *drop_scales, void *saved, size_t saved_bytes, hipStream_t stream, Probe &probe)
 {
     Geo g;
     LDIT_TRY(train_geometry(cfg, g));
-    if (batch <= 0) return fail(LDIT_EINVAL, "batch %d must be positive", batch);
-    if (!packed || !flat_params || !x || !saved) return fail(LDIT_EINVAL, "null packed / flat_params / x / saved pointer");
-    if (!aligned16(packed) || !aligned16(flat_params) || !aligned16(x) || !aligned16(saved)) return fail(LDIT_EINVAL, "pointers must be 16-byte aligned");
-    if (cfg->n_taps && !tap_out) return fail(LDIT_EINVAL, "tap_out is null");
-    for (int i = 0; i < cfg->n_taps; ++i)
-        if (!tap_out[i] || !aligned16(tap_out[i])) return fail(LDIT_EINVAL, "tap_out[%d] is null or misaligned", i);
-    if ((int64_t)batch * g.T * (int64_t)(g.F > 3 * g.C ? g.F : 3 * g.C) >= (1ll << 31))
-        return fail(LDIT_EUNSUPPORTED, "batch %d: activation index space exceeds 2^31 elements, split the batch", batch);
+    LDIT_TRY(check_forward_args(cfg, g, batch, {packed, flat_params, x, saved}, "packed / flat_params / x / saved", nullptr, tap_out));
     const SavedMap sm = saved_map(g, batch, cfg->dtype);
     if (saved_bytes < sm.total) return fail(LDIT_EWORKSPACE, "saved-activation block %zu bytes < required %zu", saved_bytes, sm.total);
     // `packed` is the bf16 MIRROR of the flat fp32 block (element i of the mirror = bf16 of element i of the master): a matrix
@@ -209,90 +182,52 @@ int forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_para
     float *rowscale = drop_scales ? reinterpret_cast<float *>(S + sm.rowscale) : nullptr;
     if (drop_scales && g.L)
         LDIT_RUN(probe, LDIT_K_OTHER, launch_expand_rowscale(static_cast<const float *>(drop_scales), rowscale, batch, g.T, 2 * g.L, stream));
-
     auto h_of = [&](int l) { return reinterpret_cast<float *>(S + (l < g.L ? sm.layer[l].h_in : sm.h_final)); };
-    auto copy_taps = [&](int hidden_idx, const float *src, const float *already) -> int {
-        for (int i = 0; i < cfg->n_taps; ++i)
-            if (cfg->taps[i] == hidden_idx && tap_out[i] != already)
-                LDIT_HIP_CHECK(hipMemcpyAsync(tap_out[i], src, act_bytes, hipMemcpyDeviceToDevice, stream));
-        return LDIT_OK;
-    };
 
     // embeddings (TF:153-176): the batch rounded to a bf16 im2col matrix (kept in the saved block: the wgrad's operand too), then
     // the bf16 MFMA GEMM on the mirror of the patch projection - mixed precision like every other GEMM of the step (the fp32
     // kernel took 161 us of a 13.4 ms ViT-B bs=64 step).  A patch length that is not a multiple of the bf16 k-tile stays fp32.
-    if (g.Kp % 64 == 0) {
-        char *patches = S + sm.patches;
-        LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows(static_cast<const float *>(x), patches, batch, g.in_ch, cfg->img_h, cfg->img_w,
-                                                         g.p, stream));
-        GemmExtra xe{};
-        xe.pos = F32(pm.pos); xe.patches = g.P;
-        LDIT_TRY(gemm(probe, patches, g.Kp, P + pm.patch_w / 2, F32(pm.patch_b), h_of(0), C, batch * g.P, C, g.Kp, EPI_EMBED, nullptr,
-                      nullptr, nullptr, xe, stream));
-        LDIT_RUN(probe, LDIT_K_OTHER, launch_cls_rows(F32(pm.cls), F32(pm.pos), h_of(0), batch, g.T, C, stream));
-        LDIT_TRY(copy_taps(0, h_of(0), nullptr));
-    } else {
-        GemmArgs a{};
-        a.A = static_cast<const float *>(x); a.W = F32(pm.patch_w); a.Y = h_of(0); a.bias = F32(pm.patch_b); a.pos = F32(pm.pos);
-        a.M = batch * g.P; a.N = C; a.K = g.Kp; a.lda = g.in_ch * cfg->img_h * cfg->img_w; a.ldy = C;
-        a.img_h = cfg->img_h; a.img_w = cfg->img_w; a.gw = g.gw; a.patches = g.P; a.patch = g.p; a.tokens = g.T;
-        LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm(a, EPI_EMBED, A_PATCH, stream));
-        LDIT_RUN(probe, LDIT_K_OTHER, launch_cls_rows(F32(pm.cls), F32(pm.pos), h_of(0), batch, g.T, C, stream));
-        LDIT_TRY(copy_taps(0, h_of(0), nullptr));
-    }
-    const float scale = 1.0f / sqrtf((float)g.D);
-    if (cfg->dtype == LDIT_MXFP8) {
-        // mxfp8 (quantisation-aware training): the inference forward of api.hip's mxfp8 branch, launch for launch and tile for tile,
-        // on the mirror's MX section; the train variants of its kernels add side stores only - the dequantised MX operands, the
-        // pre-quantisation attention output, lse, the pre-LayerScale branch outputs, gelu' - and the stochastic-depth row factors
-        const PackedMap xm = packed_map(g, LDIT_MXFP8);
-        const char *X = P + mirror_mx_offset(g);
-        char *y8 = S + sm.mx_c, *ys = y8 + (size_t)M * C, *b8 = S + sm.mx_f, *bs = b8 + (size_t)M * F;
-        for (int l = 0; l < g.L; ++l) {
-            const PackedLayer &pl = pm.layer[l], &xl = xm.layer[l];
-            const SavedLayer &sl = sm.layer[l];
-            float *h_in = h_of(l), *h_mid = reinterpret_cast<float *>(S + sl.h_mid), *h_out = h_of(l + 1);
-            float *tap = tap_of(cfg, tap_out, l + 1);
-            const float *rs1 = rowscale ? rowscale + (size_t)(2 * l) * M : nullptr, *rs2 = rowscale ? rowscale + (size_t)(2 * l + 1) * M : nullptr;
-            char *qkv = S + sl.qkv;
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout_train(h_in, F32(pl.ln1_w), F32(pl.ln1_b), y8, ys, S + sl.y1, M, C, cfg->ln_eps, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8(y8, C, ys, X + xl.wqkv, X + xl.sw_qkv, reinterpret_cast<const float *>(X + xl.bqkv), qkv,
-                                                          3 * C, nullptr, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_ATTENTION,
-                     launch_attention_bf16_mxout_train(qkv, qkv + 2 * (size_t)C, qkv + 4 * (size_t)C, y8, ys, reinterpret_cast<float *>(S + sl.lse),
-                                                       S + sl.o, S + sl.od, batch, g.T, g.H, g.D, 3 * C, 3 * C, 3 * C, C,
-                                                       0.0f /* q folded */, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8_train(y8, C, ys, X + xl.wo, X + xl.sw_o, F32(pl.bo), h_mid, C, nullptr, M, C, C,
-                                                                EPI_SCALE_RESID, F32(pl.lam1), h_in, nullptr, S + sl.z1, rs1, nullptr, stream));
-            LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_mxout_train(h_mid, F32(pl.ln2_w), F32(pl.ln2_b), y8, ys, S + sl.y2, M, C, cfg->ln_eps, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8_train(y8, C, ys, X + xl.w1, X + xl.sw_1, F32(pl.b1), b8, F, bs, M, F, C,
-                                                                EPI_BIAS_GELU, nullptr, nullptr, nullptr, S + sl.a1, nullptr, S + sl.g, stream));
-            LDIT_RUN(probe, LDIT_K_GEMM, launch_gemm_mxfp8_train(b8, F, bs, X + xl.w2, X + xl.sw_2, F32(pl.b2), h_out, C, nullptr, M, C, F,
-                                                                EPI_SCALE_RESID, F32(pl.lam2), h_mid, tap, S + sl.z2, rs2, nullptr, stream));
-            if (tap) LDIT_TRY(copy_taps(l + 1, h_out, tap));
-        }
-        return LDIT_OK;
-    }
+    if (g.Kp % 64 == 0)
+        LDIT_TRY(embed_bf16(g, static_cast<const float *>(x), nullptr, 1, S + sm.patches, P + pm.patch_w / 2, F32(pm.patch_b), F32(pm.cls),
+                            F32(pm.pos), h_of(0), batch, cfg->img_h, cfg->img_w, stream, probe));
+    else
+        LDIT_TRY(embed(g, static_cast<const float *>(x), F32(pm.patch_w), F32(pm.patch_b), F32(pm.cls), F32(pm.pos), h_of(0), batch, cfg->img_h,
+                       cfg->img_w, stream, probe));
+    LDIT_TRY(copy_taps(cfg, tap_out, 0, h_of(0), nullptr, act_bytes, stream));
+
+    // Every tensor of a layer in its own slot of the saved block.  bf16: the operands are the saved tensors themselves.  mxfp8
+    // (quantisation-aware training): the inference forward of the mxfp8 build on the mirror's MX section, its transient MX operands in
+    // mx_c / mx_f; the train variants of its kernels add side stores only - the dequantised MX operands, the pre-quantisation
+    // attention output, lse, the pre-LayerScale branch outputs, gelu' - and the stochastic-depth row factors.
+    const bool mx = cfg->dtype == LDIT_MXFP8;
+    const PackedMap xm = mx ? packed_map(g, LDIT_MXFP8) : PackedMap{};
+    const char *X = P + mirror_mx_offset(g);
+    char *y8 = S + sm.mx_c, *b8 = S + sm.mx_f;
+    Layer d{};
+    d.qk_bytes = (size_t)2 * C;
+    d.V = FP; d.W = mx ? X : P; d.div = mx ? 1 : 2;
+    d.scale = mx ? 0.0f /* q folded */ : 1.0f / sqrtf((float)g.D);
     for (int l = 0; l < g.L; ++l) {
-        const PackedLayer &pl = pm.layer[l];
         const SavedLayer &sl = sm.layer[l];
-        float *h_in = h_of(l), *h_mid = reinterpret_cast<float *>(S + sl.h_mid), *h_out = h_of(l + 1);
-        char *y1 = S + sl.y1, *qkv = S + sl.qkv, *o = S + sl.o, *y2 = S + sl.y2, *gl = S + sl.g;
-        float *tap = tap_of(cfg, tap_out, l + 1);
-        GemmExtra none{}, x1{}, x2{}, x3{};
-        x1.Ypre = S + sl.z1; x1.rowscale = rowscale ? rowscale + (size_t)(2 * l) * M : nullptr;
-        x2.Ypre = S + sl.a1;                       // gelu'(pre-activation), the backward's factor
-        x3.Ypre = S + sl.z2; x3.rowscale = rowscale ? rowscale + (size_t)(2 * l + 1) * M : nullptr;
-        LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_bf16out(h_in, F32(pl.ln1_w), F32(pl.ln1_b), y1, M, C, cfg->ln_eps, stream));
-        LDIT_TRY(gemm(probe, y1, C, P + pl.wqkv / 2, F32(pl.bqkv), qkv, 3 * C, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, none, stream));
-        LDIT_RUN(probe, LDIT_K_ATTENTION,
-                 launch_attention_bf16_lse(qkv, qkv + 2 * (size_t)C, qkv + 4 * (size_t)C, o, reinterpret_cast<float *>(S + sl.lse),
-                                           batch, g.T, g.H, g.D, 3 * C, 3 * C, 3 * C, C, scale, stream));
-        LDIT_TRY(gemm(probe, o, C, P + pl.wo / 2, F32(pl.bo), h_mid, C, M, C, C, EPI_SCALE_RESID, F32(pl.lam1), h_in, nullptr, x1, stream));
-        LDIT_RUN(probe, LDIT_K_LAYERNORM, launch_layernorm_bf16out(h_mid, F32(pl.ln2_w), F32(pl.ln2_b), y2, M, C, cfg->ln_eps, stream));
-        LDIT_TRY(gemm(probe, y2, C, P + pl.w1 / 2, F32(pl.b1), gl, F, M, F, C, EPI_BIAS_GELU, nullptr, nullptr, nullptr, x2, stream));
-        LDIT_TRY(gemm(probe, gl, F, P + pl.w2 / 2, F32(pl.b2), h_out, C, M, C, F, EPI_SCALE_RESID, F32(pl.lam2), h_mid, tap, x3, stream));
-        if (tap) LDIT_TRY(copy_taps(l + 1, h_out, tap));
+        d.h_in = h_of(l); d.h_mid = reinterpret_cast<float *>(S + sl.h_mid); d.h_out = h_of(l + 1);
+        d.v = &pm.layer[l]; d.w = mx ? &xm.layer[l] : d.v;
+        d.bqkv = mx ? reinterpret_cast<const float *>(X + d.w->bqkv) /* folded */ : F32(d.v->bqkv);
+        d.qkv = operand(S + sl.qkv, nullptr, 3 * C);
+        d.lse = reinterpret_cast<float *>(S + sl.lse);
+        d.s_o.Ypre = S + sl.z1; d.s_o.rowscale = rowscale ? rowscale + (size_t)(2 * l) * M : nullptr;
+        d.s_fc1.Ypre = S + sl.a1;                       // gelu'(pre-activation), the backward's factor
+        d.s_fc2.Ypre = S + sl.z2; d.s_fc2.rowscale = rowscale ? rowscale + (size_t)(2 * l + 1) * M : nullptr;
+        if (mx) {
+            d.y1 = d.o = d.y2 = operand(y8, y8 + (size_t)M * C, C);
+            d.hid = operand(b8, b8 + (size_t)M * F, F);
+            d.y1d = S + sl.y1; d.ob = S + sl.o; d.od = S + sl.od; d.y2d = S + sl.y2; d.s_fc1.Yd = S + sl.g;
+        } else {
+            d.y1 = operand(S + sl.y1, nullptr, C); d.o = operand(S + sl.o, nullptr, C); d.y2 = operand(S + sl.y2, nullptr, C);
+            d.hid = operand(S + sl.g, nullptr, F);
+        }
+        d.tap = tap_of(cfg, tap_out, l + 1);
+        LDIT_TRY(run_layer(Build{cfg->dtype, true}, g, batch, cfg->ln_eps, d, stream, probe));
+        if (d.tap) LDIT_TRY(copy_taps(cfg, tap_out, l + 1, d.h_out, d.tap, act_bytes, stream));
     }
     return LDIT_OK;
 }
@@ -598,8 +533,8 @@ int ldit_layernorm_mxfp8_train(const void *x, const void *gamma, const void *bet
                                float eps, ldit_stream stream)
 {
     if (rows <= 0 || C <= 0 || C > 4096 || C % 32) return fail(LDIT_EINVAL, "layernorm_mxfp8_train: bad shape");
-    return launch_layernorm_mxout_train(static_cast<const float *>(x), static_cast<const float *>(gamma), static_cast<const float *>(beta),
-                                        Y, Ys, Yd, rows, (int)C, eps, static_cast<hipStream_t>(stream));
+    return layernorm(Build{LDIT_MXFP8, true}, static_cast<const float *>(x), static_cast<const float *>(gamma), static_cast<const float *>(beta),
+                     operand(Y, Ys, C), Yd, rows, (int)C, eps, static_cast<hipStream_t>(stream));
 }
 
 int ldit_attention_mxfp8_train(const void *Q, const void *K, const void *V, void *O, void *Os, void *lse, void *Ob, void *Od, int64_t B,
@@ -608,8 +543,8 @@ int ldit_attention_mxfp8_train(const void *Q, const void *K, const void *V, void
 {
     if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_mxfp8_train: empty problem");
     if (B * N * (ldq > ldo ? ldq : ldo) >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "attention_mxfp8_train: operand exceeds 2^31 elements");
-    return launch_attention_bf16_mxout_train(Q, K, V, O, Os, static_cast<float *>(lse), Ob, Od, (int)B, (int)N, (int)H, (int)D, (int)ldq,
-                                             (int)ldk, (int)ldv, (int)ldo, scale, static_cast<hipStream_t>(stream));
+    return attention(Build{LDIT_MXFP8, true}, Q, K, V, (int)ldq, (int)ldk, (int)ldv, operand(O, Os, ldo), (int)B, (int)N, (int)H, (int)D, scale,
+                     static_cast<hipStream_t>(stream), static_cast<float *>(lse), Ob, Od);
 }
 
 int ldit_linear_mxfp8_train(const void *X, int64_t lda, const void *Xs, const void *W, const void *Ws, const void *bias, void *Y,
@@ -633,9 +568,9 @@ int ldit_linear_mxfp8_train(const void *X, int64_t lda, const void *Xs, const vo
     } else {
         return fail(LDIT_EINVAL, "linear_mxfp8_train: epilogue %d not available (scale + residual or bias + GELU)", epilogue);
     }
-    return launch_gemm_mxfp8_train(X, (int)lda, Xs, W, Ws, static_cast<const float *>(bias), Y, (int)ldy, Ys, (int)M, (int)N, (int)K, epi,
-                                   static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), Ypre,
-                                   static_cast<const float *>(rowscale), Yd, static_cast<hipStream_t>(stream));
+    return linear(Build{LDIT_MXFP8, true}, operand(X, Xs, lda), W, Ws, static_cast<const float *>(bias), operand(Y, Ys, ldy), (int)M, (int)N, (int)K, epi,
+                  static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2),
+                  Side{Ypre, static_cast<const float *>(rowscale), Yd}, static_cast<hipStream_t>(stream));
 }
 
 int ldit_attention_fwd_lse_bf16(const void *Q, const void *K, const void *V, void *O, void *lse, int64_t B, int64_t N, int64_t H,
@@ -643,8 +578,8 @@ int ldit_attention_fwd_lse_bf16(const void *Q, const void *K, const void *V, voi
 {
     if (B <= 0 || N <= 0 || H <= 0) return fail(LDIT_EINVAL, "attention_fwd_lse: empty problem");
     if (B * N * 3 * H * D >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "attention_fwd_lse: operand exceeds 2^31 elements");
-    return launch_attention_bf16_lse(Q, K, V, O, static_cast<float *>(lse), (int)B, (int)N, (int)H, (int)D, (int)ldq, (int)ldk,
-                                     (int)ldv, (int)ldo, scale, static_cast<hipStream_t>(stream));
+    return attention(Build{LDIT_BF16, true}, Q, K, V, (int)ldq, (int)ldk, (int)ldv, operand(O, nullptr, ldo), (int)B, (int)N, (int)H, (int)D, scale,
+                     static_cast<hipStream_t>(stream), static_cast<float *>(lse));
 }
 
 int ldit_attention_bwd_bf16(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *lse, void *dQ,
@@ -684,10 +619,7 @@ int ldit_linear_bf16_ex(const void *X, int64_t lda, const void *W, const void *b
                         int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, void *Ypre, const void *rowscale,
                         const void *aux, int64_t ldaux, int32_t splits, ldit_stream stream)
 {
-    if (M <= 0 || N <= 0 || K <= 0) return fail(LDIT_EINVAL, "linear_bf16_ex: empty problem");
-    if (M * (ldy > lda ? ldy : lda) >= (1ll << 31) || N * K >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "linear_bf16_ex: operand exceeds 2^31 elements");
-    if (ldy < N || lda < K) return fail(LDIT_EINVAL, "linear_bf16_ex: bad leading dimension");
-    if (!Y || !aligned16(Y) || (Y2 && !aligned16(Y2))) return fail(LDIT_EINVAL, "linear_bf16_ex: output null or misaligned");
+    LDIT_TRY(check_linear("linear_bf16_ex", M, N, K, lda, ldy, Y, Y2));
     int epi;
     switch (epilogue) {
         case LDIT_EPI_BIAS: epi = EPI_BIAS; break;

@@ -249,3 +249,37 @@ def test_concurrent_streams_do_not_interfere():
         torch.cuda.synchronize()
     for a, b in outs:
         assert torch.equal(a, r1) and torch.equal(b, r2)
+
+
+_CENSUS = [("f32", "eval"), ("f32x3", "eval"), ("f32x6", "eval"), ("bf16", "eval"), ("fp8", "eval"), ("mxfp8", "eval"),
+           ("bf16", "train"), ("mxfp8", "train"), ("bf16", "train+drop")]
+
+
+@pytest.mark.parametrize("dtype,mode", _CENSUS)
+def test_launch_census_of_every_build(dtype, mode):
+    """What one forward launches, per family of the timing probe, on vit_micro (L = 3) at batch 2: 4 L + 1 GEMMs (patch embedding; q|k|v,
+    o_proj, fc1, fc2 per layer), L attentions, 2 L LayerNorms; `other` = the CLS rows, + the im2col pass of every build that embeds on
+    the bf16 GEMM (all but f32), + the row-scale expansion when the training forward is given stochastic-depth factors.  bench.py
+    divides by the GEMM count, and the layer schedule is written once for all these builds: an edit there must not change a count."""
+    from layoutdit_amd import training
+    cfg = cfgs.vit_micro()
+    L = cfg.num_hidden_layers
+    assert L == 3
+    x = torch.from_numpy(synth.synth_images(2, 64, 64, seed=11)).to(DEV)
+    m = DiTEncoder(cfg, compute_dtype=dtype, qat=dtype == "mxfp8" and mode != "eval").load_numpy(synth.synth_weights(cfg, 11)).to(DEV).eval()
+    t = {}
+    with torch.no_grad():
+        if mode == "eval":
+            if dtype == "fp8":
+                m.calibrate_fp8(x)
+            m(x, taps=[L], _timing=t)
+        else:
+            st = training.flat_state(m, 64, 64)
+            st.repack()
+            drop = training.sample_drop_scales(L, 2, 0.1, x.device) if mode == "train+drop" else None
+            st.forward(x, [L], drop, st.saved_nograd(2), t)
+    torch.cuda.synchronize()
+    other = (1 if dtype == "f32" else 2) + (mode == "train+drop")
+    got = {k: t[k + "_launches"] for k in ("gemm", "attention", "layernorm", "other")}
+    print(dtype, mode, got)
+    assert got == {"gemm": 4 * L + 1, "attention": L, "layernorm": 2 * L, "other": other}
