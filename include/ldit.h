@@ -542,6 +542,47 @@ int ldit_nms_batched_f32(const void *boxes, const void *scores, const void *grou
                          void *keep, void *count, void *out_boxes, void *out_scores, void *workspace, size_t workspace_bytes,
                          ldit_stream stream);
 
+/* ==== box head (torchvision RoIHeads in eval mode, which the reference runs inside FasterRCNN(..., box_roi_pool =
+ * MultiScaleRoIAlign(["p2", "p3", "p4", "p5", "pool"], 7, 2)), ref src/layoutdit/modeling/model.py:34-55): the multi-scale RoIAlign in
+ * front of the head's GEMMs and the softmax / decode / filter behind them, one launch each, on the padded proposals the region-proposal
+ * stage returns: no device-to-host synchronisation (torchvision's MultiScaleRoIAlign runs one nonzero per level), no data-dependent
+ * shape, no atomics, capturable, bit-reproducible.  ldit_nms_batched_f32 with the labels as groups finishes the stage.  Inference only.
+ * Additive to ABI 6.
+ *
+ * ldit_roi_align_levels_f32: L <= 8 fp32 feature maps of C channels (C % 4 == 0) in channels-last memory, finest first.  Map l is
+ *   described by HOST arrays of length L: maps[l] (device pointer, 16-byte aligned), map_h[l] x map_w[l] cells, spatial_scale[l] and
+ *   the element strides stride_b / stride_y / stride_x [l] of batch, row and pixel (multiples of 4, stride_x >= C; the channel
+ *   stride is 1) - so a strided view such as p5[:, :, ::2, ::2] is consumed in place.  Element (b, y, x, c) of map l is
+ *   maps[l][b stride_b + y stride_y + x stride_x + c]; the caller guarantees that all of them exist.
+ *   boxes fp32 [B, R, 4] (x1, y1, x2, y2 in image coordinates), count int32 [B] or NULL (all R rows valid).
+ *   out fp32 [B R, P, P, C]; rows r >= count[b] are written as ZEROS.  levels_out (optional) int32 [B, R]: the level of each row,
+ *   -1 for padding rows.  P = 7 with sampling_ratio = 2 is built; anything else: LDIT_EUNSUPPORTED, like C % 4 != 0 and L > 8.
+ *   Level of a box (torchvision LevelMapper), in fp32:  area = (x2 - x1) * (y2 - y1);
+ *     k = floor(canonical_level + log2(sqrt(area) / canonical_scale) + 1e-6), clamped to [k_min, k_max];  level = k - k_min
+ *   (k_max - k_min < L; torchvision: canonical 224 / 4, k_min = -log2(spatial_scale[0]), k_max = -log2(spatial_scale[L - 1])).
+ *   Pooling (torchvision roi_align, aligned = False), with s = the level's spatial_scale, in fp32:
+ *     start_x = x1 s;  roi_w = max(x2 s - x1 s, 1);  bin_w = roi_w / P;  sample i of bin p at x = start_x + p bin_w + (i + 0.5) bin_w / 2
+ *     (y alike).  A sample with y < -1 or y > map_h (x alike) contributes 0.  Otherwise y = max(y, 0), y_low = (int) y; if
+ *     y_low >= map_h - 1 both rows are map_h - 1 and the weight is on y_low alone, else y_high = y_low + 1, ly = y - y_low, hy = 1 - ly;
+ *     value = hy hx v(low, low) + hy lx v(low, high) + ly hx v(high, low) + ly lx v(high, high).  A bin is the sum of its 4 samples / 4.
+ *   One workgroup per row, one wave per bin, four channels per lane.
+ * ldit_box_postprocess_f32: RoIHeads.postprocess_detections up to the NMS.  head fp32 [B R, ld]: the class logits in columns
+ *   [0, NC), the deltas (dx, dy, dw, dh) of class c in columns [NC + 4 c, NC + 4 c + 4); ld >= 5 NC.  proposals fp32 [B, R, 4], count
+ *   int32 [B] or NULL, weights HOST float[4] = the BoxCoder weights (10, 10, 5, 5).  One candidate per (proposal r, class c = 1 .. NC - 1)
+ *   at index r (NC - 1) + (c - 1) - torchvision's flattening order, so the NMS's tie-break by ascending index is torchvision's:
+ *   boxes_out fp32 [B, R (NC - 1), 4], scores_out fp32 [B, R (NC - 1)], labels_out int32 [B, R (NC - 1)] (= c).
+ *   score = softmax over all NC logits (evaluated in double, rounded once).  box = ldit_rpn_decode_f32's arithmetic on
+ *   (dx / wx, dy / wy, dw / ww, dh / wh) against the proposal (dw, dh clamped at log(1000 / 16) AFTER the division), clamped to
+ *   [0, img_w] x [0, img_h].  The score becomes -inf (the box is still written) when it is not > score_thresh (STRICTLY: the RPN
+ *   stage uses >=, torchvision's box head does not), when the clamped width or height is not >= min_size, or when r >= count[b]. */
+int ldit_roi_align_levels_f32(const void *const *maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
+                              const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
+                              const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
+                              int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream);
+int ldit_box_postprocess_f32(const void *head, int64_t ld, const void *proposals, const void *count, int32_t B, int64_t R, int32_t NC,
+                             float img_h, float img_w, const float *weights, float score_thresh, float min_size, void *boxes_out,
+                             void *scores_out, void *labels_out, ldit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

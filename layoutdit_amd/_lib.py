@@ -124,6 +124,10 @@ SIGNATURES = {
     "ldit_rpn_decode_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "ldit_nms_workspace_bytes": (_sz, [_i64, _i64]),
     "ldit_nms_batched_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # box head
+    "ldit_roi_align_levels_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
+                                            C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
+    "ldit_box_postprocess_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _f32, _f32, C.POINTER(_f32), _f32, _f32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,76 @@
+"""``LayoutDetectionModel`` in eval mode (ref ``src/layoutdit/modeling/model.py:20-88``): the reference's
+``FasterRCNN(DiTWithFPN, num_classes + 1, rpn_anchor_generator=AnchorGenerator(...), box_roi_pool=MultiScaleRoIAlign(["p2", "p3",
+"p4", "p5", "pool"], 7, 2), fixed_size=(224, 224), image_mean / std 0.5)`` assembled from this package's stages: input transform,
+``DiTWithFPN``, ``RegionProposalNetwork``, ``RoIHeads``.  ``forward(images)`` has torchvision's surface (a list of ``[3, h, w]``
+images in, a list of ``{boxes, labels, scores}`` in each image's own coordinates out, one synchronisation);
+``forward_padded(batch)`` is the fixed-size path from pixels to padded detections without any - it can sit in one graph.
+
+The ``state_dict`` keys are the reference's (``model.backbone.*``, ``model.rpn.head.*``, ``model.roi_heads.box_head.fc6.*`` ...).
+Inference only: training the RPN and the box head is not implemented.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from ..config import DiTConfig
+from .detector_input import DetectorInputTransform
+from .dit_fpn import DiTWithFPN
+from .roi_heads import FastRCNNPredictor, MultiScaleRoIAlign, RoIHeads, TwoMLPHead, _nhwc_f32
+from .rpn import AnchorGenerator, RegionProposalNetwork, RPNHead
+
+FEATMAP_NAMES = ("p2", "p3", "p4", "p5", "pool")
+
+
+class _FasterRCNN(nn.Module):
+    """The container whose attribute names give the parameters torchvision's keys: ``backbone``, ``rpn``, ``roi_heads``
+    (``transform`` holds no parameter)."""
+
+    def __init__(self, backbone: DiTWithFPN, num_classes: int, anchor_generator: AnchorGenerator):
+        super().__init__()
+        self.transform = DetectorInputTransform(fixed_size=(224, 224), image_mean=(0.5, 0.5, 0.5), image_std=(0.5, 0.5, 0.5))
+        self.backbone = backbone
+        c = backbone.out_channels
+        self.rpn = RegionProposalNetwork(anchor_generator, RPNHead(c, anchor_generator.num_anchors_per_location()[0]))
+        pool = MultiScaleRoIAlign(FEATMAP_NAMES, output_size=7, sampling_ratio=2)
+        self.roi_heads = RoIHeads(pool, TwoMLPHead(c * 7 * 7, 1024), FastRCNNPredictor(1024, num_classes))
+
+
+class LayoutDetectionModel(nn.Module):
+    def __init__(self, num_classes: int = 5, anchor_sizes=((32,), (64,), (128,), (256,), (512,)),
+                 aspect_ratios=((0.5, 1.0, 2.0),) * 5, config: Optional[DiTConfig] = None, compute_dtype: str = "f32"):
+        """``num_classes`` counts the foreground classes (the reference adds the background itself, ref model.py:47); the anchor
+        defaults are the reference's ``ModelConfig``.  ``compute_dtype`` selects the encoder build; the FPN, the RPN and the box
+        head are fp32 in every build."""
+        super().__init__()
+        if len(set(len(s) * len(r) for s, r in zip(anchor_sizes, aspect_ratios))) != 1:
+            raise ValueError("LayoutDetectionModel: every level must have the same number of anchors per location (one RPN head)")
+        backbone = DiTWithFPN(pretrained=False, config=config, compute_dtype=compute_dtype)
+        self.model = _FasterRCNN(backbone, int(num_classes) + 1, AnchorGenerator(sizes=anchor_sizes, aspect_ratios=aspect_ratios))
+
+    def forward_padded(self, batch: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``batch`` [B, 3, H, W] (already transformed) -> ``(boxes [B, D, 4], scores [B, D], labels int32 [B, D], count int32 [B])``
+        in the coordinates of the batch, zero padding, no synchronisation."""
+        m = self.model
+        if self.training:
+            raise RuntimeError("LayoutDetectionModel: inference only (the RPN and box head losses are not implemented) - call .eval() first")
+        image_size = tuple(batch.shape[-2:])
+        with torch.no_grad():
+            feats = m.backbone(batch)
+            feats = {k: _nhwc_f32(v) for k, v in feats.items()}      # low-precision inputs: the heads stay fp32
+            proposals, _, count = m.rpn(feats, image_size, padded=True)
+            return m.roi_heads(feats, proposals, count, image_size, padded=True)
+
+    def forward(self, images: List[torch.Tensor], targets=None) -> List[Dict[str, torch.Tensor]]:
+        if self.training or targets is not None:
+            raise RuntimeError("LayoutDetectionModel: inference only (the RPN and box head losses are not implemented) - call .eval() "
+                               "first and pass no targets")
+        m = self.model
+        original = [tuple(img.shape[-2:]) for img in images]
+        image_list, _ = m.transform(images)
+        boxes, scores, labels, count = self.forward_padded(image_list.tensors)
+        result = [{"boxes": boxes[i, :n], "labels": labels[i, :n].to(torch.int64), "scores": scores[i, :n]}
+                  for i, n in enumerate(count.tolist())]
+        return m.transform.postprocess(result, image_list.image_sizes, original)

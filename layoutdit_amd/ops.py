@@ -738,3 +738,103 @@ def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: torch.Tensor, i
 def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
     """torchvision ``nms``.  Synchronises (see :func:`batched_nms`)."""
     return batched_nms(boxes, scores, None, iou_threshold)
+
+
+# ---- box head (include/ldit.h "box head"; csrc/roi_heads.hip) ------------------------------------------------------------------
+NMS_MAX_CANDIDATES = 8192                # per problem (ldit_nms_batched_f32)
+
+
+def infer_scales(features: Sequence[torch.Tensor], image_size) -> list:
+    """torchvision's ``MultiScaleRoIAlign`` scale inference: per map ``2 ** round(log2(map / image))``, the same for both axes."""
+    import math
+    scales = []
+    for f in features:
+        per_axis = [2.0 ** float(round(math.log2(float(s) / float(o)))) for s, o in zip(f.shape[-2:], image_size)]
+        if per_axis[0] != per_axis[1]:
+            raise ValueError(f"map {tuple(f.shape[-2:])} of image {tuple(image_size)}: the two axes infer different scales {per_axis}")
+        scales.append(per_axis[0])
+    return scales
+
+
+def roi_align_levels(features: Sequence[torch.Tensor], boxes: torch.Tensor, count: Optional[torch.Tensor], image_size,
+                     output_size: int = 7, sampling_ratio: int = 2, canonical_scale: float = 224.0, canonical_level: float = 4.0,
+                     return_levels: bool = False):
+    """``MultiScaleRoIAlign`` forward in one launch.  ``features``: the maps ``[B, C, h, w]`` finest first, float32 in channels-last
+    memory (channel stride 1; any batch / row / pixel stride - ``p5[:, :, ::2, ::2]`` is consumed without a copy).  ``boxes`` [B, R, 4]
+    and ``count`` int32 [B] (or None: every row valid) are what ``RegionProposalNetwork.forward(..., padded=True)`` returns.
+    Returns ``[B * R, P, P, C]`` (the fc6 GEMM's A operand; rows ``r >= count[b]`` are zero) and, with ``return_levels``, the
+    int32 ``[B, R]`` level of each row (-1 for padding rows).  No synchronisation."""
+    import math
+    lib = _lib.load()
+    feats = list(features)
+    boxes = _req(boxes, "boxes")
+    if not feats or boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError(f"roi_align_levels: boxes {tuple(boxes.shape)} is not [B, R, 4] or there is no feature map")
+    B, R = boxes.shape[:2]
+    if B == 0 or R == 0:
+        raise ValueError("roi_align_levels: empty problem")
+    Cc = feats[0].shape[1]
+    for i, f in enumerate(feats):
+        if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.float32:
+            raise ValueError(f"features[{i}]: expected a float32 tensor on the GPU (libldit_hip has no CPU path)")
+        if f.dim() != 4 or f.shape[0] != B or f.shape[1] != Cc:
+            raise ValueError(f"features[{i}] {tuple(f.shape)} is not [{B}, {Cc}, h, w]")
+        if f.stride(1) != 1:
+            raise ValueError(f"features[{i}]: expected channels-last memory (channel stride 1), got strides {f.stride()}")
+    if count is not None and tuple(_req_i32(count, "count").shape) != (B,):
+        raise ValueError(f"count {tuple(count.shape)} is not [{B}]")
+    scales = infer_scales(feats, image_size)
+    k_min, k_max = int(-math.log2(scales[0])), int(-math.log2(scales[-1]))
+    L, P = len(feats), int(output_size)
+    out = torch.empty((B * R, P, P, Cc), device=boxes.device, dtype=torch.float32)
+    levels = torch.empty((B, R), device=boxes.device, dtype=torch.int32) if return_levels else None
+    _launch(_device(boxes, count, *feats), lib.ldit_roi_align_levels_f32, (C.c_void_p * L)(*[f.data_ptr() for f in feats]),
+            (C.c_int32 * L)(*[f.shape[2] for f in feats]), (C.c_int32 * L)(*[f.shape[3] for f in feats]), (C.c_float * L)(*scales),
+            (C.c_int64 * L)(*[f.stride(0) for f in feats]), (C.c_int64 * L)(*[f.stride(2) for f in feats]),
+            (C.c_int64 * L)(*[f.stride(3) for f in feats]), L, Cc, _ptr(boxes), _ptr(count), B, R, P, int(sampling_ratio), k_min, k_max,
+            float(canonical_scale), float(canonical_level), _ptr(out), _ptr(levels))
+    return (out, levels) if return_levels else out
+
+
+def _check_candidates(R: int, num_classes: int) -> None:
+    if R * (num_classes - 1) > NMS_MAX_CANDIDATES:
+        raise ValueError(f"box head: {R} proposals x {num_classes - 1} foreground classes = {R * (num_classes - 1)} candidates per image, "
+                         f"the batched NMS handles at most {NMS_MAX_CANDIDATES}")
+
+
+def box_postprocess(head_out: torch.Tensor, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size, num_classes: int,
+                    score_thresh: float = 0.05, min_size: float = 1e-2, weights=(10.0, 10.0, 5.0, 5.0)):
+    """``postprocess_detections`` up to the NMS.  ``head_out`` [B * R, ld]: class logits in columns ``[0, NC)``, deltas in
+    ``[NC, 5 NC)``; ``proposals`` [B, R, 4], ``count`` int32 [B] or None.  Returns ``boxes`` [B, R (NC - 1), 4], ``scores``
+    [B, R (NC - 1)] (``-inf`` for a candidate that is filtered or belongs to a padding row) and ``labels`` int32, candidate
+    ``r (NC - 1) + (c - 1)`` = (proposal r, class c).  No synchronisation."""
+    lib = _lib.load()
+    head_out, proposals = _req(head_out, "head_out"), _req(proposals, "proposals")
+    NC = int(num_classes)
+    if proposals.dim() != 3 or proposals.shape[2] != 4 or proposals.shape[0] == 0 or proposals.shape[1] == 0:
+        raise ValueError(f"box_postprocess: proposals {tuple(proposals.shape)} is not a non-empty [B, R, 4]")
+    B, R = proposals.shape[:2]
+    if NC < 2 or head_out.dim() != 2 or head_out.shape[0] != B * R or head_out.shape[1] < 5 * NC:
+        raise ValueError(f"box_postprocess: head_out {tuple(head_out.shape)} is not [{B * R}, >= {5 * NC}]")
+    _check_candidates(R, NC)
+    if count is not None and tuple(_req_i32(count, "count").shape) != (B,):
+        raise ValueError(f"count {tuple(count.shape)} is not [{B}]")
+    N = R * (NC - 1)
+    boxes = torch.empty((B, N, 4), device=head_out.device, dtype=torch.float32)
+    scores = torch.empty((B, N), device=head_out.device, dtype=torch.float32)
+    labels = torch.empty((B, N), device=head_out.device, dtype=torch.int32)
+    _launch(_device(head_out, proposals, count), lib.ldit_box_postprocess_f32, _ptr(head_out), head_out.shape[1], _ptr(proposals), _ptr(count),
+            B, R, NC, float(image_size[0]), float(image_size[1]), (C.c_float * 4)(*[float(w) for w in weights]), float(score_thresh),
+            float(min_size), _ptr(boxes), _ptr(scores), _ptr(labels))
+    return boxes, scores, labels
+
+
+def box_detections_padded(head_out: torch.Tensor, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size, num_classes: int,
+                          score_thresh: float = 0.05, nms_thresh: float = 0.5, detections_per_img: int = 100, min_size: float = 1e-2,
+                          weights=(10.0, 10.0, 5.0, 5.0)):
+    """:func:`box_postprocess`, the batched NMS keyed by label and the gather of the kept labels: ``(boxes [B, D, 4], scores [B, D],
+    labels int32 [B, D], count int32 [B])`` with ``D = detections_per_img``, descending score, zero padding.  No synchronisation."""
+    boxes, scores, labels = box_postprocess(head_out, proposals, count, image_size, num_classes, score_thresh, min_size, weights)
+    keep, kept, out_boxes, out_scores = batched_nms_padded(boxes, scores, labels, nms_thresh, detections_per_img)
+    picked = labels.gather(1, keep.clamp(min=0).to(torch.int64))
+    return out_boxes, out_scores, torch.where(keep >= 0, picked, torch.zeros_like(picked)), kept
