@@ -583,6 +583,51 @@ int ldit_box_postprocess_f32(const void *head, int64_t ld, const void *proposals
                              float img_h, float img_w, const float *weights, float score_thresh, float min_size, void *boxes_out,
                              void *scores_out, void *labels_out, ldit_stream stream);
 
+/* ==== RPN training (torchvision RegionProposalNetwork.assign_targets_to_anchors + compute_loss, which the reference reaches through
+ * loss_dict = model(images, targets), ref training/trainer.py:164-183): Matcher(0.7, 0.3, allow_low_quality_matches = True),
+ * BalancedPositiveNegativeSampler(256, 0.5), BoxCoder(1, 1, 1, 1).encode and the two losses, restated from their documented
+ * behaviour (parity with torchvision itself unpinned, as for the region proposals).  Enqueue only: no allocation, no host
+ * synchronisation, no data-dependent shape, no float atomics, capturable; every output is a pure function of the inputs.
+ * Additive to ABI 6.
+ *
+ * ldit_rpn_targets_f32: anchors fp32 [N, 4] (x1, y1, x2, y2), gt_boxes fp32 [B, Gmax, 4], gt_count int32 [B] (clamped to
+ *   [0, Gmax]), keys int32 [B, N]: the caller's random priorities, non-negative (only the low 31 bits are read).  N <= 16384,
+ *   Gmax <= 512 (larger: LDIT_EUNSUPPORTED).  bg_thr > fg_thr (or a NaN), batch_size_per_image <= 0, positive_fraction outside
+ *   (0, 1]: LDIT_EINVAL.  One workgroup per image.
+ *   Matching.  iou(anchor, gt) in fp32 exactly as ldit_nms_batched_f32 computes it (no contraction, correctly rounded division);
+ *     a quotient that is not > 0 counts as +0.  GT rows at or past gt_count[b] are never read.  GT boxes must have positive width
+ *     and height (torchvision asserts it with a synchronisation; here it is the caller's contract), anchors too.
+ *     1. An anchor's match is the GT of largest IoU, ties to the LOWEST GT index.
+ *     2. best >= fg_thr: positive.  best < bg_thr: negative.  Otherwise ignored.
+ *     3. Low-quality promotion, torchvision's literally: every anchor whose IoU with SOME GT g equals g's maximum over all anchors
+ *        becomes positive with ITS OWN argmax match of rule 1 - not necessarily g.  (A GT that no anchor overlaps has maximum 0,
+ *        which every anchor disjoint from it attains: torchvision promotes those too, and so does this.)
+ *     4. An image with gt_count 0: every anchor negative, zero targets.
+ *   matched int32 [B, N]: the GT index for a positive anchor, -1 for a negative one, -2 for an ignored one (so the label before
+ *     sampling is matched >= 0 / == -1 / == -2).
+ *   reg_targets fp32 [B, N, 4]: BoxCoder(1, 1, 1, 1).encode(matched GT, anchor) for every positive anchor (sampled or not), zero
+ *     elsewhere:  w = x2 - x1, cx = x1 + w / 2;  (dx, dy, dw, dh) = ((gcx - acx) / aw, (gcy - acy) / ah, log(gw / aw), log(gh / ah)).
+ *   Sampling.  quota = floor(batch_size_per_image * positive_fraction) (in double).  Of the positives the min(quota, #positives)
+ *     smallest by (key, anchor index) are taken, of the negatives the min(batch_size_per_image - taken positives, #negatives)
+ *     smallest.  With i.i.d. keys that is the distribution of torchvision's randperm sampler; with any keys it is unique.
+ *   labels int32 [B, N]: 1 = sampled positive, 0 = sampled negative, -1 = not in the loss.  sampled int32 [B, 2]: positives and
+ *     negatives taken.
+ * ldit_rpn_loss_f32: logits fp32 [B, N], deltas fp32 [B, N, 4], labels / reg_targets / sampled as above, beta >= 0.
+ *   n = the sum of all 2 B entries of sampled, read on the device.  Over the anchors with label 0 or 1 (y = label):
+ *     loss[0] = (1 / n) sum of max(x, 0) - x y + log1p(exp(-|x|))        (binary_cross_entropy_with_logits, mean)
+ *     loss[1] = (1 / n) sum over label 1 and the 4 coordinates of smooth_l1(delta - target; beta)   (torchvision's normaliser)
+ *   smooth_l1(d) = d^2 / (2 beta) when |d| < beta, else |d| - beta / 2.  n == 0: both losses 0.  No positive: loss[1] == 0 exactly.
+ *   d_logits fp32 [B, N] = d loss[0] / d logits, d_deltas fp32 [B, N, 4] = d loss[1] / d deltas, written IN FULL: exactly zero where
+ *   an anchor is not in the loss.  Sums run in a fixed order (per-block partials, then one workgroup in double).
+ *   workspace: ldit_rpn_loss_workspace_bytes(B, N) bytes; a shorter buffer is refused with LDIT_EWORKSPACE. */
+int ldit_rpn_targets_f32(const void *anchors, const void *gt_boxes, const void *gt_count, const void *keys, int32_t B, int64_t N,
+                         int32_t Gmax, float fg_thr, float bg_thr, int32_t batch_size_per_image, float positive_fraction, void *labels,
+                         void *matched, void *reg_targets, void *sampled, ldit_stream stream);
+size_t ldit_rpn_loss_workspace_bytes(int64_t B, int64_t N);
+int ldit_rpn_loss_f32(const void *logits, const void *deltas, const void *labels, const void *reg_targets, const void *sampled, int32_t B,
+                      int64_t N, float beta, void *loss, void *d_logits, void *d_deltas, void *workspace, size_t workspace_bytes,
+                      ldit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

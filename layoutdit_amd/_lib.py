@@ -124,6 +124,10 @@ SIGNATURES = {
     "ldit_rpn_decode_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "ldit_nms_workspace_bytes": (_sz, [_i64, _i64]),
     "ldit_nms_batched_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # RPN training
+    "ldit_rpn_targets_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "ldit_rpn_loss_workspace_bytes": (_sz, [_i64, _i64]),
+    "ldit_rpn_loss_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     # box head
     "ldit_roi_align_levels_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
                                             C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
@@ -165,6 +169,11 @@ def set_switch(name: str, value) -> None:
     else:
         os.environ[name] = str(value)
     load().ldit_debug_reload_env()
+
+
+def rpn_loss_workspace_bytes(batch: int, n: int) -> int:
+    """Scratch bytes ``ldit_rpn_loss_f32`` wants for ``batch`` x ``n`` anchors (host arithmetic, no launch)."""
+    return int(load().ldit_rpn_loss_workspace_bytes(batch, n))
 
 
 def nms_workspace_bytes(problems: int, n: int) -> int:

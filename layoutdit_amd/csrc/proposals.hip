@@ -19,20 +19,19 @@
 // for this whole file (areaB - iw * ih must not become an FMA) and the division is the correctly rounded one (the Makefile
 // pins -fhip-fp32-correctly-rounded-divide-sqrt for this object).
 #include "ldit_common.h"
+#include "sort_lds.h"
 
 #pragma clang fp contract(off)
 
 namespace ldit {
 namespace {
 
-constexpr int PROP_THREADS = 1024;                       // 16 waves
+constexpr int PROP_THREADS = SORT_THREADS;                // 16 waves
 constexpr int TOPK_MAX_N = 16384;                        // 128 KiB of keys
 constexpr int TOPK_MAX_LEVELS = 8;
 constexpr int NMS_MAX_N = 8192;                          // 8 candidates per thread
 constexpr int NMS_SLOTS = NMS_MAX_N / PROP_THREADS;
 constexpr unsigned INVALID_HI = 0xFF800000u;             // high key word of score -inf; everything at or above is not a candidate
-
-typedef unsigned long long u64;
 
 // order-preserving bits of a score, ascending; -0 = +0; NaN below everything (-inf included)
 __device__ __forceinline__ unsigned score_rank(float s)
@@ -45,33 +44,6 @@ __device__ __forceinline__ unsigned score_rank(float s)
 
 // ascending key order = descending score, ties by ascending index
 __device__ __forceinline__ u64 sort_key(float s, int idx) { return ((u64)(~score_rank(s)) << 32) | (unsigned)idx; }
-
-__device__ __forceinline__ int pow2_at_least(int n)
-{
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// ascending bitonic sort of n (a power of two) keys in LDS by the whole workgroup; the keys must be written and the caller
-// need not have synchronised; returns after a barrier
-__device__ void bitonic_sort(u64 *keys, int n)
-{
-    __syncthreads();
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < (n >> 1); t += PROP_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int p = i | j;
-                const u64 a = keys[i], b = keys[p];
-                if ((a > b) == ((i & k) == 0)) {
-                    keys[i] = b;
-                    keys[p] = a;
-                }
-            }
-            __syncthreads();
-        }
-}
 
 struct TopkLevels {
     int n_levels;

@@ -1,4 +1,4 @@
-"""``LayoutDetectionModel`` in eval mode (ref ``src/layoutdit/modeling/model.py:20-88``): the reference's
+"""``LayoutDetectionModel`` (ref ``src/layoutdit/modeling/model.py:20-88``): the reference's
 ``FasterRCNN(DiTWithFPN, num_classes + 1, rpn_anchor_generator=AnchorGenerator(...), box_roi_pool=MultiScaleRoIAlign(["p2", "p3",
 "p4", "p5", "pool"], 7, 2), fixed_size=(224, 224), image_mean / std 0.5)`` assembled from this package's stages: input transform,
 ``DiTWithFPN``, ``RegionProposalNetwork``, ``RoIHeads``.  ``forward(images)`` has torchvision's surface (a list of ``[3, h, w]``
@@ -6,7 +6,9 @@ images in, a list of ``{boxes, labels, scores}`` in each image's own coordinates
 ``forward_padded(batch)`` is the fixed-size path from pixels to padded detections without any - it can sit in one graph.
 
 The ``state_dict`` keys are the reference's (``model.backbone.*``, ``model.rpn.head.*``, ``model.roi_heads.box_head.fc6.*`` ...).
-Inference only: training the RPN and the box head is not implemented.
+Training: ``rpn_losses(images, targets)`` is the RPN half of the reference's ``loss_dict = model(images, targets)``
+(ref ``training/trainer.py:164-183``) - ``loss_objectness`` and ``loss_rpn_box_reg``, differentiable down to the encoder.  The box
+head's losses (proposal sampling, RoIAlign backward) are not implemented, so ``forward`` in train mode stays refused.
 """
 from __future__ import annotations
 
@@ -62,6 +64,24 @@ class LayoutDetectionModel(nn.Module):
             feats = {k: _nhwc_f32(v) for k, v in feats.items()}      # low-precision inputs: the heads stay fp32
             proposals, _, count = m.rpn(feats, image_size, padded=True)
             return m.roi_heads(feats, proposals, count, image_size, padded=True)
+
+    def rpn_losses(self, images: List[torch.Tensor], targets: List[Dict[str, torch.Tensor]],
+                   generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """The RPN half of the reference's loss dict: ``{"loss_objectness", "loss_rpn_box_reg"}`` for a list of ``[3, h, w]`` images
+        and the reference's targets (``{"boxes": [G, 4] in the image's own coordinates, ...}`` per image).  Train mode only.  The
+        transform rescales the boxes with the images, the backbone runs with gradients, the RPN in train mode; ``backward()`` on
+        the losses reaches ``rpn.head``, the FPN and the encoder.  ``loss_classifier`` / ``loss_box_reg`` of the box head are not
+        implemented (see ``forward``).  ``generator`` seeds the sampler's keys."""
+        if not self.training:
+            raise RuntimeError("LayoutDetectionModel.rpn_losses: train mode only - call .train() first")
+        if targets is None:
+            raise ValueError("LayoutDetectionModel.rpn_losses: targets are required")
+        m = self.model
+        image_list, targets = m.transform(images, targets)
+        batch = image_list.tensors
+        feats = {k: _nhwc_f32(v) for k, v in m.backbone(batch).items()}
+        _, losses = m.rpn(feats, tuple(batch.shape[-2:]), targets=targets, padded=True, generator=generator)
+        return losses
 
     def forward(self, images: List[torch.Tensor], targets=None) -> List[Dict[str, torch.Tensor]]:
         if self.training or targets is not None:

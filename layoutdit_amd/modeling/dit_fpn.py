@@ -34,6 +34,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..config import DiTConfig
+from .conv_layout import _flip_ihwo
 from .dit_backbone import DiTBackbone
 
 
@@ -54,11 +55,6 @@ class _FPNParams(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_uniform_(m.weight, a=1)
                 nn.init.constant_(m.bias, 0)
-
-
-def _flip_ihwo(w: torch.Tensor) -> torch.Tensor:
-    """OIHW 3x3 weight -> the operand of its dgrad convolution: [Cin, 3, 3, Cout] with the taps flipped."""
-    return w.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
 
 
 def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool):

@@ -11,20 +11,30 @@ re-designed for the MI355X instead of translated:
   torchvision's ``nms``, no data-dependent shape, capturable in a graph.  ``forward(..., padded=True)`` returns those padded
   tensors; the list form of torchvision slices them by the count (one synchronisation).
 
-Inference only: anchor matching, sampling and the RPN losses are not implemented, ``train()`` mode is refused.  torchvision is
-not installed offline: the semantics are restated from its documented behaviour (``tests/rpn_oracle.py``) - parity unpinned with
-respect to torchvision itself, as for the FPN.  Parameter names follow torchvision, so detector checkpoints load
-(``rpn.head.conv.0.0.weight`` ...).
+Training (``train()`` mode with targets): ``assign_targets_to_anchors`` - ``Matcher(0.7, 0.3, allow_low_quality_matches=True)``,
+``BalancedPositiveNegativeSampler(256, 0.5)``, ``BoxCoder(1, 1, 1, 1).encode`` - is ONE launch and ``compute_loss`` with both
+gradients two more (``csrc/rpn_train.hip``): fixed-size results instead of torchvision's ``nonzero`` / ``randperm``, the sampler
+driven by random keys drawn on the device, so still no synchronisation.  :class:`RPNHead` is differentiated by one
+``torch.autograd.Function`` per level whose backward runs on the library's kernels like the FPN's: the 1x1 pair's dgrad is
+``ldit_linear_f32`` on the transposed weight (15 columns padded to the GEMM's 32), the 3x3 dgrad the same implicit-im2col GEMM on
+the flipped weight, all three weight gradients bf16 MFMA GEMMs on reduction-major operands with fp32 accumulation (they carry bf16
+operand rounding, like the FPN's and the encoder's), the biases ``ldit_colsum_f32``.  ``train()`` mode WITHOUT targets stays
+refused.  The box head's training is not implemented.
+
+torchvision is not installed offline: the semantics are restated from its documented behaviour (``tests/rpn_oracle.py``,
+``tests/rpn_train_oracle.py``) - parity unpinned with respect to torchvision itself, as for the FPN.  Parameter names follow
+torchvision, so detector checkpoints load (``rpn.head.conv.0.0.weight`` ...).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
+from .conv_layout import _flip_ihwo
 
 
 class AnchorGenerator(nn.Module):
@@ -86,6 +96,93 @@ class _ConvRelu(nn.Sequential):
         super().__init__(nn.Conv2d(c, c, kernel_size=3, padding=1), nn.ReLU(inplace=True))
 
 
+class _RPNHeadLevelFn(torch.autograd.Function):
+    """One level of :class:`RPNHead` with gradients for the map and all six parameters.
+    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box) -> (logits [B, h w A], deltas [B, h w A, 4])."""
+
+    @staticmethod
+    def forward(ctx, x, w3, b3, wc, bc, wb, bb):
+        B, Cc, h, w = x.shape
+        A = wc.shape[0]
+        rows = (5 * A + 3) // 4 * 4
+        w1 = torch.zeros((rows, Cc), device=x.device, dtype=torch.float32)
+        b1 = torch.zeros((rows,), device=x.device, dtype=torch.float32)
+        w1[:A], w1[A:5 * A] = wc.detach().reshape(A, Cc), wb.detach().reshape(4 * A, Cc)
+        b1[:A], b1[A:5 * A] = bc.detach(), bb.detach()
+        xn = x.detach().permute(0, 2, 3, 1).contiguous()                                  # NHWC; free for channels-last maps
+        t = ops.conv3x3_nhwc(xn, w3.detach().permute(0, 2, 3, 1).contiguous(), b3.detach())
+        torch.relu_(t)
+        y = ops.linear(t.view(B * h * w, Cc), w1, b1)
+        ctx.saved = (xn, t, w3.detach(), w1)
+        ctx.A = A
+        return y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4)
+
+    @staticmethod
+    def backward(ctx, d_logits, d_deltas):
+        if ctx.saved is None:
+            raise RuntimeError("RPNHead: backward through a level a second time (its saved maps are freed after the first)")
+        xn, t, w3, w1 = ctx.saved
+        ctx.saved = None
+        A = ctx.A
+        B, h, w, Cc = xn.shape
+        M = B * h * w
+        need = ctx.needs_input_grad
+        # the gradient of the pixel rows [M, logits | deltas | zero padding]: 32 columns, the K the fp32 GEMM wants (and a multiple
+        # of 8, which the bf16 wgrad wants)
+        K = (5 * A + 31) // 32 * 32
+        dy = torch.zeros((M, K), device=xn.device, dtype=torch.float32)
+        if d_logits is not None:
+            dy[:, :A] = d_logits.reshape(M, A)
+        if d_deltas is not None:
+            dy[:, A:5 * A] = d_deltas.reshape(M, 4 * A)
+        w1t = torch.zeros((Cc, K), device=xn.device, dtype=torch.float32)
+        w1t[:, :5 * A] = w1[:5 * A].t()
+        dt = ops.linear(dy, w1t)                                                          # dgrad of the 1x1 pair: [M, C]
+        dt.mul_(t.view(M, Cc) > 0)                                                        # ReLU mask
+        g_wc = g_bc = g_wb = g_bb = g_w3 = g_b3 = g_x = None
+        if need[3] or need[5]:
+            g1 = ops.wgrad_bf16(ops.cast_bf16(dy), ops.cast_bf16(t.view(M, Cc)), M)       # [K, C]
+            g_wc = g1[:A].reshape(A, Cc, 1, 1) if need[3] else None
+            g_wb = g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None
+        if need[4] or need[6]:
+            gb = ops.colsum(dy)
+            g_bc = gb[:A] if need[4] else None
+            g_bb = gb[A:5 * A] if need[6] else None
+        dt4 = dt.view(B, h, w, Cc)
+        if need[2]:
+            g_b3 = ops.colsum(dt)
+        if need[1]:
+            slack = w + 3
+            dt_p = ops.pad_nhwc_bf16(dt4)                                                 # [B (h+2)(w+2), C]
+            x_p = ops.pad_nhwc_bf16(xn, slack_rows=slack)
+            rows = dt_p.shape[0]
+            taps = []
+            for ky in range(3):
+                for kx in range(3):
+                    shift = (ky - 1) * (w + 2) + (kx - 1)
+                    taps.append(ops.wgrad_bf16(dt_p, x_p, rows, w_row_offset=slack + shift))   # [co, ci]
+            g_w3 = torch.stack(taps, dim=2).view(Cc, Cc, 3, 3)
+        if need[0]:
+            g_x = ops.conv3x3_nhwc(dt4, _flip_ihwo(w3)).permute(0, 3, 1, 2)                # dgrad: same GEMM, flipped weight
+        return g_x, g_w3, g_b3, g_wc, g_bc, g_wb, g_bb
+
+
+class _RPNLossFn(torch.autograd.Function):
+    """``ldit_rpn_loss_f32`` as a differentiable node: the kernel has already written both gradients for unit upstream, the
+    backward scales them by the two upstream scalars."""
+
+    @staticmethod
+    def forward(ctx, logits, deltas, labels, reg_targets, sampled, beta):
+        loss, d_logits, d_deltas = ops.rpn_loss(logits.detach(), deltas.detach(), labels, reg_targets, sampled, beta)
+        ctx.save_for_backward(d_logits, d_deltas)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_obj, g_box):
+        d_logits, d_deltas = ctx.saved_tensors
+        return d_logits * g_obj, d_deltas * g_box, None, None, None, None
+
+
 class RPNHead(nn.Module):
     """torchvision's ``RPNHead(in_channels, num_anchors)``: ``conv.0.0`` (3x3 + ReLU), ``cls_logits`` and ``bbox_pred`` (1x1)."""
 
@@ -126,6 +223,10 @@ class RPNHead(nn.Module):
             raise ValueError(f"RPNHead: expected [B, {self.in_channels}, h, w], got {tuple(x.shape)}")
         if x.dtype != torch.float32:
             raise ValueError(f"RPNHead: expected float32 features, got {x.dtype}")
+        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # gradients are wanted: one differentiable node per level (the eval path below is untouched)
+            return _RPNHeadLevelFn.apply(x, self.conv[0][0].weight, self.conv[0][0].bias, self.cls_logits.weight, self.cls_logits.bias,
+                                         self.bbox_pred.weight, self.bbox_pred.bias)
         w3, b3, w1, b1 = self._operands()
         B, Cc, h, w = x.shape
         A = self.num_anchors
@@ -141,23 +242,34 @@ class RPNHead(nn.Module):
 
 
 class RegionProposalNetwork(nn.Module):
-    """torchvision's ``RegionProposalNetwork`` in eval mode.  ``forward(features, image_size)`` returns the list of proposal
-    boxes per image; with ``padded=True`` the fixed-size form ``(boxes [B, post, 4], scores [B, post], count [B])``."""
+    """torchvision's ``RegionProposalNetwork``.  Eval mode: ``forward(features, image_size)`` returns the list of proposal boxes
+    per image; with ``padded=True`` the fixed-size form ``(boxes [B, post, 4], scores [B, post], count [B])``.  Train mode with
+    ``targets``: ``(proposals, {"loss_objectness", "loss_rpn_box_reg"})`` - the proposals detached and from the train top-n."""
 
     def __init__(self, anchor_generator: AnchorGenerator, head: RPNHead, pre_nms_top_n: int = 1000, post_nms_top_n: int = 1000,
-                 nms_thresh: float = 0.7, score_thresh: float = 0.0, min_size: float = 1e-3):
+                 nms_thresh: float = 0.7, score_thresh: float = 0.0, min_size: float = 1e-3, pre_nms_top_n_train: int = 2000,
+                 post_nms_top_n_train: int = 2000, fg_iou_thresh: float = 0.7, bg_iou_thresh: float = 0.3,
+                 batch_size_per_image: int = 256, positive_fraction: float = 0.5):
         super().__init__()
         self.anchor_generator, self.head = anchor_generator, head
         self.pre_nms_top_n, self.post_nms_top_n = int(pre_nms_top_n), int(post_nms_top_n)
+        self.pre_nms_top_n_train, self.post_nms_top_n_train = int(pre_nms_top_n_train), int(post_nms_top_n_train)
         self.nms_thresh, self.score_thresh, self.min_size = float(nms_thresh), float(score_thresh), float(min_size)
+        self.fg_iou_thresh, self.bg_iou_thresh = float(fg_iou_thresh), float(bg_iou_thresh)
+        self.batch_size_per_image, self.positive_fraction = int(batch_size_per_image), float(positive_fraction)
+        self.smooth_l1_beta = 1.0 / 9.0                               # torchvision's compute_loss
         self._groups: Dict[tuple, torch.Tensor] = {}
 
-    def _level_ids(self, level_sizes: Sequence[int], batch: int, device) -> torch.Tensor:
+    def _top_n(self) -> Tuple[int, int]:
+        return (self.pre_nms_top_n_train, self.post_nms_top_n_train) if self.training else (self.pre_nms_top_n, self.post_nms_top_n)
+
+    def _level_ids(self, level_sizes: Sequence[int], batch: int, device, pre_nms_top_n: Optional[int] = None) -> torch.Tensor:
         """int32 [B, Ksum]: the level of every top-k column - the NMS groups.  Constant per geometry, cached."""
-        key = (tuple(level_sizes), batch, self.pre_nms_top_n, str(device))
+        k = self.pre_nms_top_n if pre_nms_top_n is None else pre_nms_top_n
+        key = (tuple(level_sizes), batch, k, str(device))
         g = self._groups.get(key)
         if g is None:
-            ids = np.concatenate([np.full(min(self.pre_nms_top_n, n), l, dtype=np.int32) for l, n in enumerate(level_sizes)])
+            ids = np.concatenate([np.full(min(k, n), l, dtype=np.int32) for l, n in enumerate(level_sizes)])
             g = torch.from_numpy(np.tile(ids, (batch, 1))).to(device)
             self._groups[key] = g
         return g
@@ -165,24 +277,67 @@ class RegionProposalNetwork(nn.Module):
     def filter_proposals_padded(self, logits: torch.Tensor, deltas: torch.Tensor, anchors: torch.Tensor, level_sizes: Sequence[int],
                                 image_size: Tuple[int, int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The three launches: top-k per level, decode, batched NMS with the level as group.  No synchronisation."""
-        idx = ops.rpn_topk(logits, level_sizes, self.pre_nms_top_n)
+        pre, post = self._top_n()
+        idx = ops.rpn_topk(logits, level_sizes, pre)
         boxes, scores = ops.rpn_decode(logits, deltas, anchors, idx, image_size, self.min_size, self.score_thresh)
-        groups = self._level_ids(level_sizes, logits.shape[0], logits.device)
-        _, count, out_boxes, out_scores = ops.batched_nms_padded(boxes, scores, groups, self.nms_thresh, self.post_nms_top_n)
+        groups = self._level_ids(level_sizes, logits.shape[0], logits.device, pre)
+        _, count, out_boxes, out_scores = ops.batched_nms_padded(boxes, scores, groups, self.nms_thresh, post)
         return out_boxes, out_scores, count
 
-    def forward(self, features: Union[Dict[str, torch.Tensor], Sequence[torch.Tensor]], image_size: Tuple[int, int], padded: bool = False):
-        if self.training:
-            raise RuntimeError("RegionProposalNetwork: inference only (anchor matching, sampling and the RPN losses are not "
-                               "implemented) - call .eval() first")
+    @staticmethod
+    def pad_targets(targets, device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's list of ``{"boxes": [G_i, 4], ...}`` -> ``(gt_boxes fp32 [B, Gmax, 4], gt_count int32 [B])``.  The shapes
+        are known on the host: copies, no synchronisation.  A padded pair passes through."""
+        if isinstance(targets, (tuple, list)) and len(targets) == 2 and isinstance(targets[0], torch.Tensor):
+            gt_boxes, gt_count = targets
+            if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4 or tuple(gt_count.shape) != (gt_boxes.shape[0],):
+                raise ValueError(f"RegionProposalNetwork: padded targets {tuple(gt_boxes.shape)} / {tuple(gt_count.shape)} are not "
+                                 "[B, Gmax, 4] / [B]")
+            return gt_boxes.to(device=device, dtype=torch.float32).contiguous(), gt_count.to(device=device, dtype=torch.int32).contiguous()
+        boxes = [t["boxes"] for t in targets]
+        for bx in boxes:
+            if bx.dim() != 2 or bx.shape[1] != 4:
+                raise ValueError(f"RegionProposalNetwork: target boxes {tuple(bx.shape)} are not [G, 4]")
+        gmax = max(max(int(bx.shape[0]) for bx in boxes), 1)
+        gt_boxes = torch.zeros((len(boxes), gmax, 4), device=device, dtype=torch.float32)
+        for i, bx in enumerate(boxes):
+            if bx.shape[0]:
+                gt_boxes[i, :bx.shape[0]] = bx.detach().to(device=device, dtype=torch.float32)
+        gt_count = torch.tensor([int(bx.shape[0]) for bx in boxes], dtype=torch.int32).to(device)
+        return gt_boxes, gt_count
+
+    def compute_loss_padded(self, logits: torch.Tensor, deltas: torch.Tensor, anchors: torch.Tensor, gt_boxes: torch.Tensor,
+                            gt_count: torch.Tensor, generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Keys, target assignment and the two losses: three launches of this library behind one ``randint``.  No synchronisation."""
+        B, N = logits.shape
+        if gt_boxes.shape[0] != B:
+            raise ValueError(f"RegionProposalNetwork: {gt_boxes.shape[0]} targets for {B} images")
+        keys = torch.randint(0, 2 ** 31 - 1, (B, N), device=logits.device, dtype=torch.int32, generator=generator)
+        labels, _, reg_targets, sampled = ops.rpn_targets(anchors, gt_boxes, gt_count, keys, self.fg_iou_thresh, self.bg_iou_thresh,
+                                                          self.batch_size_per_image, self.positive_fraction)
+        return _RPNLossFn.apply(logits, deltas, labels, reg_targets, sampled, self.smooth_l1_beta)
+
+    def forward(self, features: Union[Dict[str, torch.Tensor], Sequence[torch.Tensor]], image_size: Tuple[int, int], targets=None,
+                padded: bool = False, generator: Optional[torch.Generator] = None):
+        if self.training and targets is None:
+            raise RuntimeError("RegionProposalNetwork: inference only without targets (in train mode the RPN losses need them) - "
+                               "pass targets or call .eval() first")
         feats = list(features.values()) if isinstance(features, dict) else list(features)
+        losses = None
+        if self.training:
+            logits, deltas = self.head(feats)                         # differentiable when gradients are wanted
+        else:
+            with torch.no_grad():
+                logits, deltas = self.head(feats)
         with torch.no_grad():
-            logits, deltas = self.head(feats)
             anchors, level_sizes = self.anchor_generator([tuple(f.shape[-2:]) for f in feats], tuple(image_size), logits.device)
             A = self.head.num_anchors
             if any(n != f.shape[-2] * f.shape[-1] * A for n, f in zip(level_sizes, feats)):
                 raise ValueError("RegionProposalNetwork: the anchor generator and the head disagree on anchors per location")
-            boxes, scores, count = self.filter_proposals_padded(logits, deltas, anchors, level_sizes, image_size)
-        if padded:
-            return boxes, scores, count
-        return [boxes[i, :n] for i, n in enumerate(count.tolist())]
+            boxes, scores, count = self.filter_proposals_padded(logits.detach(), deltas.detach(), anchors, level_sizes, image_size)
+        if self.training:
+            gt_boxes, gt_count = self.pad_targets(targets, logits.device)
+            obj, box = self.compute_loss_padded(logits, deltas, anchors, gt_boxes, gt_count, generator)
+            losses = {"loss_objectness": obj, "loss_rpn_box_reg": box}
+        out = (boxes, scores, count) if padded else [boxes[i, :n] for i, n in enumerate(count.tolist())]
+        return (out, losses) if self.training else out

@@ -740,6 +740,69 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torc
     return batched_nms(boxes, scores, None, iou_threshold)
 
 
+# ---- RPN training (include/ldit.h "RPN training"; csrc/rpn_train.hip) ----------------------------------------------------------
+RPN_TARGETS_MAX_ANCHORS = 16384          # per image (ldit_rpn_targets_f32)
+RPN_TARGETS_MAX_GT = 512
+
+
+def rpn_targets(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_count: torch.Tensor, keys: torch.Tensor, fg_iou_thresh: float = 0.7,
+                bg_iou_thresh: float = 0.3, batch_size_per_image: int = 256, positive_fraction: float = 0.5):
+    """Anchor matching (``Matcher(fg, bg, allow_low_quality_matches=True)``), the balanced sampler on the caller's ``keys`` and
+    ``BoxCoder(1, 1, 1, 1).encode`` in one launch.  ``anchors`` [N, 4], ``gt_boxes`` [B, Gmax, 4], ``gt_count`` int32 [B], ``keys``
+    int32 [B, N] (non-negative random priorities).  Returns ``labels`` int32 [B, N] (1 / 0 / -1 = sampled positive / sampled
+    negative / not in the loss), ``matched`` int32 [B, N] (GT index, -1 below the background threshold, -2 between the thresholds),
+    ``reg_targets`` [B, N, 4] (zero where the anchor is no positive) and ``sampled`` int32 [B, 2].  No synchronisation."""
+    lib = _lib.load()
+    anchors, gt_boxes = _req(anchors, "anchors"), _req(gt_boxes, "gt_boxes")
+    gt_count, keys = _req_i32(gt_count, "gt_count"), _req_i32(keys, "keys")
+    if anchors.dim() != 2 or anchors.shape[1] != 4 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise ValueError(f"rpn_targets: anchors {tuple(anchors.shape)} / gt_boxes {tuple(gt_boxes.shape)} are not [N, 4] / [B, Gmax, 4]")
+    N, (B, Gmax) = anchors.shape[0], gt_boxes.shape[:2]
+    if tuple(gt_count.shape) != (B,) or tuple(keys.shape) != (B, N):
+        raise ValueError(f"rpn_targets: gt_count {tuple(gt_count.shape)} / keys {tuple(keys.shape)} are not [{B}] / [{B}, {N}]")
+    if B == 0 or N == 0 or Gmax == 0:
+        raise ValueError("rpn_targets: empty problem (pad gt_boxes to at least one row)")
+    if batch_size_per_image <= 0 or not 0.0 < positive_fraction <= 1.0 or bg_iou_thresh > fg_iou_thresh:
+        raise ValueError("rpn_targets: need batch_size_per_image > 0, 0 < positive_fraction <= 1 and bg_iou_thresh <= fg_iou_thresh")
+    dev = anchors.device
+    labels = torch.empty((B, N), device=dev, dtype=torch.int32)
+    matched = torch.empty((B, N), device=dev, dtype=torch.int32)
+    reg_targets = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
+    sampled = torch.empty((B, 2), device=dev, dtype=torch.int32)
+    _launch(_device(anchors, gt_boxes, gt_count, keys), lib.ldit_rpn_targets_f32, _ptr(anchors), _ptr(gt_boxes), _ptr(gt_count), _ptr(keys),
+            B, N, Gmax, float(fg_iou_thresh), float(bg_iou_thresh), int(batch_size_per_image), float(positive_fraction), _ptr(labels),
+            _ptr(matched), _ptr(reg_targets), _ptr(sampled))
+    return labels, matched, reg_targets, sampled
+
+
+def rpn_loss(logits: torch.Tensor, deltas: torch.Tensor, labels: torch.Tensor, reg_targets: torch.Tensor, sampled: torch.Tensor,
+             beta: float = 1.0 / 9.0):
+    """The RPN's two losses and their gradients for unit upstream.  ``logits`` [B, N], ``deltas`` [B, N, 4] and the results of
+    :func:`rpn_targets`.  Returns ``loss`` [2] (objectness: mean BCE-with-logits over the sampled anchors of the batch; box:
+    smooth-L1(``beta``) summed over the sampled positives and divided by the same count), ``d_logits`` [B, N] and ``d_deltas``
+    [B, N, 4], exactly zero where an anchor is not in the loss.  No synchronisation."""
+    lib = _lib.load()
+    logits, deltas, reg_targets = _req(logits, "logits"), _req(deltas, "deltas"), _req(reg_targets, "reg_targets")
+    labels, sampled = _req_i32(labels, "labels"), _req_i32(sampled, "sampled")
+    if logits.dim() != 2 or 0 in logits.shape:
+        raise ValueError(f"rpn_loss: logits {tuple(logits.shape)} is not a non-empty [B, N]")
+    B, N = logits.shape
+    if tuple(deltas.shape) != (B, N, 4) or tuple(reg_targets.shape) != (B, N, 4) or tuple(labels.shape) != (B, N) or tuple(sampled.shape) != (B, 2):
+        raise ValueError(f"rpn_loss: logits {tuple(logits.shape)}, deltas {tuple(deltas.shape)}, labels {tuple(labels.shape)}, reg_targets "
+                         f"{tuple(reg_targets.shape)}, sampled {tuple(sampled.shape)} do not fit together")
+    if not beta >= 0.0:
+        raise ValueError("rpn_loss: beta must be >= 0")
+    dev = logits.device
+    loss = torch.empty((4,), device=dev, dtype=torch.float32)[:2]               # 16 bytes: the library wants aligned operands
+    d_logits = torch.empty((B, N), device=dev, dtype=torch.float32)
+    d_deltas = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
+    need = _lib.rpn_loss_workspace_bytes(B, N)
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    _launch(_device(logits, deltas, labels, reg_targets, sampled), lib.ldit_rpn_loss_f32, _ptr(logits), _ptr(deltas), _ptr(labels),
+            _ptr(reg_targets), _ptr(sampled), B, N, float(beta), _ptr(loss), _ptr(d_logits), _ptr(d_deltas), _ptr(ws), need)
+    return loss, d_logits, d_deltas
+
+
 # ---- box head (include/ldit.h "box head"; csrc/roi_heads.hip) ------------------------------------------------------------------
 NMS_MAX_CANDIDATES = 8192                # per problem (ldit_nms_batched_f32)
 
