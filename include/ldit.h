@@ -628,6 +628,76 @@ int ldit_rpn_loss_f32(const void *logits, const void *deltas, const void *labels
                       int64_t N, float beta, void *loss, void *d_logits, void *d_deltas, void *workspace, size_t workspace_bytes,
                       ldit_stream stream);
 
+/* ==== box head training (torchvision RoIHeads.select_training_samples + fastrcnn_loss and the gradient of MultiScaleRoIAlign, the
+ * other half of loss_dict = model(images, targets), ref training/trainer.py:164-183): add_gt_proposals, Matcher(0.5, 0.5,
+ * allow_low_quality_matches = False), BalancedPositiveNegativeSampler(512, 0.25), BoxCoder(10, 10, 5, 5).encode, the two losses and
+ * the transposed RoIAlign, restated from their documented behaviour (parity with torchvision itself unpinned, as for the RPN).
+ * Enqueue only: no allocation, no host synchronisation, no data-dependent shape, no float atomics, capturable; every output is a
+ * pure function of the inputs.  fp32 whatever the encoder build.  Additive to ABI 6.
+ *
+ * ldit_roi_targets_f32: proposals fp32 [B, R, 4] with count int32 [B] (clamped to [0, R]) - the RPN's padded train-mode output -,
+ *   gt_boxes fp32 [B, Gmax, 4], gt_labels int32 [B, Gmax] (values in [1, NC)), gt_count int32 [B] (clamped to [0, Gmax]), keys int32
+ *   [B, R + Gmax]: the caller's random priorities, non-negative (only the low 31 bits are read), weights HOST float[4] = the BoxCoder
+ *   weights (10, 10, 5, 5).  Rows at or past count[b] / gt_count[b] are never read.  R + Gmax <= 4096 (larger: LDIT_EUNSUPPORTED).
+ *   bg_thr > fg_thr (or a NaN), batch_size_per_image <= 0, positive_fraction outside (0, 1], a weight that is not > 0: LDIT_EINVAL.
+ *   One workgroup per image.
+ *   Candidates (add_gt_proposals).  Candidate r < R is proposal r (valid when r < count[b]), candidate R + g is GT box g (valid when
+ *     g < gt_count[b]); key r resp. R + g of the image's row of keys belongs to it.
+ *   Matching.  iou(candidate, gt) in fp32 exactly as ldit_nms_batched_f32 and ldit_rpn_targets_f32 compute it; a quotient that is not
+ *     > 0 counts as +0.  A candidate's match is the GT of largest IoU, ties to the LOWEST GT index.  best >= fg_thr: positive, its
+ *     class gt_labels[match].  best < bg_thr: background, class 0.  Otherwise (only when bg_thr < fg_thr) ignored: never sampled.
+ *     No low-quality promotion.  An image with gt_count 0: every proposal background.  A GT box matches itself (IoU 1).
+ *   Sampling.  The rule of ldit_rpn_targets_f32: quota = floor(batch_size_per_image * positive_fraction) (in double); of the positives
+ *     the min(quota, #positives) smallest by (key, candidate index) are taken, of the background candidates the
+ *     min(batch_size_per_image - taken positives, #background) smallest.
+ *   Outputs, S = batch_size_per_image, all written IN FULL.  ROW ORDER: the sampled positives in ascending (key, index) order, then
+ *     the sampled background rows in ascending (key, index) order, then padding.  torchvision orders the rows by candidate index;
+ *     both losses are sums over the rows, so that order is NOT reproduced.
+ *     rois fp32 [B, S, 4]: the candidate's box, bit for bit; padding rows zero.
+ *     labels int32 [B, S]: the class of a positive row, 0 for a background row, -1 for a padding row.
+ *     reg_targets fp32 [B, S, 4]: BoxCoder(wx, wy, ww, wh).encode(matched GT, candidate) for positive rows, zero elsewhere:
+ *       w = x2 - x1, cx = x1 + w / 2;  (wx (gcx - cx) / w, wy (gcy - cy) / h, ww log(gw / w), wh log(gh / h)).
+ *     matched int32 [B, S]: the GT index of a positive row, -1 elsewhere.  sampled int32 [B, 2]: positives and background rows taken.
+ * ldit_roi_align_levels_bwd_f32: the gradient of ldit_roi_align_levels_f32 with respect to its maps.  d_out fp32 [B S, P, P, C] (the
+ *   forward's output order), boxes fp32 [B, S, 4], count int32 [B] or NULL, levels int32 [B, S] AS THE FORWARD RETURNED THEM
+ *   (levels_out; the level is not recomputed; a value outside [0, L) contributes nothing, like a row at or past count[b]).
+ *   The L gradient maps are described like the forward's maps by HOST arrays of length L: d_maps[l] (device pointer, 16-byte
+ *   aligned), map_h / map_w / spatial_scale [l] and the element strides stride_b / stride_y / stride_x [l] (multiples of 4,
+ *   stride_x >= C, channel stride 1; the elements of one map must not overlap).  EVERY element (b, y, x, c) of every map is written
+ *   EXACTLY ONCE, zeros included: the caller clears nothing.  A level the forward read through a strided view (`pool`) gets a
+ *   gradient map of its own shape; adding it into the viewed map is the caller's business.  The forward's limits (C % 4 == 0,
+ *   L <= 8, P = 7, sampling_ratio = 2).
+ *   Semantics: the exact transpose of the forward - the same sample coordinates (the same fp32 expressions), the same < -1 / > n
+ *   rejection, clamping to 0, last-cell rule and 1 / 4 mean:
+ *     d_map[y, x, c] = (1 / 4) sum over the rows r of the level in ASCENDING r, ph = 0 .. 6, pw = 0 .. 6 (in that nesting) of
+ *                      (Ay_r[ph] Ax_r[pw]) d_out[r, ph, pw, c],
+ *     Ay_r[ph] = the sum over the bin's 2 samples (in sample order) of the weight the sample puts on row y (hy if y_low == y, plus ly
+ *     if y_high == y), Ax alike - the forward's weights are products of one y and one x factor, so the sum over a bin's 4 samples
+ *     separates.  Terms with a zero factor are skipped.  One accumulation chain per element, no atomics: bit-reproducible.
+ *   A fixed grid over (image, level, 4 x 4 pixel tile); one workgroup scans the image's rows once per 256 channels.
+ * ldit_box_loss_f32: torchvision fastrcnn_loss.  head_out fp32 [M, ld] in the layout of ldit_box_postprocess_f32 (logits in columns
+ *   [0, NC), the deltas of class c in [NC + 4 c, NC + 4 c + 4), ld >= 5 NC), labels int32 [M], reg_targets fp32 [M, 4] and sampled
+ *   int32 [B, 2] as ldit_roi_targets_f32 wrote them (M = B S), beta >= 0.  n = the sum of all 2 B entries of sampled, read on the device.
+ *     loss[0] = (1 / n) sum over label >= 0 of logsumexp(logits) - logit[label]     (cross_entropy, mean; max-subtracted, in double)
+ *     loss[1] = (1 / n) sum over label >= 1 and the 4 deltas OF THE ROW'S OWN CLASS of smooth_l1(delta - target; beta)
+ *   n == 0: both losses 0.  No positive: loss[1] == 0 exactly.  A label >= NC is outside the contract: the row is left out.
+ *   d_head fp32 [M, ld], written IN FULL, ONE buffer with the two gradients in their own column ranges: columns [0, NC) hold
+ *   d loss[0] / d logits = (softmax - onehot) / n, columns [NC, 5 NC) hold d loss[1] / d deltas; the caller scales each range by its
+ *   upstream scalar.  Padding columns, rows with label -1 and the deltas of every class but the row's own are
+ *   exactly zero.  Sums run in a fixed order (per-block partials, then one workgroup in double).
+ *   workspace: ldit_box_loss_workspace_bytes(M) bytes; a shorter buffer is refused with LDIT_EWORKSPACE. */
+int ldit_roi_targets_f32(const void *proposals, const void *count, const void *gt_boxes, const void *gt_labels, const void *gt_count,
+                         const void *keys, int32_t B, int64_t R, int32_t Gmax, float fg_thr, float bg_thr, int32_t batch_size_per_image,
+                         float positive_fraction, const float *weights, void *rois, void *labels, void *reg_targets, void *matched,
+                         void *sampled, ldit_stream stream);
+int ldit_roi_align_levels_bwd_f32(const void *d_out, const void *boxes, const void *count, const void *levels, int32_t B, int64_t S,
+                                  void *const *d_maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
+                                  const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C, int32_t P,
+                                  int32_t sampling_ratio, ldit_stream stream);
+size_t ldit_box_loss_workspace_bytes(int64_t M);
+int ldit_box_loss_f32(const void *head_out, int64_t ld, const void *labels, const void *reg_targets, const void *sampled, int32_t B, int64_t M,
+                      int32_t NC, float beta, void *loss, void *d_head, void *workspace, size_t workspace_bytes, ldit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

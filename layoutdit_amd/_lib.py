@@ -128,6 +128,13 @@ SIGNATURES = {
     "ldit_rpn_targets_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "ldit_rpn_loss_workspace_bytes": (_sz, [_i64, _i64]),
     "ldit_rpn_loss_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # box head training
+    "ldit_roi_targets_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _f32, C.POINTER(_f32), _vp, _vp, _vp,
+                                       _vp, _vp, _vp]),
+    "ldit_roi_align_levels_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32),
+                                                C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32, _i64, _i32, _i32, _vp]),
+    "ldit_box_loss_workspace_bytes": (_sz, [_i64]),
+    "ldit_box_loss_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
     # box head
     "ldit_roi_align_levels_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
                                             C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
@@ -174,6 +181,11 @@ def set_switch(name: str, value) -> None:
 def rpn_loss_workspace_bytes(batch: int, n: int) -> int:
     """Scratch bytes ``ldit_rpn_loss_f32`` wants for ``batch`` x ``n`` anchors (host arithmetic, no launch)."""
     return int(load().ldit_rpn_loss_workspace_bytes(batch, n))
+
+
+def box_loss_workspace_bytes(rows: int) -> int:
+    """Scratch bytes ``ldit_box_loss_f32`` wants for ``rows`` sampled rows (host arithmetic, no launch)."""
+    return int(load().ldit_box_loss_workspace_bytes(rows))
 
 
 def nms_workspace_bytes(problems: int, n: int) -> int:

@@ -14,7 +14,7 @@
 //
 // The IoU arithmetic decides labels, and the tests compare them exactly with a float32 oracle: contraction is off for this whole
 // file and the division is the correctly rounded one (the Makefile pins -fhip-fp32-correctly-rounded-divide-sqrt), as for proposals.hip.
-#include "ldit_common.h"
+#include "det_train_common.h"
 #include "sort_lds.h"
 
 #pragma clang fp contract(off)
@@ -25,21 +25,7 @@ namespace {
 constexpr int TGT_MAX_N = SORT_MAX_N;                    // anchors per image
 constexpr int TGT_MAX_G = 512;                           // GT boxes per image: 8 KiB of boxes + 2 KiB of maxima in LDS
 constexpr int TGT_LDS_EXTRA = 16;                        // two counters
-constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_PER_BLOCK = 1024;                     // anchors per block of the loss pass: four per thread
-
-// IoU of an anchor with a GT box: fp32, in the order of ldit_nms_batched_f32 (ldit.h).  A quotient that is not > 0 counts as +0
-// (disjoint boxes skip the division: 0 / positive is 0 anyway), so the bits are those of a non-negative float.
-__device__ __forceinline__ float iou_pair(const f32x4 a, float aarea, const f32x4 g, float garea)
-{
-    const float iw = fmaxf(fminf(a.z, g.z) - fmaxf(a.x, g.x), 0.f);
-    const float ih = fmaxf(fminf(a.w, g.w) - fmaxf(a.y, g.y), 0.f);
-    const float inter = iw * ih;
-    if (!(inter > 0.f)) return 0.f;
-    const float uni = (aarea + garea) - inter;
-    const float q = inter / uni;
-    return q > 0.f ? q : 0.f;
-}
 
 __global__ __launch_bounds__(SORT_THREADS) void rpn_targets_kernel(const f32x4 *__restrict__ anchors, const f32x4 *__restrict__ gt_boxes,
                                                                    const int *__restrict__ gt_count, const int *__restrict__ keys_in,
@@ -146,31 +132,6 @@ __global__ __launch_bounds__(SORT_THREADS) void rpn_targets_kernel(const f32x4 *
     }
 }
 
-// fixed-order sum over the workgroup; every thread gets the total
-__device__ __forceinline__ float block_sum(float v, float *red)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < LOSS_THREADS / 64; ++w) s += red[w];
-    return s;
-}
-
-// sum of sampled[0 .. 2 B): the anchors in the loss - an integer, whatever the order
-__device__ __forceinline__ int sampled_total(const int *__restrict__ sampled, int B, int *slot)
-{
-    if (threadIdx.x == 0) *slot = 0;
-    __syncthreads();
-    int s = 0;
-    for (int i = threadIdx.x; i < 2 * B; i += LOSS_THREADS) s += sampled[i];
-    if (s) atomicAdd(slot, s);
-    __syncthreads();
-    return *slot;
-}
-
 __global__ __launch_bounds__(LOSS_THREADS) void rpn_loss_kernel(const float *__restrict__ logits, const f32x4 *__restrict__ deltas,
                                                                 const int *__restrict__ labels, const f32x4 *__restrict__ reg_targets,
                                                                 const int *__restrict__ sampled, int B, int N, float beta,
@@ -232,25 +193,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void rpn_loss_final_kernel(const floa
     __shared__ double red[2][LOSS_THREADS];
     __shared__ int total_slot;
     const int total = sampled_total(sampled, B, &total_slot);
-    double c = 0.0, x = 0.0;
-    for (int i = threadIdx.x; i < n_partial; i += LOSS_THREADS) {
-        c += (double)partial[2 * i];
-        x += (double)partial[2 * i + 1];
-    }
-    red[0][threadIdx.x] = c;
-    red[1][threadIdx.x] = x;
-    __syncthreads();
-    for (int o = LOSS_THREADS / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + o];
-            red[1][threadIdx.x] += red[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        loss[0] = total > 0 ? (float)(red[0][0] / (double)total) : 0.f;
-        loss[1] = total > 0 ? (float)(red[1][0] / (double)total) : 0.f;
-    }
+    loss_final(partial, n_partial, total, loss, red);
 }
 
 inline int loss_blocks(int64_t N) { return (int)((N + LOSS_PER_BLOCK - 1) / LOSS_PER_BLOCK); }

@@ -7,8 +7,9 @@ images in, a list of ``{boxes, labels, scores}`` in each image's own coordinates
 
 The ``state_dict`` keys are the reference's (``model.backbone.*``, ``model.rpn.head.*``, ``model.roi_heads.box_head.fc6.*`` ...).
 Training: ``rpn_losses(images, targets)`` is the RPN half of the reference's ``loss_dict = model(images, targets)``
-(ref ``training/trainer.py:164-183``) - ``loss_objectness`` and ``loss_rpn_box_reg``, differentiable down to the encoder.  The box
-head's losses (proposal sampling, RoIAlign backward) are not implemented, so ``forward`` in train mode stays refused.
+(ref ``training/trainer.py:164-183``) - ``loss_objectness`` and ``loss_rpn_box_reg``; ``losses(images, targets)`` is the whole dict,
+with the box head's ``loss_classifier`` and ``loss_box_reg`` on the RPN's (detached) train-mode proposals - all four differentiable
+down to the encoder.  ``forward`` and ``forward_padded`` keep torchvision's eval surface and stay refused in train mode.
 """
 from __future__ import annotations
 
@@ -57,7 +58,8 @@ class LayoutDetectionModel(nn.Module):
         in the coordinates of the batch, zero padding, no synchronisation."""
         m = self.model
         if self.training:
-            raise RuntimeError("LayoutDetectionModel: inference only (the RPN and box head losses are not implemented) - call .eval() first")
+            raise RuntimeError("LayoutDetectionModel: forward_padded is inference only (the four losses are losses(images, targets)) - "
+                               "call .eval() first")
         image_size = tuple(batch.shape[-2:])
         with torch.no_grad():
             feats = m.backbone(batch)
@@ -70,8 +72,8 @@ class LayoutDetectionModel(nn.Module):
         """The RPN half of the reference's loss dict: ``{"loss_objectness", "loss_rpn_box_reg"}`` for a list of ``[3, h, w]`` images
         and the reference's targets (``{"boxes": [G, 4] in the image's own coordinates, ...}`` per image).  Train mode only.  The
         transform rescales the boxes with the images, the backbone runs with gradients, the RPN in train mode; ``backward()`` on
-        the losses reaches ``rpn.head``, the FPN and the encoder.  ``loss_classifier`` / ``loss_box_reg`` of the box head are not
-        implemented (see ``forward``).  ``generator`` seeds the sampler's keys."""
+        the losses reaches ``rpn.head``, the FPN and the encoder.  :meth:`losses` adds the box head's two.  ``generator`` seeds the
+        sampler's keys."""
         if not self.training:
             raise RuntimeError("LayoutDetectionModel.rpn_losses: train mode only - call .train() first")
         if targets is None:
@@ -83,10 +85,31 @@ class LayoutDetectionModel(nn.Module):
         _, losses = m.rpn(feats, tuple(batch.shape[-2:]), targets=targets, padded=True, generator=generator)
         return losses
 
+    def losses(self, images: List[torch.Tensor], targets: List[Dict[str, torch.Tensor]],
+               generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """The reference's ``loss_dict = model(images, targets)``: ``{"loss_classifier", "loss_box_reg", "loss_objectness",
+        "loss_rpn_box_reg"}`` for a list of ``[3, h, w]`` images and targets ``{"boxes": [G, 4] in the image's own coordinates,
+        "labels": [G] in [1, num_classes]}``.  Train mode only.  The transform and the backbone run once; the RPN in train mode gives
+        its two losses and its proposals (detached), the box head samples from them and gives the other two.  ``backward()`` on the
+        sum reaches the box head, ``rpn.head``, the FPN and the encoder.  ``generator`` seeds both samplers' keys."""
+        if not self.training:
+            raise RuntimeError("LayoutDetectionModel.losses: train mode only - call .train() first")
+        if targets is None:
+            raise ValueError("LayoutDetectionModel.losses: targets are required")
+        m = self.model
+        image_list, targets = m.transform(images, targets)
+        batch = image_list.tensors
+        image_size = tuple(batch.shape[-2:])
+        feats = {k: _nhwc_f32(v) for k, v in m.backbone(batch).items()}
+        (proposals, _, count), rpn_losses = m.rpn(feats, image_size, targets=targets, padded=True, generator=generator)
+        out = m.roi_heads(feats, proposals.detach(), count, image_size, targets=targets, padded=True, generator=generator)
+        out.update(rpn_losses)
+        return out
+
     def forward(self, images: List[torch.Tensor], targets=None) -> List[Dict[str, torch.Tensor]]:
         if self.training or targets is not None:
-            raise RuntimeError("LayoutDetectionModel: inference only (the RPN and box head losses are not implemented) - call .eval() "
-                               "first and pass no targets")
+            raise RuntimeError("LayoutDetectionModel: forward is inference only (the four losses are losses(images, targets)) - call "
+                               ".eval() first and pass no targets")
         m = self.model
         original = [tuple(img.shape[-2:]) for img in images]
         image_list, _ = m.transform(images)

@@ -14,7 +14,15 @@ translated:
   with fixed-size padded results: ``forward(..., padded=True)`` never synchronises; the list form slices by the count (one
   synchronisation).
 
-Inference only: proposal sampling, matching and the losses are not implemented, ``train()`` mode is refused.  torchvision is not
+Training (``train()`` mode with targets): ``select_training_samples`` - the GT boxes join the proposals, ``Matcher(0.5, 0.5)``,
+``BalancedPositiveNegativeSampler(512, 0.25)``, ``BoxCoder(10, 10, 5, 5).encode`` - is ONE launch with fixed-size results and
+``fastrcnn_loss`` with its gradient two more (``csrc/roi_train.hip``); the sampler is driven by random keys drawn on the device, so
+nothing synchronises.  :class:`MultiScaleRoIAlign` is differentiated by one ``torch.autograd.Function`` over the five maps whose
+backward is ONE gather launch without atomics; :class:`TwoMLPHead` and :class:`FastRCNNPredictor` by one function each whose
+backward runs on the library's kernels like the RPN head's (``ldit_linear_f32`` on the transposed weights, bf16 MFMA weight
+gradients with fp32 accumulation, ``ldit_colsum_f32`` for the biases; ``fc6``'s gradient is permuted back to torchvision's columns).
+The sampled rows come out positives first, not in torchvision's candidate order - the losses are sums.  ``train()`` mode WITHOUT
+targets stays refused.  torchvision is not
 installed offline: the semantics are restated from its documented behaviour (``tests/roi_oracle.py``) - parity unpinned with
 respect to torchvision itself, as for the FPN and the RPN.  Parameter names follow torchvision, so detector checkpoints load
 (``roi_heads.box_head.fc6.weight`` ...).
@@ -42,6 +50,29 @@ def _nhwc_f32(f: torch.Tensor) -> torch.Tensor:
     return f
 
 
+class _RoIAlignLevelsFn(torch.autograd.Function):
+    """``ldit_roi_align_levels_f32`` with a gradient for every map: the forward keeps the level of each row, the backward is ONE launch
+    of the gather kernel (``csrc/roi_train.hip``) and hands autograd NCHW views of the NHWC gradients it wrote - a strided view such
+    as ``pool`` gets a gradient of its own shape, autograd adds it into the viewed map.
+    apply(boxes, count, image_size, output_size, sampling_ratio, canonical_scale, canonical_level, *maps) -> [B R, P, P, C]."""
+
+    @staticmethod
+    def forward(ctx, boxes, count, image_size, output_size, sampling_ratio, canonical_scale, canonical_level, *maps):
+        out, levels = ops.roi_align_levels([_nhwc_f32(f.detach()) for f in maps], boxes, count, image_size, output_size, sampling_ratio,
+                                           canonical_scale, canonical_level, return_levels=True)
+        ctx.save_for_backward(boxes, levels) if count is None else ctx.save_for_backward(boxes, levels, count)
+        ctx.geometry = ([tuple(f.shape[-2:]) for f in maps], tuple(image_size), output_size, sampling_ratio)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        boxes, levels = ctx.saved_tensors[:2]
+        count = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        shapes, image_size, output_size, sampling_ratio = ctx.geometry
+        grads = ops.roi_align_levels_bwd(d_out.contiguous(), boxes, count, levels, shapes, image_size, output_size, sampling_ratio)
+        return (None,) * 7 + tuple(grads)
+
+
 class MultiScaleRoIAlign(nn.Module):
     """torchvision's ``MultiScaleRoIAlign(featmap_names, output_size, sampling_ratio)`` on padded proposals."""
 
@@ -61,8 +92,111 @@ class MultiScaleRoIAlign(nn.Module):
         """``features``: the named maps (or the maps themselves, finest first), ``boxes`` [B, R, 4], ``count`` int32 [B] or None.
         Returns ``[B * R, P, P, C]``; rows past the count are zero."""
         feats = [features[n] for n in self.featmap_names] if isinstance(features, dict) else list(features)
+        if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
+            # gradients are wanted for the maps: the differentiable node (the path below is untouched)
+            return _RoIAlignLevelsFn.apply(boxes.detach(), count, tuple(image_size), self.output_size, self.sampling_ratio,
+                                           self.canonical_scale, self.canonical_level, *feats)
         return ops.roi_align_levels([_nhwc_f32(f.detach()) for f in feats], boxes, count, image_size, self.output_size,
                                     self.sampling_ratio, self.canonical_scale, self.canonical_level)
+
+
+def _linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: bool, need_w: bool, need_b: bool):
+    """Gradients of ``y = x @ weight.T + bias`` on the library's kernels, as the RPN head's: the input gradient is ``ldit_linear_f32``
+    on the transposed weight, the weight gradient a bf16 MFMA GEMM on reduction-major operands with fp32 accumulation (it carries
+    bf16 operand rounding), the bias gradient ``ldit_colsum_f32``.  ``dy`` [M, N], ``x`` [M, K], ``weight`` [N, K]; N % 32 == 0."""
+    M = dy.shape[0]
+    g_x = ops.linear(dy, weight.t().contiguous()) if need_x else None
+    g_w = ops.wgrad_bf16(ops.cast_bf16(dy), ops.cast_bf16(x), M) if need_w else None
+    g_b = ops.colsum(dy) if need_b else None
+    return g_x, g_w, g_b
+
+
+class _TwoMLPHeadFn(torch.autograd.Function):
+    """:class:`TwoMLPHead` with gradients for the pooled rows and the four parameters.
+    apply(pooled [M, P, P, C], fc6.weight, fc6.bias, fc7.weight, fc7.bias) -> [M, representation_size]."""
+
+    @staticmethod
+    def forward(ctx, pooled, w6, b6, w7, b7):
+        M, ph, pw, Cc = pooled.shape
+        x0 = pooled.detach().reshape(M, ph * pw * Cc)
+        w6p = w6.detach().view(w6.shape[0], Cc, ph, pw).permute(0, 2, 3, 1).reshape(w6.shape[0], -1).contiguous()      # (ph, pw, c) columns
+        h6 = ops.linear(x0, w6p, b6.detach())
+        torch.relu_(h6)
+        h7 = ops.linear(h6, w7.detach().contiguous(), b7.detach())
+        torch.relu_(h7)
+        ctx.saved = (x0, w6p, h6, w7.detach(), h7)
+        ctx.pooled_shape = (M, ph, pw, Cc)
+        return h7.clone()                                             # the saved activation is the ReLU mask: keep it private
+
+    @staticmethod
+    def backward(ctx, d7):
+        if ctx.saved is None:
+            raise RuntimeError("TwoMLPHead: backward a second time (its saved activations are freed after the first)")
+        x0, w6p, h6, w7, h7 = ctx.saved
+        ctx.saved = None
+        M, ph, pw, Cc = ctx.pooled_shape
+        need = ctx.needs_input_grad
+        d7 = d7.contiguous() * (h7 > 0)                               # ReLU mask
+        d6, g_w7, g_b7 = _linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4])
+        d6.mul_(h6 > 0)
+        g_x, g_w6p, g_b6 = _linear_bwd(d6, x0, w6p, need[0], need[1], need[2])
+        g_w6 = None
+        if g_w6p is not None:                                         # back to torchvision's (c, ph, pw) columns
+            g_w6 = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
+        return (g_x.view(M, ph, pw, Cc) if g_x is not None else None), g_w6, g_b6, g_w7, g_b7
+
+
+class _PredictorFn(torch.autograd.Function):
+    """:class:`FastRCNNPredictor`'s stacked GEMM with gradients for its input and the four parameters; the stacked weight gradient
+    is split back into ``cls_score`` and ``bbox_pred``.  apply(x [M, K], cls_score.weight, .bias, bbox_pred.weight, .bias) ->
+    [M, 5 NC (padded to a multiple of 32)]: the padding columns are zero."""
+
+    @staticmethod
+    def forward(ctx, x, wc, bc, wb, bb):
+        NC = wc.shape[0]
+        rows = (5 * NC + 31) // 32 * 32                               # the K of the dgrad GEMM, a multiple of 8 for the wgrad
+        w = torch.zeros((rows, wc.shape[1]), device=x.device, dtype=torch.float32)
+        b = torch.zeros((rows,), device=x.device, dtype=torch.float32)
+        w[:NC], w[NC:5 * NC] = wc.detach(), wb.detach()
+        b[:NC], b[NC:5 * NC] = bc.detach(), bb.detach()
+        x = x.detach().contiguous()
+        ctx.saved = (x, w)
+        ctx.NC = NC
+        return ops.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.saved is None:
+            raise RuntimeError("FastRCNNPredictor: backward a second time (its saved input is freed after the first)")
+        x, w = ctx.saved
+        ctx.saved = None
+        NC, need = ctx.NC, ctx.needs_input_grad
+        g_x, g_w, g_b = _linear_bwd(dy.contiguous(), x, w, need[0], need[1] or need[3], need[2] or need[4])
+        return (g_x, g_w[:NC] if need[1] else None, g_b[:NC] if need[2] else None, g_w[NC:5 * NC] if need[3] else None,
+                g_b[NC:5 * NC] if need[4] else None)
+
+
+class _BoxLossFn(torch.autograd.Function):
+    """``ldit_box_loss_f32`` as a differentiable node: the kernel has already written both gradients for unit upstream into their
+    column ranges of one buffer, the backward scales each range by its upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, head_out, labels, reg_targets, sampled, num_classes, beta):
+        loss, d_head = ops.box_loss(head_out.detach().contiguous(), labels, reg_targets, sampled, num_classes, beta)
+        ctx.save_for_backward(d_head)
+        ctx.NC = int(num_classes)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box):
+        (d_head,) = ctx.saved_tensors
+        NC, ld = ctx.NC, d_head.shape[1]
+        scale = torch.cat([g_cls.reshape(1).expand(NC), g_box.reshape(1).expand(4 * NC), d_head.new_zeros(ld - 5 * NC)])
+        return d_head * scale, None, None, None, None, None
+
+
+def _wants_grad(module: nn.Module, x: torch.Tensor) -> bool:
+    return module.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
 
 
 class TwoMLPHead(nn.Module):
@@ -90,6 +224,11 @@ class TwoMLPHead(nn.Module):
         if pooled.dim() != 4:
             raise ValueError(f"TwoMLPHead: expected pooled rows [M, P, P, C], got {tuple(pooled.shape)}")
         M, ph, pw, Cc = pooled.shape
+        if Cc * ph * pw != self.fc6.weight.shape[1]:
+            raise ValueError(f"TwoMLPHead: pooled rows of {ph} x {pw} x {Cc} do not match fc6's {self.fc6.weight.shape[1]} inputs")
+        if _wants_grad(self, pooled):
+            # gradients are wanted: the differentiable node (the eval path below and its cache are untouched)
+            return _TwoMLPHeadFn.apply(pooled, self.fc6.weight, self.fc6.bias, self.fc7.weight, self.fc7.bias)
         x = ops.linear(pooled.reshape(M, ph * pw * Cc), self.fc6_weight_hwc(Cc, ph, pw), self.fc6.bias.detach())
         torch.relu_(x)
         x = ops.linear(x, self.fc7.weight.detach(), self.fc7.bias.detach())
@@ -123,6 +262,9 @@ class FastRCNNPredictor(nn.Module):
 
     def forward_stacked(self, x: torch.Tensor) -> torch.Tensor:
         """[M, in_channels] -> [M, 5 NC (+ pad)]: the class logits in columns [0, NC), the deltas in [NC, 5 NC)."""
+        if _wants_grad(self, x):
+            # gradients are wanted: the differentiable node, its row padded to a multiple of 32 columns (the eval path is untouched)
+            return _PredictorFn.apply(x, self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias)
         w, b = self._operands()
         return ops.linear(x, w, b)
 
@@ -132,28 +274,89 @@ class FastRCNNPredictor(nn.Module):
 
 
 class RoIHeads(nn.Module):
-    """torchvision's ``RoIHeads`` in eval mode (box branch).  ``forward(features, proposals, count, image_size)`` returns the list of
+    """torchvision's ``RoIHeads`` (box branch).  Eval mode: ``forward(features, proposals, count, image_size)`` returns the list of
     ``{boxes, labels, scores}`` per image; with ``padded=True`` the fixed-size form ``(boxes [B, D, 4], scores [B, D], labels [B, D],
-    count [B])``, ``D = detections_per_img``."""
+    count [B])``, ``D = detections_per_img``.  Train mode with ``targets`` (the reference's list of ``{"boxes", "labels"}`` or the
+    padded triple of :meth:`pad_targets`): ``{"loss_classifier", "loss_box_reg"}``; ``generator`` seeds the sampler's keys."""
 
     def __init__(self, box_roi_pool: MultiScaleRoIAlign, box_head: TwoMLPHead, box_predictor: FastRCNNPredictor,
                  bbox_reg_weights: Optional[Sequence[float]] = None, score_thresh: float = 0.05, nms_thresh: float = 0.5,
-                 detections_per_img: int = 100, min_size: float = 1e-2):
+                 detections_per_img: int = 100, min_size: float = 1e-2, fg_iou_thresh: float = 0.5, bg_iou_thresh: float = 0.5,
+                 batch_size_per_image: int = 512, positive_fraction: float = 0.25):
         super().__init__()
         self.box_roi_pool, self.box_head, self.box_predictor = box_roi_pool, box_head, box_predictor
         self.bbox_reg_weights = tuple(float(w) for w in (bbox_reg_weights or (10.0, 10.0, 5.0, 5.0)))
         self.score_thresh, self.nms_thresh, self.min_size = float(score_thresh), float(nms_thresh), float(min_size)
         self.detections_per_img = int(detections_per_img)
+        self.fg_iou_thresh, self.bg_iou_thresh = float(fg_iou_thresh), float(bg_iou_thresh)
+        self.batch_size_per_image, self.positive_fraction = int(batch_size_per_image), float(positive_fraction)
+        self.smooth_l1_beta = 1.0 / 9.0                               # torchvision's fastrcnn_loss
 
     def head_padded(self, features, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size: Tuple[int, int]) -> torch.Tensor:
         """RoIAlign and the three GEMMs: ``[B * R, 5 NC (+ pad)]`` logits | deltas per proposal row."""
         pooled = self.box_roi_pool(features, proposals, count, image_size)
         return self.box_predictor.forward_stacked(self.box_head(pooled))
 
-    def forward(self, features, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size: Tuple[int, int], padded: bool = False):
+    @staticmethod
+    def pad_targets(targets, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The reference's list of ``{"boxes": [G_i, 4], "labels": [G_i]}`` -> ``(gt_boxes fp32 [B, Gmax, 4], gt_labels int32
+        [B, Gmax], gt_count int32 [B])``.  The shapes are known on the host: copies, no synchronisation.  A padded triple passes
+        through."""
+        if isinstance(targets, (tuple, list)) and len(targets) == 3 and isinstance(targets[0], torch.Tensor):
+            gt_boxes, gt_labels, gt_count = targets
+            if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4 or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]) or \
+                    tuple(gt_count.shape) != (gt_boxes.shape[0],):
+                raise ValueError(f"RoIHeads: padded targets {tuple(gt_boxes.shape)} / {tuple(gt_labels.shape)} / {tuple(gt_count.shape)} are "
+                                 "not [B, Gmax, 4] / [B, Gmax] / [B]")
+            return (gt_boxes.to(device=device, dtype=torch.float32).contiguous(), gt_labels.to(device=device, dtype=torch.int32).contiguous(),
+                    gt_count.to(device=device, dtype=torch.int32).contiguous())
+        for t in targets:
+            bx, lb = t["boxes"], t["labels"]
+            if bx.dim() != 2 or bx.shape[1] != 4 or tuple(lb.shape) != (bx.shape[0],):
+                raise ValueError(f"RoIHeads: target boxes {tuple(bx.shape)} / labels {tuple(lb.shape)} are not [G, 4] / [G]")
+        gmax = max(max(int(t["boxes"].shape[0]) for t in targets), 1)
+        gt_boxes = torch.zeros((len(targets), gmax, 4), device=device, dtype=torch.float32)
+        gt_labels = torch.zeros((len(targets), gmax), device=device, dtype=torch.int32)
+        for i, t in enumerate(targets):
+            g = int(t["boxes"].shape[0])
+            if g:
+                gt_boxes[i, :g] = t["boxes"].detach().to(device=device, dtype=torch.float32)
+                gt_labels[i, :g] = t["labels"].detach().to(device=device, dtype=torch.int32)
+        gt_count = torch.tensor([int(t["boxes"].shape[0]) for t in targets], dtype=torch.int32).to(device)
+        return gt_boxes, gt_labels, gt_count
+
+    def select_training_samples_padded(self, proposals: torch.Tensor, count: Optional[torch.Tensor], gt_boxes: torch.Tensor,
+                                       gt_labels: torch.Tensor, gt_count: torch.Tensor, generator: Optional[torch.Generator] = None):
+        """Keys and ``ldit_roi_targets_f32``: ``(rois [B, S, 4], labels, reg_targets, matched, sampled)``.  No synchronisation."""
+        B, R = proposals.shape[:2]
+        if gt_boxes.shape[0] != B:
+            raise ValueError(f"RoIHeads: {gt_boxes.shape[0]} targets for {B} images")
+        if count is None:
+            count = torch.full((B,), R, device=proposals.device, dtype=torch.int32)
+        keys = torch.randint(0, 2 ** 31 - 1, (B, R + gt_boxes.shape[1]), device=proposals.device, dtype=torch.int32, generator=generator)
+        return ops.roi_targets(proposals.detach().contiguous(), count, gt_boxes, gt_labels, gt_count, keys, self.fg_iou_thresh,
+                               self.bg_iou_thresh, self.batch_size_per_image, self.positive_fraction, self.bbox_reg_weights)
+
+    def losses_padded(self, features, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size: Tuple[int, int], gt_boxes: torch.Tensor,
+                      gt_labels: torch.Tensor, gt_count: torch.Tensor, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """Sampling, RoIAlign on the sampled rows, the head and ``fastrcnn_loss``: differentiable down to the maps, no
+        synchronisation."""
+        rois, labels, reg_targets, _, sampled = self.select_training_samples_padded(proposals, count, gt_boxes, gt_labels, gt_count, generator)
+        rows = sampled.sum(dim=1, dtype=torch.int32)                  # the sampled rows sit in front of the padding
+        y = self.head_padded(features, rois, rows, image_size)
+        cls, box = _BoxLossFn.apply(y, labels, reg_targets, sampled, self.box_predictor.num_classes, self.smooth_l1_beta)
+        return {"loss_classifier": cls, "loss_box_reg": box}
+
+    def forward(self, features, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size: Tuple[int, int], targets=None,
+                padded: bool = False, generator: Optional[torch.Generator] = None):
         if self.training:
-            raise RuntimeError("RoIHeads: inference only (proposal sampling, matching and the box losses are not implemented) - "
-                               "call .eval() first")
+            if targets is None:
+                raise RuntimeError("RoIHeads: inference only without targets (in train mode the box losses need them) - pass targets or "
+                                   "call .eval() first")
+            if proposals.dim() != 3 or proposals.shape[-1] != 4:
+                raise ValueError(f"RoIHeads: expected padded proposals [B, R, 4], got {tuple(proposals.shape)}")
+            gt_boxes, gt_labels, gt_count = self.pad_targets(targets, proposals.device)
+            return self.losses_padded(features, proposals, count, image_size, gt_boxes, gt_labels, gt_count, generator)
         if proposals.dim() != 3 or proposals.shape[-1] != 4:
             raise ValueError(f"RoIHeads: expected padded proposals [B, R, 4], got {tuple(proposals.shape)}")
         ops._check_candidates(proposals.shape[1], self.box_predictor.num_classes)

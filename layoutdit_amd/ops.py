@@ -901,3 +901,115 @@ def box_detections_padded(head_out: torch.Tensor, proposals: torch.Tensor, count
     keep, kept, out_boxes, out_scores = batched_nms_padded(boxes, scores, labels, nms_thresh, detections_per_img)
     picked = labels.gather(1, keep.clamp(min=0).to(torch.int64))
     return out_boxes, out_scores, torch.where(keep >= 0, picked, torch.zeros_like(picked)), kept
+
+
+# ---- box head training (include/ldit.h "box head training"; csrc/roi_train.hip) ------------------------------------------------
+ROI_TARGETS_MAX_CANDIDATES = 4096        # proposals + GT boxes per image (ldit_roi_targets_f32)
+
+
+def roi_targets(proposals: torch.Tensor, count: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_count: torch.Tensor,
+                keys: torch.Tensor, fg_iou_thresh: float = 0.5, bg_iou_thresh: float = 0.5, batch_size_per_image: int = 512,
+                positive_fraction: float = 0.25, weights=(10.0, 10.0, 5.0, 5.0)):
+    """``RoIHeads.select_training_samples`` in one launch: the GT boxes join the proposals, ``Matcher(fg, bg)``, the balanced sampler
+    on the caller's ``keys`` and ``BoxCoder(weights).encode``.  ``proposals`` [B, R, 4] with ``count`` int32 [B], ``gt_boxes``
+    [B, Gmax, 4], ``gt_labels`` int32 [B, Gmax], ``gt_count`` int32 [B], ``keys`` int32 [B, R + Gmax] (non-negative random
+    priorities).  Returns, with ``S = batch_size_per_image``, ``rois`` [B, S, 4], ``labels`` int32 [B, S] (class / 0 = background /
+    -1 = padding), ``reg_targets`` [B, S, 4], ``matched`` int32 [B, S] (GT index or -1) and ``sampled`` int32 [B, 2]; the sampled
+    positives come first, then the background rows, each in (key, index) order, then zero padding.  No synchronisation."""
+    lib = _lib.load()
+    proposals, gt_boxes = _req(proposals, "proposals"), _req(gt_boxes, "gt_boxes")
+    count, gt_labels = _req_i32(count, "count"), _req_i32(gt_labels, "gt_labels")
+    gt_count, keys = _req_i32(gt_count, "gt_count"), _req_i32(keys, "keys")
+    if proposals.dim() != 3 or proposals.shape[2] != 4 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise ValueError(f"roi_targets: proposals {tuple(proposals.shape)} / gt_boxes {tuple(gt_boxes.shape)} are not [B, R, 4] / [B, Gmax, 4]")
+    (B, R), Gmax = proposals.shape[:2], gt_boxes.shape[1]
+    if gt_boxes.shape[0] != B or tuple(gt_labels.shape) != (B, Gmax) or tuple(count.shape) != (B,) or tuple(gt_count.shape) != (B,) or \
+            tuple(keys.shape) != (B, R + Gmax):
+        raise ValueError(f"roi_targets: gt_boxes {tuple(gt_boxes.shape)}, gt_labels {tuple(gt_labels.shape)}, count {tuple(count.shape)}, gt_count "
+                         f"{tuple(gt_count.shape)}, keys {tuple(keys.shape)} do not fit [{B}, {R}, 4] proposals")
+    if B == 0 or R == 0 or Gmax == 0:
+        raise ValueError("roi_targets: empty problem (pad gt_boxes to at least one row)")
+    if batch_size_per_image <= 0 or not 0.0 < positive_fraction <= 1.0 or bg_iou_thresh > fg_iou_thresh:
+        raise ValueError("roi_targets: need batch_size_per_image > 0, 0 < positive_fraction <= 1 and bg_iou_thresh <= fg_iou_thresh")
+    if R + Gmax > ROI_TARGETS_MAX_CANDIDATES:
+        raise ValueError(f"roi_targets: {R} proposals + {Gmax} GT boxes per image, at most {ROI_TARGETS_MAX_CANDIDATES} candidates are handled")
+    dev, S = proposals.device, int(batch_size_per_image)
+    rois = torch.empty((B, S, 4), device=dev, dtype=torch.float32)
+    labels = torch.empty((B, S), device=dev, dtype=torch.int32)
+    reg_targets = torch.empty((B, S, 4), device=dev, dtype=torch.float32)
+    matched = torch.empty((B, S), device=dev, dtype=torch.int32)
+    sampled = torch.empty((B, 2), device=dev, dtype=torch.int32)
+    _launch(_device(proposals, count, gt_boxes, gt_labels, gt_count, keys), lib.ldit_roi_targets_f32, _ptr(proposals), _ptr(count), _ptr(gt_boxes),
+            _ptr(gt_labels), _ptr(gt_count), _ptr(keys), B, R, Gmax, float(fg_iou_thresh), float(bg_iou_thresh), S, float(positive_fraction),
+            (C.c_float * 4)(*[float(w) for w in weights]), _ptr(rois), _ptr(labels), _ptr(reg_targets), _ptr(matched), _ptr(sampled))
+    return rois, labels, reg_targets, matched, sampled
+
+
+def roi_align_levels_bwd(d_out: torch.Tensor, boxes: torch.Tensor, count: Optional[torch.Tensor], levels: torch.Tensor,
+                         map_shapes: Sequence, image_size, output_size: int = 7, sampling_ratio: int = 2, out: Optional[Sequence[torch.Tensor]] = None):
+    """The gradient of :func:`roi_align_levels` with respect to its maps, in one launch without atomics.  ``d_out`` [B * S, P, P, C],
+    ``boxes`` [B, S, 4], ``count`` int32 [B] or None and ``levels`` int32 [B, S] as the forward returned them; ``map_shapes``: the
+    ``(h, w)`` of every map, finest first.  Returns one gradient per map as a ``[B, C, h, w]`` tensor in channels-last memory (an
+    NCHW view of the NHWC buffer the kernel writes), every element written exactly once; ``out`` supplies such tensors (channel
+    stride 1, any batch / row / pixel stride) instead of fresh ones.  No synchronisation."""
+    lib = _lib.load()
+    d_out, boxes, levels = _req(d_out, "d_out"), _req(boxes, "boxes"), _req_i32(levels, "levels")
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or 0 in boxes.shape:
+        raise ValueError(f"roi_align_levels_bwd: boxes {tuple(boxes.shape)} is not a non-empty [B, S, 4]")
+    B, S = boxes.shape[:2]
+    P = int(output_size)
+    if d_out.dim() != 4 or tuple(d_out.shape[:3]) != (B * S, P, P) or tuple(levels.shape) != (B, S):
+        raise ValueError(f"roi_align_levels_bwd: d_out {tuple(d_out.shape)} / levels {tuple(levels.shape)} are not [{B * S}, {P}, {P}, C] / [{B}, {S}]")
+    if count is not None and tuple(_req_i32(count, "count").shape) != (B,):
+        raise ValueError(f"count {tuple(count.shape)} is not [{B}]")
+    Cc = d_out.shape[3]
+    shapes = [(int(h), int(w)) for h, w in map_shapes]
+    if not shapes:
+        raise ValueError("roi_align_levels_bwd: there is no feature map")
+    if out is None:
+        grads = [torch.empty((B, h, w, Cc), device=d_out.device, dtype=torch.float32).permute(0, 3, 1, 2) for h, w in shapes]
+    else:
+        grads = list(out)
+        for i, (g, (h, w)) in enumerate(zip(grads, shapes)):
+            if not isinstance(g, torch.Tensor) or not g.is_cuda or g.dtype != torch.float32 or tuple(g.shape) != (B, Cc, h, w) or g.stride(1) != 1:
+                raise ValueError(f"out[{i}]: expected a float32 [{B}, {Cc}, {h}, {w}] GPU tensor in channels-last memory")
+        if len(grads) != len(shapes):
+            raise ValueError("roi_align_levels_bwd: one output per map")
+    scales = infer_scales(grads, image_size)
+    L = len(grads)
+    _launch(_device(d_out, boxes, count, levels, *grads), lib.ldit_roi_align_levels_bwd_f32, _ptr(d_out), _ptr(boxes), _ptr(count), _ptr(levels),
+            B, S, (C.c_void_p * L)(*[g.data_ptr() for g in grads]), (C.c_int32 * L)(*[h for h, _ in shapes]), (C.c_int32 * L)(*[w for _, w in shapes]),
+            (C.c_float * L)(*scales), (C.c_int64 * L)(*[g.stride(0) for g in grads]), (C.c_int64 * L)(*[g.stride(2) for g in grads]),
+            (C.c_int64 * L)(*[g.stride(3) for g in grads]), L, Cc, P, int(sampling_ratio))
+    return grads
+
+
+def box_loss(head_out: torch.Tensor, labels: torch.Tensor, reg_targets: torch.Tensor, sampled: torch.Tensor, num_classes: int,
+             beta: float = 1.0 / 9.0):
+    """torchvision ``fastrcnn_loss`` and its gradient for unit upstream.  ``head_out`` [M, ld] (class logits in columns ``[0, NC)``,
+    deltas in ``[NC, 5 NC)``) and ``labels`` [B, S] / ``reg_targets`` [B, S, 4] / ``sampled`` [B, 2] of :func:`roi_targets`, ``M = B S``.
+    Returns ``loss`` [2] (classifier: cross-entropy summed over the sampled rows of the batch and divided by their number; box:
+    smooth-L1(``beta``) over the sampled positives' own class, divided by the same number) and ``d_head`` [M, ld]: ONE buffer,
+    columns ``[0, NC)`` the gradient of ``loss[0]``, columns ``[NC, 5 NC)`` that of ``loss[1]``, exactly zero everywhere else.
+    No synchronisation."""
+    lib = _lib.load()
+    head_out, reg_targets = _req(head_out, "head_out"), _req(reg_targets, "reg_targets")
+    labels, sampled = _req_i32(labels, "labels"), _req_i32(sampled, "sampled")
+    NC = int(num_classes)
+    if head_out.dim() != 2 or 0 in head_out.shape or NC < 2 or head_out.shape[1] < 5 * NC:
+        raise ValueError(f"box_loss: head_out {tuple(head_out.shape)} is not a non-empty [M, >= {5 * NC}]")
+    M, ld = head_out.shape
+    if labels.numel() != M or reg_targets.numel() != 4 * M or reg_targets.shape[-1] != 4 or sampled.dim() != 2 or sampled.shape[1] != 2 or \
+            sampled.shape[0] == 0:
+        raise ValueError(f"box_loss: head_out {tuple(head_out.shape)}, labels {tuple(labels.shape)}, reg_targets {tuple(reg_targets.shape)}, "
+                         f"sampled {tuple(sampled.shape)} do not fit together")
+    if not beta >= 0.0:
+        raise ValueError("box_loss: beta must be >= 0")
+    dev = head_out.device
+    loss = torch.empty((4,), device=dev, dtype=torch.float32)[:2]               # 16 bytes: the library wants aligned operands
+    d_head = torch.empty((M, ld), device=dev, dtype=torch.float32)
+    need = _lib.box_loss_workspace_bytes(M)
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    _launch(_device(head_out, labels, reg_targets, sampled), lib.ldit_box_loss_f32, _ptr(head_out), ld, _ptr(labels), _ptr(reg_targets),
+            _ptr(sampled), sampled.shape[0], M, NC, float(beta), _ptr(loss), _ptr(d_head), _ptr(ws), need)
+    return loss, d_head
