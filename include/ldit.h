@@ -698,6 +698,63 @@ size_t ldit_box_loss_workspace_bytes(int64_t M);
 int ldit_box_loss_f32(const void *head_out, int64_t ld, const void *labels, const void *reg_targets, const void *sampled, int32_t B, int64_t M,
                       int32_t NC, float beta, void *loss, void *d_head, void *workspace, size_t workspace_bytes, ldit_stream stream);
 
+/* ---- the detector's optimizer step: one AdamW over MANY parameter tensors, every decision in device memory ----
+ * The other half of the reference's iteration (ref training/trainer.py:164-183: scaler.scale(loss).backward(), scaler.step(optimizer),
+ * scaler.update() with AdamW(model.parameters())) in three launches per 64 parameter tensors, with no
+ * device-to-host synchronisation: the non-finite check, the skip decision, the step count, the bias corrections, the loss scale and
+ * the learning rate live in one small device block.
+ *
+ * A SEGMENT is one parameter tensor: p, g, m (exp_avg), v (exp_avg_sq) fp32 device pointers of n elements each, unrelated
+ * allocations of any length (n == 0 allowed: its pointers are not looked at) and any 4-byte alignment - 16-byte accesses are used
+ * where all four pointers of a segment allow them, single elements elsewhere and for the last n % 4.  bf16_mirror (optional, n bf16
+ * elements, 2-byte aligned; 8-byte for the 16-byte path) receives bf16(p) of the updated values in the same pass.  `segs` is a HOST array: the
+ * segments travel in the kernel arguments, 64 per launch, so nothing is copied to the device and nothing is allocated (capturable). */
+typedef struct ldit_opt_segment {
+    void *p;
+    const void *g;
+    void *m;
+    void *v;
+    int64_t n;
+    void *bf16_mirror;
+} ldit_opt_segment;
+
+/* The device state block (40 bytes, 4-byte aligned); the caller allocates and initialises it: all integers 0, scale = the initial
+ * loss scale (1 = no loss scaling), lr = the learning rate; the other floats are written before they are read. */
+typedef struct ldit_opt_state {
+    int32_t found_inf;       /* ldit_grads_check_multi_f32 ORs 1 in; ldit_opt_advance consumes and clears it */
+    int32_t skip;            /* this step's decision, read by ldit_adamw_multi_f32 */
+    int32_t step;            /* optimizer steps taken (skipped ones not counted) */
+    int32_t growth_tracker;  /* consecutive unskipped steps since the scale last changed */
+    int32_t skipped_steps;
+    float scale;             /* the loss scale of the NEXT backward */
+    float inv_scale_used;    /* 1 / the scale the current gradients were made with */
+    float lr;                /* written by the caller (a device-side store: no synchronisation) */
+    float bc1;               /* 1 - beta1^step */
+    float bc2_sqrt;          /* sqrt(1 - beta2^step) */
+} ldit_opt_state;
+
+/* state->found_inf |= 1 if any element of any segment's g is NaN or +-inf (only g and n of a segment are read).  One wave ballot per
+ * workgroup and one integer atomic per offending workgroup; no float atomics. */
+int ldit_grads_check_multi_f32(const ldit_opt_segment *segs, int32_t S, ldit_opt_state *state, ldit_stream stream);
+
+/* One thread: torch.amp.GradScaler's step / update and the optimizer's step count.
+ *   skip = found_inf ; inv_scale_used = 1 / scale ; found_inf = 0 ;
+ *   not skipped: step += 1, bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step) (in double, rounded once), growth_tracker += 1 and,
+ *                when it reaches growth_interval, scale *= growth_factor and growth_tracker = 0 ;
+ *   skipped:     scale *= backoff_factor, growth_tracker = 0, skipped_steps += 1.
+ * growth_factor >= 1, 0 < backoff_factor <= 1, growth_interval >= 1 (1, 1, any = a constant scale).  The betas are doubles here: the
+ * bias corrections are those torch.optim.AdamW forms from its Python floats (1 - 0.9f^t is 2.4e-7 off 1 - 0.9^t at t = 1). */
+int ldit_opt_advance(ldit_opt_state *state, double beta1, double beta2, float growth_factor, float backoff_factor, int32_t growth_interval,
+                     ldit_stream stream);
+
+/* state->skip set: nothing is written.  Otherwise ldit_adamw_step's arithmetic in its order of operations on every segment, with
+ * g = grads * (grad_mul * inv_scale_used) and lr, bc1, bc2_sqrt read from the state block.  The betas are doubles: the kernel gets
+ * float(beta) and float(1 - beta), each rounded once (1.0f - 0.999f is 4.7e-5 off 0.001); the step size is float(double(lr) /
+ * double(bc1)) and the second moment adds (1 - beta2) * (g * g), the roundings of torch.optim.AdamW.  ceil(S' / 64) launches, S' the non-empty
+ * segments. */
+int ldit_adamw_multi_f32(const ldit_opt_segment *segs, int32_t S, const ldit_opt_state *state, double beta1, double beta2, float eps,
+                         float weight_decay, float grad_mul, ldit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

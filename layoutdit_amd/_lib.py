@@ -43,6 +43,22 @@ class LditWeights(C.Structure):
                 ("layer", C.POINTER(LditLayerWeights))]
 
 
+class LditOptSegment(C.Structure):
+    """One parameter tensor of the multi-tensor optimizer step (``ldit_opt_segment``)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
+                ("bf16_mirror", C.c_void_p)]
+
+
+class LditOptState(C.Structure):
+    """Host-side picture of the optimizer's device state block (``ldit_opt_state``): field order and sizes only."""
+    _fields_ = [("found_inf", C.c_int32), ("skip", C.c_int32), ("step", C.c_int32), ("growth_tracker", C.c_int32),
+                ("skipped_steps", C.c_int32), ("scale", C.c_float), ("inv_scale_used", C.c_float), ("lr", C.c_float),
+                ("bc1", C.c_float), ("bc2_sqrt", C.c_float)]
+
+
+OPT_STATE_FIELDS = tuple(n for n, _ in LditOptState._fields_)       # index of a field = its 4-byte slot in the block
+OPT_MAX_SEGMENTS = 64                                               # segments per launch (csrc/optim_multi.hip)
+
 # name -> (restype, argtypes); every symbol include/ldit.h declares
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -135,6 +151,10 @@ SIGNATURES = {
                                                 C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32, _i64, _i32, _i32, _vp]),
     "ldit_box_loss_workspace_bytes": (_sz, [_i64]),
     "ldit_box_loss_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    # detector optimizer step
+    "ldit_grads_check_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, _vp]),
+    "ldit_opt_advance": (C.c_int, [_vp, C.c_double, C.c_double, _f32, _f32, _i32, _vp]),
+    "ldit_adamw_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, C.c_double, C.c_double, _f32, _f32, _f32, _vp]),
     # box head
     "ldit_roi_align_levels_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
                                             C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),

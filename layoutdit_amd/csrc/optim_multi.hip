@@ -1,0 +1,293 @@
+// The detector's optimizer step: the non-finite check, the loss-scale / step-count state machine and one AdamW
+// over MANY unrelated parameter tensors ("segments") in a fixed number of launches, with every decision in device memory.
+//
+// A segment is {p, g, m, v, n, bf16_mirror}: four fp32 device pointers of n elements each (any 4-byte alignment, n >= 0) and an
+// optional bf16 copy of p.  Up to OPT_SEGS segments travel BY VALUE in the kernel arguments together with a prefix table that maps
+// a block index to its segment (reduce_jobs_kernel's scheme, train_ops.hip): no table is copied to the device and nothing is
+// allocated, so the step neither synchronises nor breaks a graph capture.  A workgroup owns 1024 consecutive elements of ONE
+// segment.  Where p, g, m and v of a segment are all 16-byte aligned (and the mirror 8-byte) a thread moves one 16-byte quad and the
+// last n % 4 elements go one by one; any other segment is walked element by element, a wave on consecutive addresses.
+//
+// Three launches, because each needs the one before it complete on the WHOLE parameter set: the update may not touch a single element
+// before every gradient element was seen finite, and the step count / bias corrections / loss scale change once per step, not per block.
+#include "api_internal.h"
+
+namespace ldit {
+
+namespace {
+
+typedef __bf16 bf16_t;
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int OPT_SEGS = 64;              // segments per launch: 64 x 48 bytes + the prefix table stay under the 4 KB of kernel arguments
+constexpr int OPT_BLOCK_ELEMS = 1024;     // elements per workgroup (256 threads x one quad)
+constexpr int64_t OPT_MAX_BLOCKS = 0x7fffffff;
+
+struct OptLaunch {
+    ldit_opt_segment seg[OPT_SEGS];
+    int first_block[OPT_SEGS + 1];        // first_block[j] = blocks of segments 0 .. j-1; [n] = the grid
+    int n;
+};
+static_assert(sizeof(OptLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
+
+// the segment of this block: the last j with first_block[j] <= blk (every segment in a launch has at least one block)
+__device__ __forceinline__ int find_segment(const OptLaunch &a, int blk)
+{
+    int lo = 0, hi = a.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk >= a.first_block[mid]) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool quad_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// ---- 1. found_inf |= "some gradient element is NaN or +-inf" -------------------------------------------------------------------
+// one ballot per wave, one integer atomic per offending workgroup, no float atomics
+__global__ void __launch_bounds__(256) grads_check_kernel(const OptLaunch a, ldit_opt_state *__restrict__ st)
+{
+    __shared__ int flag;
+    const int tid = threadIdx.x;
+    const int j = find_segment(a, (int)blockIdx.x);
+    const float *g = static_cast<const float *>(a.seg[j].g);
+    const int64_t n = a.seg[j].n;
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    bool bad = false;
+    if (quad_aligned(g)) {
+        const int64_t i = base + 4 * tid;
+        if (i + 4 <= n) {
+            const f32x4 G = *reinterpret_cast<const f32x4 *>(g + i);
+            bad = nonfinite(G[0]) || nonfinite(G[1]) || nonfinite(G[2]) || nonfinite(G[3]);
+        } else {
+            for (int64_t e = i; e < n; ++e) bad |= nonfinite(g[e]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t e = base + tid + 256 * k;
+            if (e < n) bad |= nonfinite(g[e]);
+        }
+    }
+    if (tid == 0) flag = 0;
+    __syncthreads();
+    if (__ballot(bad) != 0ull && (tid & 63) == 0) flag = 1;
+    __syncthreads();
+    if (tid == 0 && flag) atomicOr(&st->found_inf, 1);
+}
+
+// ---- 2. the state machine of torch.amp.GradScaler.step / update and of the optimizer's step count, one thread ------------------
+__global__ void opt_advance_kernel(ldit_opt_state *__restrict__ st, double b1, double b2, float growth, float backoff, int interval)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int skip = st->found_inf != 0;
+    st->skip = skip;
+    st->inv_scale_used = 1.0f / st->scale;          // of the scale the backward ran with, before it changes below
+    st->found_inf = 0;
+    if (!skip) {
+        const int step = st->step + 1;
+        st->step = step;
+        st->bc1 = (float)(1.0 - pow(b1, (double)step));
+        st->bc2_sqrt = (float)sqrt(1.0 - pow(b2, (double)step));
+        const int t = st->growth_tracker + 1;
+        if (t >= interval) {
+            st->scale = st->scale * growth;
+            st->growth_tracker = 0;
+        } else {
+            st->growth_tracker = t;
+        }
+    } else {
+        st->scale = st->scale * backoff;
+        st->growth_tracker = 0;
+        st->skipped_steps = st->skipped_steps + 1;
+    }
+}
+
+// ---- 3. AdamW over the segments: adamw_kernel's statements (train_ops.hip) in its order, constants from the state block ---------
+// 1 - beta arrives as its own argument, formed in double on the host and rounded once: 1.0f - 0.999f is 4.7e-5 off 0.001, which puts
+// exp_avg_sq 70x further from the float64 result than torch.optim.AdamW (which hands addcmul_ the double 1 - beta2) ever is.
+struct AdamwConsts { float b1, omb1, b2, omb2, eps, step, decay, bc2_sqrt, gs; };
+
+__device__ __forceinline__ void adamw_element(float &P, const float G, float &Mo, float &Vo, const AdamwConsts &c)
+{
+    const float gr = G * c.gs;
+    const float mo = c.b1 * Mo + c.omb1 * gr;
+    const float vo = c.b2 * Vo + c.omb2 * (gr * gr);      // the square first, as torch's addcmul_(g, g, value = 1 - beta2) forms it
+    const float denom = sqrtf(vo) / c.bc2_sqrt + c.eps;
+    P = P * c.decay - c.step * (mo / denom);
+    Mo = mo;
+    Vo = vo;
+}
+
+__global__ void __launch_bounds__(256) adamw_multi_kernel(const OptLaunch a, const ldit_opt_state *__restrict__ st, float b1, float omb1,
+                                                          float b2, float omb2, float eps, float wd, float grad_mul)
+{
+    if (st->skip) return;                            // a skipped step writes nothing at all
+    const int tid = threadIdx.x;
+    const int j = find_segment(a, (int)blockIdx.x);
+    float *p = static_cast<float *>(a.seg[j].p), *m = static_cast<float *>(a.seg[j].m), *v = static_cast<float *>(a.seg[j].v);
+    const float *g = static_cast<const float *>(a.seg[j].g);
+    bf16_t *mirror = static_cast<bf16_t *>(a.seg[j].bf16_mirror);
+    const int64_t n = a.seg[j].n;
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    const float lr = st->lr;
+    AdamwConsts c;
+    c.b1 = b1; c.omb1 = omb1; c.b2 = b2; c.omb2 = omb2; c.eps = eps;
+    // lr and bc1 are floats in the block: their quotient is formed in double and rounded once, like torch's lr / (1 - beta1^t) on
+    // Python floats - a float division rounds a second time and lands one ulp off that in about half of all cases
+    c.step = (float)((double)lr / (double)st->bc1);
+    c.decay = 1.0f - lr * wd;
+    c.bc2_sqrt = st->bc2_sqrt;
+    c.gs = grad_mul * st->inv_scale_used;
+    const bool vec = quad_aligned(p) && quad_aligned(g) && quad_aligned(m) && quad_aligned(v) &&
+                     (reinterpret_cast<uintptr_t>(mirror) & 7u) == 0;
+    if (vec) {
+        const int64_t i = base + 4 * tid;
+        if (i + 4 <= n) {
+            f32x4 P = *reinterpret_cast<f32x4 *>(p + i), Mo = *reinterpret_cast<f32x4 *>(m + i), Vo = *reinterpret_cast<f32x4 *>(v + i);
+            const f32x4 G = *reinterpret_cast<const f32x4 *>(g + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = P[e], me = Mo[e], ve = Vo[e];
+                adamw_element(pe, G[e], me, ve, c);
+                P[e] = pe; Mo[e] = me; Vo[e] = ve;
+            }
+            *reinterpret_cast<f32x4 *>(p + i) = P;
+            if (mirror) *reinterpret_cast<bf16x4 *>(mirror + i) = bf16x4{(bf16_t)P[0], (bf16_t)P[1], (bf16_t)P[2], (bf16_t)P[3]};
+            *reinterpret_cast<f32x4 *>(m + i) = Mo;
+            *reinterpret_cast<f32x4 *>(v + i) = Vo;
+        } else {
+            for (int64_t e = i; e < n; ++e) {        // the last n % 4 elements of the segment
+                float P = p[e], Mo = m[e], Vo = v[e];
+                adamw_element(P, g[e], Mo, Vo, c);
+                p[e] = P; m[e] = Mo; v[e] = Vo;
+                if (mirror) mirror[e] = (bf16_t)P;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t e = base + tid + 256 * k;
+            if (e < n) {
+                float P = p[e], Mo = m[e], Vo = v[e];
+                adamw_element(P, g[e], Mo, Vo, c);
+                p[e] = P; m[e] = Mo; v[e] = Vo;
+                if (mirror) mirror[e] = (bf16_t)P;
+            }
+        }
+    }
+}
+
+#define LAUNCH_CHECKED(...)              \
+    do {                                 \
+        hipLaunchKernelGGL(__VA_ARGS__); \
+        LDIT_HIP_CHECK(hipGetLastError()); \
+    } while (0)
+
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// all: the update's view of a segment (p, g, m, v and the mirror); else the check's (g alone).  Empty segments carry no pointer.
+int validate(const char *what, const ldit_opt_segment *segs, int32_t S, const void *state, bool all)
+{
+    if (S < 0) return fail(LDIT_EINVAL, "%s: negative segment count %d", what, S);
+    if (S > 0 && !segs) return fail(LDIT_EINVAL, "%s: null segment array", what);
+    if (!state) return fail(LDIT_EINVAL, "%s: null state block", what);
+    if (!aligned4(state)) return fail(LDIT_EINVAL, "%s: state block must be 4-byte aligned", what);
+    for (int32_t s = 0; s < S; ++s) {
+        const ldit_opt_segment &q = segs[s];
+        if (q.n < 0) return fail(LDIT_EINVAL, "%s: segment %d has negative length %lld", what, s, (long long)q.n);
+        if (q.n == 0) continue;
+        if (q.n > OPT_MAX_BLOCKS * (int64_t)OPT_BLOCK_ELEMS) return fail(LDIT_EUNSUPPORTED, "%s: segment %d longer than 2^41 elements", what, s);
+        if (!q.g || (all && (!q.p || !q.m || !q.v))) return fail(LDIT_EINVAL, "%s: segment %d has a null pointer", what, s);
+        if (!aligned4(q.g) || (all && (!aligned4(q.p) || !aligned4(q.m) || !aligned4(q.v))))
+            return fail(LDIT_EINVAL, "%s: segment %d: fp32 pointers must be 4-byte aligned", what, s);
+        if (all && (reinterpret_cast<uintptr_t>(q.bf16_mirror) & 1u)) return fail(LDIT_EINVAL, "%s: segment %d: bf16 mirror must be 2-byte aligned", what, s);
+    }
+    return LDIT_OK;
+}
+
+// the launches of one entry point: segments in order, OPT_SEGS non-empty ones (and at most 2^31 - 1 blocks) per launch
+template <typename F>
+int for_each_launch(const ldit_opt_segment *segs, int32_t S, F &&launch)
+{
+    OptLaunch a;
+    a.n = 0;
+    int64_t blocks = 0;
+    for (int32_t s = 0; s < S; ++s) {
+        if (segs[s].n == 0) continue;
+        const int64_t nb = (segs[s].n + OPT_BLOCK_ELEMS - 1) / OPT_BLOCK_ELEMS;
+        if (a.n == OPT_SEGS || blocks + nb > OPT_MAX_BLOCKS) {
+            a.first_block[a.n] = (int)blocks;
+            if (int rc = launch(a, (unsigned)blocks)) return rc;
+            a.n = 0;
+            blocks = 0;
+        }
+        a.seg[a.n] = segs[s];
+        a.first_block[a.n] = (int)blocks;
+        ++a.n;
+        blocks += nb;
+    }
+    if (a.n > 0) {
+        a.first_block[a.n] = (int)blocks;
+        if (int rc = launch(a, (unsigned)blocks)) return rc;
+    }
+    return LDIT_OK;
+}
+
+int need_device()
+{
+    int dev = 0;
+    LDIT_HIP_CHECK(hipGetDevice(&dev));          // no HIP device: LDIT_EHIP, there is no CPU path
+    return LDIT_OK;
+}
+
+}  // namespace
+
+}  // namespace ldit
+
+using namespace ldit;
+
+extern "C" {
+
+int ldit_grads_check_multi_f32(const ldit_opt_segment *segs, int32_t S, ldit_opt_state *state, ldit_stream stream_)
+{
+    LDIT_TRY(validate("grads_check_multi", segs, S, state, false));
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return for_each_launch(segs, S, [&](const OptLaunch &a, unsigned blocks) -> int {
+        LAUNCH_CHECKED(grads_check_kernel, dim3(blocks), dim3(256), 0, stream, a, state);
+        return LDIT_OK;
+    });
+}
+
+int ldit_opt_advance(ldit_opt_state *state, double beta1, double beta2, float growth_factor, float backoff_factor, int32_t growth_interval,
+                     ldit_stream stream)
+{
+    if (!state || !aligned4(state)) return fail(LDIT_EINVAL, "opt_advance: null or misaligned state block");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LDIT_EINVAL, "opt_advance: betas must lie in [0, 1)");
+    if (!(growth_factor >= 1.0f) || !(backoff_factor > 0.0f && backoff_factor <= 1.0f))
+        return fail(LDIT_EINVAL, "opt_advance: growth_factor must be >= 1 and backoff_factor in (0, 1]");
+    if (growth_interval < 1) return fail(LDIT_EINVAL, "opt_advance: growth_interval must be at least 1");
+    LDIT_TRY(need_device());
+    LAUNCH_CHECKED(opt_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), state, beta1, beta2, growth_factor, backoff_factor,
+                   growth_interval);
+    return LDIT_OK;
+}
+
+int ldit_adamw_multi_f32(const ldit_opt_segment *segs, int32_t S, const ldit_opt_state *state, double beta1, double beta2, float eps,
+                         float weight_decay, float grad_mul, ldit_stream stream_)
+{
+    LDIT_TRY(validate("adamw_multi", segs, S, state, true));
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LDIT_EINVAL, "adamw_multi: betas must lie in [0, 1)");
+    const float b1 = (float)beta1, omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return for_each_launch(segs, S, [&](const OptLaunch &a, unsigned blocks) -> int {
+        LAUNCH_CHECKED(adamw_multi_kernel, dim3(blocks), dim3(256), 0, stream, a, state, b1, omb1, b2, omb2, eps, weight_decay, grad_mul);
+        return LDIT_OK;
+    });
+}
+
+}  // extern "C"

@@ -1013,3 +1013,97 @@ def box_loss(head_out: torch.Tensor, labels: torch.Tensor, reg_targets: torch.Te
     _launch(_device(head_out, labels, reg_targets, sampled), lib.ldit_box_loss_f32, _ptr(head_out), ld, _ptr(labels), _ptr(reg_targets),
             _ptr(sampled), sampled.shape[0], M, NC, float(beta), _ptr(loss), _ptr(d_head), _ptr(ws), need)
     return loss, d_head
+
+
+# ---- the detector's optimizer step (csrc/optim_multi.hip) -------------------------------------------------------------------------
+OPT_MAX_SEGMENTS = _lib.OPT_MAX_SEGMENTS
+
+
+def new_opt_state(device, scale: float = 1.0, lr: float = 1e-4) -> torch.Tensor:
+    """A fresh ``ldit_opt_state`` block on ``device`` as an int32 tensor of ten 4-byte slots in ``_lib.OPT_STATE_FIELDS`` order
+    (the five floats are read through ``.view(torch.float32)``): counters zero, ``scale`` and ``lr`` as given."""
+    host = torch.zeros(len(_lib.OPT_STATE_FIELDS), dtype=torch.int32)
+    f = host.view(torch.float32)
+    f[_lib.OPT_STATE_FIELDS.index("scale")] = float(scale)
+    f[_lib.OPT_STATE_FIELDS.index("inv_scale_used")] = 1.0 / float(scale)
+    f[_lib.OPT_STATE_FIELDS.index("lr")] = float(lr)
+    f[_lib.OPT_STATE_FIELDS.index("bc1")] = 1.0
+    f[_lib.OPT_STATE_FIELDS.index("bc2_sqrt")] = 1.0
+    return host.to(device)
+
+
+def _req_opt_state(state: torch.Tensor) -> torch.Tensor:
+    """The block's form; that it lives on the GPU beside the segments is _device's check."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.numel() != len(_lib.OPT_STATE_FIELDS) or not state.is_contiguous():
+        raise ValueError(f"state: expected the contiguous int32 block of {len(_lib.OPT_STATE_FIELDS)} slots that new_opt_state makes")
+    return state
+
+
+def _req_list(ts, name: str, n: int):
+    ts = list(ts)
+    if len(ts) != n:
+        raise ValueError(f"{name}: {len(ts)} tensors for {n} segments")
+    for i, t in enumerate(ts):                   # the tensors' form only: where they live is _device's check, after every form check
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}[{i}]: expected a tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}[{i}]: expected float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}[{i}]: expected a contiguous tensor")
+    return ts
+
+
+def _opt_segments(params, grads, exp_avgs, exp_avg_sqs, mirrors):
+    """The host array of ``ldit_opt_segment`` for lists of tensors (``params`` None: the check's view, gradients alone)."""
+    grads = list(grads)
+    grads = _req_list(grads, "grads", len(grads))
+    S = len(grads)
+    segs = (_lib.LditOptSegment * max(S, 1))()
+    if params is None:
+        for s, g in zip(segs, grads):
+            s.g, s.n = g.data_ptr(), g.numel()
+        return segs, S, grads
+    params, exp_avgs, exp_avg_sqs = _req_list(params, "params", S), _req_list(exp_avgs, "exp_avgs", S), _req_list(exp_avg_sqs, "exp_avg_sqs", S)
+    mirrors = [None] * S if mirrors is None else list(mirrors)
+    if len(mirrors) != S:
+        raise ValueError(f"mirrors: {len(mirrors)} entries for {S} segments")
+    for i, (s, p, g, m, v, mi) in enumerate(zip(segs, params, grads, exp_avgs, exp_avg_sqs, mirrors)):
+        if not (p.numel() == g.numel() == m.numel() == v.numel()):
+            raise ValueError(f"segment {i}: params, grads and moments differ in length")
+        if mi is not None:
+            if not isinstance(mi, torch.Tensor) or not mi.is_cuda or mi.dtype != torch.bfloat16 or not mi.is_contiguous() or mi.numel() != p.numel():
+                raise ValueError(f"mirrors[{i}]: expected a contiguous bfloat16 GPU tensor of the parameter's length")
+            s.bf16_mirror = mi.data_ptr()
+        s.p, s.g, s.m, s.v, s.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    return segs, S, params + grads + exp_avgs + exp_avg_sqs + [mi for mi in mirrors if mi is not None]
+
+
+def grads_check_multi(grads: Sequence[torch.Tensor], state: torch.Tensor) -> None:
+    """``state.found_inf |= 1`` if any element of any tensor of ``grads`` is NaN or infinite.  No synchronisation."""
+    lib = _lib.load()
+    state = _req_opt_state(state)
+    segs, S, used = _opt_segments(None, grads, None, None, None)
+    _launch(_device(state, *used), lib.ldit_grads_check_multi_f32, segs, S, _ptr(state))
+
+
+def opt_advance(state: torch.Tensor, betas=(0.9, 0.999), growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                growth_interval: int = 2000) -> None:
+    """``torch.amp.GradScaler``'s step / update decision and the optimizer's step count on the device state block (one thread):
+    consumes ``found_inf``, sets ``skip`` and ``inv_scale_used``, advances ``step`` and the bias corrections or backs the scale off."""
+    lib = _lib.load()
+    state = _req_opt_state(state)
+    _launch(_device(state), lib.ldit_opt_advance, _ptr(state), float(betas[0]), float(betas[1]), float(growth_factor), float(backoff_factor),
+            int(growth_interval))
+
+
+def adamw_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+                exp_avg_sqs: Sequence[torch.Tensor], state: torch.Tensor, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                grad_mul: float = 1.0, mirrors: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """AdamW on every ``(param, grad, exp_avg, exp_avg_sq)`` of the lists in ``ceil(S / OPT_MAX_SEGMENTS)`` launches, or nothing at all
+    when ``state.skip`` is set.  The learning rate, the bias corrections and the inverse loss scale are read from ``state`` on the
+    device; ``mirrors[i]`` (bfloat16, optional) receives the rounded updated parameter.  Tensors may be views at any element offset."""
+    lib = _lib.load()
+    state = _req_opt_state(state)
+    segs, S, used = _opt_segments(params, grads, exp_avgs, exp_avg_sqs, mirrors)
+    _launch(_device(state, *used), lib.ldit_adamw_multi_f32, segs, S, _ptr(state), float(betas[0]), float(betas[1]), float(eps),
+            float(weight_decay), float(grad_mul))

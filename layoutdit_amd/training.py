@@ -13,6 +13,9 @@ Three pieces:
   the gradient all-reduce of each finished layer (one bucket per layer, RCCL over xGMI) overlapped with the rest of the
   backward, fused AdamW on the flat block, re-pack of the bf16 operand copies.
 
+:class:`DetectorTrainStep` (``layoutdit_amd/detector_training.py``, re-exported here) is the whole detector's iteration: the four
+losses, loss scaling and one multi-tensor AdamW over every parameter, with no host synchronisation behind the backward.
+
 PyTorch is plumbing here (device memory, streams, ``torch.distributed``, the stochastic-depth coin flips); there is no
 eager fallback - every FLOP of forward, backward and update runs in ``libldit_hip.so``.
 """
@@ -337,8 +340,9 @@ def encoder_forward_autograd(encoder, x: torch.Tensor, taps: Sequence[int], drop
 
 class TrainStep:
     """Fused train step on the flat state: forward, staged backward with overlapped per-layer gradient all-reduce,
-    AdamW, re-pack.  ``dtaps`` stands in for the detector head: fixed synthetic upstream gradients, one per tap
-    (the head - FPN / RPN / RoI, torchvision - is outside this repository's scope)."""
+    AdamW, re-pack.  ``dtaps`` stands in for the detector head: fixed synthetic upstream gradients, one per tap - this is the
+    ENCODER's step, the one ``bench.py --config 2`` measures, and the only one that trains the quantisation-aware mxfp8 build.  The
+    whole detector (FPN, RPN and box head behind the encoder, real losses, loss scaling) trains with :class:`DetectorTrainStep`."""
 
     def __init__(self, encoder, rank: Optional[Rank] = None, lr: float = 1e-4, weight_decay: float = 0.0,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
@@ -456,3 +460,6 @@ class TrainStep:
         self.encoder._packed_key = None       # the eval path's packed copy (DiTEncoder._pack)
         self.encoder._pos_cache.clear()       # bicubic resamples of the position table for other grids (_position_table)
         return taps
+
+
+from .detector_training import DetectorTrainStep  # noqa: E402,F401  (the whole detector's step, next to the encoder's)
