@@ -755,6 +755,50 @@ int ldit_opt_advance(ldit_opt_state *state, double beta1, double beta2, float gr
 int ldit_adamw_multi_f32(const ldit_opt_segment *segs, int32_t S, const ldit_opt_state *state, double beta1, double beta2, float eps,
                          float weight_decay, float grad_mul, ldit_stream stream);
 
+/* ---- COCO box evaluation: matching, accumulation ----
+ * The arithmetic of the reference's Evaluator.score() (ref evaluation/evaluator.py:219-286, which hands a JSON file to a per-image,
+ * per-category host loop) on padded device tensors: no host round trip, no allocation, no float atomics, capturable, every output a
+ * pure function of the inputs.  Categories are 1 .. K.  All IoU, area, precision and recall arithmetic is double.
+ *
+ * ldit_coco_match: one workgroup per image.  boxes fp32 [B, D, 4] (xyxy), scores fp32 [B, D], labels int32 [B, D], count int32 [B];
+ *   gt_boxes fp32 [B, G, 4], gt_labels int32 [B, G], gt_crowd uint8 [B, G] or NULL (none is a crowd), gt_area fp32 [B, G] or NULL (the
+ *   box's own area (x2 - x1) (y2 - y1) in double), gt_count int32 [B].  Rows at or past a count are never read.  iou_thrs HOST double[10],
+ *   area_rng HOST double[8] = (lo, hi) of the 4 area ranges: passed to the kernel by value, bit for bit.  D <= 128, G <= 128, K <= 64
+ *   (larger: LDIT_EUNSUPPORTED).  The results of image b go to row image_offset + b of the caller's store of `capacity` rows of
+ *   store_D >= D slots (capacity * store_D <= 2^24), every row written IN FULL:
+ *     code uint8 [capacity, store_D, 4, 10]: per detection slot, area range and threshold 0 = unmatched (a false positive), 1 = matched
+ *       to a non-ignored GT box (a true positive), 2 = ignored, 3 = absent: a slot at or past count[b] (or D), a label outside 1 .. K,
+ *       a rank >= 100.
+ *     rank int32 [capacity, store_D]: the detection's rank among those of its (image, category) by (score descending, slot ascending),
+ *       -1 = absent.  scores_out fp32 / labels_out int32 [capacity, store_D]: copies (-0 stored as +0), zero where absent.
+ *     npig int32 [capacity, K, 4]: the non-ignored GT boxes of (image, category, area range).
+ *   Per (image, category k, area range a = [lo, hi]): the detections of k in rank order, the first 100; a GT box of k is IGNORED when
+ *   it is a crowd or its area (gt_area) is < lo or > hi; the GT are scanned non-ignored first, each group by index.
+ *   iou(d, g) on [x, y, w, h] with w = x2 - x1: iw = min(xd + wd, xg + wg) - max(xd, xg), ih alike; 0 if iw <= 0 or ih <= 0; else
+ *   i = iw ih, u = crowd_g ? wd hd : wd hd + wg hg - i, iou = i / u.  Per threshold t, detections in rank order: best = min(t, 1 - 1e-10),
+ *   m = none; scan the GT: skip one already matched at t unless it is a crowd; stop when m is a non-ignored GT and this one is ignored;
+ *   skip if iou < best; else best = iou, m = g (an equal IoU replaces m).  m set: matched, code 2 if m is ignored else 1, m is taken.
+ *   Unmatched: code 2 if the detection's own area is < lo or > hi, else 0.
+ * ldit_coco_keys: keys int64 [n_images * store_D], one per stored slot: (category << 56) | (inverted ordered score bits << 24) |
+ *   (image * store_D + rank); an absent slot gets INT64_MAX.  Ascending key order is (category, score descending, image ascending,
+ *   rank ascending), a total order.  Sorting the keys (with the permutation) is the caller's business.
+ * ldit_coco_accumulate: sorted_keys / sorted_index int64 [n_images * store_D]: the keys in ascending order and, for each, the index
+ *   (image * store_D + slot) it came from.  rec_thrs HOST double[101] (ascending from 0), max_dets HOST int32[3] (each in [1, 100]), by
+ *   value.  One workgroup per (category, area range, maxDet M, threshold t) over the category's run of the sorted detections with
+ *   rank < M: npig = the sum of npig(image, k, a) over the n_images images; npig == 0: the cell is -1, detections or not.  Otherwise tp / fp =
+ *   cumulative counts of codes 1 / 0 (integers), rc = tp / npig, pr = tp / (tp + fp + 2.220446049250313e-16), pr made non-increasing
+ *   from the back; recall[t, k, a, M] = the last rc (0 with no detections); precision[t, r, k, a, M] = pr at the first index with
+ *   rc >= rec_thrs[r], 0 if there is none.  precision fp64 [10, 101, K, 4, 3], recall fp64 [10, K, 4, 3], every element written.
+ *   n_images == 0 is allowed (everything -1; the sorted arrays are not looked at). */
+int ldit_coco_match(const void *boxes, const void *scores, const void *labels, const void *count, const void *gt_boxes,
+                    const void *gt_labels, const void *gt_crowd, const void *gt_area, const void *gt_count, int32_t B, int32_t D, int32_t G,
+                    int32_t K, const double *iou_thrs, const double *area_rng, void *code, void *rank, void *npig, void *scores_out,
+                    void *labels_out, int64_t capacity, int32_t store_D, int64_t image_offset, ldit_stream stream);
+int ldit_coco_keys(const void *rank, const void *scores, const void *labels, int64_t n_images, int32_t store_D, void *keys, ldit_stream stream);
+int ldit_coco_accumulate(const void *sorted_keys, const void *sorted_index, const void *code, const void *rank, const void *npig,
+                         int64_t n_images, int32_t store_D, int32_t K, const double *rec_thrs, const int32_t *max_dets, void *precision,
+                         void *recall, ldit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

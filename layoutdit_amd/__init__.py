@@ -21,4 +21,7 @@ def __getattr__(name):
     if name == "DetectorInputTransform":
         from .modeling.detector_input import DetectorInputTransform
         return DetectorInputTransform
+    if name in ("CocoBoxEvaluator", "evaluate"):
+        from . import evaluation
+        return getattr(evaluation, name)
     raise AttributeError(name)

@@ -155,6 +155,11 @@ SIGNATURES = {
     "ldit_grads_check_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, _vp]),
     "ldit_opt_advance": (C.c_int, [_vp, C.c_double, C.c_double, _f32, _f32, _i32, _vp]),
     "ldit_adamw_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, C.c_double, C.c_double, _f32, _f32, _f32, _vp]),
+    # COCO box evaluation
+    "ldit_coco_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp]),
+    "ldit_coco_keys": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "ldit_coco_accumulate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(C.c_double), C.POINTER(_i32), _vp, _vp, _vp]),
     # box head
     "ldit_roi_align_levels_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
                                             C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),

@@ -1107,3 +1107,116 @@ def adamw_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], e
     segs, S, used = _opt_segments(params, grads, exp_avgs, exp_avg_sqs, mirrors)
     _launch(_device(state, *used), lib.ldit_adamw_multi_f32, segs, S, _ptr(state), float(betas[0]), float(betas[1]), float(eps),
             float(weight_decay), float(grad_mul))
+
+
+# ---- COCO box evaluation (include/ldit.h "COCO box evaluation"; csrc/coco_eval.hip) -----------------------------------------------------
+COCO_MAX_DETS, COCO_MAX_GT, COCO_MAX_CLASSES = 128, 128, 64      # per image: detection slots, GT boxes; categories
+COCO_MAX_SLOTS = 1 << 24                                         # capacity * slots per image the total-order key has room for
+
+
+def _req_form(t, name: str, dtype: torch.dtype, shape) -> torch.Tensor:
+    """The tensor's form only (dtype, contiguity, shape): where it lives is _device's check, after every form check."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _coco_caps(D: int, G: int, K: int) -> None:
+    if D > COCO_MAX_DETS or G > COCO_MAX_GT or K > COCO_MAX_CLASSES:
+        raise ValueError(f"coco: D={D} G={G} K={K}: at most {COCO_MAX_DETS} detections and {COCO_MAX_GT} GT boxes per image and "
+                         f"{COCO_MAX_CLASSES} categories are handled")
+    if D < 1 or G < 1 or K < 1:
+        raise ValueError(f"coco: D={D} G={G} K={K}: empty problem (pad to at least one row)")
+
+
+def _coco_store(code, rank, npig, scores_out, labels_out, K: int):
+    """The evaluator's store: ``code`` uint8 [N, Ds, 4, 10], ``rank`` int32 [N, Ds], ``npig`` int32 [N, K, 4], ``scores_out`` fp32 and
+    ``labels_out`` int32 [N, Ds].  Returns ``(N, Ds)``."""
+    if not isinstance(rank, torch.Tensor) or rank.dim() != 2:
+        raise ValueError("coco: rank: expected an int32 [N, D] tensor")
+    N, Ds = rank.shape
+    _req_form(code, "code", torch.uint8, (N, Ds, 4, 10))
+    _req_form(rank, "rank", torch.int32, (N, Ds))
+    _req_form(npig, "npig", torch.int32, (N, K, 4))
+    _req_form(scores_out, "scores_out", torch.float32, (N, Ds))
+    _req_form(labels_out, "labels_out", torch.int32, (N, Ds))
+    if N < 1 or N * Ds > COCO_MAX_SLOTS:
+        raise ValueError(f"coco: a store of {N} x {Ds} slots: between 1 and 2^24 are handled")
+    return N, Ds
+
+
+def coco_match(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, count: torch.Tensor, gt_boxes: torch.Tensor,
+               gt_labels: torch.Tensor, gt_count: torch.Tensor, gt_crowd: Optional[torch.Tensor], gt_area: Optional[torch.Tensor],
+               num_classes: int, code: torch.Tensor, rank: torch.Tensor, npig: torch.Tensor, scores_out: torch.Tensor,
+               labels_out: torch.Tensor, image_offset: int, iou_thrs: Sequence[float], area_rng: Sequence[Sequence[float]]) -> None:
+    """COCO's per-image matching for a padded batch, written into rows ``[image_offset, image_offset + B)`` of the caller's store
+    (``ldit_coco_match``).  ``boxes`` [B, D, 4], ``scores`` [B, D], ``labels`` int32 [B, D], ``count`` int32 [B]; ``gt_boxes`` [B, G, 4],
+    ``gt_labels`` int32 [B, G], ``gt_count`` int32 [B], ``gt_crowd`` uint8 [B, G] or None, ``gt_area`` fp32 [B, G] or None.  ``iou_thrs``:
+    10 doubles, ``area_rng``: 4 ``(lo, hi)`` pairs - they reach the kernel bit for bit.  No synchronisation, no allocation."""
+    lib = _lib.load()
+    K = int(num_classes)
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or not isinstance(gt_labels, torch.Tensor) or gt_labels.dim() != 2:
+        raise ValueError("coco_match: scores / gt_labels: expected [B, D] / [B, G] tensors")
+    (B, D), G = scores.shape, gt_labels.shape[1]
+    _coco_caps(D, G, K)
+    _req_form(boxes, "boxes", torch.float32, (B, D, 4)), _req_form(scores, "scores", torch.float32, (B, D))
+    _req_form(labels, "labels", torch.int32, (B, D)), _req_form(count, "count", torch.int32, (B,))
+    _req_form(gt_boxes, "gt_boxes", torch.float32, (B, G, 4)), _req_form(gt_labels, "gt_labels", torch.int32, (B, G))
+    _req_form(gt_count, "gt_count", torch.int32, (B,))
+    if gt_crowd is not None:
+        _req_form(gt_crowd, "gt_crowd", torch.uint8, (B, G))
+    if gt_area is not None:
+        _req_form(gt_area, "gt_area", torch.float32, (B, G))
+    N, Ds = _coco_store(code, rank, npig, scores_out, labels_out, K)
+    if B < 1 or Ds < D:
+        raise ValueError(f"coco_match: a batch of {B} images x {D} detections does not fit rows of {Ds} slots")
+    if image_offset < 0 or image_offset + B > N:
+        raise ValueError(f"coco_match: images [{image_offset}, {image_offset + B}) do not fit a store of {N}")
+    thr = [float(x) for x in iou_thrs]
+    rng = [float(x) for pair in area_rng for x in pair]
+    if len(thr) != 10 or len(rng) != 8:
+        raise ValueError("coco_match: 10 IoU thresholds and 4 (lo, hi) area ranges are expected")
+    _launch(_device(boxes, scores, labels, count, gt_boxes, gt_labels, gt_count, gt_crowd, gt_area, code, rank, npig, scores_out, labels_out),
+            lib.ldit_coco_match, _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(count), _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_crowd),
+            _ptr(gt_area), _ptr(gt_count), B, D, G, K, (C.c_double * 10)(*thr), (C.c_double * 8)(*rng), _ptr(code), _ptr(rank), _ptr(npig),
+            _ptr(scores_out), _ptr(labels_out), N, Ds, int(image_offset))
+
+
+def coco_accumulate(code: torch.Tensor, rank: torch.Tensor, npig: torch.Tensor, scores_out: torch.Tensor, labels_out: torch.Tensor,
+                    n_images: int, num_classes: int, rec_thrs: Sequence[float], max_dets: Sequence[int] = (1, 10, 100),
+                    precision: Optional[torch.Tensor] = None, recall: Optional[torch.Tensor] = None):
+    """COCO's accumulation over the first ``n_images`` rows of the store :func:`coco_match` filled: one total-order key per stored
+    detection (``ldit_coco_keys``), ``torch.sort`` of the keys (the device-wide sort is plumbing), then ``ldit_coco_accumulate``.
+    Returns ``precision`` fp64 [10, 101, K, 4, 3] and ``recall`` fp64 [10, K, 4, 3] (``-1`` where a cell has no GT).  No synchronisation."""
+    lib = _lib.load()
+    K = int(num_classes)
+    _coco_caps(1, 1, K)
+    N, Ds = _coco_store(code, rank, npig, scores_out, labels_out, K)
+    n = int(n_images)
+    if n < 0 or n > N:
+        raise ValueError(f"coco_accumulate: {n} images in a store of {N}")
+    rec = [float(x) for x in rec_thrs]
+    md = [int(m) for m in max_dets]
+    if len(rec) != 101 or len(md) != 3:
+        raise ValueError("coco_accumulate: 101 recall thresholds and 3 maxDets are expected")
+    dev = _device(code, rank, npig, scores_out, labels_out, precision, recall)
+    if precision is None:
+        precision = torch.empty((10, 101, K, 4, 3), device=dev, dtype=torch.float64)
+    if recall is None:
+        recall = torch.empty((10, K, 4, 3), device=dev, dtype=torch.float64)
+    _req_form(precision, "precision", torch.float64, (10, 101, K, 4, 3)), _req_form(recall, "recall", torch.float64, (10, K, 4, 3))
+    keys = index = None
+    if n:
+        keys = torch.empty(n * Ds, device=dev, dtype=torch.int64)
+        _launch(_device(rank, scores_out, labels_out, keys), lib.ldit_coco_keys, _ptr(rank), _ptr(scores_out), _ptr(labels_out), n, Ds, _ptr(keys))
+        with torch.cuda.device(dev):
+            keys, index = torch.sort(keys)
+    _launch(_device(code, rank, npig, precision, recall, keys, index), lib.ldit_coco_accumulate, _ptr(keys), _ptr(index), _ptr(code), _ptr(rank),
+            _ptr(npig), n, Ds, K, (C.c_double * 101)(*rec), (C.c_int32 * 3)(*md), _ptr(precision), _ptr(recall))
+    return precision, recall
