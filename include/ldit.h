@@ -159,6 +159,14 @@ int ldit_set_fp8_act_scales(const ldit_cfg *cfg, void *packed, size_t packed_byt
 /* Scratch bytes ldit_vit_forward needs for a batch of `batch` images. */
 size_t ldit_workspace_bytes(const ldit_cfg *cfg, int32_t batch);
 
+/* Streams the forward of this (cfg, batch) runs on - host arithmetic, nothing is launched.  2: the fp32 forward of a large batch
+ * runs its layers as two half-batch lanes, one on `stream` and one on an internal stream (one per device, created on first use and
+ * kept), forked after the embedding and joined before the call returns to `stream`'s order: the entry points stay enqueue-only (no
+ * synchronisation, no device allocation) and everything they enqueue is ordered against `stream` as if it ran there.  1: everything
+ * runs on `stream` - every other build, small batches, the timed forward, and any forward enqueued on a capturing stream (a captured
+ * forward is a linear graph).  The diagnostic switch LDIT_FWD_LANES=1|2 forces one lane / two lanes (fp32, batch >= 2).  0: bad cfg. */
+int32_t ldit_forward_lanes(const ldit_cfg *cfg, int32_t batch);
+
 /* x: [batch, in_ch, img_h, img_w] NCHW contiguous.  tap_out[i]: [batch, 1+P, C] row-major receives hidden state
  * cfg->taps[i] (the raw residual stream: no final LayerNorm, TF:504-506,557).  The pooler (TF:558,563-572) is not
  * computed: LayoutDiT never reads pooler_output. */

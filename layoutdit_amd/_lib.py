@@ -68,6 +68,7 @@ SIGNATURES = {
     "ldit_packed_bytes": (_sz, [C.POINTER(LditCfg)]),
     "ldit_pack_weights": (C.c_int, [C.POINTER(LditCfg), C.POINTER(LditWeights), _vp, _sz, _vp]),
     "ldit_workspace_bytes": (_sz, [C.POINTER(LditCfg), _i32]),
+    "ldit_forward_lanes": (_i32, [C.POINTER(LditCfg), _i32]),
     "ldit_vit_forward": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _i32, C.POINTER(_vp), _vp, _sz, _vp]),
     "ldit_vit_forward_images": (C.c_int, [C.POINTER(LditCfg), _vp, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _f32, _i32,
                                           C.POINTER(_vp), _vp, _sz, _vp]),

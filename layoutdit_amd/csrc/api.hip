@@ -2,6 +2,8 @@
 // arithmetic happens in the HIP kernels of this directory; there is no CPU fallback.
 #include "api_internal.h"
 
+#include <mutex>
+
 namespace ldit {
 
 char *err_buf()
@@ -71,6 +73,7 @@ DiagSwitches read_switches()
     d.seg_order = digit("LDIT_GEMM_SEG_ORDER", 0, 1);
     if (const char *e = getenv("LDIT_PLANES_TAIL_WAVES")) d.planes_tail_waves = atol(e);
     d.attn_bf16_nw = digit("LDIT_ATTN_BF16_NW", 4, 8);
+    d.fwd_lanes = digit("LDIT_FWD_LANES", 1, 2);
     return d;
 }
 DiagSwitches &switches()
@@ -189,28 +192,55 @@ int attention(Build b, const void *Q, const void *K, const void *V, int ldq, int
 
 // The seven launches of one encoder layer.  The residual stream, LayerNorm statistics, softmax and every accumulation are fp32 in
 // every build; what the build decides is the format of the four GEMM operands and of q|k|v (Operand), behind the three dispatchers.
-int run_layer(Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe)
+int layer_launch(int i, Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe)
 {
     const int M = batch * g.T, C = g.C, F = g.F;
     const char *q = static_cast<const char *>(d.qkv.p), *k = q + d.qk_bytes, *v = k + d.qk_bytes;
     const Operand mid = operand(d.h_mid, nullptr, C), out = operand(d.h_out, nullptr, C);
     const PackedLayer &pv = *d.v, &pw = *d.w;
-    // y1 = LN1(h_in)                                                            TF:426
-    LDIT_RUN(probe, LDIT_K_LAYERNORM, layernorm(b, d.h_in, d.vec(pv.ln1_w), d.vec(pv.ln1_b), d.y1, d.y1d, M, C, eps, stream));
-    // qkv[:, 0:3C] = y1 . [Wq;Wk;Wv]^T + [bq;0;bv]                              TF:319-321
-    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.y1, d.mat(pw.wqkv), d.W + pw.sw_qkv, d.bqkv, d.qkv, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, Side{}, stream));
-    // o = softmax(q k^T / sqrt(D)) v, heads merged token-major                  TF:323-338
-    LDIT_RUN(probe, LDIT_K_ATTENTION, attention(b, q, k, v, d.qkv.ld, d.qkv.ld, d.qkv.ld, d.o, batch, g.T, g.H, g.D, d.scale, stream, d.lse, d.ob, d.od,
-                                                d.qkv.planes ? d.qkv.ld / d.qkv.planes : 0));
-    // h_mid = h_in + lam1 (.) (o . Wo^T + bo)                                   TF:339, 432-434
-    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.o, d.mat(pw.wo), d.W + pw.sw_o, d.vec(pv.bo), mid, M, C, C, EPI_SCALE_RESID, d.vec(pv.lam1), d.h_in, nullptr, d.s_o, stream));
-    // y2 = LN2(h_mid)                                                           TF:438
-    LDIT_RUN(probe, LDIT_K_LAYERNORM, layernorm(b, d.h_mid, d.vec(pv.ln2_w), d.vec(pv.ln2_b), d.y2, d.y2d, M, C, eps, stream));
-    // hid[:, 0:F] = gelu(y2 . W1^T + b1)                                        TF:353-354
-    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.y2, d.mat(pw.w1), d.W + pw.sw_1, d.vec(pv.b1), d.hid, M, F, C, EPI_BIAS_GELU, nullptr, nullptr, nullptr, d.s_fc1, stream));
-    // h_out = h_mid + lam2 (.) (hid . W2^T + b2)  (+ tap copy of the new hidden state)   TF:355, 440-442
-    LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.hid, d.mat(pw.w2), d.W + pw.sw_2, d.vec(pv.b2), out, M, C, F, EPI_SCALE_RESID, d.vec(pv.lam2), d.h_mid, d.tap, d.s_fc2, stream));
+    switch (i) {
+        case 0:   // y1 = LN1(h_in)                                                            TF:426
+            LDIT_RUN(probe, LDIT_K_LAYERNORM, layernorm(b, d.h_in, d.vec(pv.ln1_w), d.vec(pv.ln1_b), d.y1, d.y1d, M, C, eps, stream));
+            return LDIT_OK;
+        case 1:   // qkv[:, 0:3C] = y1 . [Wq;Wk;Wv]^T + [bq;0;bv]                              TF:319-321
+            LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.y1, d.mat(pw.wqkv), d.W + pw.sw_qkv, d.bqkv, d.qkv, M, 3 * C, C, EPI_BIAS, nullptr, nullptr, nullptr, Side{}, stream));
+            return LDIT_OK;
+        case 2:   // o = softmax(q k^T / sqrt(D)) v, heads merged token-major                  TF:323-338
+            LDIT_RUN(probe, LDIT_K_ATTENTION, attention(b, q, k, v, d.qkv.ld, d.qkv.ld, d.qkv.ld, d.o, batch, g.T, g.H, g.D, d.scale, stream, d.lse, d.ob, d.od,
+                                                        d.qkv.planes ? d.qkv.ld / d.qkv.planes : 0));
+            return LDIT_OK;
+        case 3:   // h_mid = h_in + lam1 (.) (o . Wo^T + bo)                                   TF:339, 432-434
+            LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.o, d.mat(pw.wo), d.W + pw.sw_o, d.vec(pv.bo), mid, M, C, C, EPI_SCALE_RESID, d.vec(pv.lam1), d.h_in, nullptr, d.s_o, stream));
+            return LDIT_OK;
+        case 4:   // y2 = LN2(h_mid)                                                           TF:438
+            LDIT_RUN(probe, LDIT_K_LAYERNORM, layernorm(b, d.h_mid, d.vec(pv.ln2_w), d.vec(pv.ln2_b), d.y2, d.y2d, M, C, eps, stream));
+            return LDIT_OK;
+        case 5:   // hid[:, 0:F] = gelu(y2 . W1^T + b1)                                        TF:353-354
+            LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.y2, d.mat(pw.w1), d.W + pw.sw_1, d.vec(pv.b1), d.hid, M, F, C, EPI_BIAS_GELU, nullptr, nullptr, nullptr, d.s_fc1, stream));
+            return LDIT_OK;
+        case 6:   // h_out = h_mid + lam2 (.) (hid . W2^T + b2)  (+ tap copy of the new hidden state)   TF:355, 440-442
+            LDIT_RUN(probe, LDIT_K_GEMM, linear(b, d.hid, d.mat(pw.w2), d.W + pw.sw_2, d.vec(pv.b2), out, M, C, F, EPI_SCALE_RESID, d.vec(pv.lam2), d.h_mid, d.tap, d.s_fc2, stream));
+            return LDIT_OK;
+        default: return fail(LDIT_EINVAL, "layer_launch: no launch %d", i);
+    }
+}
+
+int run_layer(Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe)
+{
+    for (int i = 0; i < LAYER_LAUNCHES; ++i) LDIT_TRY(layer_launch(i, b, g, batch, eps, d, stream, probe));
     return LDIT_OK;
+}
+
+// Token rows M = batch * T from which the fp32 forward runs as two lanes.  Measured on ViT-B/16 224^2 (profiles/forward_lanes_ab.txt):
+// batch 64 +2.2 .. 2.6 %, batch 48 +8.7 % in all three alternations; batch 32 a tie (+-0.3 %), batch 16 -7 %: a half-batch no
+// longer fills the chip.  The smallest batch that won every time sets the bound.
+constexpr int FWD_LANES_MIN_ROWS = 48 * 197;
+
+int forward_lanes(int dtype, const Geo &g, int batch)
+{
+    if (dtype != LDIT_F32 || batch < 2) return 1;
+    if (const int force = diag().fwd_lanes; force > 0) return force;
+    return (int64_t)batch * g.T >= FWD_LANES_MIN_ROWS ? 2 : 1;
 }
 
 namespace {
@@ -281,6 +311,61 @@ int preprocess(bool half_in, const void *const *images, const int32_t *heights, 
                              static_cast<hipStream_t>(stream));
 }
 
+// The side stream of the two-lane forward: one non-blocking stream per device ordinal, created on first use and kept for the life
+// of the process (with the dynamic-LDS bits and the CU count, the library's only per-device state).  Null: ordinal out of range.
+int side_stream(hipStream_t &out)
+{
+    static std::mutex mu;
+    static hipStream_t streams[64] = {};
+    int dev = 0;
+    LDIT_HIP_CHECK(hipGetDevice(&dev));
+    out = nullptr;
+    if (dev < 0 || dev >= 64) return LDIT_OK;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!streams[dev]) LDIT_HIP_CHECK(hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking));
+    out = streams[dev];
+    return LDIT_OK;
+}
+
+// Layers of the two-lane fp32 forward.  `full` addresses the whole batch; lane A = images [0, bA) on the caller's stream, lane B =
+// the rest on `side`.  Every buffer is indexed by token row, so lane B's Layer is lane A's moved by bA * T rows (of `wide` floats in
+// `big`, where q|k|v and the MLP hidden have different row lengths) - no second workspace.  The host alternates the lanes launch by
+// launch so that neither queue runs dry behind the other's host work.  Both lanes start together: starting B behind A's q|k|v or
+// o_proj measured 0.6 - 2.1 % SLOWER than one lane, starting together 2.2 - 2.6 % faster (profiles/forward_lanes_ab.txt).
+int enqueue_lanes(const ldit_cfg *cfg, const Geo &g, const PackedMap &pm, const Layer &full, char *yb, char *bb, int batch, void *const *tap_out,
+                  hipStream_t stream, hipStream_t side, hipEvent_t start, bool &forked, Probe &probe)
+{
+    const int C = g.C, F = g.F, bA = (batch + 1) / 2;
+    const size_t wide = (size_t)(3 * C > F ? 3 * C : F);
+    const char *P = full.V;
+    struct Lane { Layer d; int batch; size_t row0; hipStream_t s; } lane[2] = {{full, bA, 0, stream}, {full, batch - bA, (size_t)bA * g.T, side}};
+    for (Lane &n : lane) {
+        float *h = const_cast<float *>(full.h_in) + n.row0 * C;
+        n.d.h_in = n.d.h_mid = n.d.h_out = h;
+        n.d.y1 = n.d.o = n.d.y2 = operand(yb + n.row0 * C * 4, nullptr, C);
+        n.d.qkv = operand(bb + n.row0 * wide * 4, nullptr, 3 * C);
+        n.d.hid = operand(bb + n.row0 * wide * 4, nullptr, F);
+    }
+    // the fork: lane B starts behind the embedding
+    LDIT_HIP_CHECK(hipEventRecord(start, stream));
+    LDIT_HIP_CHECK(hipStreamWaitEvent(side, start, 0));
+    forked = true;
+    for (int at = 0; at < g.L * LAYER_LAUNCHES; ++at)
+        for (Lane &n : lane) {
+            const int l = at / LAYER_LAUNCHES, i = at % LAYER_LAUNCHES;
+            if (i == 0) {
+                const PackedLayer &pl = pm.layer[l];
+                n.d.v = n.d.w = &pl; n.d.bqkv = reinterpret_cast<const float *>(P + pl.bqkv);
+                float *tap = tap_of(cfg, tap_out, l + 1);
+                n.d.tap = tap ? tap + n.row0 * C : nullptr;
+            }
+            LDIT_TRY(layer_launch(i, Build{LDIT_F32, false}, g, n.batch, cfg->ln_eps, n.d, n.s, probe));
+            if (i == LAYER_LAUNCHES - 1 && n.d.tap)
+                LDIT_TRY(copy_taps(cfg, tap_out, l + 1, full.h_in, tap_of(cfg, tap_out, l + 1), (size_t)n.batch * g.T * C * 4, n.s, n.row0 * C * 4));
+        }
+    return LDIT_OK;
+}
+
 int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batch, void *const *tap_out, void *workspace,
             size_t ws_bytes, hipStream_t stream, Probe &probe, const ImgSrc *imgs = nullptr)
 {
@@ -331,6 +416,36 @@ int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batc
     d.hid = operand(bb, mx ? bb + (size_t)M * F : nullptr, Sp * F, S);
     d.qk_bytes = (size_t)(dt == LDIT_F32 ? 4 : 2) * C;
     d.scale = dt == LDIT_F32 ? 1.0f / sqrtf((float)g.D) : 0.0f /* q pre-scaled at pack time */;
+
+    // Two half-batch lanes on two streams (fp32, large batches: forward_lanes) - never under the probe, whose events bracket launches
+    // of one stream, nor on a capturing stream, so that a captured forward stays a linear graph
+    hipStream_t side = nullptr;
+    if (!probe.on && g.L > 0 && forward_lanes(dt, g, batch) == 2) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        LDIT_HIP_CHECK(hipStreamIsCapturing(stream, &cap));
+        if (cap == hipStreamCaptureStatusNone) LDIT_TRY(side_stream(side));
+    }
+    if (side) {
+        if (C & 3) return fail(LDIT_EINVAL, "forward: hidden %d is not a multiple of 4, lane rows would lose their 16-byte alignment", C);
+        hipEvent_t start = nullptr, done = nullptr;
+        LDIT_HIP_CHECK(hipEventCreateWithFlags(&start, hipEventDisableTiming));
+        if (hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming); e != hipSuccess) {
+            (void)hipEventDestroy(start);
+            return fail(LDIT_EHIP, "hipEventCreateWithFlags: %s", hipGetErrorString(e));
+        }
+        bool forked = false;
+        int rc = enqueue_lanes(cfg, g, pm, d, yb, bb, batch, tap_out, stream, side, start, forked, probe);
+        // the join, on every path out once the side stream has been given work: the caller's stream is never left unordered
+        // against launches that touch its buffers
+        if (forked) {
+            hipError_t e = hipEventRecord(done, side);
+            if (e == hipSuccess) e = hipStreamWaitEvent(stream, done, 0);
+            if (e != hipSuccess && rc == LDIT_OK) rc = fail(LDIT_EHIP, "forward: joining the side stream: %s", hipGetErrorString(e));
+        }
+        (void)hipEventDestroy(start);
+        (void)hipEventDestroy(done);
+        return rc;
+    }
     for (int l = 0; l < g.L; ++l) {
         const PackedLayer &pl = pm.layer[l];
         d.v = d.w = &pl; d.bqkv = F32(pl.bqkv);
@@ -470,6 +585,13 @@ int ldit_set_fp8_act_scales(const ldit_cfg *cfg, void *packed, size_t packed_byt
                                           hipMemcpyHostToDevice, stream));
         }
     return LDIT_OK;
+}
+
+int32_t ldit_forward_lanes(const ldit_cfg *cfg, int32_t batch)
+{
+    Geo g;
+    if (batch <= 0 || geometry(cfg, g) != LDIT_OK) return 0;
+    return forward_lanes(cfg->dtype, g, batch);
 }
 
 size_t ldit_workspace_bytes(const ldit_cfg *cfg, int32_t batch)

@@ -216,11 +216,14 @@ inline float *tap_of(const ldit_cfg *cfg, void *const *taps, int hidden_idx)
 }
 
 // hidden state `hidden_idx` to every destination that asked for it, except the one already written
-inline int copy_taps(const ldit_cfg *cfg, void *const *taps, int hidden_idx, const float *src, const float *already, size_t bytes, hipStream_t stream)
+// (a lane of the two-lane forward copies its own rows: `bytes` from byte `offset` of the source and of every destination)
+inline int copy_taps(const ldit_cfg *cfg, void *const *taps, int hidden_idx, const float *src, const float *already, size_t bytes, hipStream_t stream,
+                     size_t offset = 0)
 {
     for (int i = 0; i < cfg->n_taps; ++i)
         if (cfg->taps[i] == hidden_idx && taps[i] != already)
-            LDIT_HIP_CHECK(hipMemcpyAsync(taps[i], src, bytes, hipMemcpyDeviceToDevice, stream));
+            LDIT_HIP_CHECK(hipMemcpyAsync(static_cast<char *>(taps[i]) + offset, reinterpret_cast<const char *>(src) + offset, bytes,
+                                          hipMemcpyDeviceToDevice, stream));
     return LDIT_OK;
 }
 
@@ -297,6 +300,12 @@ int linear(Build b, const Operand &A, const void *W, const void *Ws, const float
 int attention(Build b, const void *Q, const void *K, const void *V, int ldq, int ldk, int ldv, const Operand &O, int B, int N, int H, int D, float scale,
               hipStream_t stream, float *lse = nullptr, void *Ob = nullptr, void *Od = nullptr, int plane_in = 0);
 int run_layer(Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe);
+constexpr int LAYER_LAUNCHES = 7;
+// launch `i` (0 .. LAYER_LAUNCHES - 1) of run_layer alone: the two-lane forward alternates its lanes launch by launch
+int layer_launch(int i, Build b, const Geo &g, int batch, float eps, const Layer &d, hipStream_t stream, Probe &probe);
+// Lanes of the inference forward: 2 = the fp32 forward runs images [0, (batch + 1) / 2) and the rest as two lanes on two streams
+// that share the chip (api.hip: forward), 1 = one stream.  Host arithmetic; honours LDIT_FWD_LANES.
+int forward_lanes(int dtype, const Geo &g, int batch);
 // patch embedding + CLS rows into `out`: on the fp32 GEMM straight from the NCHW batch, or on the bf16 GEMM from an im2col pass
 int embed(const Geo &g, const float *x, const float *pw, const float *pb, const float *cls, const float *pos, float *out, int batch, int img_h, int img_w, hipStream_t stream, Probe &probe);
 int embed_bf16(const Geo &g, const float *x, const ImgSrc *imgs, int planes, void *patches, const void *w16, const float *pb, const float *cls,

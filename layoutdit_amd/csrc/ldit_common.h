@@ -62,6 +62,7 @@ struct DiagSwitches {
     int attn_bf16_nw = -1;       // LDIT_ATTN_BF16_NW=8: eight query tiles per workgroup (one staging of a chunk per 256 queries)
     long planes_tail_waves = 700;    // LDIT_PLANES_TAIL_WAVES: split-fp32 GEMMs of at most this many 32 x 32 output tiles run on the one-wave-per-tile kernel
     int seg_order = -1;          // LDIT_GEMM_SEG_ORDER 0 = plane segments outermost (whole K per segment), 1 = innermost (per k-tile)
+    int fwd_lanes = -1;          // LDIT_FWD_LANES 1 = the fp32 forward never runs as two half-batch lanes, 2 = always when batch >= 2 (-1 = policy)
 };
 const DiagSwitches &diag();
 void reload_diag();
