@@ -524,6 +524,13 @@ int ldit_linear_bf16_tr(const void *A, int64_t lda, int32_t a_reduction_major, c
  *   LDIT_EUNSUPPORTED).  For every image and level l, columns [Koff_l, Koff_l + k_l) of idx_out (int32 [B, Ksum], k_l = min(k, N_l),
  *   Ksum = sum k_l) receive the positions on the concatenated axis of the level's k_l largest logits, in DESCENDING logit order, ties
  *   by ASCENDING index; -inf sorts last and NaN after -inf (a total order: the result is unique).  One workgroup per (level, image).
+ * ldit_rpn_topk_chunked_f32: the arguments and the result of ldit_rpn_topk_f32 for levels of up to 2^20 = 1048576 anchors and
+ *   k <= 8192 (larger: LDIT_EUNSUPPORTED).  A tournament in the same 16384-slot buffer: after a sort the level's best k_l keys so far
+ *   sit in slots [0, k_l); the next 16384 - k_l anchors are written behind them (unused slots padded) and the buffer is sorted again
+ *   until the level is exhausted.  The key is a total order that contains the level-local index, and the best k of a set under a
+ *   total order do not depend on the chunking: the result is DEFINED as what one sort of the whole level would give, and a level
+ *   that fits one chunk gets ldit_rpn_topk_f32's bits.  One workgroup per (level, image), a workgroup-uniform trip count; no
+ *   workspace, no extra launch, no atomics, capturable, a pure function of its input.
  * ldit_rpn_decode_f32: for each idx[b, j] gathers anchors [Ntot, 4] (x1, y1, x2, y2), deltas [B, Ntot, 4] (dx, dy, dw, dh) and the
  *   logit, and decodes like BoxCoder(weights = (1, 1, 1, 1)):  w = x2 - x1, cx = x1 + w / 2;  dw, dh = min(., log(1000 / 16));
  *   pcx = dx w + cx, pw = exp(dw) w;  box = pc -+ p / 2 (y alike), clamped to [0, img_w] x [0, img_h];  score = sigmoid(logit).
@@ -542,6 +549,8 @@ int ldit_linear_bf16_tr(const void *A, int64_t lda, int32_t a_reduction_major, c
  *   workspace: ldit_nms_workspace_bytes(P, N) bytes (currently 0: the kernel keeps its state in registers and LDS; NULL is then fine);
  *   a shorter buffer is refused with LDIT_EWORKSPACE. */
 int ldit_rpn_topk_f32(const void *logits, const int64_t *level_sizes, int32_t L, int32_t B, int32_t k, void *idx_out, ldit_stream stream);
+int ldit_rpn_topk_chunked_f32(const void *logits, const int64_t *level_sizes, int32_t L, int32_t B, int32_t k, void *idx_out,
+                              ldit_stream stream);
 int ldit_rpn_decode_f32(const void *logits, const void *deltas, const void *anchors, const void *idx, int32_t B, int64_t Ntot, int64_t Ksum,
                         float img_h, float img_w, float min_size, float score_thresh, void *boxes_out, void *scores_out,
                         ldit_stream stream);
@@ -620,6 +629,16 @@ int ldit_box_postprocess_f32(const void *head, int64_t ld, const void *proposals
  *     smallest.  With i.i.d. keys that is the distribution of torchvision's randperm sampler; with any keys it is unique.
  *   labels int32 [B, N]: 1 = sampled positive, 0 = sampled negative, -1 = not in the loss.  sampled int32 [B, 2]: positives and
  *     negatives taken.
+ * ldit_rpn_targets_chunked_f32: the arguments and the four outputs of ldit_rpn_targets_f32 for N <= 2^20 = 1048576 anchors per image,
+ *   batch_size_per_image <= 4096 and Gmax <= 512 (larger: LDIT_EUNSUPPORTED).  One workgroup per image; matching and regression
+ *   targets stream over the anchors with the statements of ldit_rpn_targets_f32 (the IoU bits cannot differ) and labels are first
+ *   written as -1 everywhere.  The sampler is a tournament in the 16384-slot sort buffer on the key (class, key & 0x7fffffff, anchor
+ *   index in 20 bits) - the order of ldit_rpn_targets_f32: anchors enter 16384 - 2 batch_size_per_image at a time behind a carry;
+ *   after each sort the carry kept is the first min(batch_size_per_image, positives in the buffer) positive and the first
+ *   min(batch_size_per_image, negatives in the buffer) negative keys, compacted to the front; ignored anchors never enter.  After
+ *   the last chunk, with P and Q the positives and negatives of the whole image, take_pos = min(quota, P) and
+ *   take_neg = min(batch_size_per_image - take_pos, Q) of the carried keys get labels 1 and 0 (take_pos <= quota <=
+ *   batch_size_per_image: the carry always suffices).  Where both entry points apply, all four outputs are bit-identical.
  * ldit_rpn_loss_f32: logits fp32 [B, N], deltas fp32 [B, N, 4], labels / reg_targets / sampled as above, beta >= 0.
  *   n = the sum of all 2 B entries of sampled, read on the device.  Over the anchors with label 0 or 1 (y = label):
  *     loss[0] = (1 / n) sum of max(x, 0) - x y + log1p(exp(-|x|))        (binary_cross_entropy_with_logits, mean)
@@ -631,6 +650,9 @@ int ldit_box_postprocess_f32(const void *head, int64_t ld, const void *proposals
 int ldit_rpn_targets_f32(const void *anchors, const void *gt_boxes, const void *gt_count, const void *keys, int32_t B, int64_t N,
                          int32_t Gmax, float fg_thr, float bg_thr, int32_t batch_size_per_image, float positive_fraction, void *labels,
                          void *matched, void *reg_targets, void *sampled, ldit_stream stream);
+int ldit_rpn_targets_chunked_f32(const void *anchors, const void *gt_boxes, const void *gt_count, const void *keys, int32_t B, int64_t N,
+                                 int32_t Gmax, float fg_thr, float bg_thr, int32_t batch_size_per_image, float positive_fraction,
+                                 void *labels, void *matched, void *reg_targets, void *sampled, ldit_stream stream);
 size_t ldit_rpn_loss_workspace_bytes(int64_t B, int64_t N);
 int ldit_rpn_loss_f32(const void *logits, const void *deltas, const void *labels, const void *reg_targets, const void *sampled, int32_t B,
                       int64_t N, float beta, void *loss, void *d_logits, void *d_deltas, void *workspace, size_t workspace_bytes,

@@ -138,11 +138,13 @@ SIGNATURES = {
     "ldit_linear_bf16_tr": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i32, _vp, _vp]),
     # region proposals
     "ldit_rpn_topk_f32": (C.c_int, [_vp, C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp]),
+    "ldit_rpn_topk_chunked_f32": (C.c_int, [_vp, C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp]),
     "ldit_rpn_decode_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "ldit_nms_workspace_bytes": (_sz, [_i64, _i64]),
     "ldit_nms_batched_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # RPN training
     "ldit_rpn_targets_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "ldit_rpn_targets_chunked_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "ldit_rpn_loss_workspace_bytes": (_sz, [_i64, _i64]),
     "ldit_rpn_loss_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     # box head training

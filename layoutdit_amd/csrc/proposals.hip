@@ -5,6 +5,9 @@
 //
 //   rpn_topk     one workgroup per (level, image): a bitonic sort of 8-byte keys (~rank(logit) : index) in LDS.  The key is a
 //                total order - descending logit, ascending index, -inf last, NaN after -inf - so the result is unique.
+//   rpn_topk_chunked  the same result for a level that does not fit the 16 384 keys of LDS: a tournament in the same buffer.
+//                After a sort the level's best k keys so far sit in slots [0, k); the next 16 384 - k anchors are written behind
+//                them and the buffer is sorted again.  The best k of a set under a total order do not depend on the chunking.
 //   rpn_decode   one thread per selected candidate.
 //   nms_batched  one workgroup per problem.  The candidates are sorted like above (invalid ones - score -inf / NaN - behind all
 //                others), then every thread takes the candidates at sorted positions tid, tid + 1024, ... into REGISTERS.  Sorted
@@ -29,6 +32,8 @@ namespace {
 constexpr int PROP_THREADS = SORT_THREADS;                // 16 waves
 constexpr int TOPK_MAX_N = 16384;                        // 128 KiB of keys
 constexpr int TOPK_MAX_LEVELS = 8;
+constexpr int TOPK_CHUNKED_MAX_N = 1 << 20;              // anchors per level of the chunked kernel
+constexpr int TOPK_CHUNKED_MAX_K = SORT_MAX_N / 2;       // the carry leaves at least half of the buffer to every chunk
 constexpr int NMS_MAX_N = 8192;                          // 8 candidates per thread
 constexpr int NMS_SLOTS = NMS_MAX_N / PROP_THREADS;
 constexpr unsigned INVALID_HI = 0xFF800000u;             // high key word of score -inf; everything at or above is not a candidate
@@ -64,6 +69,32 @@ __global__ __launch_bounds__(PROP_THREADS) void rpn_topk_kernel(const float *__r
     const float *src = logits + (size_t)b * Ntot + off;
     for (int i = threadIdx.x; i < n2; i += PROP_THREADS) keys[i] = i < n ? sort_key(src[i], i) : ~0ull;
     bitonic_sort(keys, n2);
+    int *dst = idx_out + (size_t)b * Ksum + kofs;
+    for (int j = threadIdx.x; j < k; j += PROP_THREADS) dst[j] = off + (int)(unsigned)(keys[j] & 0xffffffffu);
+}
+
+// Levels of up to TOPK_CHUNKED_MAX_N anchors in the buffer of rpn_topk_kernel.  A level that fits is one sort of the same keys: the
+// bits of rpn_topk_kernel.  A larger one (then k <= TOPK_CHUNKED_MAX_K < S, checked on the host) keeps its best k keys in slots
+// [0, k) and refills slots [k, S).  n, k and S depend on blockIdx alone, so the trip count is workgroup-uniform (bitonic_sort
+// holds barriers).  Every refilled slot was last read before the barrier that ends the sort.
+__global__ __launch_bounds__(PROP_THREADS) void rpn_topk_chunked_kernel(const float *__restrict__ logits, int *__restrict__ idx_out,
+                                                                         TopkLevels lv, int Ntot, int Ksum)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    u64 *keys = reinterpret_cast<u64 *>(smem);
+    const int l = blockIdx.x, b = blockIdx.y;
+    const int n = lv.n[l], off = lv.off[l], k = lv.k[l], kofs = lv.kofs[l];
+    const int S = n < SORT_MAX_N ? pow2_at_least(n) : SORT_MAX_N;
+    const float *src = logits + (size_t)b * Ntot + off;
+    int kept = 0;                                         // slots in front that hold the best keys so far
+    for (int pos = 0; pos < n; pos += S - kept, kept = k) {
+        const int room = S - kept;
+        for (int j = threadIdx.x; j < room; j += PROP_THREADS) {
+            const int i = pos + j;
+            keys[kept + j] = i < n ? sort_key(src[i], i) : ~0ull;
+        }
+        bitonic_sort(keys, S);
+    }
     int *dst = idx_out + (size_t)b * Ksum + kofs;
     for (int j = threadIdx.x; j < k; j += PROP_THREADS) dst[j] = off + (int)(unsigned)(keys[j] & 0xffffffffu);
 }
@@ -250,6 +281,32 @@ __global__ __launch_bounds__(PROP_THREADS) void nms_batched_kernel(const f32x4 *
     if (tid == 0) count[p] = kept;
 }
 
+// host side of both top-k entry points: argument checks (messages begin with `who`), the level table, the totals and the LDS bytes
+// of the largest level (at most the whole sort buffer)
+int topk_levels(const char *who, const void *logits, const int64_t *level_sizes, int L, int B, int k, const void *idx_out, int max_n,
+                TopkLevels &lv, int &ntot, int &ksum, int &lds)
+{
+    if (!logits || !idx_out || !level_sizes) return fail(LDIT_EINVAL, "%s: null argument", who);
+    if (!aligned16(logits) || !aligned16(idx_out)) return fail(LDIT_EINVAL, "%s: operands must be 16-byte aligned", who);
+    if (L <= 0 || B <= 0 || B > 65535 || k <= 0) return fail(LDIT_EINVAL, "%s: bad geometry (L=%d B=%d k=%d)", who, L, B, k);
+    if (L > TOPK_MAX_LEVELS) return fail(LDIT_EUNSUPPORTED, "%s: %d levels, at most %d are handled", who, L, TOPK_MAX_LEVELS);
+    lv.n_levels = L;
+    int64_t off = 0, kofs = 0, nmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const int64_t n = level_sizes[l];
+        if (n <= 0) return fail(LDIT_EINVAL, "%s: level %d has %lld anchors", who, l, (long long)n);
+        if (n > max_n)
+            return fail(LDIT_EUNSUPPORTED, "%s: level %d has %lld anchors, at most %d per level are handled", who, l, (long long)n, max_n);
+        lv.off[l] = (int)off; lv.n[l] = (int)n; lv.kofs[l] = (int)kofs; lv.k[l] = (int)(k < n ? k : n);
+        off += n; kofs += lv.k[l];
+        nmax = n > nmax ? n : nmax;
+    }
+    int n2 = 2;
+    while (n2 < nmax && n2 < SORT_MAX_N) n2 <<= 1;
+    ntot = (int)off; ksum = (int)kofs; lds = n2 * (int)sizeof(u64);
+    return LDIT_OK;
+}
+
 }  // namespace
 }  // namespace ldit
 
@@ -259,28 +316,26 @@ extern "C" {
 
 int ldit_rpn_topk_f32(const void *logits, const int64_t *level_sizes, int32_t L, int32_t B, int32_t k, void *idx_out, ldit_stream stream)
 {
-    if (!logits || !idx_out || !level_sizes) return fail(LDIT_EINVAL, "rpn_topk: null argument");
-    if (!aligned16(logits) || !aligned16(idx_out)) return fail(LDIT_EINVAL, "rpn_topk: operands must be 16-byte aligned");
-    if (L <= 0 || B <= 0 || B > 65535 || k <= 0) return fail(LDIT_EINVAL, "rpn_topk: bad geometry (L=%d B=%d k=%d)", L, B, k);
-    if (L > TOPK_MAX_LEVELS) return fail(LDIT_EUNSUPPORTED, "rpn_topk: %d levels, at most %d are handled", L, TOPK_MAX_LEVELS);
     TopkLevels lv{};
-    lv.n_levels = L;
-    int64_t off = 0, kofs = 0, nmax = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t n = level_sizes[l];
-        if (n <= 0) return fail(LDIT_EINVAL, "rpn_topk: level %d has %lld anchors", l, (long long)n);
-        if (n > TOPK_MAX_N)
-            return fail(LDIT_EUNSUPPORTED, "rpn_topk: level %d has %lld anchors, at most %d per level are handled", l, (long long)n, TOPK_MAX_N);
-        lv.off[l] = (int)off; lv.n[l] = (int)n; lv.kofs[l] = (int)kofs; lv.k[l] = (int)(k < n ? k : n);
-        off += n; kofs += lv.k[l];
-        nmax = n > nmax ? n : nmax;
-    }
-    int n2 = 2;
-    while (n2 < nmax) n2 <<= 1;
-    const int lds = n2 * (int)sizeof(u64);
+    int ntot = 0, ksum = 0, lds = 0;
+    if (int rc = topk_levels("rpn_topk", logits, level_sizes, L, B, k, idx_out, TOPK_MAX_N, lv, ntot, ksum, lds)) return rc;
     LDIT_DYN_LDS(rpn_topk_kernel, TOPK_MAX_N * (int)sizeof(u64));
     hipLaunchKernelGGL(rpn_topk_kernel, dim3((unsigned)L, (unsigned)B), dim3(PROP_THREADS), lds, static_cast<hipStream_t>(stream),
-                       static_cast<const float *>(logits), static_cast<int *>(idx_out), lv, (int)off, (int)kofs);
+                       static_cast<const float *>(logits), static_cast<int *>(idx_out), lv, ntot, ksum);
+    LDIT_HIP_CHECK(hipGetLastError());
+    return LDIT_OK;
+}
+
+int ldit_rpn_topk_chunked_f32(const void *logits, const int64_t *level_sizes, int32_t L, int32_t B, int32_t k, void *idx_out,
+                              ldit_stream stream)
+{
+    TopkLevels lv{};
+    int ntot = 0, ksum = 0, lds = 0;
+    if (int rc = topk_levels("rpn_topk_chunked", logits, level_sizes, L, B, k, idx_out, TOPK_CHUNKED_MAX_N, lv, ntot, ksum, lds)) return rc;
+    if (k > TOPK_CHUNKED_MAX_K) return fail(LDIT_EUNSUPPORTED, "rpn_topk_chunked: k=%d, at most %d are handled", k, TOPK_CHUNKED_MAX_K);
+    LDIT_DYN_LDS(rpn_topk_chunked_kernel, SORT_MAX_N * (int)sizeof(u64));
+    hipLaunchKernelGGL(rpn_topk_chunked_kernel, dim3((unsigned)L, (unsigned)B), dim3(PROP_THREADS), lds, static_cast<hipStream_t>(stream),
+                       static_cast<const float *>(logits), static_cast<int *>(idx_out), lv, ntot, ksum);
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
 }

@@ -659,10 +659,14 @@ def _req_i32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
+RPN_SORT_SLOTS = 16384                   # keys of the LDS sort buffer (SORT_MAX_N, csrc/sort_lds.h): above it the chunked kernels run
+
+
 def rpn_topk(logits: torch.Tensor, level_sizes: Sequence[int], k: int) -> torch.Tensor:
     """Per-level top-k of the objectness logits.  ``logits``: [B, Ntot] with the levels concatenated (``sum(level_sizes) ==
     Ntot``).  Returns int32 [B, sum(min(k, n_l))]: for each level the positions on the concatenated axis of its largest logits,
-    descending, ties by ascending index.  No synchronisation."""
+    descending, ties by ascending index.  A level above ``RPN_SORT_SLOTS`` anchors (up to 2^20, ``k`` <= 8192) sends the call to
+    the chunked kernel, which defines the same result.  No synchronisation."""
     lib = _lib.load()
     logits = _req(logits, "logits")
     sizes = [int(n) for n in level_sizes]
@@ -672,7 +676,11 @@ def rpn_topk(logits: torch.Tensor, level_sizes: Sequence[int], k: int) -> torch.
         raise ValueError("k must be positive")
     B = logits.shape[0]
     idx = torch.empty((B, sum(min(k, n) for n in sizes)), device=logits.device, dtype=torch.int32)
-    _launch(_device(logits), lib.ldit_rpn_topk_f32, _ptr(logits), (C.c_int64 * len(sizes))(*sizes), len(sizes), B, int(k), _ptr(idx))
+    args = (_ptr(logits), (C.c_int64 * len(sizes))(*sizes), len(sizes), B, int(k), _ptr(idx))
+    if max(sizes) > RPN_SORT_SLOTS:
+        _launch(_device(logits), lib.ldit_rpn_topk_chunked_f32, *args)
+    else:
+        _launch(_device(logits), lib.ldit_rpn_topk_f32, *args)
     return idx
 
 
@@ -741,7 +749,7 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torc
 
 
 # ---- RPN training (include/ldit.h "RPN training"; csrc/rpn_train.hip) ----------------------------------------------------------
-RPN_TARGETS_MAX_ANCHORS = 16384          # per image (ldit_rpn_targets_f32)
+RPN_TARGETS_MAX_ANCHORS = 16384          # per image (ldit_rpn_targets_f32; above it ldit_rpn_targets_chunked_f32, up to 2^20)
 RPN_TARGETS_MAX_GT = 512
 
 
@@ -751,7 +759,9 @@ def rpn_targets(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_count: torch.T
     ``BoxCoder(1, 1, 1, 1).encode`` in one launch.  ``anchors`` [N, 4], ``gt_boxes`` [B, Gmax, 4], ``gt_count`` int32 [B], ``keys``
     int32 [B, N] (non-negative random priorities).  Returns ``labels`` int32 [B, N] (1 / 0 / -1 = sampled positive / sampled
     negative / not in the loss), ``matched`` int32 [B, N] (GT index, -1 below the background threshold, -2 between the thresholds),
-    ``reg_targets`` [B, N, 4] (zero where the anchor is no positive) and ``sampled`` int32 [B, 2].  No synchronisation."""
+    ``reg_targets`` [B, N, 4] (zero where the anchor is no positive) and ``sampled`` int32 [B, 2].  More than ``RPN_SORT_SLOTS``
+    anchors (up to 2^20, ``batch_size_per_image`` <= 4096) send the call to the chunked kernel, which defines the same result.  No
+    synchronisation."""
     lib = _lib.load()
     anchors, gt_boxes = _req(anchors, "anchors"), _req(gt_boxes, "gt_boxes")
     gt_count, keys = _req_i32(gt_count, "gt_count"), _req_i32(keys, "keys")
@@ -769,9 +779,12 @@ def rpn_targets(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_count: torch.T
     matched = torch.empty((B, N), device=dev, dtype=torch.int32)
     reg_targets = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
     sampled = torch.empty((B, 2), device=dev, dtype=torch.int32)
-    _launch(_device(anchors, gt_boxes, gt_count, keys), lib.ldit_rpn_targets_f32, _ptr(anchors), _ptr(gt_boxes), _ptr(gt_count), _ptr(keys),
-            B, N, Gmax, float(fg_iou_thresh), float(bg_iou_thresh), int(batch_size_per_image), float(positive_fraction), _ptr(labels),
-            _ptr(matched), _ptr(reg_targets), _ptr(sampled))
+    args = (_ptr(anchors), _ptr(gt_boxes), _ptr(gt_count), _ptr(keys), B, N, Gmax, float(fg_iou_thresh), float(bg_iou_thresh),
+            int(batch_size_per_image), float(positive_fraction), _ptr(labels), _ptr(matched), _ptr(reg_targets), _ptr(sampled))
+    if N > RPN_SORT_SLOTS:
+        _launch(_device(anchors, gt_boxes, gt_count, keys), lib.ldit_rpn_targets_chunked_f32, *args)
+    else:
+        _launch(_device(anchors, gt_boxes, gt_count, keys), lib.ldit_rpn_targets_f32, *args)
     return labels, matched, reg_targets, sampled
 
 
