@@ -87,7 +87,9 @@ enum ldit_epilogue {
     LDIT_EPI_SCALE_RESID = 2,/* Y = R + lam (.) (X W^T + b)           TF:432-434 and TF:440-442 (LayerScale + residual) */
     /* train step, ldit_linear_bf16_ex only: */
     LDIT_EPI_F32 = 4,        /* Y fp32 = X W^T (+ b)                  dgrad into LayerNorm backward; wgrad (split-K slabs) */
-    LDIT_EPI_GELU_BWD = 5    /* Y bf16 = (X W^T) (.) aux              dgrad of fc2 times the saved GELU derivative */
+    LDIT_EPI_GELU_BWD = 5,   /* Y bf16 = (X W^T) (.) aux              dgrad of fc2 times the saved GELU derivative */
+    /* ldit_linear_bf16 and ldit_linear_bf16_ex only (every other linear entry refuses it with LDIT_EINVAL): */
+    LDIT_EPI_BIAS_RELU = 6   /* Y bf16 = max(X W^T + b, 0)            fc6 / fc7 of the bf16 box head: relu of LDIT_EPI_BIAS's Y, bit for bit */
 };
 
 typedef void *ldit_stream;
@@ -232,7 +234,8 @@ int ldit_tap_to_map_bwd_f32(const void *dmap, void *dtap, int64_t B, int64_t Gh,
 
 /* ---- bf16 path (first build; BASELINE configs 3-5) ------------------------------------------------------------------
  * Y[M,N] = epilogue(X[M,K] . W[N,K]^T), X and W bf16 (K-contiguous), fp32 accumulation on v_mfma_f32_32x32x16_bf16.
- * K % 64 == 0, lda % 8 == 0.  bias / lam fp32.  LDIT_EPI_BIAS and LDIT_EPI_BIAS_GELU write bf16 Y;
+ * K % 64 == 0, lda % 8 == 0.  bias / lam fp32.  LDIT_EPI_BIAS, LDIT_EPI_BIAS_GELU and LDIT_EPI_BIAS_RELU write bf16 Y (the max of
+ * LDIT_EPI_BIAS_RELU is taken on the fp32 value in front of the conversion: its Y is relu of LDIT_EPI_BIAS's Y bit for bit);
  * LDIT_EPI_SCALE_RESID reads the fp32 residual R (may alias Y), writes fp32 Y and the optional fp32 copy Y2. */
 int ldit_linear_bf16(const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M,
                      int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2,
@@ -583,6 +586,10 @@ int ldit_nms_batched_f32(const void *boxes, const void *scores, const void *grou
  *     y_low >= map_h - 1 both rows are map_h - 1 and the weight is on y_low alone, else y_high = y_low + 1, ly = y - y_low, hy = 1 - ly;
  *     value = hy hx v(low, low) + hy lx v(low, high) + ly hx v(high, low) + ly lx v(high, high).  A bin is the sum of its 4 samples / 4.
  *   One workgroup per row, one wave per bin, four channels per lane.
+ * ldit_roi_align_levels_bf16: the same arguments, refusals and arithmetic; out is bf16 [B R, P, P, C] - every element the fp32 entry's
+ *   value rounded to bf16 (to nearest even, ldit_cast_f32_bf16's conversion) at the store, padding rows bf16 zeros; levels_out is
+ *   unchanged.  The maps stay fp32.  The row is the A operand of ldit_linear_bf16 as it stands (P P C a multiple of 64 at C % 64 == 0)
+ *   at half the bytes of the fp32 row.  Additive to ABI 6.
  * ldit_box_postprocess_f32: RoIHeads.postprocess_detections up to the NMS.  head fp32 [B R, ld]: the class logits in columns
  *   [0, NC), the deltas (dx, dy, dw, dh) of class c in columns [NC + 4 c, NC + 4 c + 4); ld >= 5 NC.  proposals fp32 [B, R, 4], count
  *   int32 [B] or NULL, weights HOST float[4] = the BoxCoder weights (10, 10, 5, 5).  One candidate per (proposal r, class c = 1 .. NC - 1)
@@ -596,6 +603,10 @@ int ldit_roi_align_levels_f32(const void *const *maps, const int32_t *map_h, con
                               const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
                               const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
                               int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream);
+int ldit_roi_align_levels_bf16(const void *const *maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
+                               const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
+                               const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
+                               int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream);
 int ldit_box_postprocess_f32(const void *head, int64_t ld, const void *proposals, const void *count, int32_t B, int64_t R, int32_t NC,
                              float img_h, float img_w, const float *weights, float score_thresh, float min_size, void *boxes_out,
                              void *scores_out, void *labels_out, ldit_stream stream);

@@ -18,7 +18,7 @@ LDIT_MAX_TAPS = 8
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8, DTYPE_F32X3, DTYPE_F32X6, DTYPE_MXFP8 = 0, 1, 3, 4, 5, 6
 FP8_A_COUNT = 4
 LDIT_OK, LDIT_EINVAL, LDIT_EWORKSPACE, LDIT_EHIP, LDIT_EUNSUPPORTED = 0, -1, -2, -3, -4
-EPI_BIAS, EPI_BIAS_GELU, EPI_SCALE_RESID, EPI_F32, EPI_GELU_BWD = 0, 1, 2, 4, 5
+EPI_BIAS, EPI_BIAS_GELU, EPI_SCALE_RESID, EPI_F32, EPI_GELU_BWD, EPI_BIAS_RELU = 0, 1, 2, 4, 5, 6
 K_GEMM, K_ATTENTION, K_LAYERNORM, K_OTHER, K_COUNT = 0, 1, 2, 3, 4
 KERNEL_FAMILIES = ("gemm", "attention", "layernorm", "other")
 
@@ -166,6 +166,8 @@ SIGNATURES = {
     # box head
     "ldit_roi_align_levels_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
                                             C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
+    "ldit_roi_align_levels_bf16": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), C.POINTER(_i64), C.POINTER(_i64),
+                                             C.POINTER(_i64), _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "ldit_box_postprocess_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i64, _i32, _f32, _f32, C.POINTER(_f32), _f32, _f32, _vp, _vp, _vp, _vp]),
 }
 

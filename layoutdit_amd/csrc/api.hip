@@ -277,7 +277,7 @@ int embed_bf16_entry(const char *name, const void *x, const ImgSrc *imgs, const 
                       (int)B, (int)img_h, (int)img_w, static_cast<hipStream_t>(stream), probe);
 }
 
-// ldit_linear_f32 / ldit_linear_bf16
+// ldit_linear_f32
 int linear_entry(const char *name, int dtype, const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M, int64_t N,
                  int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, ldit_stream stream)
 {
@@ -740,7 +740,18 @@ int ldit_tap_to_map_bwd_f32(const void *dmap, void *dtap, int64_t B, int64_t Gh,
 int ldit_linear_bf16(const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M,
                      int64_t N, int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, ldit_stream stream)
 {
-    return linear_entry("linear_bf16", LDIT_BF16, X, lda, W, bias, Y, ldy, M, N, K, epilogue, lam, R, Y2, stream);
+    int epi;
+    switch (epilogue) {
+        case LDIT_EPI_BIAS: epi = EPI_BIAS; break;
+        case LDIT_EPI_BIAS_GELU: epi = EPI_BIAS_GELU; break;
+        case LDIT_EPI_SCALE_RESID: epi = EPI_SCALE_RESID; break;
+        case LDIT_EPI_BIAS_RELU: epi = EPI_BIAS_RELU; break;          // (the bf16 GEMM alone has it: every other entry refuses it)
+        default: return fail(LDIT_EINVAL, "linear_bf16: unknown epilogue %d", epilogue);
+    }
+    LDIT_TRY(check_linear("linear_bf16", M, N, K, lda, ldy, Y, Y2));
+    return linear(Build{LDIT_BF16, false}, operand(X, nullptr, lda), W, nullptr, static_cast<const float *>(bias), operand(Y, nullptr, ldy), (int)M,
+                  (int)N, (int)K, epi, static_cast<const float *>(lam), static_cast<const float *>(R), static_cast<float *>(Y2), Side{},
+                  static_cast<hipStream_t>(stream));
 }
 
 int ldit_attention_bf16(const void *Q, const void *K, const void *V, void *O, int64_t B, int64_t N, int64_t H, int64_t D,

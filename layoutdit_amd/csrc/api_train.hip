@@ -627,6 +627,7 @@ int ldit_linear_bf16_ex(const void *X, int64_t lda, const void *W, const void *b
         case LDIT_EPI_SCALE_RESID: epi = EPI_SCALE_RESID; break;
         case LDIT_EPI_F32: epi = EPI_F32; break;
         case LDIT_EPI_GELU_BWD: epi = EPI_GELU_BWD; break;
+        case LDIT_EPI_BIAS_RELU: epi = EPI_BIAS_RELU; break;
         default: return fail(LDIT_EINVAL, "linear_bf16_ex: unknown epilogue %d", epilogue);
     }
     GemmExtra x{};

@@ -194,6 +194,14 @@ __device__ __forceinline__ void store_rows_via_lds(const ACC &acc, char *buf, vo
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[hq][e] = gelu_erf(v[hq][e]);
                 }
+                if (EPI == EPI_BIAS_RELU) {
+                    // on the fp32 value, in front of the conversion: rounding to bf16 is monotone and keeps the sign, so the stored
+                    // row is relu() of EPI_BIAS's row bit for bit
+#pragma unroll
+                    for (int hq = 0; hq < NQ; ++hq)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[hq][e] = fmaxf(v[hq][e], 0.0f);
+                }
                 if (EPI == EPI_GELU_BWD) {
                     const __bf16 *ap = static_cast<const __bf16 *>(x.aux) + ((unsigned)(mw + 32 * i + row) * (unsigned)x.ldaux + n);
                     if constexpr (NQ == 2) {

@@ -10,7 +10,7 @@
 // Block = 2 x 2 waves, wave tile TM x TN 32x32 tiles; 256x256 (TM = TN = 4) keeps the DMA issue (one 1-KiB piece per
 // ~60 cycles per wave) under the MFMA time of a k-tile; smaller tiles are DMA-issue bound.
 //
-// Epilogues: bias -> bf16 ; bias + erf-GELU -> bf16 ; R + lam (.) (acc + bias) -> fp32 (in place on the fp32 residual
+// Epilogues: bias -> bf16 ; bias + erf-GELU -> bf16 ; bias + ReLU -> bf16 ; R + lam (.) (acc + bias) -> fp32 (in place on the fp32 residual
 // stream, optional fp32 tap copy).
 #include <algorithm>
 #include <cstdlib>
@@ -609,8 +609,10 @@ int launch_h_tiled(const GemmArgsH &a, hipStream_t stream)
     // Measured and dropped (profiles/README.md): a four-stage and a five-stage counted-vmcnt ring, a 256 x 128 ring at two
     // workgroups per CU, a barrier-phased ping-pong of the two waves per SIMD, a v_mfma_f32_16x16x32_bf16 build and a
     // four-wave 256 x 256 tile - none beat this kernel on any shape; the 256 x 128 tile stays selectable for experiments.
-    // (EPI_EMBED and EPI_F32 priced like the residual epilogue, EPI_GELU_BWD like the GELU one)
-    const double a256[8] = {19.0, 18.5, 25.0, 25.0, 25.0, 18.5, 25.0, 25.0}, r128[8] = {5.2, 5.0, 7.7, 7.7, 7.7, 5.0, 7.7, 7.7};
+    // (EPI_EMBED and EPI_F32 priced like the residual epilogue, EPI_GELU_BWD like the GELU one, EPI_BIAS_RELU like EPI_BIAS: the
+    // same tile for the same shape)
+    const double a256[9] = {19.0, 18.5, 25.0, 25.0, 25.0, 18.5, 25.0, 25.0, 19.0}, r128[9] = {5.2, 5.0, 7.7, 7.7, 7.7, 5.0, 7.7, 7.7, 5.2};
+    static_assert(EPI >= 0 && EPI < 9, "an epilogue without a price");
     const long sp = a.x.splits;
     const int depth = a.x.nseg > 1 ? a.K * a.x.nseg : a.K;     // k-depth of one output element (all plane segments)
     const long t256 = sp * ((a.M + 255) / 256) * ((a.N + 255) / 256), t128 = sp * ((a.M + 127) / 128) * ((a.N + 127) / 128);
@@ -767,6 +769,7 @@ static int launch_gemm_bf16_one(const void *A, int lda, const void *W, const flo
     switch (epi) {
         case EPI_BIAS: return launch_h_tiled<EPI_BIAS>(a, stream);
         case EPI_BIAS_GELU: return launch_h_tiled<EPI_BIAS_GELU>(a, stream);
+        case EPI_BIAS_RELU: return launch_h_tiled<EPI_BIAS_RELU>(a, stream);
         case EPI_SCALE_RESID:
             if (!lam || !R) return fail(LDIT_EINVAL, "gemm_bf16: scale+residual epilogue needs lam and R");
             return launch_h_tiled<EPI_SCALE_RESID>(a, stream);

@@ -60,7 +60,7 @@ __device__ __forceinline__ const T *uniform_ptr(const T *q)
 struct GemmArgsH {
     const bf16_t *A;     // [M, K] bf16
     const bf16_t *W;     // [N, K] bf16
-    void *Y;             // [M, N] bf16 (BIAS, BIAS_GELU) or fp32 (SCALE_RESID)
+    void *Y;             // [M, N] bf16 (BIAS, BIAS_GELU, BIAS_RELU) or fp32 (SCALE_RESID, F32)
     float *Y2;           // optional fp32 tap copy (SCALE_RESID)
     const float *bias;   // [N] fp32 or null
     const float *lam;    // [N] fp32
@@ -176,6 +176,7 @@ __device__ __forceinline__ void store_h(const GemmArgsH &p, const ACC &acc, int 
                 for (int e = 0; e < 4; ++e) {
                     float t = v[e];
                     if (EPI == EPI_BIAS_GELU && !gelu_done) t = gelu_lp(t);
+                    if (EPI == EPI_BIAS_RELU) t = fmaxf(t, 0.0f);           // as the slab epilogue: relu() of EPI_BIAS's bits
                     if (EPI == EPI_SCALE_RESID) t = p.x.rowscale ? __builtin_fmaf(lam[g][e] * rs, t, res[g][e]) : __builtin_fmaf(lam[g][e], t, res[g][e]);
                     v[e] = t;
                 }

@@ -175,7 +175,8 @@ enum Epi { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_SCALE_RESID = 2, EPI_EMBED = 3,
            EPI_F32 = 4,        // bf16 GEMM only: Y fp32 = acc (+ bias); dgrad into LayerNorm backward, wgrad slabs
            EPI_GELU_BWD = 5,   // bf16 GEMM only: Y bf16 = acc * aux, aux = gelu'(pre-activation) saved by the forward
            EPI_GELU_SPLIT = 6, // bf16 GEMM, split-fp32 build only: Y = split_bf16(gelu_erf(acc + bias)), `nsplit_out` bf16 planes per row
-           EPI_BIAS_SPLIT = 7 }; // the same without the GELU (q|k|v of the split-fp32 build, consumed as planes by attention_planes)
+           EPI_BIAS_SPLIT = 7, // the same without the GELU (q|k|v of the split-fp32 build, consumed as planes by attention_planes)
+           EPI_BIAS_RELU = 8 };  // bf16 GEMM only: Y bf16 = max(acc + bias, 0) (fc6 / fc7 of the bf16 box head)
 
 // Optional operands of the bf16 GEMM used by the train step (training.hip); all null / 1 for inference.
 struct GemmExtra {

@@ -8,6 +8,8 @@
 //                      and every row picks its own level.  One workgroup (4 waves) per row; a wave takes the bins wave, wave + 4, ...
 //                      and lane l the channels 4 l .. 4 l + 3 (+ 256 per further pass): at C = 256 every corner read and every store
 //                      is one coalesced 1 KiB access.  The output row (P, P, C) is the A operand of the fc6 GEMM as it stands.
+//                      Templated on the output element: the bf16 instantiation (ldit_roi_align_levels_bf16, the bf16 box head) rounds
+//                      the fp32 instantiation's value at the store - 8 bytes per lane - and shares every other statement with it.
 //   box_postprocess    softmax over the class logits, BoxCoder(10, 10, 5, 5).decode of the class's deltas against the proposal,
 //                      clip, score / small-box / padding filter; one thread per (proposal, foreground class), candidates in
 //                      torchvision's flattening order so that ldit_nms_batched_f32 keyed by label finishes the stage.
@@ -23,6 +25,19 @@ namespace {
 
 constexpr int ROI_MAX_LEVELS = 8;
 constexpr int ROI_THREADS = 256;                         // 4 waves
+
+typedef __bf16 roi_bf16x4 __attribute__((ext_vector_type(4)));
+
+// four channels of an output row: fp32 as they are (16 bytes), or rounded to bf16 (to nearest even) at the store (8 bytes)
+template <typename T> struct RoiOut;
+template <> struct RoiOut<float> {
+    typedef f32x4 vec;
+    static __device__ __forceinline__ vec pack(const f32x4 &v) { return v; }
+};
+template <> struct RoiOut<__bf16> {
+    typedef roi_bf16x4 vec;
+    static __device__ __forceinline__ vec pack(const f32x4 &v) { return vec{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]}; }
+};
 
 struct RoiLevels {
     const float *map[ROI_MAX_LEVELS];
@@ -48,9 +63,9 @@ __device__ __forceinline__ bool axis_sample(float v, int n, int &lo, int &hi, fl
     return true;
 }
 
-template <int P, int S>
+template <int P, int S, typename T>
 __global__ __launch_bounds__(ROI_THREADS) void roi_align_levels_kernel(RoiLevels lv, int L, const f32x4 *__restrict__ boxes,
-                                                                        const int *__restrict__ count, float *__restrict__ out,
+                                                                        const int *__restrict__ count, T *__restrict__ out,
                                                                         int *__restrict__ levels_out, int R, int C, int k_min, int k_max,
                                                                         float canonical_scale, float canonical_level)
 {
@@ -58,10 +73,11 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_align_levels_kernel(RoiLevels
     const int b = (int)(row / R), r = (int)(row - (long long)b * R);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c4n = C >> 2;
-    f32x4 *dst = reinterpret_cast<f32x4 *>(out + (size_t)row * (P * P) * C);
+    typedef typename RoiOut<T>::vec out4;
+    out4 *dst = reinterpret_cast<out4 *>(out + (size_t)row * (P * P) * C);
     const bool valid = !count || r < count[b];
     if (!valid) {                                        // padding row: zeros (uniform per workgroup)
-        for (int i = threadIdx.x; i < P * P * c4n; i += ROI_THREADS) dst[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = threadIdx.x; i < P * P * c4n; i += ROI_THREADS) dst[i] = RoiOut<T>::pack(f32x4{0.f, 0.f, 0.f, 0.f});
         if (levels_out && threadIdx.x == 0) levels_out[row] = -1;
         return;
     }
@@ -119,7 +135,7 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_align_levels_kernel(RoiLevels
                     const float w1 = wylo[iy] * wxlo[ix], w2 = wylo[iy] * wxhi[ix], w3 = wyhi[iy] * wxlo[ix], w4 = wyhi[iy] * wxhi[ix];
                     acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
                 }
-            dst[(size_t)bin * c4n + c4] = acc / (float)(S * S);
+            dst[(size_t)bin * c4n + c4] = RoiOut<T>::pack(acc / (float)(S * S));
         }
     }
 }
@@ -169,12 +185,12 @@ __global__ __launch_bounds__(256) void box_postprocess_kernel(const float *__res
 
 using namespace ldit;
 
-extern "C" {
-
-int ldit_roi_align_levels_f32(const void *const *maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
-                              const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
-                              const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
-                              int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream)
+// ldit_roi_align_levels_f32 / ldit_roi_align_levels_bf16: one set of refusals, the output element decides the instantiation
+template <typename T>
+static int roi_align_levels_entry(const void *const *maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
+                                  const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
+                                  const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
+                                  int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream)
 {
     if (!maps || !map_h || !map_w || !spatial_scale || !stride_b || !stride_y || !stride_x || !boxes || !out)
         return fail(LDIT_EINVAL, "roi_align_levels: null argument");
@@ -199,11 +215,31 @@ int ldit_roi_align_levels_f32(const void *const *maps, const int32_t *map_h, con
         lv.h[l] = map_h[l]; lv.w[l] = map_w[l]; lv.scale[l] = spatial_scale[l];
         lv.sb[l] = stride_b[l]; lv.sy[l] = stride_y[l]; lv.sx[l] = stride_x[l];
     }
-    hipLaunchKernelGGL((roi_align_levels_kernel<7, 2>), dim3((unsigned)((int64_t)B * R)), dim3(ROI_THREADS), 0, static_cast<hipStream_t>(stream), lv,
-                       (int)L, static_cast<const f32x4 *>(boxes), static_cast<const int *>(count), static_cast<float *>(out),
+    hipLaunchKernelGGL((roi_align_levels_kernel<7, 2, T>), dim3((unsigned)((int64_t)B * R)), dim3(ROI_THREADS), 0, static_cast<hipStream_t>(stream), lv,
+                       (int)L, static_cast<const f32x4 *>(boxes), static_cast<const int *>(count), static_cast<T *>(out),
                        static_cast<int *>(levels_out), (int)R, (int)C, (int)k_min, (int)k_max, canonical_scale, canonical_level);
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
+}
+
+extern "C" {
+
+int ldit_roi_align_levels_f32(const void *const *maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
+                              const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
+                              const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
+                              int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream)
+{
+    return roi_align_levels_entry<float>(maps, map_h, map_w, spatial_scale, stride_b, stride_y, stride_x, L, C, boxes, count, B, R, P,
+                                         sampling_ratio, k_min, k_max, canonical_scale, canonical_level, out, levels_out, stream);
+}
+
+int ldit_roi_align_levels_bf16(const void *const *maps, const int32_t *map_h, const int32_t *map_w, const float *spatial_scale,
+                               const int64_t *stride_b, const int64_t *stride_y, const int64_t *stride_x, int32_t L, int64_t C,
+                               const void *boxes, const void *count, int32_t B, int64_t R, int32_t P, int32_t sampling_ratio, int32_t k_min,
+                               int32_t k_max, float canonical_scale, float canonical_level, void *out, void *levels_out, ldit_stream stream)
+{
+    return roi_align_levels_entry<__bf16>(maps, map_h, map_w, spatial_scale, stride_b, stride_y, stride_x, L, C, boxes, count, B, R, P,
+                                          sampling_ratio, k_min, k_max, canonical_scale, canonical_level, out, levels_out, stream);
 }
 
 int ldit_box_postprocess_f32(const void *head, int64_t ld, const void *proposals, const void *count, int32_t B, int64_t R, int32_t NC,

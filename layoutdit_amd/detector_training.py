@@ -101,7 +101,7 @@ class DetectorTrainStep:
     def invalidate_caches(self, _mirror_current: bool = False) -> None:
         """The update goes through raw pointers, so no tensor version moves and every copy of the weights keyed on versions is stale:
         the encoder's packed inference block and resampled position tables, the FPN's re-laid 3x3 weights, the RPN head's and the box
-        head's stacked / re-ordered matrices.  The training mirror of the encoder was refreshed by the update itself where it was
+        head's stacked / re-ordered matrices and their bf16 copies.  The training mirror of the encoder was refreshed by the update itself where it was
         current before (``_mirror_current``); otherwise the next forward rebuilds it."""
         from .modeling.dit_fpn import DiTWithFPN
         from .modeling.roi_heads import FastRCNNPredictor, TwoMLPHead
@@ -118,8 +118,10 @@ class DetectorTrainStep:
         for mod in self.model.modules():
             if isinstance(mod, DiTWithFPN):
                 mod._cache.clear()
-            elif isinstance(mod, (RPNHead, TwoMLPHead, FastRCNNPredictor)):
+            elif isinstance(mod, RPNHead):
                 mod._packed = None
+            elif isinstance(mod, (TwoMLPHead, FastRCNNPredictor)):
+                mod._packed = mod._packed_bf16 = None     # the bf16 head's operands are keyed on versions like the fp32 re-layouts
 
     def epoch_end(self) -> None:
         """``StepLR(step_size, gamma).step()``: after every ``step_size`` calls the learning rate is multiplied by ``gamma``; the new

@@ -26,6 +26,13 @@ targets stays refused.  torchvision is not
 installed offline: the semantics are restated from its documented behaviour (``tests/roi_oracle.py``) - parity unpinned with
 respect to torchvision itself, as for the FPN and the RPN.  Parameter names follow torchvision, so detector checkpoints load
 (``roi_heads.box_head.fc6.weight`` ...).
+
+``head_dtype="bf16"`` (default ``"f32"``; :meth:`RoIHeads.set_head_dtype` switches one set of weights) runs the eval-mode head in
+bf16: RoIAlign rounds its fp32 rows to bf16 at the store (``ldit_roi_align_levels_bf16`` - half the bytes written and read back),
+``fc6`` and ``fc7`` run on the bf16 MFMA GEMM with the ReLU in its epilogue (``LDIT_EPI_BIAS_RELU``: no ``relu_`` launch), the
+predictor on the same GEMM with an fp32 result.  The parameters stay fp32 (the ``state_dict`` does not depend on the option); their
+bf16 copies are cached beside the fp32 re-layouts.  Train mode and every path that wants a gradient stay fp32 whatever the option
+says.
 """
 from __future__ import annotations
 
@@ -34,11 +41,20 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 
 
 def _param_key(*ps) -> tuple:
     return tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
+
+
+HEAD_DTYPES = ("f32", "bf16")
+
+
+def _check_head_dtype(head_dtype: str) -> str:
+    if head_dtype not in HEAD_DTYPES:
+        raise ValueError(f"head_dtype {head_dtype!r}: the box head is built for {' and '.join(repr(d) for d in HEAD_DTYPES)}")
+    return head_dtype
 
 
 def _nhwc_f32(f: torch.Tensor) -> torch.Tensor:
@@ -88,10 +104,14 @@ class MultiScaleRoIAlign(nn.Module):
         self.canonical_scale, self.canonical_level = float(canonical_scale), float(canonical_level)
 
     def forward(self, features: Union[Dict[str, torch.Tensor], Sequence[torch.Tensor]], boxes: torch.Tensor, count: Optional[torch.Tensor],
-                image_size: Tuple[int, int]) -> torch.Tensor:
+                image_size: Tuple[int, int], out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """``features``: the named maps (or the maps themselves, finest first), ``boxes`` [B, R, 4], ``count`` int32 [B] or None.
-        Returns ``[B * R, P, P, C]``; rows past the count are zero."""
+        Returns ``[B * R, P, P, C]``; rows past the count are zero.  ``out_dtype=torch.bfloat16`` (no gradient): the rows rounded
+        to bf16 at the kernel's store."""
         feats = [features[n] for n in self.featmap_names] if isinstance(features, dict) else list(features)
+        if out_dtype != torch.float32:
+            return ops.roi_align_levels([_nhwc_f32(f.detach()) for f in feats], boxes, count, image_size, self.output_size,
+                                        self.sampling_ratio, self.canonical_scale, self.canonical_level, out_dtype=out_dtype)
         if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
             # gradients are wanted for the maps: the differentiable node (the path below is untouched)
             return _RoIAlignLevelsFn.apply(boxes.detach(), count, tuple(image_size), self.output_size, self.sampling_ratio,
@@ -207,6 +227,7 @@ class TwoMLPHead(nn.Module):
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
         self._packed = None
+        self._packed_bf16 = None
 
     def fc6_weight_hwc(self, channels: int, ph: int, pw: int) -> torch.Tensor:
         """``fc6.weight`` with its columns re-ordered from torchvision's ``flatten(start_dim=1)`` of (c, ph, pw) to (ph, pw, c) - the
@@ -218,6 +239,24 @@ class TwoMLPHead(nn.Module):
         if self._packed is None or self._packed[0] != key:
             self._packed = (key, w.detach().view(w.shape[0], channels, ph, pw).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
         return self._packed[1]
+
+    def operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The bf16 GEMM's weight operands: :meth:`fc6_weight_hwc` and ``fc7.weight`` rounded to bf16, re-made when a parameter
+        changes."""
+        key = (_param_key(self.fc6.weight, self.fc7.weight), channels, ph, pw)
+        if self._packed_bf16 is None or self._packed_bf16[0] != key:
+            self._packed_bf16 = (key, ops.cast_bf16(self.fc6_weight_hwc(channels, ph, pw)), ops.cast_bf16(self.fc7.weight.detach().contiguous()))
+        return self._packed_bf16[1:]
+
+    def forward_bf16(self, pooled: torch.Tensor) -> torch.Tensor:
+        """``pooled`` bf16 [M, P, P, C] -> bf16 [M, representation_size]: both layers on the bf16 GEMM, the ReLU in its epilogue.
+        No gradient."""
+        if pooled.dim() != 4 or pooled.dtype != torch.bfloat16:
+            raise ValueError(f"TwoMLPHead: expected bfloat16 pooled rows [M, P, P, C], got {pooled.dtype} {tuple(pooled.shape)}")
+        M, ph, pw, Cc = pooled.shape
+        w6, w7 = self.operands_bf16(Cc, ph, pw)
+        x = ops.linear_bf16(pooled.reshape(M, ph * pw * Cc), w6, self.fc6.bias.detach(), _lib.EPI_BIAS_RELU)
+        return ops.linear_bf16(x, w7, self.fc7.bias.detach(), _lib.EPI_BIAS_RELU)
 
     def forward(self, pooled: torch.Tensor) -> torch.Tensor:
         """``pooled`` [M, P, P, C] (channels innermost) -> [M, representation_size]."""
@@ -245,6 +284,7 @@ class FastRCNNPredictor(nn.Module):
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
         self.num_classes = int(num_classes)
         self._packed = None
+        self._packed_bf16 = None
 
     def _operands(self):
         """Both layers as one [5 NC (padded to a multiple of 4), in_channels] matrix, re-laid when a parameter changes."""
@@ -259,6 +299,15 @@ class FastRCNNPredictor(nn.Module):
             b[:NC], b[NC:5 * NC] = ps[1].detach(), ps[3].detach()
             self._packed = (key, w, b)
         return self._packed[1:]
+
+    def forward_stacked_bf16(self, x: torch.Tensor) -> torch.Tensor:
+        """bf16 [M, in_channels] -> fp32 [M, 5 NC (+ pad)] on the bf16 GEMM: the stacked weight rounded to bf16 (re-made when a
+        parameter changes), fp32 bias, the accumulator stored unrounded; the padding columns are zero.  No gradient."""
+        key = _param_key(self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias)
+        if self._packed_bf16 is None or self._packed_bf16[0] != key:
+            w, b = self._operands()
+            self._packed_bf16 = (key, ops.cast_bf16(w), b)
+        return ops.linear_bf16(x, self._packed_bf16[1], self._packed_bf16[2], _lib.EPI_F32)
 
     def forward_stacked(self, x: torch.Tensor) -> torch.Tensor:
         """[M, in_channels] -> [M, 5 NC (+ pad)]: the class logits in columns [0, NC), the deltas in [NC, 5 NC)."""
@@ -282,8 +331,9 @@ class RoIHeads(nn.Module):
     def __init__(self, box_roi_pool: MultiScaleRoIAlign, box_head: TwoMLPHead, box_predictor: FastRCNNPredictor,
                  bbox_reg_weights: Optional[Sequence[float]] = None, score_thresh: float = 0.05, nms_thresh: float = 0.5,
                  detections_per_img: int = 100, min_size: float = 1e-2, fg_iou_thresh: float = 0.5, bg_iou_thresh: float = 0.5,
-                 batch_size_per_image: int = 512, positive_fraction: float = 0.25):
+                 batch_size_per_image: int = 512, positive_fraction: float = 0.25, head_dtype: str = "f32"):
         super().__init__()
+        self.head_dtype = _check_head_dtype(head_dtype)
         self.box_roi_pool, self.box_head, self.box_predictor = box_roi_pool, box_head, box_predictor
         self.bbox_reg_weights = tuple(float(w) for w in (bbox_reg_weights or (10.0, 10.0, 5.0, 5.0)))
         self.score_thresh, self.nms_thresh, self.min_size = float(score_thresh), float(nms_thresh), float(min_size)
@@ -293,9 +343,23 @@ class RoIHeads(nn.Module):
         self.smooth_l1_beta = 1.0 / 9.0                               # torchvision's fastrcnn_loss
 
     def head_padded(self, features, proposals: torch.Tensor, count: Optional[torch.Tensor], image_size: Tuple[int, int]) -> torch.Tensor:
-        """RoIAlign and the three GEMMs: ``[B * R, 5 NC (+ pad)]`` logits | deltas per proposal row."""
+        """RoIAlign and the three GEMMs: ``[B * R, 5 NC (+ pad)]`` fp32 logits | deltas per proposal row.  ``head_dtype="bf16"``
+        in eval mode, where no gradient is wanted: bf16 pooled rows, ``fc6`` / ``fc7`` on the bf16 GEMM with the ReLU epilogue, the
+        predictor on it with an fp32 result - no fp32 pooled tensor, no ``relu_`` launch."""
+        if self.head_dtype == "bf16" and not self.training and not self._wants_grad(features):
+            pooled = self.box_roi_pool(features, proposals, count, image_size, out_dtype=torch.bfloat16)
+            return self.box_predictor.forward_stacked_bf16(self.box_head.forward_bf16(pooled))
         pooled = self.box_roi_pool(features, proposals, count, image_size)
         return self.box_predictor.forward_stacked(self.box_head(pooled))
+
+    def set_head_dtype(self, head_dtype: str) -> "RoIHeads":
+        """``"f32"`` or ``"bf16"``: how the eval-mode head runs from now on.  The parameters are untouched."""
+        self.head_dtype = _check_head_dtype(head_dtype)
+        return self
+
+    def _wants_grad(self, features) -> bool:
+        feats = features.values() if isinstance(features, dict) else features
+        return torch.is_grad_enabled() and any(f.requires_grad for f in feats)
 
     @staticmethod
     def pad_targets(targets, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

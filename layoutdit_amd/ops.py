@@ -248,8 +248,9 @@ def cast_bf16(x: torch.Tensor) -> torch.Tensor:
 def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = _lib.EPI_BIAS,
                 lam: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """bf16 MFMA GEMM: ``x`` [M, K] bf16, ``weight`` [N, K] bf16, fp32 accumulation; bf16 result for the bias / GELU
-    epilogues, fp32 (in place on ``residual`` if ``out is residual``) for the scale+residual epilogue."""
+    """bf16 MFMA GEMM: ``x`` [M, K] bf16, ``weight`` [N, K] bf16, fp32 accumulation; bf16 result for the bias / GELU / ReLU
+    epilogues (``EPI_BIAS_RELU``: ``relu`` of the ``EPI_BIAS`` result bit for bit), fp32 (in place on ``residual`` if ``out is
+    residual``) for the scale+residual epilogue and for ``EPI_F32`` (``x @ weight.T + bias`` without the rounding of the result)."""
     lib = _lib.load()
     for t, n in ((x, "x"), (weight, "weight")):
         if not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous():
@@ -258,10 +259,15 @@ def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     N = weight.shape[0]
     if out is None:
         out = torch.empty((M, N), device=x.device,
-                          dtype=torch.float32 if epilogue == _lib.EPI_SCALE_RESID else torch.bfloat16)
+                          dtype=torch.float32 if epilogue in (_lib.EPI_SCALE_RESID, _lib.EPI_F32) else torch.bfloat16)
     for t, n in ((bias, "bias"), (lam, "lam"), (residual, "residual"), (out2, "out2")):
         if t is not None:
             _req(t, n)
+    if epilogue == _lib.EPI_F32:
+        # the train step's entry has this epilogue (one K range, no side stores): the same GEMM, its fp32 value stored unrounded
+        _launch(_device(x, weight, bias, out), lib.ldit_linear_bf16_ex, _ptr(x), K, _ptr(weight), _ptr(bias), _ptr(out), N, M, N, K, epilogue, None, None, None, None,
+                None, None, 0, 1)
+        return out
     _launch(_device(x, weight, bias, lam, residual, out, out2), lib.ldit_linear_bf16, _ptr(x), K, _ptr(weight), _ptr(bias), _ptr(out), N, M, N, K, epilogue, _ptr(lam),
                                     _ptr(residual), _ptr(out2))
     return out
@@ -834,14 +840,18 @@ def infer_scales(features: Sequence[torch.Tensor], image_size) -> list:
 
 def roi_align_levels(features: Sequence[torch.Tensor], boxes: torch.Tensor, count: Optional[torch.Tensor], image_size,
                      output_size: int = 7, sampling_ratio: int = 2, canonical_scale: float = 224.0, canonical_level: float = 4.0,
-                     return_levels: bool = False):
+                     return_levels: bool = False, out_dtype: torch.dtype = torch.float32):
     """``MultiScaleRoIAlign`` forward in one launch.  ``features``: the maps ``[B, C, h, w]`` finest first, float32 in channels-last
     memory (channel stride 1; any batch / row / pixel stride - ``p5[:, :, ::2, ::2]`` is consumed without a copy).  ``boxes`` [B, R, 4]
     and ``count`` int32 [B] (or None: every row valid) are what ``RegionProposalNetwork.forward(..., padded=True)`` returns.
     Returns ``[B * R, P, P, C]`` (the fc6 GEMM's A operand; rows ``r >= count[b]`` are zero) and, with ``return_levels``, the
-    int32 ``[B, R]`` level of each row (-1 for padding rows).  No synchronisation."""
+    int32 ``[B, R]`` level of each row (-1 for padding rows).  ``out_dtype=torch.bfloat16``: the same rows rounded to bf16 (to
+    nearest even) at the kernel's store - the A operand of the bf16 fc6 GEMM at half the bytes; the maps stay float32.  No
+    synchronisation."""
     import math
     lib = _lib.load()
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"roi_align_levels: out_dtype {out_dtype} (torch.float32 or torch.bfloat16 is built)")
     feats = list(features)
     boxes = _req(boxes, "boxes")
     if not feats or boxes.dim() != 3 or boxes.shape[2] != 4:
@@ -862,9 +872,10 @@ def roi_align_levels(features: Sequence[torch.Tensor], boxes: torch.Tensor, coun
     scales = infer_scales(feats, image_size)
     k_min, k_max = int(-math.log2(scales[0])), int(-math.log2(scales[-1]))
     L, P = len(feats), int(output_size)
-    out = torch.empty((B * R, P, P, Cc), device=boxes.device, dtype=torch.float32)
+    out = torch.empty((B * R, P, P, Cc), device=boxes.device, dtype=out_dtype)
     levels = torch.empty((B, R), device=boxes.device, dtype=torch.int32) if return_levels else None
-    _launch(_device(boxes, count, *feats), lib.ldit_roi_align_levels_f32, (C.c_void_p * L)(*[f.data_ptr() for f in feats]),
+    entry = getattr(lib, "ldit_roi_align_levels_bf16" if out_dtype == torch.bfloat16 else "ldit_roi_align_levels_f32")     # one signature
+    _launch(_device(boxes, count, *feats), entry, (C.c_void_p * L)(*[f.data_ptr() for f in feats]),
             (C.c_int32 * L)(*[f.shape[2] for f in feats]), (C.c_int32 * L)(*[f.shape[3] for f in feats]), (C.c_float * L)(*scales),
             (C.c_int64 * L)(*[f.stride(0) for f in feats]), (C.c_int64 * L)(*[f.stride(2) for f in feats]),
             (C.c_int64 * L)(*[f.stride(3) for f in feats]), L, Cc, _ptr(boxes), _ptr(count), B, R, P, int(sampling_ratio), k_min, k_max,
