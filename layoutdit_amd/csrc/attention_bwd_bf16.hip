@@ -9,9 +9,17 @@
 // the blocked form at the end of this file), so Q, K, V and dO
 // of the head live in LDS for the whole kernel (row-major 128-B rows, 16-B chunk XOR-swizzled with (row>>1)&7: b128 row
 // reads for the operands that are consumed row-wise, ds_read_b64_tr_b16 for the ones consumed column-wise - one image
-// serves both).  Rows past N are ZERO in all four images, which makes every padded contribution vanish without masks:
-// a padded key has K = V = 0 (no term in dQ, and its own dK / dV rows are never stored), a padded query has Q = dO = 0,
-// delta = 0, L2 = 0 (p = 1, finite) and adds nothing to dK / dV.
+// serves both).  Rows past N are ZERO in all four images.  A padded query needs no mask: Q = dO = 0, delta = 0, L2 = 0, so p = 1
+// (finite) and it adds nothing to dK / dV.  A padded KEY does: its score is 0, so its recomputed probability is exp2(-L2) of
+// the query's row - not small when that row's logits are all very negative, and +inf once L2 < ~-128 (all logits of the row below
+// ~-88 natural units), where dS = inf (0 - delta) scale times the zero K row is inf 0 = NaN in every element of that query's dQ.
+// So p and dS of a padded key are made exactly 0, and full key blocks pay nothing for it:
+//   phase 1 (key = lane): the lanes of padded keys read every row's L2 from Linf, an LDS array of +inf, instead of L2s: p = exp2(-inf)
+//            = 0, dS = 0 (0 - delta) scale = 0 with the loop's instructions unchanged (a second copy of the loop body for the partial
+//            block does not fit the blocked kernel's registers: 256 VGPRs and 8 spilled);
+//   phase 2 (key = register): dS of the padded keys is SELECTED to 0 (mask_key_regs) in a copy of the loop body that only the last,
+//            partial block of 32 keys runs, peeled behind the loop.
+// No sum that was finite before changes a bit.
 //
 // Two phases, every product on v_mfma_f32_32x32x16_bf16 with the accumulator of the first product reused as the B operand
 // of the second one (guide section 3, "An accumulator tile as the next MFMA's operand"; same trick as the forward):
@@ -22,6 +30,8 @@
 // S and dP are therefore computed twice (28 MFMAs per (query block, key block) pair instead of 20) - the price for
 // keeping every sum inside one wave: no atomics, no cross-wave reduction, bit-reproducible.  Attention backward is 4 % of
 // the train step's FLOPs.
+#include <type_traits>
+
 #include "ldit_common.h"
 
 namespace ldit {
@@ -68,6 +78,17 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16 &v, int s)
     return o;
 }
 
+// Padded keys of the last, partial key block, phase 2 / ROLE 1 (phase 1 / ROLE 0 need no instruction: see Linf).  The callers
+// instantiate their loop body twice - std::false_type for full blocks (the body as it always was, one scheduling region from the
+// first MFMA to the last), std::true_type for the block that reaches past N, peeled behind the loop: a branch INSIDE the body cuts
+// it in two between the softmax arithmetic and the second products (measured: +2 % at N = 197, +6 % at N = 1025).
+// Phase 2 / ROLE 1: the key is the register, r <-> key (r&3) + 8 (r>>2) + 4 h of the block; nkeys of its 32 keys exist.
+__device__ __forceinline__ void mask_key_regs(f32x16 &ds, int nkeys, int h)
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ds[r] = ((r & 3) + 8 * (r >> 2) + 4 * h) >= nkeys ? 0.0f : ds[r];
+}
+
 __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__restrict__ Q, const bf16_t *__restrict__ K,
                                                              const bf16_t *__restrict__ V, const bf16_t *__restrict__ O,
                                                              const bf16_t *__restrict__ dO, const float *__restrict__ lse,
@@ -78,7 +99,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nb = (N + 31) >> 5, NP = nb * 32;
     char *Qs = smem, *Ks = Qs + NP * ROWB, *Vs = Ks + NP * ROWB, *Gs = Vs + NP * ROWB;      // Gs = dO image
-    float *L2s = reinterpret_cast<float *>(Gs + NP * ROWB), *dlt = L2s + NP;
+    float *L2s = reinterpret_cast<float *>(Gs + NP * ROWB), *dlt = L2s + NP, *Linf = dlt + NP;     // Linf: NP times +inf
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -123,6 +144,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
                 if (ch == 0) {
                     dlt[row] = d;
                     L2s[row] = row < N ? lse[((size_t)b * H + head) * N + row] : 0.0f;
+                    Linf[row] = INFINITY;
                 }
             }
         }
@@ -143,6 +165,8 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
             vf[s] = row_frag(Vs, key0 + c32, 2 * s + h);
         }
         f32x16 dk[2] = {zero16, zero16}, dv[2] = {zero16, zero16};
+        // a padded key reads +inf for every row's L2: p = exp2(0 c - inf) = 0 and dS = 0 (delta - 0) = 0, at no cost in the loop
+        const float *L2k = key0 + c32 < N ? L2s : Linf;
         for (int i = 0; i < nb; ++i) {
             const int q0 = i * 32;
             f32x16 sc = zero16, dp = zero16;
@@ -154,7 +178,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
             // register r <-> query q0 + (r&3) + 8 (r>>2) + 4 h
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const f32x4 l2 = *reinterpret_cast<const f32x4 *>(L2s + q0 + 8 * g + 4 * h);
+                const f32x4 l2 = *reinterpret_cast<const f32x4 *>(L2k + q0 + 8 * g + 4 * h);
                 const f32x4 de = *reinterpret_cast<const f32x4 *>(dlt + q0 + 8 * g + 4 * h);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -200,7 +224,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
         }
         const float l2 = L2s[q0 + c32], de = dlt[q0 + c32];
         f32x16 dq[2] = {zero16, zero16};
-        for (int j = 0; j < nb; ++j) {
+        auto keys = [&](int j, auto tail_c) {
             const int key0 = j * 32;
             f32x16 sc = zero16, dp = zero16;
 #pragma unroll
@@ -213,6 +237,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
                 const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c, -l2));
                 dp[r] = p * (dp[r] - de) * scale;
             }
+            if constexpr (decltype(tail_c)::value) mask_key_regs(dp, N - key0, h);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const bf16x8 db = pack8(dp, s);
@@ -220,7 +245,10 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16(const bf16_t *__res
                 for (int dt = 0; dt < 2; ++dt)
                     dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(Ks, key0 + 16 * s, 32 * dt, lane), db, dq[dt], 0, 0, 0);
             }
-        }
+        };
+        const int nfull = N >> 5;
+        for (int j = 0; j < nfull; ++j) keys(j, std::false_type{});
+        if (nfull < nb) keys(nfull, std::true_type{});                     // the last, partial key block, peeled
         const int q = q0 + c32;
         if (q < N) {
             bf16_t *pq = dQ + (tok0 + q) * lddqkv + head * 64 + 4 * h;
@@ -258,7 +286,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16_blk(const bf16_t *_
     constexpr int BR = 256;                               // rows per block
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *Qs = smem, *Ks = Qs + BR * ROWB, *Vs = Ks + BR * ROWB, *Gs = Vs + BR * ROWB;      // Gs = dO image
-    float *L2s = reinterpret_cast<float *>(Gs + BR * ROWB), *dlt = L2s + BR;
+    float *L2s = reinterpret_cast<float *>(Gs + BR * ROWB), *dlt = L2s + BR, *Linf = dlt + BR;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -315,6 +343,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16_blk(const bf16_t *_
             if (ch == 0) {
                 dlt[lrow] = d;
                 L2s[lrow] = row < N ? lse[((size_t)b * H + head) * N + row] : 0.0f;
+                Linf[lrow] = INFINITY;
             }
         }
     };
@@ -328,6 +357,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16_blk(const bf16_t *_
         stage_keys(r_res);
         f32x16 dk[2] = {zero16, zero16}, dv[2] = {zero16, zero16};
         const int key0 = wave * 32;
+        const float *L2k = r_res + key0 + c32 < N ? L2s : Linf;         // a padded key reads +inf for every row's L2 (see the kernel above)
         for (int qb = 0; qb < nblk; ++qb) {
             if (qb) __syncthreads();                             // the previous query block is consumed
             stage_queries(qb * BR);
@@ -350,7 +380,7 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16_blk(const bf16_t *_
                 }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const f32x4 l2 = *reinterpret_cast<const f32x4 *>(L2s + q0 + 8 * g + 4 * h);
+                    const f32x4 l2 = *reinterpret_cast<const f32x4 *>(L2k + q0 + 8 * g + 4 * h);
                     const f32x4 de = *reinterpret_cast<const f32x4 *>(dlt + q0 + 8 * g + 4 * h);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -388,6 +418,28 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16_blk(const bf16_t *_
         stage_queries(r_res);
         f32x16 dq[2] = {zero16, zero16};
         const int q0 = wave * 32;
+        // 32 keys (rows key0 .. of the K / V images, nkeys of them real) against this wave's 32 queries
+        auto keys = [&](int key0, int nkeys, const bf16x8 (&qf)[4], const bf16x8 (&gf)[4], float l2, float de, auto tail_c) {
+            f32x16 sc = zero16, dp = zero16;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Ks, key0 + c32, 2 * s + h), qf[s], sc, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Vs, key0 + c32, 2 * s + h), gf[s], dp, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c, -l2));
+                dp[r] = p * (dp[r] - de) * scale;
+            }
+            if constexpr (decltype(tail_c)::value) mask_key_regs(dp, nkeys, h);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 db = pack8(dp, s);
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+                    dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(Ks, key0 + 16 * s, 32 * dt, lane), db, dq[dt], 0, 0, 0);
+            }
+        };
         for (int kb = 0; kb < nblk; ++kb) {
             if (kb) __syncthreads();
             stage_keys(kb * BR);
@@ -400,28 +452,19 @@ __global__ void __launch_bounds__(512, 2) attention_bwd_bf16_blk(const bf16_t *_
                 gf[s] = row_frag(Gs, q0 + c32, 2 * s + h);
             }
             const float l2 = L2s[q0 + c32], de = dlt[q0 + c32];
-            const int nk = (N - kb * BR) < BR ? (N - kb * BR + 31) >> 5 : BR / 32;
-            for (int j = 0; j < nk; ++j) {
-                const int key0 = j * 32;
-                f32x16 sc = zero16, dp = zero16;
+            const int nk = (N - kb * BR) < BR ? (N - kb * BR) >> 5 : BR / 32;       // sub-blocks of 32 keys that are all real
+            for (int j = 0; j < nk; ++j) keys(j * 32, 32, qf, gf, l2, de, std::false_type{});
+        }
+        // the last, partial block of 32 keys of the sequence, peeled behind the loop nest (the K / V images still hold its block)
+        if (live && (N & 31)) {
+            bf16x8 qf[4], gf[4];
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Ks, key0 + c32, 2 * s + h), qf[s], sc, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Vs, key0 + c32, 2 * s + h), gf[s], dp, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c, -l2));
-                    dp[r] = p * (dp[r] - de) * scale;
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const bf16x8 db = pack8(dp, s);
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt)
-                        dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(Ks, key0 + 16 * s, 32 * dt, lane), db, dq[dt], 0, 0, 0);
-                }
+            for (int s = 0; s < 4; ++s) {
+                qf[s] = row_frag(Qs, q0 + c32, 2 * s + h);
+                gf[s] = row_frag(Gs, q0 + c32, 2 * s + h);
             }
+            const int key0 = ((N - (nblk - 1) * BR) >> 5) * 32;
+            keys(key0, N - (nblk - 1) * BR - key0, qf, gf, L2s[q0 + c32], dlt[q0 + c32], std::true_type{});
         }
         const int q = r_res + q0 + c32;
         if (live && q < N) {
@@ -452,7 +495,7 @@ int launch_attention_bwd_bf16(const void *Q, const void *K, const void *V, const
         return fail(LDIT_EINVAL, "attention_bwd: operands must be 16-byte (inputs) / 8-byte (outputs) aligned");
     if (N > 256) {
         // blocked form: one launch per role, a workgroup per (image, head, 256-row block)
-        const int nblk = (N + 255) / 256, ldsb = 4 * 256 * ROWB + 2 * 256 * 4;
+        const int nblk = (N + 255) / 256, ldsb = 4 * 256 * ROWB + 3 * 256 * 4;
         LDIT_DYN_LDS(attention_bwd_bf16_blk<0>, ldsb);
         LDIT_DYN_LDS(attention_bwd_bf16_blk<1>, ldsb);
         hipLaunchKernelGGL(attention_bwd_bf16_blk<0>, dim3((unsigned)(B * H * nblk)), dim3(512), ldsb, stream, static_cast<const bf16_t *>(Q),
@@ -466,8 +509,8 @@ int launch_attention_bwd_bf16(const void *Q, const void *K, const void *V, const
         LDIT_HIP_CHECK(hipGetLastError());
         return LDIT_OK;
     }
-    const int NP = ((N + 31) / 32) * 32, lds = 4 * NP * ROWB + 2 * NP * 4;
-    LDIT_DYN_LDS(attention_bwd_bf16, 4 * 256 * ROWB + 2 * 256 * 4);
+    const int NP = ((N + 31) / 32) * 32, lds = 4 * NP * ROWB + 3 * NP * 4;
+    LDIT_DYN_LDS(attention_bwd_bf16, 4 * 256 * ROWB + 3 * 256 * 4);
     hipLaunchKernelGGL(attention_bwd_bf16, dim3((unsigned)(B * H)), dim3(512), lds, stream, static_cast<const bf16_t *>(Q),
                        static_cast<const bf16_t *>(K), static_cast<const bf16_t *>(V), static_cast<const bf16_t *>(O),
                        static_cast<const bf16_t *>(dO), lse, static_cast<bf16_t *>(dQ), static_cast<bf16_t *>(dK),
