@@ -117,11 +117,13 @@ class DetectorTrainStep:
         self.encoder._pos_cache.clear()
         for mod in self.model.modules():
             if isinstance(mod, DiTWithFPN):
-                mod._cache.clear()
+                for c in mod._cache:
+                    c.clear()
             elif isinstance(mod, RPNHead):
-                mod._packed = None
+                mod._packed.clear()
             elif isinstance(mod, (TwoMLPHead, FastRCNNPredictor)):
-                mod._packed = mod._packed_bf16 = None     # the bf16 head's operands are keyed on versions like the fp32 re-layouts
+                mod._packed.clear()
+                mod._packed_bf16.clear()                  # the bf16 head's operands are keyed on versions like the fp32 re-layouts
 
     def epoch_end(self) -> None:
         """``StepLR(step_size, gamma).step()``: after every ``step_size`` calls the learning rate is multiplied by ``gamma``; the new

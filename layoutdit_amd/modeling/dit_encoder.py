@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from .. import _lib
 from ..config import DiTConfig
+from .grad_ops import param_key
 from .keys import to_v4
 
 
@@ -209,7 +210,7 @@ class DiTEncoder(nn.Module):
         g0 = self.config.image_size // self.config.patch_size
         if gh == g0 and gw == g0:
             return pe.detach().reshape(-1, pe.shape[-1])
-        key = (pe.data_ptr(), pe._version, str(pe.device))
+        key = param_key(pe)
         hit = self._pos_cache.get((gh, gw))
         if hit is not None and hit[0] == key:
             return hit[1]

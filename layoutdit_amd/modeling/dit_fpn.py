@@ -18,8 +18,9 @@ Parameter names follow torchvision (``fpn.inner_blocks.{i}.0.weight`` ...), so d
 
 Training (round 3): ``self.fpn(feats)`` is differentiated as the reference's loop does it (ref dit_backbone.py:87-90 under
 ref trainer.py:169-178) - :class:`_FPNFn` is one ``torch.autograd.Function`` over the whole stage whose backward runs on the
-library's kernels: 3x3 dgrad = the same implicit-im2col fp32 GEMM on the flipped weight, 3x3 and lateral wgrad = bf16 MFMA
-GEMMs on reduction-major operands (fp32 accumulation; gradients of the FPN weights carry bf16 operand rounding, like the
+library's kernels: the 3x3 convolutions through ``grad_ops.conv3x3_bwd`` and the laterals through ``grad_ops.linear_bwd``, which
+the RPN head and the box head share (dgrad = the forward's fp32 GEMM on the flipped / transposed weight, wgrad = bf16 MFMA
+GEMMs on reduction-major operands with fp32 accumulation, so gradients of the FPN weights carry bf16 operand rounding, like the
 encoder's), the merge adjoint and the bias column sums in ``csrc/fpn_bwd.hip``.  Gradients reach the four taps, hence the
 encoder (``layoutdit_amd.training``).  Oracle: autograd of ``oracle/fpn_oracle_torch.py`` (parity unpinned, as above).
 """
@@ -27,15 +28,15 @@ from __future__ import annotations
 
 import math
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..config import DiTConfig
-from .conv_layout import _flip_ihwo
 from .dit_backbone import DiTBackbone
+from .grad_ops import ParamCache, conv3x3_bwd, linear_bwd, param_key
 
 
 class _Conv(nn.Sequential):
@@ -103,27 +104,12 @@ class _FPNFn(torch.autograd.Function):
         d_inner = [None] * 4
         g_cw, g_cb = [None] * 4, [None] * 4
         for i in range(4):                                            # finest first: the top-down adjoint flows fine -> coarse
-            h, w = inners[i].shape[1], inners[i].shape[2]
             dp = dps[i]
             if dp is not None:
                 dy = dp.permute(0, 2, 3, 1)
                 dy = dy.float() if dy.dtype != torch.float32 else dy
                 dy = dy.contiguous()                                  # NHWC [B, h, w, Ch]; a no-op for channels-last gradients
-                d_inner[i] = ops.conv3x3_nhwc(dy, _flip_ihwo(cw[i]))                    # dgrad: same GEMM, flipped weight
-                if need[13 + 2 * i]:
-                    g_cb[i] = ops.colsum(dy.view(B * h * w, Ch))
-                if need[12 + 2 * i]:
-                    slack = w + 3
-                    dy_p = ops.pad_nhwc_bf16(dy)                                         # [B (h+2)(w+2), Ch]
-                    in_p = ops.pad_nhwc_bf16(inners[i], slack_rows=slack)
-                    K = dy_p.shape[0]
-                    taps = []
-                    for ky in range(3):
-                        for kx in range(3):
-                            shift = (ky - 1) * (w + 2) + (kx - 1)
-                            taps.append(ops.wgrad_bf16(dy_p, in_p, K, w_row_offset=slack + shift))   # [co, ci]
-                    g_cw[i] = torch.stack(taps, dim=2).view(Ch, Ch, 3, 3)               # [co, ci, ky, kx] (layout plumbing)
-                    del dy_p, in_p
+                d_inner[i], g_cw[i], g_cb[i] = conv3x3_bwd(dy, inners[i], cw[i], True, need[12 + 2 * i], need[13 + 2 * i])
             else:
                 d_inner[i] = torch.zeros_like(inners[i])
             if i > 0:
@@ -133,14 +119,10 @@ class _FPNFn(torch.autograd.Function):
         for i in range(4):
             d_lat = ops.fpn_merge_bwd(d_inner[i], gh, gw, scales[i])                     # [B, T, Ch], CLS row zero
             d_inner[i] = None
-            d2 = d_lat.view(B * T, Ch)
-            if need[5 + 2 * i]:
-                g_lb[i] = ops.colsum(d2)
-            if need[4 + 2 * i]:
-                g_lw[i] = ops.wgrad_bf16(ops.cast_bf16(d2), ops.cast_bf16(toks[i].view(B * T, Cc)), B * T).view(Ch, Cc, 1, 1)
-            if need[i]:
-                wt = lw[i].reshape(Ch, Cc).t().contiguous()                              # [C, Ch]: the dgrad's K-contiguous operand
-                g_tok[i] = ops.linear(d2, wt).view(B, T, Cc)
+            g_x, g_w, g_lb[i] = linear_bwd(d_lat.view(B * T, Ch), toks[i].view(B * T, Cc), lw[i].reshape(Ch, Cc), need[i],
+                                           need[4 + 2 * i], need[5 + 2 * i])
+            g_tok[i] = g_x.view(B, T, Cc) if need[i] else None
+            g_lw[i] = g_w.view(Ch, Cc, 1, 1) if need[4 + 2 * i] else None
         grads = [None] + g_tok
         for i in range(4):
             grads += [g_lw[i], g_lb[i]]
@@ -162,17 +144,12 @@ class DiTWithFPN(nn.Module):
         self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype, qat=qat)
         self.fpn = _FPNParams([self.backbone.hidden_size] * 4, 256)
         self.out_channels = 256
-        self._cache: Dict[int, tuple] = {}
+        self._cache = [ParamCache() for _ in range(4)]
 
     def _ohwi(self, i: int) -> torch.Tensor:
         """3x3 weight of level i as [Cout, 3, 3, Cin] (GEMM operand layout), re-laid when the parameter changes."""
         w = self.fpn.layer_blocks[i][0].weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._cache.get(i)
-        if hit is None or hit[0] != key:
-            hit = (key, w.detach().permute(0, 2, 3, 1).contiguous())
-            self._cache[i] = hit
-        return hit[1]
+        return self._cache[i].get(param_key(w), lambda: w.detach().permute(0, 2, 3, 1).contiguous())
 
     def forward(self, x: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
         bb = self.backbone

@@ -19,8 +19,9 @@ Training (``train()`` mode with targets): ``select_training_samples`` - the GT b
 ``fastrcnn_loss`` with its gradient two more (``csrc/roi_train.hip``); the sampler is driven by random keys drawn on the device, so
 nothing synchronises.  :class:`MultiScaleRoIAlign` is differentiated by one ``torch.autograd.Function`` over the five maps whose
 backward is ONE gather launch without atomics; :class:`TwoMLPHead` and :class:`FastRCNNPredictor` by one function each whose
-backward runs on the library's kernels like the RPN head's (``ldit_linear_f32`` on the transposed weights, bf16 MFMA weight
-gradients with fp32 accumulation, ``ldit_colsum_f32`` for the biases; ``fc6``'s gradient is permuted back to torchvision's columns).
+backward is ``grad_ops.linear_bwd`` per layer, which the RPN head and the FPN laterals share (``ldit_linear_f32`` on the transposed
+weights, bf16 MFMA weight gradients with fp32 accumulation, ``ldit_colsum_f32`` for the biases; ``fc6``'s gradient is permuted back
+to torchvision's columns).
 The sampled rows come out positives first, not in torchvision's candidate order - the losses are sums.  ``train()`` mode WITHOUT
 targets stays refused.  torchvision is not
 installed offline: the semantics are restated from its documented behaviour (``tests/roi_oracle.py``) - parity unpinned with
@@ -42,10 +43,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-
-
-def _param_key(*ps) -> tuple:
-    return tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
+from .grad_ops import ParamCache, linear_bwd, param_key, stack_rows
 
 
 HEAD_DTYPES = ("f32", "bf16")
@@ -120,17 +118,6 @@ class MultiScaleRoIAlign(nn.Module):
                                     self.sampling_ratio, self.canonical_scale, self.canonical_level)
 
 
-def _linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: bool, need_w: bool, need_b: bool):
-    """Gradients of ``y = x @ weight.T + bias`` on the library's kernels, as the RPN head's: the input gradient is ``ldit_linear_f32``
-    on the transposed weight, the weight gradient a bf16 MFMA GEMM on reduction-major operands with fp32 accumulation (it carries
-    bf16 operand rounding), the bias gradient ``ldit_colsum_f32``.  ``dy`` [M, N], ``x`` [M, K], ``weight`` [N, K]; N % 32 == 0."""
-    M = dy.shape[0]
-    g_x = ops.linear(dy, weight.t().contiguous()) if need_x else None
-    g_w = ops.wgrad_bf16(ops.cast_bf16(dy), ops.cast_bf16(x), M) if need_w else None
-    g_b = ops.colsum(dy) if need_b else None
-    return g_x, g_w, g_b
-
-
 class _TwoMLPHeadFn(torch.autograd.Function):
     """:class:`TwoMLPHead` with gradients for the pooled rows and the four parameters.
     apply(pooled [M, P, P, C], fc6.weight, fc6.bias, fc7.weight, fc7.bias) -> [M, representation_size]."""
@@ -157,9 +144,9 @@ class _TwoMLPHeadFn(torch.autograd.Function):
         M, ph, pw, Cc = ctx.pooled_shape
         need = ctx.needs_input_grad
         d7 = d7.contiguous() * (h7 > 0)                               # ReLU mask
-        d6, g_w7, g_b7 = _linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4])
+        d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4])
         d6.mul_(h6 > 0)
-        g_x, g_w6p, g_b6 = _linear_bwd(d6, x0, w6p, need[0], need[1], need[2])
+        g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2])
         g_w6 = None
         if g_w6p is not None:                                         # back to torchvision's (c, ph, pw) columns
             g_w6 = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
@@ -174,11 +161,7 @@ class _PredictorFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wc, bc, wb, bb):
         NC = wc.shape[0]
-        rows = (5 * NC + 31) // 32 * 32                               # the K of the dgrad GEMM, a multiple of 8 for the wgrad
-        w = torch.zeros((rows, wc.shape[1]), device=x.device, dtype=torch.float32)
-        b = torch.zeros((rows,), device=x.device, dtype=torch.float32)
-        w[:NC], w[NC:5 * NC] = wc.detach(), wb.detach()
-        b[:NC], b[NC:5 * NC] = bc.detach(), bb.detach()
+        w, b = stack_rows((wc, wb), (bc, bb), 32)                     # 32: the K of the dgrad GEMM, a multiple of 8 for the wgrad
         x = x.detach().contiguous()
         ctx.saved = (x, w)
         ctx.NC = NC
@@ -191,7 +174,7 @@ class _PredictorFn(torch.autograd.Function):
         x, w = ctx.saved
         ctx.saved = None
         NC, need = ctx.NC, ctx.needs_input_grad
-        g_x, g_w, g_b = _linear_bwd(dy.contiguous(), x, w, need[0], need[1] or need[3], need[2] or need[4])
+        g_x, g_w, g_b = linear_bwd(dy.contiguous(), x, w, need[0], need[1] or need[3], need[2] or need[4])
         return (g_x, g_w[:NC] if need[1] else None, g_b[:NC] if need[2] else None, g_w[NC:5 * NC] if need[3] else None,
                 g_b[NC:5 * NC] if need[4] else None)
 
@@ -226,8 +209,7 @@ class TwoMLPHead(nn.Module):
         super().__init__()
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
-        self._packed = None
-        self._packed_bf16 = None
+        self._packed, self._packed_bf16 = ParamCache(), ParamCache()
 
     def fc6_weight_hwc(self, channels: int, ph: int, pw: int) -> torch.Tensor:
         """``fc6.weight`` with its columns re-ordered from torchvision's ``flatten(start_dim=1)`` of (c, ph, pw) to (ph, pw, c) - the
@@ -235,18 +217,15 @@ class TwoMLPHead(nn.Module):
         w = self.fc6.weight
         if channels * ph * pw != w.shape[1]:
             raise ValueError(f"TwoMLPHead: pooled rows of {ph} x {pw} x {channels} do not match fc6's {w.shape[1]} inputs")
-        key = (_param_key(w), channels, ph, pw)
-        if self._packed is None or self._packed[0] != key:
-            self._packed = (key, w.detach().view(w.shape[0], channels, ph, pw).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
-        return self._packed[1]
+        return self._packed.get((param_key(w), channels, ph, pw), lambda: w.detach().view(w.shape[0], channels, ph, pw)
+                                .permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
 
     def operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The bf16 GEMM's weight operands: :meth:`fc6_weight_hwc` and ``fc7.weight`` rounded to bf16, re-made when a parameter
         changes."""
-        key = (_param_key(self.fc6.weight, self.fc7.weight), channels, ph, pw)
-        if self._packed_bf16 is None or self._packed_bf16[0] != key:
-            self._packed_bf16 = (key, ops.cast_bf16(self.fc6_weight_hwc(channels, ph, pw)), ops.cast_bf16(self.fc7.weight.detach().contiguous()))
-        return self._packed_bf16[1:]
+        return self._packed_bf16.get((param_key(self.fc6.weight, self.fc7.weight), channels, ph, pw),
+                                     lambda: (ops.cast_bf16(self.fc6_weight_hwc(channels, ph, pw)),
+                                              ops.cast_bf16(self.fc7.weight.detach().contiguous())))
 
     def forward_bf16(self, pooled: torch.Tensor) -> torch.Tensor:
         """``pooled`` bf16 [M, P, P, C] -> bf16 [M, representation_size]: both layers on the bf16 GEMM, the ReLU in its epilogue.
@@ -283,31 +262,19 @@ class FastRCNNPredictor(nn.Module):
         self.cls_score = nn.Linear(in_channels, num_classes)
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
         self.num_classes = int(num_classes)
-        self._packed = None
-        self._packed_bf16 = None
+        self._packed, self._packed_bf16 = ParamCache(), ParamCache()
 
     def _operands(self):
         """Both layers as one [5 NC (padded to a multiple of 4), in_channels] matrix, re-laid when a parameter changes."""
-        ps = (self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias)
-        key = _param_key(*ps)
-        if self._packed is None or self._packed[0] != key:
-            NC = self.num_classes
-            rows = (5 * NC + 3) // 4 * 4
-            w = torch.zeros((rows, ps[0].shape[1]), device=ps[0].device, dtype=torch.float32)
-            b = torch.zeros((rows,), device=ps[0].device, dtype=torch.float32)
-            w[:NC], w[NC:5 * NC] = ps[0].detach(), ps[2].detach()
-            b[:NC], b[NC:5 * NC] = ps[1].detach(), ps[3].detach()
-            self._packed = (key, w, b)
-        return self._packed[1:]
+        wc, bc, wb, bb = self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias
+        return self._packed.get(param_key(wc, bc, wb, bb), lambda: stack_rows((wc, wb), (bc, bb), 4))
 
     def forward_stacked_bf16(self, x: torch.Tensor) -> torch.Tensor:
         """bf16 [M, in_channels] -> fp32 [M, 5 NC (+ pad)] on the bf16 GEMM: the stacked weight rounded to bf16 (re-made when a
         parameter changes), fp32 bias, the accumulator stored unrounded; the padding columns are zero.  No gradient."""
-        key = _param_key(self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias)
-        if self._packed_bf16 is None or self._packed_bf16[0] != key:
-            w, b = self._operands()
-            self._packed_bf16 = (key, ops.cast_bf16(w), b)
-        return ops.linear_bf16(x, self._packed_bf16[1], self._packed_bf16[2], _lib.EPI_F32)
+        w, b = self._operands()
+        w16 = self._packed_bf16.get(param_key(self.cls_score.weight, self.bbox_pred.weight), lambda: ops.cast_bf16(w))
+        return ops.linear_bf16(x, w16, b, _lib.EPI_F32)
 
     def forward_stacked(self, x: torch.Tensor) -> torch.Tensor:
         """[M, in_channels] -> [M, 5 NC (+ pad)]: the class logits in columns [0, NC), the deltas in [NC, 5 NC)."""

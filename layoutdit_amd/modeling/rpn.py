@@ -15,11 +15,11 @@ Training (``train()`` mode with targets): ``assign_targets_to_anchors`` - ``Matc
 ``BalancedPositiveNegativeSampler(256, 0.5)``, ``BoxCoder(1, 1, 1, 1).encode`` - is ONE launch and ``compute_loss`` with both
 gradients two more (``csrc/rpn_train.hip``): fixed-size results instead of torchvision's ``nonzero`` / ``randperm``, the sampler
 driven by random keys drawn on the device, so still no synchronisation.  :class:`RPNHead` is differentiated by one
-``torch.autograd.Function`` per level whose backward runs on the library's kernels like the FPN's: the 1x1 pair's dgrad is
-``ldit_linear_f32`` on the transposed weight (15 columns padded to the GEMM's 32), the 3x3 dgrad the same implicit-im2col GEMM on
-the flipped weight, all three weight gradients bf16 MFMA GEMMs on reduction-major operands with fp32 accumulation (they carry bf16
-operand rounding, like the FPN's and the encoder's), the biases ``ldit_colsum_f32``.  ``train()`` mode WITHOUT targets stays
-refused.  The box head's training is not implemented.
+``torch.autograd.Function`` per level, which reads the head's cached operands and whose backward is the FPN's and the box head's
+(``grad_ops.py``): ``linear_bwd`` for the 1x1 pair (``ldit_linear_f32`` on the transposed weight, its 15 columns padded to the
+GEMM's 32), ``conv3x3_bwd`` for the 3x3 (the same implicit-im2col GEMM on the flipped weight), all three weight gradients bf16
+MFMA GEMMs on reduction-major operands with fp32 accumulation (they carry bf16 operand rounding, like the encoder's), the biases
+``ldit_colsum_f32``.  ``train()`` mode WITHOUT targets stays refused.
 
 torchvision is not installed offline: the semantics are restated from its documented behaviour (``tests/rpn_oracle.py``,
 ``tests/rpn_train_oracle.py``) - parity unpinned with respect to torchvision itself, as for the FPN.  Parameter names follow
@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .conv_layout import _flip_ihwo
+from .grad_ops import ParamCache, conv3x3_bwd, linear_bwd, param_key, stack_rows
 
 
 class AnchorGenerator(nn.Module):
@@ -96,26 +96,28 @@ class _ConvRelu(nn.Sequential):
         super().__init__(nn.Conv2d(c, c, kernel_size=3, padding=1), nn.ReLU(inplace=True))
 
 
+def _level_forward(x, operands, A: int):
+    """One level on :meth:`RPNHead._operands`: the NHWC map, the 3x3's activation and ``(logits [B, h w A], deltas [B, h w A, 4])``."""
+    w3, b3, w1, b1 = operands
+    B, Cc, h, w = x.shape
+    xn = x.detach().permute(0, 2, 3, 1).contiguous()                                      # NHWC; free for channels-last maps
+    t = ops.conv3x3_nhwc(xn, w3, b3)
+    torch.relu_(t)
+    y = ops.linear(t.view(B * h * w, Cc), w1, b1)                      # [B h w, 5 A (+ pad)]: logits | deltas per pixel row
+    return xn, t, (y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4))
+
+
 class _RPNHeadLevelFn(torch.autograd.Function):
-    """One level of :class:`RPNHead` with gradients for the map and all six parameters.
-    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box) -> (logits [B, h w A], deltas [B, h w A, 4])."""
+    """One level of :class:`RPNHead` with gradients for the map and all six parameters.  ``operands`` is the head's cached
+    :meth:`RPNHead._operands` - the same weights as the GEMMs read them, no gradient of their own.
+    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box, operands) -> (logits [B, h w A], deltas [B, h w A, 4])."""
 
     @staticmethod
-    def forward(ctx, x, w3, b3, wc, bc, wb, bb):
-        B, Cc, h, w = x.shape
-        A = wc.shape[0]
-        rows = (5 * A + 3) // 4 * 4
-        w1 = torch.zeros((rows, Cc), device=x.device, dtype=torch.float32)
-        b1 = torch.zeros((rows,), device=x.device, dtype=torch.float32)
-        w1[:A], w1[A:5 * A] = wc.detach().reshape(A, Cc), wb.detach().reshape(4 * A, Cc)
-        b1[:A], b1[A:5 * A] = bc.detach(), bb.detach()
-        xn = x.detach().permute(0, 2, 3, 1).contiguous()                                  # NHWC; free for channels-last maps
-        t = ops.conv3x3_nhwc(xn, w3.detach().permute(0, 2, 3, 1).contiguous(), b3.detach())
-        torch.relu_(t)
-        y = ops.linear(t.view(B * h * w, Cc), w1, b1)
-        ctx.saved = (xn, t, w3.detach(), w1)
-        ctx.A = A
-        return y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4)
+    def forward(ctx, x, w3, b3, wc, bc, wb, bb, operands):
+        xn, t, out = _level_forward(x, operands, wc.shape[0])
+        ctx.saved = (xn, t, w3.detach(), operands[2])
+        ctx.A = wc.shape[0]
+        return out
 
     @staticmethod
     def backward(ctx, d_logits, d_deltas):
@@ -135,36 +137,12 @@ class _RPNHeadLevelFn(torch.autograd.Function):
             dy[:, :A] = d_logits.reshape(M, A)
         if d_deltas is not None:
             dy[:, A:5 * A] = d_deltas.reshape(M, 4 * A)
-        w1t = torch.zeros((Cc, K), device=xn.device, dtype=torch.float32)
-        w1t[:, :5 * A] = w1[:5 * A].t()
-        dt = ops.linear(dy, w1t)                                                          # dgrad of the 1x1 pair: [M, C]
+        dt, g1, gb = linear_bwd(dy, t.view(M, Cc), w1, True, need[3] or need[5], need[4] or need[6])   # [M, C], [K, C], [K]
         dt.mul_(t.view(M, Cc) > 0)                                                        # ReLU mask
-        g_wc = g_bc = g_wb = g_bb = g_w3 = g_b3 = g_x = None
-        if need[3] or need[5]:
-            g1 = ops.wgrad_bf16(ops.cast_bf16(dy), ops.cast_bf16(t.view(M, Cc)), M)       # [K, C]
-            g_wc = g1[:A].reshape(A, Cc, 1, 1) if need[3] else None
-            g_wb = g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None
-        if need[4] or need[6]:
-            gb = ops.colsum(dy)
-            g_bc = gb[:A] if need[4] else None
-            g_bb = gb[A:5 * A] if need[6] else None
-        dt4 = dt.view(B, h, w, Cc)
-        if need[2]:
-            g_b3 = ops.colsum(dt)
-        if need[1]:
-            slack = w + 3
-            dt_p = ops.pad_nhwc_bf16(dt4)                                                 # [B (h+2)(w+2), C]
-            x_p = ops.pad_nhwc_bf16(xn, slack_rows=slack)
-            rows = dt_p.shape[0]
-            taps = []
-            for ky in range(3):
-                for kx in range(3):
-                    shift = (ky - 1) * (w + 2) + (kx - 1)
-                    taps.append(ops.wgrad_bf16(dt_p, x_p, rows, w_row_offset=slack + shift))   # [co, ci]
-            g_w3 = torch.stack(taps, dim=2).view(Cc, Cc, 3, 3)
-        if need[0]:
-            g_x = ops.conv3x3_nhwc(dt4, _flip_ihwo(w3)).permute(0, 3, 1, 2)                # dgrad: same GEMM, flipped weight
-        return g_x, g_w3, g_b3, g_wc, g_bc, g_wb, g_bb
+        g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2])
+        return (g_x.permute(0, 3, 1, 2) if need[0] else None, g_w3, g_b3,
+                g1[:A].reshape(A, Cc, 1, 1) if need[3] else None, gb[:A] if need[4] else None,
+                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None)
 
 
 class _RPNLossFn(torch.autograd.Function):
@@ -196,25 +174,18 @@ class RPNHead(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.normal_(m.weight, std=0.01)
                 nn.init.constant_(m.bias, 0)
-        self._packed = None
+        self._packed = ParamCache()
+
+    def _params(self):
+        return (self.conv[0][0].weight, self.conv[0][0].bias, self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight,
+                self.bbox_pred.bias)
 
     def _operands(self):
-        """The 3x3 weight as [Cout, 3, 3, Cin] and both 1x1 convolutions as one [5 A (padded to a multiple of 4), C] matrix,
-        re-laid when a parameter changes."""
-        ps = (self.conv[0][0].weight, self.conv[0][0].bias, self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight,
-              self.bbox_pred.bias)
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-        if self._packed is None or self._packed[0] != key:
-            A, Cc = self.num_anchors, self.in_channels
-            rows = (5 * A + 3) // 4 * 4
-            w = torch.zeros((rows, Cc), device=ps[0].device, dtype=torch.float32)
-            b = torch.zeros((rows,), device=ps[0].device, dtype=torch.float32)
-            w[:A] = ps[2].detach().reshape(A, Cc)
-            w[A:5 * A] = ps[4].detach().reshape(4 * A, Cc)
-            b[:A] = ps[3].detach()
-            b[A:5 * A] = ps[5].detach()
-            self._packed = (key, ps[0].detach().permute(0, 2, 3, 1).contiguous(), ps[1].detach(), w, b)
-        return self._packed[1:]
+        """``(w3, b3, w1, b1)``: the 3x3 weight as [Cout, 3, 3, Cin] with its bias, and both 1x1 convolutions as one [5 A (padded
+        to a multiple of 4), C] matrix with theirs, re-laid when a parameter changes."""
+        w3, b3, wc, bc, wb, bb = ps = self._params()
+        return self._packed.get(param_key(*ps), lambda: (w3.detach().permute(0, 2, 3, 1).contiguous(), b3.detach(),
+                                                         *stack_rows((wc.flatten(1), wb.flatten(1)), (bc, bb), 4)))
 
     def forward_level(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """One map ``[B, C, h, w]`` (any memory layout; channels-last costs no copy) -> objectness logits ``[B, h w A]`` and box
@@ -224,16 +195,9 @@ class RPNHead(nn.Module):
         if x.dtype != torch.float32:
             raise ValueError(f"RPNHead: expected float32 features, got {x.dtype}")
         if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            # gradients are wanted: one differentiable node per level (the eval path below is untouched)
-            return _RPNHeadLevelFn.apply(x, self.conv[0][0].weight, self.conv[0][0].bias, self.cls_logits.weight, self.cls_logits.bias,
-                                         self.bbox_pred.weight, self.bbox_pred.bias)
-        w3, b3, w1, b1 = self._operands()
-        B, Cc, h, w = x.shape
-        A = self.num_anchors
-        t = ops.conv3x3_nhwc(x.detach().permute(0, 2, 3, 1).contiguous(), w3, b3)
-        torch.relu_(t)
-        y = ops.linear(t.view(B * h * w, Cc), w1, b1)                  # [B h w, 5 A (+ pad)]: logits | deltas per pixel row
-        return y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4)
+            # gradients are wanted: one differentiable node per level, on the operands of the eval path below
+            return _RPNHeadLevelFn.apply(x, *self._params(), self._operands())
+        return _level_forward(x, self._operands(), self.num_anchors)[2]
 
     def forward(self, features: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         """All levels: logits ``[B, Ntot]`` and deltas ``[B, Ntot, 4]``, levels concatenated in the order given."""

@@ -116,13 +116,16 @@ def test_fpn_merge_adjoint(gh, gw, scale, with_top):
 
 
 def test_fpn_backward_building_blocks():
-    """colsum, the zero-padded bf16 copy, the 3x3 dgrad (same GEMM, flipped weight) and the nine-tap bf16 wgrad on padded
-    NHWC operands - each against float64 torch (the wgrad on the bf16-rounded operands it actually multiplies)."""
+    """colsum, the zero-padded bf16 copy, and ``conv3x3_bwd`` - the 3x3 dgrad (same GEMM, flipped weight), the nine-tap bf16 wgrad
+    on padded NHWC operands and the bias sum - each against float64 torch (the wgrad on the bf16-rounded operands it actually
+    multiplies).  Other shapes and the ``need_*`` switches: tests/test_gpu_grad_ops.py."""
+    from layoutdit_amd.modeling.grad_ops import conv3x3_bwd, flip_ihwo
     B, H, W, Ch = 2, 6, 9, 64
     x, dy = _rand(50, B, H, W, Ch), _rand(51, B, H, W, Ch)
     wt = _rand(52, Ch, Ch, 3, 3, scale=0.05)
     xd, dyd = torch.from_numpy(x).to(DEV), torch.from_numpy(dy).to(DEV)
-    assert rel_l2(ops.colsum(dyd.view(-1, Ch)).cpu().numpy(), dy.reshape(-1, Ch).astype(np.float64).sum(0)) < 1e-6
+    dx, dw, db = conv3x3_bwd(dyd, xd, torch.from_numpy(wt).to(DEV), True, True, True)
+    assert rel_l2(db.cpu().numpy(), dy.reshape(-1, Ch).astype(np.float64).sum(0)) < 1e-6
     big = torch.from_numpy(_rand(53, 3000, 96)).to(DEV)
     assert rel_l2(ops.colsum(big).cpu().numpy(), big.cpu().double().sum(0).numpy()) < 1e-6
     slack = W + 3
@@ -134,16 +137,8 @@ def test_fpn_backward_building_blocks():
     xr = torch.from_numpy(x).double().permute(0, 3, 1, 2).requires_grad_(True)
     wr = torch.from_numpy(wt).double().requires_grad_(True)
     (F.conv2d(xr, wr, padding=1) * torch.from_numpy(dy).double().permute(0, 3, 1, 2)).sum().backward()
-    from layoutdit_amd.modeling.dit_fpn import _flip_ihwo
-    dx = ops.conv3x3_nhwc(dyd, _flip_ihwo(torch.from_numpy(wt).to(DEV)))
+    assert torch.equal(dx, ops.conv3x3_nhwc(dyd, flip_ihwo(torch.from_numpy(wt).to(DEV))))
     assert rel_l2(dx.cpu().numpy(), xr.grad.permute(0, 2, 3, 1).numpy()) < 1e-5
-    dyp = ops.pad_nhwc_bf16(dyd)
-    taps = []
-    for ky in range(3):
-        for kx in range(3):
-            shift = (ky - 1) * (W + 2) + (kx - 1)
-            taps.append(ops.wgrad_bf16(dyp, xp, dyp.shape[0], w_row_offset=slack + shift))
-    dw = torch.stack(taps, dim=2).view(Ch, Ch, 3, 3)
     xb = torch.from_numpy(x).to(torch.bfloat16).double().permute(0, 3, 1, 2).requires_grad_(False)
     wr2 = torch.from_numpy(wt).double().requires_grad_(True)
     (F.conv2d(xb, wr2, padding=1) * torch.from_numpy(dy).to(torch.bfloat16).double().permute(0, 3, 1, 2)).sum().backward()
