@@ -363,6 +363,17 @@ int ldit_fpn_merge_f32(const void *lat, const void *top, void *out, int64_t B, i
                        int64_t top_h, int64_t top_w, ldit_stream stream);
 int ldit_conv3x3_nhwc_f32(const void *x, const void *w, const void *bias, void *y, int64_t B, int64_t H, int64_t W, int64_t Cin,
                           int64_t Cout, const void *zeros, ldit_stream stream);
+/* The same convolution on the bf16 matrix pipe (the eval-mode neck, neck_dtype="bf16"): the implicit-im2col mode of the bf16 MFMA
+ * GEMM on a map that is ALREADY zero-padded.  xpad bf16 [B, H+2, W+2, Cin], exactly what ldit_pad_nhwc_f32_bf16 writes (no slack
+ * rows: the highest address read is its last pixel); w bf16 [Cout, 3, 3, Cin]; bias fp32 [Cout] or NULL; y [B*H*W, Cout], row stride
+ * ldy >= Cout elements: fp32 = acc + bias for LDIT_EPI_F32, bf16 for LDIT_EPI_BIAS and LDIT_EPI_BIAS_RELU (relu of LDIT_EPI_BIAS's y
+ * bit for bit).  fp32 accumulation, k order (ky, kx, c) in 64-deep tiles: y equals, bit for bit, ldit_linear_bf16(_ex) with the
+ * same epilogue on the materialised im2col matrix [B*H*W, 9 Cin] of xpad.  LDIT_EINVAL: null operand, xpad / w / y not 16-byte
+ * aligned, empty problem, any other epilogue, ldy < Cout (every ldy >= Cout is taken: a stride the vector stores cannot take
+ * goes element-wise).  LDIT_EUNSUPPORTED: Cin not a multiple of 64; padded map, output (B*H*W*ldy) or weight of 2^31 elements
+ * or more (element offsets are 32 bits wide). */
+int ldit_conv3x3_nhwc_bf16(const void *xpad, const void *w, const void *bias, void *y, int64_t ldy, int64_t B, int64_t H, int64_t W,
+                           int64_t Cin, int64_t Cout, int32_t epilogue, ldit_stream stream);
 
 /* ---- FPN backward (training through `self.fpn(feats)`, ref dit_backbone.py:87-90 under ref trainer.py:169-178).  The MFMA work
  * reuses entry points above and below (layoutdit_amd/modeling/dit_fpn.py sequences them): dgrad of a 3x3 convolution =

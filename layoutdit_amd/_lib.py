@@ -106,6 +106,7 @@ SIGNATURES = {
     "ldit_cast_f32_f16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "ldit_fpn_merge_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _i64, _i64, _vp]),
     "ldit_conv3x3_nhwc_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "ldit_conv3x3_nhwc_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     "ldit_fpn_merge_bwd_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _i64, _i64, _vp]),
     "ldit_pad_nhwc_f32_bf16": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "ldit_colsum_scratch_bytes": (_sz, [_i64, _i64]),

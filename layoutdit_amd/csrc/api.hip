@@ -868,6 +868,19 @@ int ldit_conv3x3_nhwc_f32(const void *x, const void *w, const void *bias, void *
     return launch_gemm(a, EPI_BIAS, A_CONV3, static_cast<hipStream_t>(stream));
 }
 
+int ldit_conv3x3_nhwc_bf16(const void *xpad, const void *w, const void *bias, void *y, int64_t ldy, int64_t B, int64_t H, int64_t W,
+                           int64_t Cin, int64_t Cout, int32_t epilogue, ldit_stream stream)
+{
+    int epi;
+    switch (epilogue) {
+        case LDIT_EPI_F32: epi = EPI_F32; break;
+        case LDIT_EPI_BIAS: epi = EPI_BIAS; break;
+        case LDIT_EPI_BIAS_RELU: epi = EPI_BIAS_RELU; break;
+        default: return fail(LDIT_EINVAL, "conv3x3_bf16: unknown epilogue %d", epilogue);
+    }
+    return launch_conv3x3_bf16(xpad, w, static_cast<const float *>(bias), y, ldy, B, H, W, Cin, Cout, epi, static_cast<hipStream_t>(stream));
+}
+
 int ldit_fpn_merge_bwd_f32(const void *d_inner, void *d_lat, void *d_top, int64_t B, int64_t Gh, int64_t Gw, int64_t Ch, float scale,
                            int64_t top_h, int64_t top_w, ldit_stream stream)
 {

@@ -96,10 +96,25 @@ __device__ __forceinline__ void tail_tile(const GemmArgsH &p, int tile, int lane
     else store_h<1, 1, EPI, 2, true, 1>(p, acc, m0, n0, lane);
 }
 
-template <int WM, int WN, int TM, int TN, int EPI>
-__global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(const GemmArgsH p0)
+// CONV (launch_conv3x3_bf16 below): the A operand is the zero-padded bf16 NHWC map [B, H+2, W+2, C] that pad_nhwc_bf16 (fpn_bwd.hip) writes,
+// read as the implicit im2col of a 3x3 / pad 1 convolution: output row m = pixel (b, y, x), k = (ky, kx, c), K = 9 C, C % 64 == 0, so
+// a 64-deep k-tile lies inside ONE tap and the A row of a tap is the contiguous C-vector of padded pixel (b, y + ky, x + kx) - no
+// bounds test, no zero page; the highest address read is padded pixel (B-1, H+1, W+1), the buffer's last row.  Only two things
+// differ from the row-major kernel: the lane's row offset src[u] and the k-tile's scalar A offset (tile_off).  The LDS image, the
+// pipeline, the MFMA order and the epilogues are the same code, so per output element the accumulation chain is that of the
+// row-major GEMM on the materialised im2col matrix: the same bits.  The geometry travels behind the GEMM's own arguments, which
+// keeps the row-major kernels' argument block - and their instruction stream - what it was.
+struct ConvArgsH {
+    GemmArgsH g;         // M = B H W, N = Cout, K = 9 C; A = the padded map, W = [Cout, 3, 3, C]; lda unused
+    int H, W, C;
+};
+__device__ __forceinline__ const GemmArgsH &gemm_args(const GemmArgsH &a) { return a; }
+__device__ __forceinline__ const GemmArgsH &gemm_args(const ConvArgsH &a) { return a.g; }
+
+template <int WM, int WN, int TM, int TN, int EPI, bool CONV = false>
+__global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(const std::conditional_t<CONV, ConvArgsH, GemmArgsH> p0)
 {
-    GemmArgsH p = p0;
+    GemmArgsH p = gemm_args(p0);
     constexpr int NWAVES = WM * WN;
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, ROWS = BM + BN;
     static_assert(BM % 8 == 0, "a DMA piece is eight rows");
@@ -119,7 +134,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
 
     const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
     const int ntiles = nbm * nbn, nblocks = ntiles * p.x.splits;
-    if (p.x.tail_rows > 0 && (int)blockIdx.x >= nblocks) {
+    if (!CONV && p.x.tail_rows > 0 && (int)blockIdx.x >= nblocks) {     // (no peeled tail in conv mode)
         // The peeled tail of THIS GEMM (launch_gemm_bf16_ex): rows M .. M + tail_rows - 1, one 32 x 16 tile per wave of the workgroups
         // behind the last tile - the same code, hence the same bits, as the separate gemm_bf16_tail launch it replaces (round 4:
         // one launch and one kernel boundary less per GEMM of ViT-L 512^2, M = 64 x 256 + 16).
@@ -144,7 +159,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
     }
     int nk = p.K / BKB;
-    if (EPI == EPI_F32 && p.x.splits > 1) {
+    if (!CONV && EPI == EPI_F32 && p.x.splits > 1) {
         // split-K (wgrad: K = tokens of the batch, output tiles few): this block multiplies k-tiles [kt0, kt0 + nk) into its
         // own fp32 slab; ldit's reduce kernel adds the slabs in a fixed order
         const int split = tile / ntiles, per = (nk + p.x.splits - 1) / p.x.splits, kt0 = split * per;
@@ -192,7 +207,14 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         if (8 * ((wave % LW) + LW * u) < BM) {
             int gm = m0 + row;
             gm = gm < p.M ? gm : p.M - 1;
-            src[u] = (unsigned)gm * (unsigned)p.lda + c * 8;
+            if constexpr (CONV) {
+                // output pixel gm = (b, y, x) -> its tap (0, 0): padded pixel (b, y, x); tile_off adds the tap's (ky, kx)
+                const unsigned hw = (unsigned)p0.H * (unsigned)p0.W, b = (unsigned)gm / hw, r = (unsigned)gm - b * hw;
+                const unsigned y = r / (unsigned)p0.W, x = r - y * (unsigned)p0.W;
+                src[u] = ((b * (unsigned)(p0.H + 2) + y) * (unsigned)(p0.W + 2) + x) * (unsigned)p0.C + c * 8;
+            } else {
+                src[u] = (unsigned)gm * (unsigned)p.lda + c * 8;
+            }
         } else {
             int gn = n0 + row - BM;
             gn = gn < p.N ? gn : p.N - 1;
@@ -205,6 +227,14 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
     const int nkt = nk * nseg;
     auto tile_off = [&](int t, unsigned &ka, unsigned &kw) {
         t = t < nkt ? t : nkt - 1;
+        if constexpr (CONV) {
+            // k-tile t = (tap, 64-channel slice): the tap (ky, kx) is a constant offset of ky padded rows and kx pixels on every A
+            // row; W [Cout, 3, 3, C] is walked straight through.  The division is made scalar here like the plane offsets below.
+            const unsigned cpt = (unsigned)p0.C / BKB, tap = (unsigned)t / cpt, ky = tap / 3u, kx = tap - 3u * ky;
+            ka = __builtin_amdgcn_readfirstlane((ky * (unsigned)(p0.W + 2) + kx) * (unsigned)p0.C + ((unsigned)t - tap * cpt) * BKB);
+            kw = __builtin_amdgcn_readfirstlane((unsigned)t * BKB);
+            return;
+        }
         int seg = 0;
         if (p.x.nseg > 1) {
             if (p.x.seg_inner) { const int kb = t / p.x.nseg; seg = t - kb * p.x.nseg; t = kb; }
@@ -591,17 +621,10 @@ int launch_tail(const GemmArgsH &a, hipStream_t stream)
     return LDIT_OK;
 }
 
+// the tile (2: 128 x 128, 3: 256 x 256, 4: 192 x 256, 5: 320 x 256) for one problem; LDIT_GEMM_BF16_TILE overrides
 template <int EPI>
-int launch_h_tiled(const GemmArgsH &a, hipStream_t stream)
+int pick_tile_h(const GemmArgsH &a)
 {
-    if (a.M <= 64 && a.x.splits == 1 && !diag().bf16_tile_env) return launch_tail<EPI>(a, stream);
-    // Split-fp32 operands at serving sizes: the plane products make the k-loop 3 - 6 x as deep (K' = 2 304 ... 18 432) while a few
-    // images give the tile kernels only a handful of tiles - twelve 128 x 128 tiles walking K' = 9 216 took 170 us.  The one-wave-per-
-    // 32 x 32-tile kernel spreads the same work over hundreds of waves (bit-identical rows).  It re-reads its operands from L2 per
-    // wave, so it only pays while there are few of them: up to 700 waves (scripts/latency_bench.py, f32x3 at bs = 1 / 2 / 4: 3.03 /
-    // 3.04 / 3.07 ms on the tile kernels alone, 1.49 / 2.24 / 2.77 ms with this rule; 6 144 waves: 1.49 / 2.42 / 3.83 ms).
-    if (a.x.nseg > 1 && a.x.splits == 1 && !diag().bf16_tile_env && (long)((a.M + 31) / 32) * ((a.N + 31) / 32) <= diag().planes_tail_waves)
-        return launch_tail<EPI>(a, stream);
     // Time model fitted to scripts/gemm_bf16_bench.py on ViT-B / ViT-L shapes, M = 3 k .. 25 k (profiles/README.md), in us:
     //   256 x 256, 8 waves (one workgroup per CU):  strict rounds of 256 tiles, each  a[epi] + 19.5e-3 K
     //   128 x 128 (two per CU, they overlap each other's prologue / epilogue):  rounds of 256 tiles, each  r[epi] + 7.6e-3 K,
@@ -634,11 +657,53 @@ int launch_h_tiled(const GemmArgsH &a, hipStream_t stream)
         if (c < best) { best = c; pick = bm == 192 ? 4 : 5; }
     }
     if (const int force = diag().bf16_tile; force >= 2 && force <= 5) pick = force;
-    switch (pick) {
+    return pick;
+}
+
+template <int EPI>
+int launch_h_tiled(const GemmArgsH &a, hipStream_t stream)
+{
+    if (a.M <= 64 && a.x.splits == 1 && !diag().bf16_tile_env) return launch_tail<EPI>(a, stream);
+    // Split-fp32 operands at serving sizes: the plane products make the k-loop 3 - 6 x as deep (K' = 2 304 ... 18 432) while a few
+    // images give the tile kernels only a handful of tiles - twelve 128 x 128 tiles walking K' = 9 216 took 170 us.  The one-wave-per-
+    // 32 x 32-tile kernel spreads the same work over hundreds of waves (bit-identical rows).  It re-reads its operands from L2 per
+    // wave, so it only pays while there are few of them: up to 700 waves (scripts/latency_bench.py, f32x3 at bs = 1 / 2 / 4: 3.03 /
+    // 3.04 / 3.07 ms on the tile kernels alone, 1.49 / 2.24 / 2.77 ms with this rule; 6 144 waves: 1.49 / 2.42 / 3.83 ms).
+    if (a.x.nseg > 1 && a.x.splits == 1 && !diag().bf16_tile_env && (long)((a.M + 31) / 32) * ((a.N + 31) / 32) <= diag().planes_tail_waves)
+        return launch_tail<EPI>(a, stream);
+    switch (pick_tile_h<EPI>(a)) {
         case 3: return launch_h<2, 4, 4, 2, EPI>(a, stream);     // 256 x 256, 8 waves (2 per SIMD)
         case 4: return launch_h<2, 4, 3, 2, EPI>(a, stream);     // 192 x 256
         case 5: return launch_h<2, 4, 5, 2, EPI>(a, stream);     // 320 x 256
         default: return launch_h<2, 2, 2, 2, EPI>(a, stream);    // 128 x 128, 4 waves
+    }
+}
+
+// ---- implicit-im2col 3x3 convolution on the padded bf16 map (gemm_bf16_mfma<..., CONV = true>) ------------------------------------
+template <int WM, int WN, int TM, int TN, int EPI>
+int launch_conv_h(const ConvArgsH &a, hipStream_t stream)
+{
+    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
+    constexpr int lds = 2 * (BM + BN) * ROWB;
+    const int tiles = ((a.g.M + BM - 1) / BM) * ((a.g.N + BN - 1) / BN);
+    auto kern = gemm_bf16_mfma<WM, WN, TM, TN, EPI, true>;
+    LDIT_DYN_LDS(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(64 * WM * WN), lds, stream, a);
+    LDIT_HIP_CHECK(hipGetLastError());
+    return LDIT_OK;
+}
+
+// Every size runs on a tile kernel (the ragged last row tile and ragged N through its clamped rows and checked stores; no peeled
+// tail, no one-wave kernel): a map of at most 64 pixels takes the smallest tile, every other one the row-major picker's.
+template <int EPI>
+int launch_conv_tiled(const ConvArgsH &a, hipStream_t stream)
+{
+    const int pick = (a.g.M <= 64 && !diag().bf16_tile_env) ? 2 : pick_tile_h<EPI>(a.g);
+    switch (pick) {
+        case 3: return launch_conv_h<2, 4, 4, 2, EPI>(a, stream);
+        case 4: return launch_conv_h<2, 4, 3, 2, EPI>(a, stream);
+        case 5: return launch_conv_h<2, 4, 5, 2, EPI>(a, stream);
+        default: return launch_conv_h<2, 2, 2, 2, EPI>(a, stream);
     }
 }
 
@@ -790,6 +855,34 @@ static int launch_gemm_bf16_one(const void *A, int lda, const void *W, const flo
             if (!x.aux || (x.ldaux & 3) || (reinterpret_cast<uintptr_t>(x.aux) & 7u)) return fail(LDIT_EINVAL, "gemm_bf16: GELU-backward epilogue needs an aligned pre-activation operand");
             return launch_h_tiled<EPI_GELU_BWD>(a, stream);
         default: return fail(LDIT_EINVAL, "gemm_bf16: unknown epilogue %d", epi);
+    }
+}
+
+// y [B H W, Cout] (row stride ldy) = epi(conv3x3(xpad, w, padding 1) + bias): xpad bf16 [B, H+2, W+2, Cin] as pad_nhwc_bf16 writes it,
+// w bf16 [Cout, 3, 3, Cin]; EPI_F32 writes fp32, EPI_BIAS / EPI_BIAS_RELU bf16.  Element offsets are 32 bits wide in the kernel.
+int launch_conv3x3_bf16(const void *xpad, const void *w, const float *bias, void *y, int64_t ldy, int64_t B, int64_t H, int64_t W,
+                        int64_t Cin, int64_t Cout, int epi, hipStream_t stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail(LDIT_EINVAL, "conv3x3_bf16: empty problem");
+    if (epi != EPI_F32 && epi != EPI_BIAS && epi != EPI_BIAS_RELU) return fail(LDIT_EINVAL, "conv3x3_bf16: unknown epilogue %d", epi);
+    if (!xpad || !w || !y) return fail(LDIT_EINVAL, "conv3x3_bf16: null operand");
+    if (!aligned16(xpad) || !aligned16(w) || !aligned16(y)) return fail(LDIT_EINVAL, "conv3x3_bf16: operands must be 16-byte aligned");
+    if (ldy < Cout) return fail(LDIT_EINVAL, "conv3x3_bf16: ldy=%lld is less than Cout=%lld", (long long)ldy, (long long)Cout);
+    if (Cin % BKB) return fail(LDIT_EUNSUPPORTED, "conv3x3_bf16: Cin=%lld must be a multiple of %d", (long long)Cin, BKB);
+    const int64_t lim = 1ll << 31;
+    // (each factor first: the products below stay inside 64 bits)
+    if (B >= lim || H >= lim || W >= lim || Cin >= lim || Cout >= lim || ldy >= lim || (B * (H + 2)) >= lim || (B * (H + 2)) * (W + 2) >= lim ||
+        (B * (H + 2)) * (W + 2) * Cin >= lim || (B * H * W) * ldy >= lim || Cout * Cin >= lim || Cout * Cin * 9 >= lim)
+        return fail(LDIT_EUNSUPPORTED, "conv3x3_bf16: padded map, output or weight exceeds 2^31 elements");
+    ConvArgsH a{};
+    a.g.A = static_cast<const bf16_t *>(xpad); a.g.W = static_cast<const bf16_t *>(w); a.g.Y = y; a.g.bias = bias;
+    a.g.M = (int)(B * H * W); a.g.N = (int)Cout; a.g.K = (int)(9 * Cin); a.g.lda = (int)Cin; a.g.ldw = a.g.K; a.g.ldy = (int)ldy;
+    a.g.direct_epi = diag().direct_epi ? 1 : 0;
+    a.H = (int)H; a.W = (int)W; a.C = (int)Cin;
+    switch (epi) {
+        case EPI_F32: return launch_conv_tiled<EPI_F32>(a, stream);
+        case EPI_BIAS: return launch_conv_tiled<EPI_BIAS>(a, stream);
+        default: return launch_conv_tiled<EPI_BIAS_RELU>(a, stream);
     }
 }
 

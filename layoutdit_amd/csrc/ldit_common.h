@@ -282,6 +282,9 @@ int launch_gemm_bf16_ex(const void *A, int lda, const void *W, const float *bias
                         const float *lam, const float *R, float *Y2, const GemmExtra &x, hipStream_t stream);
 int launch_gemm_bf16_tr(const void *A, int lda, bool a_reduction_major, const void *W, int ldw, const float *bias, void *Y, int ldy,
                         int M, int N, int K, int epi, const GemmExtra &x, hipStream_t stream);
+// 3x3 / pad 1 convolution as the bf16 GEMM's implicit-im2col mode (gemm_bf16.hip) on the padded bf16 map of launch_pad_nhwc_bf16
+int launch_conv3x3_bf16(const void *xpad, const void *w, const float *bias, void *y, int64_t ldy, int64_t B, int64_t H, int64_t W,
+                        int64_t Cin, int64_t Cout, int epi, hipStream_t stream);
 int gemm_bf16_tr_colsum_rows(int M, int N, int *bm = nullptr);     // partial rows written through GemmExtra::colsum
 int launch_cvt_bf16(const float *src, void *dst, size_t n, hipStream_t stream, float mul = 1.0f);
 // split-fp32 build: dst bf16 [rows, planes * cols] = the `planes` bf16 planes of src fp32 [rows, cols] (row stride lds) side by side

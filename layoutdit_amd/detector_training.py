@@ -117,10 +117,11 @@ class DetectorTrainStep:
         self.encoder._pos_cache.clear()
         for mod in self.model.modules():
             if isinstance(mod, DiTWithFPN):
-                for c in mod._cache:
+                for c in mod._cache + mod._cache_bf16:
                     c.clear()
             elif isinstance(mod, RPNHead):
                 mod._packed.clear()
+                mod._packed_bf16.clear()                  # the bf16 neck's operands likewise
             elif isinstance(mod, (TwoMLPHead, FastRCNNPredictor)):
                 mod._packed.clear()
                 mod._packed_bf16.clear()                  # the bf16 head's operands are keyed on versions like the fp32 re-layouts

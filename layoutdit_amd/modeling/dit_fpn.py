@@ -23,6 +23,12 @@ the RPN head and the box head share (dgrad = the forward's fp32 GEMM on the flip
 GEMMs on reduction-major operands with fp32 accumulation, so gradients of the FPN weights carry bf16 operand rounding, like the
 encoder's), the merge adjoint and the bias column sums in ``csrc/fpn_bwd.hip``.  Gradients reach the four taps, hence the
 encoder (``layoutdit_amd.training``).  Oracle: autograd of ``oracle/fpn_oracle_torch.py`` (parity unpinned, as above).
+
+``neck_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_neck_dtype` switches one set of weights) moves the four 3x3 output
+convolutions of the path that wants no gradient onto the bf16 matrix pipe: per level the merged fp32 map is copied once into a
+zero-padded bf16 map (``ldit_pad_nhwc_f32_bf16``) and ``ldit_conv3x3_nhwc_bf16`` - the implicit-im2col mode of the bf16 MFMA GEMM,
+fp32 accumulation, bf16 operand rounding - writes the fp32 NHWC result, so every consumer sees the tensors it sees today.  Laterals
+and merges stay fp32, parameters stay fp32, the ``state_dict`` does not depend on the option and :class:`_FPNFn` ignores it.
 """
 from __future__ import annotations
 
@@ -33,10 +39,10 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 from ..config import DiTConfig
 from .dit_backbone import DiTBackbone
-from .grad_ops import ParamCache, conv3x3_bwd, linear_bwd, param_key
+from .grad_ops import ParamCache, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, linear_bwd, param_key
 
 
 class _Conv(nn.Sequential):
@@ -58,15 +64,19 @@ class _FPNParams(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
 
-def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool):
+def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool, bf16_conv: bool = False):
     """The stage on fp32 contiguous token tensors [B, 1+P, C]; returns NHWC outputs (coarsest last) and, for the backward,
-    the four merged maps."""
+    the four merged maps.  ``bf16_conv`` (the eval path under ``neck_dtype="bf16"``): ``conv_w_ohwi`` holds bf16 copies and the 3x3
+    convolutions run on the bf16 MFMA GEMM - laterals, merges and the fp32 NHWC results are what they are without it."""
     B, T, Cc = toks[0].shape
     lats = [ops.linear(toks[i].reshape(B * T, Cc), lat_w[i], lat_b[i]).view(B, T, -1) for i in range(4)]
     inner, outs, inners = None, [None] * 4, [None] * 4
     for i in (3, 2, 1, 0):                                            # coarsest first (top-down)
         inner = ops.fpn_merge(lats[i], gh, gw, bb_scales[i], top=inner)
-        outs[i] = ops.conv3x3_nhwc(inner, conv_w_ohwi[i], conv_b[i])
+        if bf16_conv:
+            outs[i] = conv3x3_bf16(inner, conv_w_ohwi[i], conv_b[i], _lib.EPI_F32).view(*inner.shape[:3], -1)
+        else:
+            outs[i] = ops.conv3x3_nhwc(inner, conv_w_ohwi[i], conv_b[i])
         if keep_inner:
             inners[i] = inner
     return outs, inners
@@ -139,17 +149,30 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 
 class DiTWithFPN(nn.Module):
     def __init__(self, pretrained: bool = False, config: Optional[DiTConfig] = None, checkpoint: Optional[str] = None,
-                 compute_dtype: str = "f32", qat: bool = False):
+                 compute_dtype: str = "f32", qat: bool = False, neck_dtype: str = "f32"):
         super().__init__()
+        self.neck_dtype = check_neck_dtype(neck_dtype)
         self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype, qat=qat)
         self.fpn = _FPNParams([self.backbone.hidden_size] * 4, 256)
         self.out_channels = 256
         self._cache = [ParamCache() for _ in range(4)]
+        self._cache_bf16 = [ParamCache() for _ in range(4)]
+
+    def set_neck_dtype(self, neck_dtype: str) -> "DiTWithFPN":
+        """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where no gradient is wanted, on the same
+        weights."""
+        self.neck_dtype = check_neck_dtype(neck_dtype)
+        return self
 
     def _ohwi(self, i: int) -> torch.Tensor:
         """3x3 weight of level i as [Cout, 3, 3, Cin] (GEMM operand layout), re-laid when the parameter changes."""
         w = self.fpn.layer_blocks[i][0].weight
         return self._cache[i].get(param_key(w), lambda: w.detach().permute(0, 2, 3, 1).contiguous())
+
+    def _ohwi_bf16(self, i: int) -> torch.Tensor:
+        """The bf16 copy of :meth:`_ohwi` (``neck_dtype="bf16"``), cached beside it under the same key."""
+        w = self.fpn.layer_blocks[i][0].weight
+        return self._cache_bf16[i].get(param_key(w), lambda: ops.cast_bf16(self._ohwi(i)))
 
     def forward(self, x: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
         bb = self.backbone
@@ -172,9 +195,11 @@ class DiTWithFPN(nn.Module):
             results = list(_FPNFn.apply((gh, gw, tuple(bb.scales)), *args))
         else:
             Cc = bb.hidden_size
+            bf16_conv = self.neck_dtype == "bf16"
             outs, _ = _fpn_forward(bb.scales, gh, gw, [_f32c(t.detach()) for t in toks],
                                    [m.weight.detach().reshape(256, Cc) for m in lat], [m.bias.detach() for m in lat],
-                                   [self._ohwi(i) for i in range(4)], [m.bias.detach() for m in conv], keep_inner=False)
+                                   [self._ohwi_bf16(i) if bf16_conv else self._ohwi(i) for i in range(4)],
+                                   [m.bias.detach() for m in conv], keep_inner=False, bf16_conv=bf16_conv)
             results = [o.permute(0, 3, 1, 2) for o in outs]          # [B, 256, h, w], channels-last memory
         feats = OrderedDict((f"p{i + 2}", r) for i, r in enumerate(results))
         feats["pool"] = results[3][:, :, ::2, ::2]                    # LastLevelMaxPool: max_pool2d(kernel 1, stride 2)

@@ -68,6 +68,24 @@ def stack_rows(weights, biases, multiple: int):
     return w, b
 
 
+NECK_DTYPES = ("f32", "bf16")
+
+
+def check_neck_dtype(neck_dtype: str) -> str:
+    """The option of the FPN, the RPN head and the detector that holds them: how their 3x3 convolutions run where no gradient is
+    wanted."""
+    if neck_dtype not in NECK_DTYPES:
+        raise ValueError(f"neck_dtype {neck_dtype!r}: the FPN and the RPN head are built for {' and '.join(repr(d) for d in NECK_DTYPES)}")
+    return neck_dtype
+
+
+def conv3x3_bf16(x_nhwc: torch.Tensor, weight_ohwi_bf16: torch.Tensor, bias, epilogue: int) -> torch.Tensor:
+    """The eval-mode bf16 3x3 convolution of an fp32 NHWC map: one launch for its zero-padded bf16 copy, one for the implicit-im2col
+    bf16 MFMA GEMM on it.  Returns the pixel rows ``[B h w, Cout]`` (fp32 for ``EPI_F32``, else bf16)."""
+    B, h, w, _ = x_nhwc.shape
+    return ops.conv3x3_nhwc_bf16(ops.pad_nhwc_bf16(x_nhwc), B, h, w, weight_ohwi_bf16, bias, epilogue)
+
+
 def param_key(*params: torch.Tensor) -> tuple:
     """Changes when one of the parameters is replaced, moved or written in place (autograd's version counter)."""
     return tuple((p.data_ptr(), p._version, str(p.device)) for p in params)

@@ -21,6 +21,11 @@ GEMM's 32), ``conv3x3_bwd`` for the 3x3 (the same implicit-im2col GEMM on the fl
 MFMA GEMMs on reduction-major operands with fp32 accumulation (they carry bf16 operand rounding, like the encoder's), the biases
 ``ldit_colsum_f32``.  ``train()`` mode WITHOUT targets stays refused.
 
+``neck_dtype="bf16"`` (default ``"f32"``; :meth:`RPNHead.set_neck_dtype`) runs the head's non-differentiable branch on the bf16 matrix
+pipe: per level one zero-padded bf16 copy of the map, the 3x3 as ``ldit_conv3x3_nhwc_bf16`` with bias and ReLU in the GEMM's epilogue
+(bf16 activation rows; no ``relu_`` launch, no fp32 activation), the 1x1 pair as one bf16 GEMM whose fp32 value is stored unrounded -
+fp32 logits and deltas in the layout above.  Parameters stay fp32; :class:`_RPNHeadLevelFn` and the losses ignore the option.
+
 torchvision is not installed offline: the semantics are restated from its documented behaviour (``tests/rpn_oracle.py``,
 ``tests/rpn_train_oracle.py``) - parity unpinned with respect to torchvision itself, as for the FPN.  Parameter names follow
 torchvision, so detector checkpoints load (``rpn.head.conv.0.0.weight`` ...).
@@ -33,8 +38,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ops
-from .grad_ops import ParamCache, conv3x3_bwd, linear_bwd, param_key, stack_rows
+from .. import _lib, ops
+from .grad_ops import ParamCache, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, linear_bwd, param_key, stack_rows
 
 
 class AnchorGenerator(nn.Module):
@@ -107,6 +112,18 @@ def _level_forward(x, operands, A: int):
     return xn, t, (y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4))
 
 
+def _level_forward_bf16(x, operands_bf16, A: int):
+    """:func:`_level_forward` under ``neck_dtype="bf16"``, on :meth:`RPNHead._operands_bf16`: the zero-padded bf16 copy of the map,
+    the 3x3 on the bf16 MFMA GEMM with bias and ReLU in its epilogue (bf16 activation rows, no ``relu_`` launch, no fp32 activation),
+    the 1x1 pair as one bf16 GEMM with its fp32 value stored unrounded.  Same results layout."""
+    w3, b3, w1, b1 = operands_bf16
+    B, _, h, w = x.shape
+    xn = x.detach().permute(0, 2, 3, 1).contiguous()
+    t = conv3x3_bf16(xn, w3, b3, _lib.EPI_BIAS_RELU)                                      # bf16 [B h w, C]
+    y = ops.linear_bf16(t, w1, b1, _lib.EPI_F32)                                          # fp32 [B h w, 5 A (+ pad)]
+    return y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4)
+
+
 class _RPNHeadLevelFn(torch.autograd.Function):
     """One level of :class:`RPNHead` with gradients for the map and all six parameters.  ``operands`` is the head's cached
     :meth:`RPNHead._operands` - the same weights as the GEMMs read them, no gradient of their own.
@@ -164,8 +181,9 @@ class _RPNLossFn(torch.autograd.Function):
 class RPNHead(nn.Module):
     """torchvision's ``RPNHead(in_channels, num_anchors)``: ``conv.0.0`` (3x3 + ReLU), ``cls_logits`` and ``bbox_pred`` (1x1)."""
 
-    def __init__(self, in_channels: int = 256, num_anchors: int = 3):
+    def __init__(self, in_channels: int = 256, num_anchors: int = 3, neck_dtype: str = "f32"):
         super().__init__()
+        self.neck_dtype = check_neck_dtype(neck_dtype)
         self.conv = nn.Sequential(_ConvRelu(in_channels))
         self.cls_logits = nn.Conv2d(in_channels, num_anchors, kernel_size=1)
         self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1)
@@ -174,7 +192,12 @@ class RPNHead(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.normal_(m.weight, std=0.01)
                 nn.init.constant_(m.bias, 0)
-        self._packed = ParamCache()
+        self._packed, self._packed_bf16 = ParamCache(), ParamCache()
+
+    def set_neck_dtype(self, neck_dtype: str) -> "RPNHead":
+        """``"f32"`` or ``"bf16"``: how the head runs from now on where no gradient is wanted, on the same weights."""
+        self.neck_dtype = check_neck_dtype(neck_dtype)
+        return self
 
     def _params(self):
         return (self.conv[0][0].weight, self.conv[0][0].bias, self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight,
@@ -187,6 +210,14 @@ class RPNHead(nn.Module):
         return self._packed.get(param_key(*ps), lambda: (w3.detach().permute(0, 2, 3, 1).contiguous(), b3.detach(),
                                                          *stack_rows((wc.flatten(1), wb.flatten(1)), (bc, bb), 4)))
 
+    def _operands_bf16(self):
+        """:meth:`_operands` with both matrices as bf16 copies (``neck_dtype="bf16"``; the biases stay fp32, the stacked matrix's
+        zero padding rows stay zero), cached beside them under the same key."""
+        def build():
+            w3, b3, w1, b1 = self._operands()
+            return ops.cast_bf16(w3), b3, ops.cast_bf16(w1), b1
+        return self._packed_bf16.get(param_key(*self._params()), build)
+
     def forward_level(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """One map ``[B, C, h, w]`` (any memory layout; channels-last costs no copy) -> objectness logits ``[B, h w A]`` and box
         deltas ``[B, h w A, 4]`` in (y, x, anchor) order."""
@@ -197,6 +228,8 @@ class RPNHead(nn.Module):
         if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             # gradients are wanted: one differentiable node per level, on the operands of the eval path below
             return _RPNHeadLevelFn.apply(x, *self._params(), self._operands())
+        if self.neck_dtype == "bf16":
+            return _level_forward_bf16(x, self._operands_bf16(), self.num_anchors)
         return _level_forward(x, self._operands(), self.num_anchors)[2]
 
     def forward(self, features: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -595,9 +595,34 @@ def pad_nhwc_bf16(x: torch.Tensor, slack_rows: int = 0) -> torch.Tensor:
     x = _req(x, "x")
     B, H, W, Cc = x.shape
     rows = B * (H + 2) * (W + 2)
-    buf = torch.zeros((rows + 2 * slack_rows, Cc), device=x.device, dtype=torch.bfloat16)
+    # (the kernel writes every element of the padded map, borders included: only slack rows need the fill)
+    alloc = torch.zeros if slack_rows else torch.empty
+    buf = alloc((rows + 2 * slack_rows, Cc), device=x.device, dtype=torch.bfloat16)
     _launch(_device(x), lib.ldit_pad_nhwc_f32_bf16, _ptr(x), buf[slack_rows:].data_ptr(), B, H, W, Cc)
     return buf
+
+
+def conv3x3_nhwc_bf16(xpad_rows: torch.Tensor, B: int, H: int, W: int, weight_ohwi_bf16: torch.Tensor,
+                      bias: Optional[torch.Tensor] = None, epilogue: int = _lib.EPI_F32) -> torch.Tensor:
+    """3x3 / padding 1 convolution on the bf16 MFMA GEMM's implicit-im2col mode.  ``xpad_rows``: what ``pad_nhwc_bf16(x)`` returns
+    for an NHWC map ``x`` [B, H, W, Cin] (no slack rows): bf16 ``[B (H+2) (W+2), Cin]``; ``weight_ohwi_bf16``: bf16 [Cout, 3, 3, Cin].
+    Returns the pixel rows ``[B H W, Cout]``: fp32 ``acc + bias`` for ``EPI_F32``, bf16 for ``EPI_BIAS`` / ``EPI_BIAS_RELU`` - bit for
+    bit :func:`linear_bf16` with the same epilogue on the im2col matrix of the padded map."""
+    lib = _lib.load()
+    for t, n in ((xpad_rows, "xpad_rows"), (weight_ohwi_bf16, "weight_ohwi_bf16")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError(f"{n}: expected a contiguous bfloat16 GPU tensor")
+    Cout, Cin = weight_ohwi_bf16.shape[0], weight_ohwi_bf16.shape[-1]
+    if tuple(weight_ohwi_bf16.shape) != (Cout, 3, 3, Cin):
+        raise ValueError(f"weight {tuple(weight_ohwi_bf16.shape)} is not [Cout, 3, 3, Cin]")
+    if tuple(xpad_rows.shape) != (B * (H + 2) * (W + 2), Cin):
+        raise ValueError(f"xpad_rows {tuple(xpad_rows.shape)} is not the padded map [{B} * {H + 2} * {W + 2}, {Cin}]")
+    if bias is not None:
+        _req(bias, "bias")
+    y = torch.empty((B * H * W, Cout), device=xpad_rows.device, dtype=torch.float32 if epilogue == _lib.EPI_F32 else torch.bfloat16)
+    _launch(_device(xpad_rows, weight_ohwi_bf16, bias), lib.ldit_conv3x3_nhwc_bf16, _ptr(xpad_rows), _ptr(weight_ohwi_bf16), _ptr(bias),
+            _ptr(y), Cout, B, H, W, Cin, Cout, epilogue)
+    return y
 
 
 def colsum(x: torch.Tensor) -> torch.Tensor:
