@@ -185,6 +185,13 @@ int ldit_vit_forward_images(const ldit_cfg *cfg, const void *packed, const void 
                             const int32_t *widths, int32_t half_in, float mean, float std, int32_t batch, void *const *tap_out,
                             void *workspace, size_t workspace_bytes, ldit_stream stream);
 
+/* ldit_vit_forward_images fed by uint8 images as a decoder leaves them (the pixel contract and the two layouts: ldit_preprocess_u8
+ * below; `interleaved` stands where half_in stands).  Every build ldit_vit_forward_images serves, the same launches per build, fp32
+ * taps, and they EQUAL ldit_preprocess_u8 followed by ldit_vit_forward. */
+int ldit_vit_forward_images_u8(const ldit_cfg *cfg, const void *packed, const void *const *images, const int32_t *heights,
+                               const int32_t *widths, int32_t interleaved, float mean, float std, int32_t batch, void *const *tap_out,
+                               void *workspace, size_t workspace_bytes, ldit_stream stream);
+
 /* Same, but brackets every kernel launch with HIP events on `stream`, synchronises, and ADDS the elapsed
  * milliseconds / launch counts per kernel family into ms[LDIT_K_COUNT] / launches[LDIT_K_COUNT].
  * Measurement aid for bench.py's roofline block; not for production use (it blocks the host). */
@@ -289,6 +296,12 @@ int ldit_embed_bf16_images(const void *const *images, const int32_t *heights, co
                            float std, const void *patch_w_bf16, const void *patch_b, const void *cls, const void *pos, void *out,
                            void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream);
 
+/* ldit_embed_bf16_images fed by uint8 images (ldit_preprocess_u8 below: the pixel contract, the two layouts, `interleaved`): the
+ * result EQUALS ldit_preprocess_u8 followed by ldit_embed_bf16.  One launch per 48 images, as its sibling. */
+int ldit_embed_bf16_images_u8(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t interleaved, float mean,
+                              float std, const void *patch_w_bf16, const void *patch_b, const void *cls, const void *pos, void *out,
+                              void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream);
+
 /* ---- fp8 (OCP e4m3) building blocks of the fp8 build (BASELINE.json configs[4]) -----------------------------------------
  * Symmetric scaling: activations per tensor (T ~= scale_T * q, scale_T = amax(T) / 448), weights per output channel
  * (W[n,:] ~= w_scales[n] * q[n,:]).
@@ -343,6 +356,15 @@ int ldit_preprocess_f32(const void *const *images, const int32_t *heights, const
  * ref src/layoutdit/training/trainer.py:153-155); arithmetic and output fp32. */
 int ldit_preprocess_f16(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch,
                         float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream);
+
+/* Same with uint8 images as a decoder leaves them.  A code c stands for (float)c / 255.0f, the correctly rounded single-precision
+ * quotient (what ToTensor() computes on the CPU; c * (1 / 255) differs from it at 126 of the 256 codes), and everything after that
+ * value is the statement of ldit_preprocess_f32: the result EQUALS, bit for bit, ldit_preprocess_f32 on the planar fp32 image
+ * c / 255.  interleaved == 0: images[i] is planar, [in_ch, h_i, w_i] contiguous; interleaved == 1: [h_i, w_i, in_ch] contiguous
+ * (channel c of pixel (y, x) at byte (y * w_i + x) * in_ch + c); any other value is LDIT_EINVAL.  images[i] may have ANY byte
+ * alignment, and no byte outside [images[i], images[i] + in_ch * h_i * w_i) is read.  Output fp32, one launch per 48 images. */
+int ldit_preprocess_u8(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t interleaved, int32_t B,
+                       int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream);
 
 /* fp16 <-> fp32 conversion of a pixel batch / of the returned taps for an fp16 caller (round to nearest even), n elements;
  * the fp16 side 8-byte aligned, the fp32 side 16-byte aligned. */

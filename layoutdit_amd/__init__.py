@@ -24,4 +24,7 @@ def __getattr__(name):
     if name in ("CocoBoxEvaluator", "evaluate"):
         from . import evaluation
         return getattr(evaluation, name)
+    if name in ("stage_images", "StagingBuffer"):
+        from . import data
+        return getattr(data, name)
     raise AttributeError(name)

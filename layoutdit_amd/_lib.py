@@ -72,6 +72,8 @@ SIGNATURES = {
     "ldit_vit_forward": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _i32, C.POINTER(_vp), _vp, _sz, _vp]),
     "ldit_vit_forward_images": (C.c_int, [C.POINTER(LditCfg), _vp, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _f32, _i32,
                                           C.POINTER(_vp), _vp, _sz, _vp]),
+    "ldit_vit_forward_images_u8": (C.c_int, [C.POINTER(LditCfg), _vp, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _f32, _i32,
+                                             C.POINTER(_vp), _vp, _sz, _vp]),
     "ldit_vit_forward_timed": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _i32, C.POINTER(_vp), _vp, _sz, _vp,
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ldit_linear_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
@@ -85,6 +87,8 @@ SIGNATURES = {
     "ldit_embed_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
     "ldit_embed_bf16_images": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "ldit_embed_bf16_images_u8": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
     "ldit_tap_to_map_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
     "ldit_tap_to_map_bwd_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
     "ldit_linear_bf16": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
@@ -102,6 +106,8 @@ SIGNATURES = {
                                       _vp, _vp]),
     "ldit_preprocess_f16": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _f32, _f32, _i32, _i32,
                                       _vp, _vp]),
+    "ldit_preprocess_u8": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _f32, _f32, _i32, _i32,
+                                     _vp, _vp]),
     "ldit_cast_f16_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
     "ldit_cast_f32_f16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "ldit_fpn_merge_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _i64, _i64, _vp]),

@@ -107,7 +107,7 @@ int embed_bf16(const Geo &g, const float *x, const ImgSrc *imgs, int planes, voi
                const float *cls, const float *pos, float *out, int batch, int img_h, int img_w, hipStream_t stream, Probe &probe)
 {
     if (imgs)       // normalise + bilinear resize of the ragged list INSIDE this pass - no fp32 batch in between
-        LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows_images(imgs->images, imgs->half_in, imgs->heights, imgs->widths, batch, g.in_ch,
+        LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows_images(imgs->images, imgs->fmt, imgs->heights, imgs->widths, batch, g.in_ch,
                                                                 imgs->mean, imgs->std, img_h, img_w, g.p, patches, stream, planes));
     else
         LDIT_RUN(probe, LDIT_K_OTHER, launch_patches_rows(x, patches, batch, g.in_ch, img_h, img_w, g.p, stream, planes));
@@ -300,14 +300,22 @@ int attention_entry(const char *name, int dtype, int64_t qtile, const void *Q, c
                      static_cast<hipStream_t>(stream));
 }
 
-int preprocess(bool half_in, const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch, float mean,
+// the storage of a uint8 image list from the `interleaved` argument of the *_u8 entries (0 or 1)
+int u8_format(const char *name, int32_t interleaved, ImgFmt &fmt)
+{
+    if (interleaved != 0 && interleaved != 1) return fail(LDIT_EINVAL, "%s: interleaved = %d (0: planar, 1: interleaved)", name, interleaved);
+    fmt = interleaved ? IMG_U8_HWC : IMG_U8;
+    return LDIT_OK;
+}
+
+int preprocess(ImgFmt fmt, const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch, float mean,
                float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
 {
     if (!images || !heights || !widths || !out) return fail(LDIT_EINVAL, "preprocess: null argument");
     if (B <= 0 || B > 65535 || in_ch <= 0 || out_h <= 0 || out_w <= 0) return fail(LDIT_EINVAL, "preprocess: bad geometry");
     if (!(std > 0.0f)) return fail(LDIT_EINVAL, "preprocess: std must be positive");
     if ((int64_t)B * in_ch * out_h * out_w >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "preprocess: batch exceeds 2^31 elements");
-    return launch_preprocess(images, half_in, heights, widths, B, in_ch, mean, std, out_h, out_w, static_cast<float *>(out),
+    return launch_preprocess(images, fmt, heights, widths, B, in_ch, mean, std, out_h, out_w, static_cast<float *>(out),
                              static_cast<hipStream_t>(stream));
 }
 
@@ -396,7 +404,7 @@ int forward(const ldit_cfg *cfg, const void *packed, const void *x, int32_t batc
             const size_t pix = (size_t)batch * g.in_ch * cfg->img_h * cfg->img_w * 4;
             if (wm.total - wm.big < pix) return fail(LDIT_EUNSUPPORTED, "image list: the pixel batch does not fit the workspace of this geometry");
             xp = reinterpret_cast<const float *>(bb);
-            LDIT_RUN(probe, LDIT_K_OTHER, launch_preprocess(imgs->images, imgs->half_in, imgs->heights, imgs->widths, batch, g.in_ch, imgs->mean,
+            LDIT_RUN(probe, LDIT_K_OTHER, launch_preprocess(imgs->images, imgs->fmt, imgs->heights, imgs->widths, batch, g.in_ch, imgs->mean,
                                                            imgs->std, cfg->img_h, cfg->img_w, reinterpret_cast<float *>(bb), stream));
         }
         LDIT_TRY(embed(g, xp, F32(pm.patch_w), F32(pm.patch_b), F32(pm.cls), F32(pm.pos), h, batch, cfg->img_h, cfg->img_w, stream, probe));
@@ -613,7 +621,17 @@ int ldit_vit_forward_images(const ldit_cfg *cfg, const void *packed, const void 
                             void *workspace, size_t workspace_bytes, ldit_stream stream)
 {
     Probe probe;
-    const ImgSrc src{images, heights, widths, half_in != 0, mean, std};
+    const ImgSrc src{images, heights, widths, half_in ? IMG_F16 : IMG_F32, mean, std};
+    return forward(cfg, packed, nullptr, batch, tap_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), probe, &src);
+}
+
+int ldit_vit_forward_images_u8(const ldit_cfg *cfg, const void *packed, const void *const *images, const int32_t *heights,
+                               const int32_t *widths, int32_t interleaved, float mean, float std, int32_t batch, void *const *tap_out,
+                               void *workspace, size_t workspace_bytes, ldit_stream stream)
+{
+    Probe probe;
+    ImgSrc src{images, heights, widths, IMG_U8, mean, std};
+    LDIT_TRY(u8_format("vit_forward_images_u8", interleaved, src.fmt));
     return forward(cfg, packed, nullptr, batch, tap_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), probe, &src);
 }
 
@@ -716,8 +734,17 @@ int ldit_embed_bf16_images(const void *const *images, const int32_t *heights, co
                            float std, const void *patch_w_bf16, const void *patch_b, const void *cls, const void *pos, void *out,
                            void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream)
 {
-    const ImgSrc src{images, heights, widths, half_in != 0, mean, std};
+    const ImgSrc src{images, heights, widths, half_in ? IMG_F16 : IMG_F32, mean, std};
     return embed_bf16_entry("embed_bf16_images", nullptr, &src, patch_w_bf16, patch_b, cls, pos, out, scratch, B, in_ch, img_h, img_w, p, C, stream);
+}
+
+int ldit_embed_bf16_images_u8(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t interleaved, float mean,
+                              float std, const void *patch_w_bf16, const void *patch_b, const void *cls, const void *pos, void *out,
+                              void *scratch, int64_t B, int64_t in_ch, int64_t img_h, int64_t img_w, int64_t p, int64_t C, ldit_stream stream)
+{
+    ImgSrc src{images, heights, widths, IMG_U8, mean, std};
+    LDIT_TRY(u8_format("embed_bf16_images_u8", interleaved, src.fmt));
+    return embed_bf16_entry("embed_bf16_images_u8", nullptr, &src, patch_w_bf16, patch_b, cls, pos, out, scratch, B, in_ch, img_h, img_w, p, C, stream);
 }
 
 int ldit_tap_to_map_f32(const void *tap, void *out, int64_t B, int64_t Gh, int64_t Gw, int64_t C, float scale,
@@ -837,13 +864,21 @@ int ldit_amax_f32(const void *src, int64_t n, void *out, ldit_stream stream)
 int ldit_preprocess_f32(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch,
                         float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
 {
-    return preprocess(false, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
+    return preprocess(IMG_F32, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
 }
 
 int ldit_preprocess_f16(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t B, int32_t in_ch,
                         float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
 {
-    return preprocess(true, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
+    return preprocess(IMG_F16, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
+}
+
+int ldit_preprocess_u8(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t interleaved, int32_t B,
+                       int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
+{
+    ImgFmt fmt;
+    LDIT_TRY(u8_format("preprocess_u8", interleaved, fmt));
+    return preprocess(fmt, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
 }
 
 int ldit_fpn_merge_f32(const void *lat, const void *top, void *out, int64_t B, int64_t Gh, int64_t Gw, int64_t Ch, float scale,

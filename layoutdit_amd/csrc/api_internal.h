@@ -203,7 +203,7 @@ inline GemmExtra split_segments(int planes)
 struct ImgSrc {
     const void *const *images;
     const int32_t *heights, *widths;
-    bool half_in;
+    ImgFmt fmt;
     float mean, std;
 };
 

@@ -259,12 +259,15 @@ int launch_attention(const float *Q, const float *K, const float *V, float *O, i
 int launch_cls_rows(const float *cls, const float *pos, float *out, int B, int tokens, int C, hipStream_t stream);
 int launch_tap_to_map(const float *tap, float *out, int B, int Gh, int Gw, int C, float scale, hipStream_t stream);
 int launch_tap_to_map_bwd(const float *dmap, float *dtap, int B, int Gh, int Gw, int C, float scale, hipStream_t stream);
-int launch_preprocess(const void *const *images, bool half_in, const int *heights, const int *widths, int B, int in_ch, float mean,
+// how the images of a ragged list are stored: planar [in_ch, h, w] fp32 / fp16 / uint8 codes, or interleaved [h, w, in_ch] uint8 codes
+// (a uint8 code c stands for c / 255, image_blend.h)
+enum ImgFmt { IMG_F32 = 0, IMG_F16 = 1, IMG_U8 = 2, IMG_U8_HWC = 3 };
+int launch_preprocess(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, int B, int in_ch, float mean,
                       float std, int out_h, int out_w, float *out, hipStream_t stream);
 struct ImageList;
 int fill_image_list(ImageList &l, const void *const *images, const int *heights, const int *widths, int B, int first, float mean, float std);
 // the bf16 (or plane) im2col rows of the patch embedding straight from a ragged image list: the input transform fused into the load
-int launch_patches_rows_images(const void *const *images, bool half_in, const int *heights, const int *widths, int B, int in_ch,
+int launch_patches_rows_images(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, int B, int in_ch,
                                float mean, float std, int out_h, int out_w, int p, void *out, hipStream_t stream, int planes = 1);
 int launch_cast_f16(const void *src, void *dst, size_t n, bool widen, hipStream_t stream);
 int launch_fpn_merge(const float *lat, const float *top, float *out, int B, int Gh, int Gw, int Ch, float scale, int top_h,

@@ -117,8 +117,8 @@ struct PreArgs {
     int in_ch, out_h, out_w;
 };
 
-// IN = float or _Float16 (the reference's trainer hands fp16 images to the detector, ref trainer.py:153-155); arithmetic and
-// output stay fp32.
+// IN = float, _Float16 (the reference's trainer hands fp16 images to the detector, ref trainer.py:153-155) or uint8_t (planar codes
+// as a decoder leaves them, read byte by byte: any base alignment, nothing outside the image); arithmetic and output stay fp32.
 template <typename IN>
 __global__ void __launch_bounds__(256) preprocess_images(const PreArgs a)
 {
@@ -137,6 +137,31 @@ __global__ void __launch_bounds__(256) preprocess_images(const PreArgs a)
     for (int e = 0; e < 4; ++e) {
         if (ox0 + e >= a.out_w) break;
         dst[e] = blend_pixel(r0, r1, ox0 + e, w, a.out_w, br, a.l.mean, a.l.inv_std);
+    }
+}
+
+// Interleaved uint8 images ([h, w, in_ch] in memory): one thread per 4 consecutive output pixels of one (image, row).  A pixel's
+// columns and weights are formed once and every channel is blended from the same four source pixels, whose in_ch bytes are
+// neighbours; the stores stay those of the planar kernel, 16 B per lane and contiguous across the wave in each plane.
+__global__ void __launch_bounds__(256) preprocess_images_hwc(const PreArgs a)
+{
+    const int owv = (a.out_w + 3) / 4;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.y;
+    if (idx >= a.out_h * owv) return;
+    const int oy = idx / owv, ox0 = (idx - oy * owv) * 4;
+    const int h = a.l.h[i], w = a.l.w[i];
+    const uint8_t *src = static_cast<const uint8_t *>(a.l.img[i]);
+    const BlendRow br = blend_row(oy, h, a.out_h);
+    const uint8_t *r0 = src + (size_t)br.y0 * w * a.in_ch, *r1 = src + (size_t)br.y1 * w * a.in_ch;
+    const size_t plane = (size_t)a.out_h * a.out_w;
+    float *dst = a.out + ((size_t)(a.l.first + i) * a.in_ch * a.out_h + oy) * a.out_w + ox0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (ox0 + e >= a.out_w) break;
+        const BlendCol bc = blend_col(ox0 + e, w, a.out_w);
+        for (int ch = 0; ch < a.in_ch; ++ch)
+            dst[ch * plane + e] = blend_at(r0 + ch, r1 + ch, bc, a.in_ch, br, a.l.mean, a.l.inv_std);
     }
 }
 
@@ -210,15 +235,17 @@ int fill_image_list(ImageList &l, const void *const *images, const int *heights,
     return LDIT_OK;
 }
 
-int launch_preprocess(const void *const *images, bool half_in, const int *heights, const int *widths, int B, int in_ch, float mean,
+int launch_preprocess(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, int B, int in_ch, float mean,
                       float std, int out_h, int out_w, float *out, hipStream_t stream)
 {
     for (int first = 0; first < B; first += PRE_MAX) {
         PreArgs a{};
         if (int rc = fill_image_list(a.l, images, heights, widths, B, first, mean, std)) return rc;
         a.out = out; a.in_ch = in_ch; a.out_h = out_h; a.out_w = out_w;
-        const int per_img = in_ch * out_h * ((out_w + 3) / 4);
-        if (half_in) hipLaunchKernelGGL(preprocess_images<_Float16>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        const int per_row = out_h * ((out_w + 3) / 4), per_img = in_ch * per_row;
+        if (fmt == IMG_F16) hipLaunchKernelGGL(preprocess_images<_Float16>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        else if (fmt == IMG_U8) hipLaunchKernelGGL(preprocess_images<uint8_t>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        else if (fmt == IMG_U8_HWC) hipLaunchKernelGGL(preprocess_images_hwc, dim3((per_row + 255) / 256, a.l.n), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(preprocess_images<float>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
         LDIT_HIP_CHECK(hipGetLastError());
     }

@@ -566,6 +566,32 @@ __global__ void __launch_bounds__(256) patches_rows_images(const PatchImgArgs a)
     }
 }
 
+// Interleaved uint8 images ([h, w, in_ch] in memory): one workgroup per (image, patch row); a thread forms an output pixel's rows,
+// columns and weights once and blends every channel from the same four source pixels.  Element by element the value and its
+// destination are those of the planar kernel.
+__global__ void __launch_bounds__(256) patches_rows_images_hwc(const PatchImgArgs a)
+{
+    const int gy = blockIdx.x % a.gh, i = blockIdx.x / a.gh;
+    const int h = a.l.h[i], w = a.l.w[i], b = a.l.first + i;
+    const uint8_t *src = static_cast<const uint8_t *>(a.l.img[i]);
+    for (int t = threadIdx.x; t < a.p * a.out_w; t += 256) {
+        const int dy = t / a.out_w, xx = t - dy * a.out_w, gx = xx / a.p, dx = xx - gx * a.p;
+        const BlendRow br = blend_row(gy * a.p + dy, h, a.out_h);
+        const BlendCol bc = blend_col(xx, w, a.out_w);
+        const uint8_t *r0 = src + (size_t)br.y0 * w * a.in_ch, *r1 = src + (size_t)br.y1 * w * a.in_ch;
+        const size_t m = ((size_t)b * a.gh + gy) * a.gw + gx;
+        for (int ch = 0; ch < a.in_ch; ++ch) {
+            float v = blend_at(r0 + ch, r1 + ch, bc, a.in_ch, br, a.l.mean, a.l.inv_std);
+            bf16_t *d = a.out + m * ((size_t)a.planes * a.Kp) + (ch * a.p + dy) * a.p + dx;
+            for (int sp = 0; sp < a.planes; ++sp) {
+                const bf16_t q = (bf16_t)v;
+                d[(size_t)sp * a.Kp] = q;
+                v -= (float)q;
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) zero_pad_columns(bf16_t *__restrict__ buf, int rows, int M, int Mp)
 {
     const int r = blockIdx.x, pad = Mp - M;
@@ -837,7 +863,7 @@ int launch_patches_rows(const float *x, void *out, int B, int in_ch, int img_h, 
     return LDIT_OK;
 }
 
-int launch_patches_rows_images(const void *const *images, bool half_in, const int *heights, const int *widths, int B, int in_ch,
+int launch_patches_rows_images(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, int B, int in_ch,
                                float mean, float std, int out_h, int out_w, int p, void *out, hipStream_t stream, int planes)
 {
     const int gh = out_h / p, gw = out_w / p;
@@ -846,7 +872,9 @@ int launch_patches_rows_images(const void *const *images, bool half_in, const in
         if (int rc = fill_image_list(a.l, images, heights, widths, B, first, mean, std)) return rc;
         a.out = static_cast<bf16_t *>(out); a.in_ch = in_ch; a.out_h = out_h; a.out_w = out_w; a.p = p; a.gw = gw; a.gh = gh;
         a.Kp = in_ch * p * p; a.planes = planes;
-        if (half_in) LAUNCH_CHECKED(patches_rows_images<_Float16>, dim3((unsigned)(a.l.n * gh * in_ch)), dim3(256), 0, stream, a);
+        if (fmt == IMG_F16) LAUNCH_CHECKED(patches_rows_images<_Float16>, dim3((unsigned)(a.l.n * gh * in_ch)), dim3(256), 0, stream, a);
+        else if (fmt == IMG_U8) LAUNCH_CHECKED(patches_rows_images<uint8_t>, dim3((unsigned)(a.l.n * gh * in_ch)), dim3(256), 0, stream, a);
+        else if (fmt == IMG_U8_HWC) LAUNCH_CHECKED(patches_rows_images_hwc, dim3((unsigned)(a.l.n * gh)), dim3(256), 0, stream, a);
         else LAUNCH_CHECKED(patches_rows_images<float>, dim3((unsigned)(a.l.n * gh * in_ch)), dim3(256), 0, stream, a);
     }
     return LDIT_OK;

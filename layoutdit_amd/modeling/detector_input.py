@@ -11,6 +11,9 @@ of the targets are scaled by the same ratios, and detections are scaled back aft
 the pixel arithmetic is ONE launch of ``ldit_preprocess_f32`` / ``_f16`` for the whole ragged list (no per-image host loop,
 no intermediate normalised copy).  Parity is pinned against ``torch.nn.functional.interpolate`` only ("parity unpinned" with
 respect to torchvision itself).  Box arithmetic is a handful of scalars per image and stays in torch.
+
+The images may also be the decoder's uint8 pages, planar or interleaved (``ops.image_list_args``; ``ldit_preprocess_u8``): a code
+``c`` stands for ``c / 255``, so the batch is bit for bit that of the ``ToTensor()`` list, and ``img.shape[-2:]`` is still the page.
 """
 from __future__ import annotations
 
@@ -53,6 +56,12 @@ class DetectorInputTransform(nn.Module):
                                       "would pad (LayoutDiT's 224x224 does not)")
         self.mean, self.std = float(image_mean[0]), float(image_std[0])
 
+    @staticmethod
+    def _operands(images: List[torch.Tensor]) -> List[torch.Tensor]:
+        """The images as the kernels take them: fp32 / fp16 made contiguous; uint8 left where it is, because a decoder's interleaved
+        ``[h, w, C]`` page under ``permute(2, 0, 1)`` is read in place (``ops.image_list_args``) and a copy would undo that."""
+        return [img if img.dtype == torch.uint8 else img.contiguous() for img in images]
+
     def forward(self, images: List[torch.Tensor], targets: Optional[List[Dict[str, torch.Tensor]]] = None):
         if len(images) == 0:
             raise ValueError("empty image list")
@@ -61,7 +70,7 @@ class DetectorInputTransform(nn.Module):
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(img.shape)}")
         if targets is not None and len(targets) != len(images):
             raise ValueError("one target per image")
-        batch = ops.preprocess([img.contiguous() for img in images], size=(self.out_h, self.out_w), mean=self.mean, std=self.std)
+        batch = ops.preprocess(self._operands(images), size=(self.out_h, self.out_w), mean=self.mean, std=self.std)
         out_targets = None
         if targets is not None:
             out_targets = []
@@ -77,7 +86,7 @@ class DetectorInputTransform(nn.Module):
         (``DiTEncoder.forward_image_list`` -> ``ldit_vit_forward_images``): same taps bit for bit, and the bf16 /
         fp8 / split-fp32 builds skip the fp32 ``[B, 3, H, W]`` batch altogether.  For callers that own the loop; torchvision's
         ``GeneralizedRCNN.forward`` hands the backbone the already transformed batch, which stays the two-step path."""
-        return encoder.forward_image_list([img.contiguous() for img in images], size=(self.out_h, self.out_w), mean=self.mean,
+        return encoder.forward_image_list(self._operands(images), size=(self.out_h, self.out_w), mean=self.mean,
                                           std=self.std, taps=taps)
 
     def postprocess(self, result: List[Dict[str, torch.Tensor]], image_shapes: List[Tuple[int, int]],

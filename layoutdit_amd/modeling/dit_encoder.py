@@ -457,7 +457,8 @@ class DiTEncoder(nn.Module):
                            std: float = 0.5, taps: Optional[Sequence[int]] = None) -> DiTEncoderOutput:
         """Inference forward fed by the detector's image list BEFORE its input transform (ref model.py:50-54: torchvision's
         ``GeneralizedRCNNTransform`` with ``fixed_size``, ``image_mean = image_std = 0.5``): a ragged list of ``[3, h, w]`` tensors in
-        [0, 1], fp32 or fp16.  Equal - bit for bit - to ``self(DetectorInputTransform(...)(images).tensors)``, but the bf16 / fp8 /
+        [0, 1], fp32 or fp16, or of uint8 codes ``c`` standing for ``c / 255``, planar or interleaved (``ops.image_list_args``; fp32
+        hidden states).  Equal - bit for bit - to ``self(DetectorInputTransform(...)(images).tensors)``, but the bf16 / fp8 /
         split-fp32 builds never materialise the resized fp32 batch: the pass that writes the patch-embedding operand evaluates the
         normalise + bilinear resize itself (C ABI ``ldit_vit_forward_images``).  Eval mode only (the training
         forward keeps the two-step path: its backward re-reads the resized pixels)."""
@@ -469,7 +470,8 @@ class DiTEncoder(nn.Module):
         p = cfg.patch_size
         if H % p or W % p:
             raise ValueError(f"target size {H}x{W} is not a multiple of the patch size {p}")
-        imgs, ptrs, hs, ws_, half, ch = ops.image_list_args(images)
+        imgs, ptrs, hs, ws_, fmt, ch = ops.image_list_args(images)
+        u8 = fmt in (ops.IMG_U8, ops.IMG_U8_HWC)
         if ch != cfg.num_channels:
             raise ValueError("Make sure that the channel dimension of the pixel values match with the one set in the "
                              f"configuration. Expected {cfg.num_channels} but got {ch}.")
@@ -485,12 +487,13 @@ class DiTEncoder(nn.Module):
             T = gh * gw + 1
             outs = [torch.empty((B, T, cfg.hidden_size), dtype=torch.float32, device=device) for _ in taps]
             tap_ptrs = (C.c_void_p * max(len(outs), 1))(*[o.data_ptr() for o in outs])
-            _lib.check(lib.ldit_vit_forward_images(C.byref(lcfg), packed.data_ptr(), ptrs, hs, ws_, int(half), float(mean), float(std), B,
-                                                   tap_ptrs, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+            entry = lib.ldit_vit_forward_images_u8 if u8 else lib.ldit_vit_forward_images
+            _lib.check(entry(C.byref(lcfg), packed.data_ptr(), ptrs, hs, ws_, int(fmt == ops.IMG_U8_HWC if u8 else fmt == ops.IMG_F16), float(mean),
+                             float(std), B, tap_ptrs, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(device).cuda_stream))
         hidden: List[Optional[torch.Tensor]] = [None] * (cfg.num_hidden_layers + 1)
         for t, o in zip(taps, outs):
             hidden[t] = o
-        hidden = self._like_input(hidden, torch.float16 if half else torch.float32)
+        hidden = self._like_input(hidden, torch.float16 if fmt == ops.IMG_F16 else torch.float32)
         return DiTEncoderOutput(hidden_states=tuple(hidden), last_hidden_state=hidden[cfg.num_hidden_layers])
 
     @staticmethod

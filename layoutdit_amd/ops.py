@@ -186,42 +186,86 @@ def tap_to_map_autograd(tap: torch.Tensor, gh: int, gw: int, scale: float) -> to
 def preprocess(images: Sequence[torch.Tensor], size=224, mean: float = 0.5, std: float = 0.5) -> torch.Tensor:
     """The detector's input transform in one kernel (ref src/layoutdit/modeling/model.py:50-54: fixed_size 224,
     mean = std = 0.5): list of ``[3, h, w]`` images in [0, 1] (all fp32 or all fp16) -> normalised, bilinearly resized
-    fp32 ``[B, 3, size, size]``."""
+    fp32 ``[B, 3, size, size]``.  A uint8 list (codes ``c`` standing for ``c / 255``, planar or interleaved: ``image_list_args``)
+    gives, bit for bit, what the fp32 list ``img.float().div(255)`` gives (``ldit_preprocess_u8``)."""
     lib = _lib.load()
-    imgs, ptrs, hs, ws, half, ch = image_list_args(images)
+    imgs, ptrs, hs, ws, fmt, ch = image_list_args(images)
     B = len(imgs)
     out_h, out_w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
     out = torch.empty((B, ch, out_h, out_w), device=imgs[0].device, dtype=torch.float32)
-    if half:
+    if fmt in (IMG_U8, IMG_U8_HWC):
+        _launch(_device(*imgs), lib.ldit_preprocess_u8, ptrs, hs, ws, int(fmt == IMG_U8_HWC), B, ch, mean, std, out_h, out_w, _ptr(out))
+    elif fmt == IMG_F16:
         _launch(_device(*imgs), lib.ldit_preprocess_f16, ptrs, hs, ws, B, ch, mean, std, out_h, out_w, _ptr(out))
     else:
         _launch(_device(*imgs), lib.ldit_preprocess_f32, ptrs, hs, ws, B, ch, mean, std, out_h, out_w, _ptr(out))
     return out
 
 
+# how the images of one list are stored: planar fp32 / fp16 / uint8, or interleaved uint8
+IMG_F32, IMG_F16, IMG_U8, IMG_U8_HWC = 0, 1, 2, 3
+
+
+def _u8_layouts(t: torch.Tensor, name: str):
+    """``(planar, interleaved)``: which of the two accepted memory layouts the uint8 ``[C, h, w]`` image has.  The stride of an axis
+    of length 1 says nothing, so a 1 x 1 image (or a one-channel one) has both."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError(f"{name}: one list has one dtype: expected uint8 like images[0], got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 3:
+        raise ValueError("every image must be [C, h, w] with the same C")
+    ch, h, w = t.shape
+
+    def has(strides):
+        return all(n == 1 or s == q for n, s, q in zip(t.shape, t.stride(), strides))
+
+    planar, interleaved = has((h * w, w, 1)), has((1, w * ch, ch))
+    if not (planar or interleaved):
+        raise ValueError(f"{name}: a uint8 [C, h, w] image must be contiguous (planar) or have the strides (1, w*C, C) of an "
+                         f"interleaved [h, w, C] array permuted (2, 0, 1); got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    return planar, interleaved
+
+
 def image_list_args(images: Sequence[torch.Tensor]):
-    """``(checked tensors, device pointers, heights, widths, half_in, channels)`` of a ragged list of ``[C, h, w]`` images (all fp32
-    or all fp16, same C, one GPU) - the HOST arrays the image-list entries of the C ABI take."""
+    """``(checked tensors, device pointers, heights, widths, format, channels)`` of a ragged list of ``[C, h, w]`` images (same C, one
+    GPU) - the HOST arrays the image-list entries of the C ABI take.  One list has one dtype and one memory layout; ``format`` is
+    ``IMG_F32`` / ``IMG_F16`` (contiguous, values in [0, 1]) or, for uint8 codes, ``IMG_U8`` (contiguous ``[C, h, w]``) /
+    ``IMG_U8_HWC`` (strides ``(1, w*C, C)``: a decoder's ``[h, w, C]`` array under ``permute(2, 0, 1)``, never copied)."""
     if len(images) == 0:
         raise ValueError("empty image list")
-    half = images[0].dtype == torch.float16
-    imgs = [(_req16 if half else _req)(t, f"images[{i}]") for i, t in enumerate(images)]
+    if isinstance(images[0], torch.Tensor) and images[0].dtype == torch.uint8:
+        imgs = list(images)
+        layouts = [_u8_layouts(t, f"images[{i}]") for i, t in enumerate(imgs)]
+        if all(p for p, _ in layouts):
+            fmt = IMG_U8
+        elif all(q for _, q in layouts):
+            fmt = IMG_U8_HWC
+        else:
+            first = next(i for i, l in enumerate(layouts) if l != (True, True))      # the image that sets the list's layout
+            bad = next(i for i, l in enumerate(layouts) if not l[0 if layouts[first][0] else 1])
+            kinds = ("planar", "interleaved") if layouts[first][0] else ("interleaved", "planar")
+            raise ValueError(f"images[{bad}]: one list has one memory layout, but images[{first}] is {kinds[0]} and this uint8 image is {kinds[1]}")
+    else:
+        fmt = IMG_F16 if images[0].dtype == torch.float16 else IMG_F32
+        imgs = [(_req16 if fmt == IMG_F16 else _req)(t, f"images[{i}]") for i, t in enumerate(images)]
     ch = imgs[0].shape[0]
     if any(t.dim() != 3 or t.shape[0] != ch for t in imgs):
         raise ValueError("every image must be [C, h, w] with the same C")
+    for i, t in enumerate(imgs):         # (fp32 / fp16 images were checked above; a uint8 list's dtype and layout rules come first)
+        if not t.is_cuda:
+            raise ValueError(f"images[{i}]: expected a tensor on the GPU (libldit_hip has no CPU path)")
     B = len(imgs)
     ptrs = (C.c_void_p * B)(*[t.data_ptr() for t in imgs])
     hs = (C.c_int32 * B)(*[t.shape[1] for t in imgs])
     ws = (C.c_int32 * B)(*[t.shape[2] for t in imgs])
-    return imgs, ptrs, hs, ws, half, ch
+    return imgs, ptrs, hs, ws, fmt, ch
 
 
 def embed_bf16_images(images: Sequence[torch.Tensor], patch_w_bf16: torch.Tensor, patch_b: torch.Tensor, cls: torch.Tensor,
                       pos: torch.Tensor, patch: int, size=224, mean: float = 0.5, std: float = 0.5) -> torch.Tensor:
     """``embed_bf16(preprocess(images, size, mean, std), ...)`` with the input transform evaluated inside the im2col pass (SURVEY.md
-    8(f)-2; ref model.py:50-54): same bits, no fp32 batch in between."""
+    8(f)-2; ref model.py:50-54): same bits, no fp32 batch in between.  uint8 lists as for ``preprocess``."""
     lib = _lib.load()
-    imgs, ptrs, hs, ws, half, ch = image_list_args(images)
+    imgs, ptrs, hs, ws, fmt, ch = image_list_args(images)
     patch_b, cls, pos = _req(patch_b, "patch_b"), _req(cls, "cls"), _req(pos, "pos")
     if patch_w_bf16.dtype != torch.bfloat16 or not patch_w_bf16.is_contiguous():
         raise ValueError("patch_w_bf16 must be a contiguous bfloat16 tensor")
@@ -231,8 +275,11 @@ def embed_bf16_images(images: Sequence[torch.Tensor], patch_w_bf16: torch.Tensor
     dev = imgs[0].device
     out = torch.empty((B, P + 1, Cc), device=dev, dtype=torch.float32)
     scratch = torch.empty((B * P, ch * patch * patch), device=dev, dtype=torch.bfloat16)
-    _launch(_device(*imgs, patch_w_bf16, patch_b, cls, pos), lib.ldit_embed_bf16_images, ptrs, hs, ws, int(half), mean, std,
-            _ptr(patch_w_bf16), _ptr(patch_b), _ptr(cls), _ptr(pos), _ptr(out), _ptr(scratch), B, ch, out_h, out_w, patch, Cc)
+    rest = (mean, std, _ptr(patch_w_bf16), _ptr(patch_b), _ptr(cls), _ptr(pos), _ptr(out), _ptr(scratch), B, ch, out_h, out_w, patch, Cc)
+    if fmt in (IMG_U8, IMG_U8_HWC):
+        _launch(_device(*imgs, patch_w_bf16, patch_b, cls, pos), lib.ldit_embed_bf16_images_u8, ptrs, hs, ws, int(fmt == IMG_U8_HWC), *rest)
+    else:
+        _launch(_device(*imgs, patch_w_bf16, patch_b, cls, pos), lib.ldit_embed_bf16_images, ptrs, hs, ws, int(fmt == IMG_F16), *rest)
     return out
 
 
