@@ -69,7 +69,6 @@ DiagSwitches read_switches()
     d.fp8_k16 = is("LDIT_GEMM_FP8_K16", '1');
     d.fp8_noskinny = is("LDIT_GEMM_FP8_NOSKINNY", '1');
     d.direct_epi = is("LDIT_GEMM_DIRECT_EPILOGUE", '1');
-    d.attn_bf16_kt4 = is("LDIT_ATTN_BF16_KT", '4');
     d.seg_order = digit("LDIT_GEMM_SEG_ORDER", 0, 1);
     if (const char *e = getenv("LDIT_PLANES_TAIL_WAVES")) d.planes_tail_waves = atol(e);
     d.attn_bf16_nw = digit("LDIT_ATTN_BF16_NW", 4, 8);
@@ -149,7 +148,7 @@ int linear(Build b, const Operand &A, const void *W, const void *Ws, const float
         }
         case LDIT_BF16: case LDIT_F32X3: case LDIT_F32X6: {
             // split-fp32 builds: the bf16 MFMA over the plane products of the operands, fp32 accumulation; an output that is an operand
-            // leaves as planes [M, S N] (q pre-multiplied by scale log2 e at pack time: attention_planes.hip runs on the plane products too)
+            // leaves as planes [M, S N] (q pre-multiplied by scale log2 e at pack time: attention_flash.hip runs on the plane products too)
             GemmExtra x = split_segments(A.planes);
             x.Ypre = t.Ypre; x.rowscale = t.rowscale;
             if (Y.planes) { x.nsplit_out = Y.planes; epi = epi == EPI_BIAS_GELU ? EPI_GELU_SPLIT : EPI_BIAS_SPLIT; }
@@ -176,16 +175,24 @@ int attention(Build b, const void *Q, const void *K, const void *V, int ldq, int
         case LDIT_F32:
             return launch_attention(static_cast<const float *>(Q), static_cast<const float *>(K), static_cast<const float *>(V),
                                     static_cast<float *>(O.p), B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream);
-        case LDIT_BF16:
-            return b.train ? launch_attention_bf16_lse(Q, K, V, O.p, lse, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream)
-                           : launch_attention_bf16(Q, K, V, O.p, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream);
-        case LDIT_FP8:
-            return launch_attention_bf16_fp8out(Q, K, V, O.p, B, N, H, D, ldq, ldk, ldv, O.ld, scale, static_cast<const float *>(O.s), stream);
-        case LDIT_MXFP8:
-            return b.train ? launch_attention_bf16_mxout_train(Q, K, V, O.p, O.s, lse, Ob, Od, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream)
-                           : launch_attention_bf16_mxout(Q, K, V, O.p, O.s, B, N, H, D, ldq, ldk, ldv, O.ld, scale, stream);
-        case LDIT_F32X3: case LDIT_F32X6:
-            return (O.planes == 2 ? launch_attention_planes2 : launch_attention_planes3)(Q, K, V, O.p, B, N, H, D, ldq, plane_in, O.ld, stream);
+        case LDIT_BF16: case LDIT_FP8: case LDIT_MXFP8: case LDIT_F32X3: case LDIT_F32X6: {
+            AttnArgs a{};
+            a.Q = Q; a.K = K; a.V = V; a.O = O.p;
+            a.B = B; a.N = N; a.H = H; a.D = D; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = O.ld;
+            a.scale = scale;
+            if (b.dtype == LDIT_BF16) {
+                if (b.train && !lse) return fail(LDIT_EINVAL, "attention_bf16: lse is null");
+                a.out = ATTN_BF16; a.lse = b.train ? lse : nullptr;
+            } else if (b.dtype == LDIT_FP8) {
+                a.out = ATTN_FP8; a.qscale = static_cast<const float *>(O.s);
+            } else if (b.dtype == LDIT_MXFP8) {
+                a.out = b.train ? ATTN_MX_TRAIN : ATTN_MX; a.Os = O.s;
+                if (b.train) { a.lse = lse; a.Ob = Ob; a.Od = Od; }
+            } else {
+                a.out = ATTN_PLANES; a.planes = O.planes; a.plane_in = plane_in;
+            }
+            return launch_attention_flash(a, stream);
+        }
         default: return fail(LDIT_EUNSUPPORTED, "attention: no kernel for dtype %d", b.dtype);
     }
 }
@@ -514,7 +521,7 @@ int ldit_pack_weights(const ldit_cfg *cfg, const ldit_weights *w, void *packed, 
     // scale per row written to the fp32 vector at sw_off (+ row0)
     // `mul` (bf16 / fp8 builds only): a factor folded into the matrix as it is packed (bf16: into the values before the one
     // rounding; fp8: into the per-row scales).  Used for W_q: q' = (scale log2 e) q, so that the attention kernel's scores
-    // are exp2-domain exponents (attention_bf16.hip, PRE) - the same single rounding of q as before, no extra error.
+    // are exp2-domain exponents (attention_flash.hip, PRE) - the same single rounding of q as before, no extra error.
     auto put_mat = [&](size_t off, size_t elt_off, const void *src, size_t rows, size_t cols, size_t sw_off, size_t row0,
                        const char *what, float mul = 1.0f) -> int {
         if (!src) return fail(LDIT_EINVAL, "weights: %s is null", what);
@@ -534,7 +541,7 @@ int ldit_pack_weights(const ldit_cfg *cfg, const ldit_weights *w, void *packed, 
                                          reinterpret_cast<float *>(P + sw_off) + row0, (int)rows, (int)cols, stream, mul);
         return launch_cvt_bf16(static_cast<const float *>(src), P + off + elt_off * 2, rows * cols, stream, mul);
     };
-    // (the split-fp32 builds too: their attention runs on bf16-plane operands with exp2-domain scores, attention_planes.hip)
+    // (the split-fp32 builds too: their attention runs on bf16-plane operands with exp2-domain scores, attention_flash.hip)
     const float qfold = cfg->dtype != LDIT_F32 ? qfold_of(g) : 1.0f;
     const size_t C = g.C, F = g.F;
     LDIT_TRY(put(pm.patch_w, w->patch_w, C * g.Kp, "patch_w"));

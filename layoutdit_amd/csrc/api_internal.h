@@ -182,7 +182,7 @@ struct Probe {
         LDIT_TRY((probe).end());       \
     } while (0)
 
-// q fold of the packed builds (ldit_pack_weights; the mxfp8 train mirror): q' = (D^-1/2 log2 e) q - exp2-domain scores (attention_bf16.hip, PRE)
+// q fold of the packed builds (ldit_pack_weights; the mxfp8 train mirror): q' = (D^-1/2 log2 e) q - exp2-domain scores (attention_flash.hip, PRE)
 inline float qfold_of(const Geo &g) { return (1.0f / sqrtf((float)g.D)) * 1.44269504088896340736f; }
 
 // split-fp32 builds: the plane products of one output element, SMALLEST FIRST (their sum is formed at its own magnitude

@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
             const int piece = (wave % LW) + LW * u;
             const bool isA = 8 * piece < BM;
             const bf16_t *opnd = isA ? p.A : p.W;
-            glds16h(opnd + (src[u] + (isA ? ka : kw)), base + piece * 1024);
+            glds16(opnd + (src[u] + (isA ? ka : kw)), base + piece * 1024);
         }
 #else
         // the k-tile's column offset travels in the scalar base, the lane's row / chunk offset is the kernel constant src[u]
@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         for (int u = 0; u < NLW; ++u) {
             if (u < lo || u >= hi) continue;
             const int piece = (wave % LW) + LW * u;
-            glds16h_sbase(8 * piece < BM ? abase : wbase, 2u * src[u], dst + piece * 1024);
+            glds16_sbase(8 * piece < BM ? abase : wbase, 2u * src[u], dst + piece * 1024);
         }
 #endif
     };

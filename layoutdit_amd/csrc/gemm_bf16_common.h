@@ -2,6 +2,7 @@
 // launch arguments and the direct (ragged-tile) epilogue of the swapped-operand bf16 GEMMs.
 #pragma once
 #include "ldit_common.h"
+#include "lds_dma.h"
 #include "epilogue_rows.h"
 
 namespace ldit {
@@ -13,40 +14,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BKB = 64;            // bf16 per k-tile: one 128-B LDS row
 constexpr int ROWB = 128;
-
-__device__ __forceinline__ void glds16h(const void *gsrc, char *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-
-// LDS-DMA piece with a wave-uniform 64-bit base in SGPRs and a per-lane 32-bit BYTE offset: `global_load_lds_dwordx4 voff, s[base]`.
-// The builtin takes a per-lane 64-bit pointer: two or three VALU instructions per piece (offset + k, widen, add) and a live VGPR
-// pair; here the k-tile's advance lives in the scalar base and the lane offset is a constant of the kernel.  M0 (the LDS
-// destination) is compiler-reserved: saved and restored inside the statement (cdna guide 5.7).  Invisible to hipcc's waitcnt pass:
-// every consumer of the staged data sits behind an explicit s_waitcnt vmcnt.
-__device__ __forceinline__ void glds16h_sbase(const void *ubase, unsigned voff_bytes, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff_bytes), "s"(ubase), "s"(lds_dst)
-                 : "memory");
-}
-
-// The same piece from a per-lane 64-bit address (ragged tiles, zero-page redirects), also as an asm statement: a kernel whose every
-// LDS-DMA is invisible to hipcc keeps its LDS reads free of the vmcnt(0) guards hipcc puts in front of reads that may alias a
-// builtin LDS-DMA in flight.  `lds_dst` must be wave-uniform (it travels in M0).
-__device__ __forceinline__ void glds16h_vaddr(const void *gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
 
 // a wave-uniform pointer that hipcc computed on the vector unit (integer divisions, 64-bit multiplies) -> scalar registers
 template <typename T>

@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
         }
     }
     // every k-tile but a ragged last one: the tile's advance travels in a scalar base, the lane's offset is the kernel constant src[u]
-    // (glds16h_sbase, gemm_bf16_common.h) - no vector address arithmetic per piece.  Pieces lo .. hi-1 of this wave's NLW.
+    // (glds16_sbase, lds_dma.h) - no vector address arithmetic per piece.  Pieces lo .. hi-1 of this wave's NLW.
     // (k0 is scalar - kbeg was made so at its definition, far from here - so the bases are scalar-unit arithmetic on kernel-argument
     // pointers: no v_readfirstlane result reaches the DMA's scalar base within its five wait states, cdna guide 5.7 item 2)
     auto issue_sbase = [&](int stage, int k0, int lo, int hi) {
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
             if (u < lo || u >= hi) continue;
             const int piece = piece_of(u);
             const bool isA = 8 * piece < BM;
-            glds16h_sbase((!TA && isA) ? a_k : isA ? a_r : w_r, 2u * src[u], dst + piece * 1024);
+            glds16_sbase((!TA && isA) ? a_k : isA ? a_r : w_r, 2u * src[u], dst + piece * 1024);
         }
     };
     // (the 320-row tile has no register left for the three scalar bases' set-up)
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
                 g = opnd + ((size_t)k0 * (size_t)(isA ? p.lda : p.ldw) + src[u]);
                 if (ragged && k0 + krow_of(u) >= p.K) g = static_cast<const bf16_t *>(p.x.zeros) + 8 * (lane & 7);
             }
-            glds16h_vaddr(g, (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(base + piece * 1024)));
+            glds16_vaddr(g, (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(base + piece * 1024)));
         }
     };
 

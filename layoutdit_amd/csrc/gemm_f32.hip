@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "ldit_common.h"
+#include "lds_dma.h"
 
 namespace ldit {
 
@@ -25,13 +26,6 @@ namespace {
 
 constexpr int BK = 32;            // floats per k-tile: one 128-B LDS row
 constexpr int ROW_BYTES = BK * 4;
-
-__device__ __forceinline__ void glds16(const float *gsrc, char *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
 
 // Epilogue of one wave: register r of lanes 0-31 / 32-63 = 128 contiguous bytes of output rows 8(r>>2)+(r&3) / +4 of
 // each 32x32 tile.  CHECK = false for blocks wholly inside the matrix: no per-element bounds work at all.

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "ldit_common.h"
+#include "lds_dma.h"
 #include "epilogue_rows.h"
 
 namespace ldit {
@@ -22,12 +23,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_8 __attribute__((ext_vector_type(4)));
 constexpr int BKE = 128, ROW8 = 128;
-
-__device__ __forceinline__ void glds16q(const void *gsrc, char *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
 
 struct GemmArgs8 {
     const unsigned char *A, *W;   // fp8 e4m3
@@ -262,18 +257,14 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
     }
     auto issue = [&](int stage, int k0) {
         // the k-tile's advance travels in a scalar base, the lane's row / chunk offset is the kernel constant src[u]: no vector address
-        // arithmetic per piece (`global_load_lds_dwordx4 voff, s[base]`; invisible to hipcc's waitcnt pass - every hand-over below
+        // arithmetic per piece (glds16_sbase, lds_dma.h; invisible to hipcc's waitcnt pass - every hand-over below
         // carries its explicit s_waitcnt vmcnt)
         const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(smem + stage * (ROWS * ROW8))));
         const unsigned char *abase = p.A + k0, *wbase = p.W + k0;
 #pragma unroll
         for (int u = 0; u < NLD; ++u) {
             const int piece = wave + NWAVES * u;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(src[u]), "s"(8 * piece < BM ? abase : wbase), "s"(dst + piece * 1024)
-                         : "memory");
+            glds16_sbase(8 * piece < BM ? abase : wbase, src[u], dst + piece * 1024);
         }
     };
 

@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "ldit_common.h"
+#include "lds_dma.h"
 
 namespace ldit {
 
@@ -43,13 +44,6 @@ namespace {
 constexpr int BK = 32;
 constexpr int ROW_BYTES = BK * 4;
 constexpr int BNP = 128;
-
-__device__ __forceinline__ void glds16p(const float *gsrc, char *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
 
 // One float4 of the output: row m, columns n..n+3.  MODE 1: 16-B accesses, no bounds checks (block inside the matrix,
 // ldy % 4 == 0); MODE 2: 16-B accesses behind a row check (the ragged last row panel: columns inside, rows past M
@@ -285,7 +279,7 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
                 // saddr + 32-bit voffset form with no per-piece VALU address arithmetic
                 g = reinterpret_cast<const float *>(reinterpret_cast<const char *>(opnd + k0) + src[u]);
             }
-            glds16p(g, base + piece * 1024);
+            glds16(g, base + piece * 1024);
         }
     };
 

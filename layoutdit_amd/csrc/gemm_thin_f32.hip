@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "ldit_common.h"
+#include "lds_dma.h"
 
 namespace ldit {
 
@@ -37,12 +38,6 @@ constexpr int STAGE = 2 * HALF;                          // a stage = TWO k-tile
 constexpr int NS = 4;                                    // ring depth: 64 KB, two workgroups per CU
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void glds16t(const float *gsrc, char *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
 
 template <int EPI>
 __global__ void __launch_bounds__(256) gemm_thin_f32(const GemmArgs p, const int nbm, const int nbn)
@@ -80,8 +75,8 @@ __global__ void __launch_bounds__(256) gemm_thin_f32(const GemmArgs p, const int
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int kt = 2 * sc + t < nk ? 2 * sc + t : nk - 1;
-            glds16t(p.A + (src_a + (unsigned)(kt * BK)), base + t * HALF + wave * 1024);
-            glds16t(p.W + (src_w + (unsigned)(kt * BK)), base + t * HALF + (4 + wave) * 1024);
+            glds16(p.A + (src_a + (unsigned)(kt * BK)), base + t * HALF + wave * 1024);
+            glds16(p.W + (src_w + (unsigned)(kt * BK)), base + t * HALF + (4 + wave) * 1024);
         }
     };
 

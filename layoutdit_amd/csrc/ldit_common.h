@@ -58,7 +58,6 @@ struct DiagSwitches {
     int fp8_tile = -1;           // LDIT_GEMM_FP8_TILE 0..4
     bool fp8_k16 = false, fp8_noskinny = false;   // LDIT_GEMM_FP8_K16, LDIT_GEMM_FP8_NOSKINNY
     bool direct_epi = false;     // LDIT_GEMM_DIRECT_EPILOGUE=1
-    bool attn_bf16_kt4 = false;  // LDIT_ATTN_BF16_KT=4
     int attn_bf16_nw = -1;       // LDIT_ATTN_BF16_NW=8: eight query tiles per workgroup (one staging of a chunk per 256 queries)
     long planes_tail_waves = 700;    // LDIT_PLANES_TAIL_WAVES: split-fp32 GEMMs of at most this many 32 x 32 output tiles run on the one-wave-per-tile kernel
     int seg_order = -1;          // LDIT_GEMM_SEG_ORDER 0 = plane segments outermost (whole K per segment), 1 = innermost (per k-tile)
@@ -252,8 +251,24 @@ int launch_layernorm(const float *X, const float *g, const float *b, float *Y, i
                      hipStream_t stream);
 int launch_layernorm_bf16out(const float *X, const float *g, const float *b, void *Y, int64_t rows, int C, float eps,
                              hipStream_t stream);
-int launch_attention_bf16(const void *Q, const void *K, const void *V, void *O, int B, int N, int H, int D, int ldq, int ldk,
-                          int ldv, int ldo, float scale, hipStream_t stream);
+// Flash attention forward on the bf16 MFMA (attention_flash.hip): every build but fp32.  Output forms (store_o there):
+enum AttnOut { ATTN_BF16 = 0,      // bf16 [rows, ldo]
+               ATTN_FP8 = 1,       // fp8 e4m3 codes of o / *qscale
+               ATTN_MX = 2,        // MX codes + E8M0 block scales Os [rows, ldo / 32]
+               ATTN_MX_TRAIN = 3,  // ATTN_MX plus lse, Ob (bf16 O before quantisation) and Od (bf16 dequantised codes), both [rows, ldo]
+               ATTN_PLANES = 4 };  // split-fp32 builds: `planes` bf16 planes of the fp32 value, plane s at column s * H * 64
+struct AttnArgs {
+    const void *Q, *K, *V;         // bf16 column slices, row strides ldq / ldk / ldv (elements); plane s of a row lies s * plane_in further
+    void *O;                       // row stride ldo (elements)
+    int B, N, H, D, ldq, ldk, ldv, ldo;
+    int planes = 1, plane_in = 0;  // 2 / 3 with ATTN_PLANES (one input stride: ldq == ldk == ldv), else 1
+    AttnOut out = ATTN_BF16;
+    float scale = 0.0f;            // softmax factor; 0 = the queries arrive multiplied by scale * log2(e) (always so with planes)
+    const float *qscale = nullptr; // ATTN_FP8: device scale of the output
+    float *lse = nullptr;          // optional (ATTN_MX_TRAIN: required): log2-domain log-sum-exp [B, H, N] for attention_bwd_bf16
+    void *Os = nullptr, *Ob = nullptr, *Od = nullptr;
+};
+int launch_attention_flash(const AttnArgs &a, hipStream_t stream);
 int launch_attention(const float *Q, const float *K, const float *V, float *O, int B, int N, int H, int D, int ldq,
                      int ldk, int ldv, int ldo, float scale, hipStream_t stream);
 int launch_cls_rows(const float *cls, const float *pos, float *out, int B, int tokens, int C, hipStream_t stream);
@@ -292,11 +307,6 @@ int gemm_bf16_tr_colsum_rows(int M, int N, int *bm = nullptr);     // partial ro
 int launch_cvt_bf16(const float *src, void *dst, size_t n, hipStream_t stream, float mul = 1.0f);
 // split-fp32 build: dst bf16 [rows, planes * cols] = the `planes` bf16 planes of src fp32 [rows, cols] (row stride lds) side by side
 int launch_split_planes(const float *src, int lds, void *dst, int rows, int cols, int planes, hipStream_t stream, float mul = 1.0f);
-// f32x3 build: attention on bf16-plane operands (attention_planes.hip); queries pre-multiplied by scale * log2(e)
-int launch_attention_planes2(const void *Q, const void *K, const void *V, void *O, int B, int N, int H, int D, int ld_in, int plane_in,
-                             int ldo, hipStream_t stream);
-int launch_attention_planes3(const void *Q, const void *K, const void *V, void *O, int B, int N, int H, int D, int ld_in, int plane_in,
-                             int ldo, hipStream_t stream);     // three planes, six products (f32x6)
 int launch_layernorm_splitout(const float *X, const float *g, const float *b, void *Y, int64_t rows, int C, float eps, int planes,
                               hipStream_t stream);
 // fp8: the per-tensor part of the accumulator's dequantisation is d_act[0] when d_act is non-null (device), else the host
@@ -311,8 +321,6 @@ int launch_gemm_mxfp8(const void *A, int lda, const void *As, const void *W, con
 int launch_quant_mx(const float *src, int64_t lds, void *codes, void *scales, int64_t rows, int K, float mul, hipStream_t stream);
 int launch_layernorm_mxout_train(const float *X, const float *g, const float *b, void *Y, void *Ys, void *Yd, int64_t rows, int C,
                                  float eps, hipStream_t stream);
-int launch_attention_bf16_mxout_train(const void *Q, const void *K, const void *V, void *O, void *Os, float *lse, void *Ob, void *Od,
-                                      int B, int N, int H, int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t stream);
 int launch_gemm_mxfp8_train(const void *A, int lda, const void *As, const void *W, const void *Ws, const float *bias, void *Y, int ldy,
                             void *Ys, int M, int N, int K, int epi, const float *lam, const float *R, float *Y2, void *Ypre,
                             const float *rowscale, void *Yd, hipStream_t stream);
@@ -323,16 +331,12 @@ int launch_adamw_mx(float *p, const float *g, float *m, float *v, int64_t e0, in
                     int64_t bias_start, int64_t bias_dst, int C, float fold, hipStream_t stream);
 int launch_layernorm_mxout(const float *X, const float *g, const float *b, void *Y, void *Ys, int64_t rows, int C, float eps,
                            hipStream_t stream);
-int launch_attention_bf16_mxout(const void *Q, const void *K, const void *V, void *O, void *Os, int B, int N, int H, int D, int ldq,
-                                int ldk, int ldv, int ldo, float scale, hipStream_t stream);
 int launch_quant_rows_fp8(const float *W, void *dst, float *scales, int N, int K, hipStream_t stream, float mul = 1.0f);
 int launch_quant_fp8(const float *src, void *dst, size_t n, float inv_scale, const float *d_scale, hipStream_t stream);
 int launch_amax_f32(const float *src, size_t n, float *out, bool accumulate, hipStream_t stream);
 int launch_amax_to_scale(float *p, int n, hipStream_t stream);   // p[i] = max(p[i], tiny) / 448
 int launch_layernorm_fp8out(const float *X, const float *g, const float *b, void *Y, int64_t rows, int C, float eps,
                             const float *qscale, hipStream_t stream);
-int launch_attention_bf16_fp8out(const void *Q, const void *K, const void *V, void *O, int B, int N, int H, int D, int ldq,
-                                 int ldk, int ldv, int ldo, float scale, const float *qscale, hipStream_t stream);
 int launch_pack_qkv_bias(const float *bq, const float *bv, float *dst, int C, hipStream_t stream, float qmul = 1.0f);
 
 // ---- train step (train_ops.hip, attention_bwd_bf16.hip, api_train.hip) ----------------------------------------------------
@@ -352,8 +356,6 @@ struct ReduceJobs {
     }
 };
 int launch_reduce_jobs(ReduceJobs &jobs, hipStream_t stream);     // resets jobs.n
-int launch_attention_bf16_lse(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int N, int H, int D, int ldq,
-                              int ldk, int ldv, int ldo, float scale, hipStream_t stream);
 int launch_attention_bwd_bf16(const void *Q, const void *K, const void *V, const void *O, const void *dO, const float *lse,
                               void *dQ, void *dK, void *dV, int B, int N, int H, int D, int ldqkv, int ldo, int lddo, int lddqkv,
                               float scale, hipStream_t stream);

@@ -31,7 +31,7 @@ def sgprs_written_by_vector_op(p: str) -> set:
 
 def main() -> int:
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    files = sys.argv[1:] or ["gemm_bf16.hip", "gemm_bf16_tr.hip", "gemm_fp8.hip", "attention_bf16.hip", "attention_planes.hip"]
+    files = sys.argv[1:] or ["gemm_bf16.hip", "gemm_bf16_tr.hip", "gemm_fp8.hip", "attention_flash.hip"]
     total = suspect = 0
     for f in files:
         with tempfile.TemporaryDirectory() as d:

@@ -218,7 +218,7 @@ def _fp32_grade_gates(name, got, ref, v, gate, shifted_case):
 # ---- mxfp8: the codes against the host MX pack ---------------------------------------------------------------------------------
 def _check_mx_pack(name, codes, scales, ob, od, exact):
     """od is the exact dequantisation of (codes, scales).  exact (the selecting cases: o is bf16-exact in fp32 already): codes and
-    scales EQUAL the host MX pack of ob.  Otherwise the kernel quantises its fp32 o, of which ob is the bf16 rounding (attention_bf16.hip,
+    scales EQUAL the host MX pack of ob.  Otherwise the kernel quantises its fp32 o, of which ob is the bf16 rounding (attention_flash.hip,
     OUT_MX epilogue: amax and pack_fp8x4 read o[dt][e], Ob stores (bf16)o[dt][e]), so the pack of ob is a SECOND rounding of o and may
     differ from the codes wherever ob landed on an e4m3 tie (1 in 16 bf16 values is one).  What must hold: the block's scale byte is
     the scale rule's byte for an amax inside ob's bf16 rounding interval, and each code lies between the e4m3 roundings of the two
@@ -333,7 +333,7 @@ _ids = [f"{k}-N{N}-t{t}{'-alternating' if a else ''}" for k, N, t, a in LEVELS]
 def test_forwards_at_every_level(kind, N, t, alternate):
     """Every forward on logits at level t: finite, inside its existing tensor gate (with and without the offset channel) and inside
     the per-element bound.  bf16 kernels: |o^ - o| <= 1.25 * 2u * (P |V|) (P to bf16 and the output to bf16, u = 2^-9 each; 1.25
-    for fp32 accumulation and v_exp_f32).  The mxfp8 train kernel rounds P to bf16 like the others (attention_bf16.hip: the same
+    for fp32 accumulation and v_exp_f32).  The mxfp8 train kernel rounds P to bf16 like the others (attention_flash.hip: the same
     `pf[st][jj] = (bf16_t)s[kt][...]`; only its OUTPUT is MX), so it keeps u.  lse: 2e-3 + D 2^-24 c max_j sum_d |q k|."""
     sh = kind == "shifted"
     case, ref = _plain(kind, N, t, alternate)

@@ -89,7 +89,7 @@ def test_attention_bf16(B, N, H):
 @pytest.mark.parametrize("N", [197, 130, 256, 257, 100])
 def test_attention_bf16_workgroup_width_does_not_change_a_bit(N):
     """Five to eight query tiles (N = 129 .. 256) run as one eight-wave workgroup per (image, head), everything else on four-wave
-    workgroups (attention_bf16.hip, launch_attn).  A query tile's arithmetic does not depend on its workgroup: both widths forced,
+    workgroups (attention_flash.hip, launch_form).  A query tile's arithmetic does not depend on its workgroup: both widths forced,
     both entry modes, bit-equal - so batch and shape invariance of the bf16 / fp8 builds and of the train step are untouched."""
     B, H, D = 2, 3, 64
     q, k, v = (torch.from_numpy(_bf16_round(_rand(220 + i, B, N, H * D))).to(DEV).to(torch.bfloat16) for i in range(3))

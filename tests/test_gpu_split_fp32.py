@@ -97,7 +97,7 @@ def test_linear_planes_vs_float64(planes, M, N, K):
 @pytest.mark.parametrize("planes", [2, 3])
 @pytest.mark.parametrize("B,N,H", [(2, 197, 3), (1, 1025, 2), (3, 64, 1), (2, 33, 2), (1, 130, 4)])
 def test_attention_planes_vs_float64(B, N, H, planes):
-    """attention_planes.hip against float64 softmax(q k^T / sqrt(D)) v on the unsplit operands: whole chunks, a ragged last chunk
+    """attention_flash.hip against float64 softmax(q k^T / sqrt(D)) v on the unsplit operands: whole chunks, a ragged last chunk
     (N = 197: 5 keys; N = 1025: 1 key), a single partial chunk, a query tile past the end.  The error budget of two planes is their
     2^-17 on q, k (amplified by the exp), p and v: <= 2e-5 relative-L2, the fp32 gate; three planes (six products): fp32 level,
     <= 2e-6.  A large-logit head forces the deferred rescale."""

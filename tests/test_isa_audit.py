@@ -100,3 +100,26 @@ def test_residual_epilogues_do_not_wait_for_their_own_stores(tmp_path):
     for slab in slabs[1:3]:                               # (the last one runs into the direct-store paths of the ragged tiles)
         assert "S" in slab, slab
         assert "[v(" not in slab[slab.index("S"):], slab
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc (cross-compiles without a GPU)")
+def test_attention_forward_kernels_keep_their_registers_and_do_not_spill(tmp_path):
+    """attention_flash.hip is one body for one, two and three planes.  What tips it over is the grouping of the V reads of the second
+    product: per 16-key step with one plane it spills at 128 registers (private segment 12 bytes), per key tile with planes it outgrows
+    their budget.  Metadata only: every kernel of the file has no private segment and stays within the register count its occupancy
+    is built on (one plane 128 = four workgroups per CU; two planes 169, three planes 217 = one eight-wave workgroup per CU)."""
+    import re
+    asm = _device_asm("attention_flash.hip", tmp_path)
+    heads = list(re.finditer(r"^\s+\.name:\s+(_Z\S+)\s*$", asm, re.M))
+    seen = 0
+    for i, m in enumerate(heads):
+        name = m.group(1)
+        entry = asm[m.end():heads[i + 1].start() if i + 1 < len(heads) else len(asm)]
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1))
+        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1))
+        limit = 169 if "attention_planesILi2" in name else 217 if "attention_planesILi3" in name else 128
+        assert "attention_planes" in name or "attention_bf16" in name, name
+        assert scratch == 0, (name, scratch)
+        assert vgprs <= limit, (name, vgprs, limit)
+        seen += 1
+    assert seen == 18
