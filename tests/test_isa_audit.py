@@ -123,3 +123,25 @@ def test_attention_forward_kernels_keep_their_registers_and_do_not_spill(tmp_pat
         assert vgprs <= limit, (name, vgprs, limit)
         seen += 1
     assert seen == 18
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc (cross-compiles without a GPU)")
+def test_attention_backward_kernels_keep_two_waves_per_simd_and_do_not_spill(tmp_path):
+    """attention_bwd_bf16.hip is one staging routine and one body per phase behind three kernels (one-block, blocked ROLE 0 / 1), all
+    built on two eight-wave workgroups per CU: at most 256 registers (vector + accumulation) and nothing in scratch.  The blocked
+    ROLE 0 kernel sits at 254; a second instance of the phase 1 body took it to 256 with 8 spilled.  Metadata only."""
+    import re
+    asm = _device_asm("attention_bwd_bf16.hip", tmp_path)
+    heads = list(re.finditer(r"^\s+\.name:\s+(_Z\S+)\s*$", asm, re.M))
+    assert len(heads) == 3, [m.group(1) for m in heads]
+    for i, m in enumerate(heads):
+        name = m.group(1)
+        # an entry of the metadata list starts at its first key (.agpr_count, in front of .name): take the whole list item
+        start = asm.rfind("\n  - ", 0, m.start())
+        end = asm.find("\n  - ", m.end())
+        entry = asm[start:end if end >= 0 else len(asm)]
+        field = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, entry).group(1))                          # noqa: E731
+        assert "attention_bwd_bf16" in name, name
+        assert field("private_segment_fixed_size") == 0, (name, field("private_segment_fixed_size"))
+        assert field("vgpr_spill_count") == 0, (name, field("vgpr_spill_count"))
+        assert field("vgpr_count") + field("agpr_count") <= 256, (name, field("vgpr_count"), field("agpr_count"))
