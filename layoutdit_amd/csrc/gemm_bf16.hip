@@ -3,12 +3,17 @@
 //
 // Same skeleton as the fp32 kernels: K-contiguous operands -> LDS by LDS-DMA (global_load_lds_dwordx4), 128-B LDS rows
 // (64 bf16), 16-B chunk XOR-swizzled with (row>>1)&7 on the source address and on the read, two stages, fragments of
-// k-step s+1 read while step s multiplies.  v_mfma_f32_32x32x16_bf16: lane (r, h) supplies 8 consecutive k (16 B =
-// ONE ds_read_b128) per 32-row tile and 16-deep step, so a 64-deep k-tile is four steps of TM*TN MFMAs.
+// k-step s+1 read while step s multiplies.  v_mfma_f32_16x16x32_bf16: a 32 x 32 block of the output is 2 x 2 tiles of
+// 16 x 16, lane (r16, q) supplies 8 consecutive k (16 B = ONE ds_read_b128) per 16-row fragment and 32-deep step.
 // Operands are swapped in the MFMA (A-operand <- W rows, B-operand <- activation rows): an accumulator register quad
 // holds 4 consecutive output columns of one row -> 16-B fp32 / 8-B bf16 stores.
-// Block = 2 x 2 waves, wave tile TM x TN 32x32 tiles; 256x256 (TM = TN = 4) keeps the DMA issue (one 1-KiB piece per
-// ~60 cycles per wave) under the MFMA time of a k-tile; smaller tiles are DMA-issue bound.
+// Block = WM x WN waves, wave tile TM x TN blocks of 32 x 32; the 256-wide eight-wave tiles keep the DMA issue (one 1-KiB
+// piece per ~60 cycles per wave) under the MFMA time of a k-tile; smaller tiles are DMA-issue bound.
+// Retired builds of this loop ("Retired compile-time variants", names the commit that last held each): the
+// v_mfma_f32_32x32x16_bf16 pipeline of rounds 1-3, same bits, lost 2 % inside the models (profiles/r04_model_ab_mfma16.txt);
+// every wave issuing its own DMA pieces idled the matrix pipe (profiles/r02_dma_issue.txt); per-lane 64-bit DMA addresses
+// cost 4 - 7 % per GEMM (profiles/r03_dma_scalar_base_ab.txt); DMA bursts staggered between the two waves of a SIMD lost up to
+// 3 % on the model shapes (profiles/r04_bf16_gemm_stamps.txt).
 //
 // Epilogues: bias -> bf16 ; bias + erf-GELU -> bf16 ; bias + ReLU -> bf16 ; R + lam (.) (acc + bias) -> fp32 (in place on the fp32 residual
 // stream, optional fp32 tap copy).
@@ -29,8 +34,6 @@ namespace ldit {
 
 namespace {
 
-// WM x WN waves per workgroup, each owning TM x TN 32x32 tiles.  2 x 4 waves (512 threads, two waves per SIMD) let one
-// wave's MFMAs cover the other's LDS reads, DMA issue and barrier waits.
 // One wave, one 32 x 16 output tile over all of K (the tail kernel's body - see gemm_bf16_tail below for what it promises; it stands
 // in front of the tile kernel because a peeled tail now rides in the main launch as a few extra workgroups, each wave one tile).
 template <int EPI>
@@ -108,9 +111,11 @@ struct ConvArgsH {
     GemmArgsH g;         // M = B H W, N = Cout, K = 9 C; A = the padded map, W = [Cout, 3, 3, C]; lda unused
     int H, W, C;
 };
-__device__ __forceinline__ const GemmArgsH &gemm_args(const GemmArgsH &a) { return a; }
-__device__ __forceinline__ const GemmArgsH &gemm_args(const ConvArgsH &a) { return a.g; }
+__host__ __device__ __forceinline__ const GemmArgsH &gemm_args(const GemmArgsH &a) { return a; }
+__host__ __device__ __forceinline__ const GemmArgsH &gemm_args(const ConvArgsH &a) { return a.g; }
 
+// The tile kernel: WM x WN waves per workgroup, each owning TM x TN blocks of 32 x 32.  2 x 4 waves (512 threads, two waves per
+// SIMD) let one wave's MFMAs cover the other's LDS reads, DMA issue and barrier waits.
 template <int WM, int WN, int TM, int TN, int EPI, bool CONV = false>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(const std::conditional_t<CONV, ConvArgsH, GemmArgsH> p0)
 {
@@ -119,11 +124,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, ROWS = BM + BN;
     static_assert(BM % 8 == 0, "a DMA piece is eight rows");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifndef LDIT_BF16_MFMA32
-    constexpr bool L16 = true;       // v_mfma_f32_16x16x32_bf16 (default)
-#else
-    constexpr bool L16 = false;      // A/B build: v_mfma_f32_32x32x16_bf16, as rounds 1-3 (same bits)
-#endif
+    constexpr bool L16 = true;       // accumulator layout of v_mfma_f32_16x16x32_bf16, for the epilogues (gemm_bf16_common.h)
 
 #ifdef LDIT_GEMM_STAMPS
     const unsigned long long st_entry = __builtin_amdgcn_s_memtime();
@@ -153,11 +154,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         if (wave == 0) tail_tile<EPI>(t, (int)blockIdx.x - nblocks, lane);
         return;
     }
-    int tile;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3, qq = nblocks >> 3, rr = nblocks & 7;
-        tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-    }
+    int tile = xcd_contiguous_tile(nblocks);
     int nk = p.K / BKB;
     if (!CONV && EPI == EPI_F32 && p.x.splits > 1) {
         // split-K (wgrad: K = tokens of the batch, output tiles few): this block multiplies k-tiles [kt0, kt0 + nk) into its
@@ -182,23 +179,11 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
     // still reach every hand-over barrier: ViT-L/16 512x512 bs=16 forward 15.75 -> 15.40 ms (raising the loaders' priority
     // with s_setprio changes nothing).  The 4-wave tiles stay symmetric.
     // (the 320-row tile with the residual / fp32 epilogues has no registers left for the loaders' 18 source offsets: symmetric)
-#ifdef LDIT_BF16_NO_SPLIT            // A/B build only (scripts/ab_bf16_split.sh): every wave issues its own pieces, as in round 1
-    constexpr bool SPLIT = false;
-#else
     constexpr bool SPLIT = NWAVES == 8 && !(TM == 5 && (EPI == EPI_SCALE_RESID || EPI == EPI_F32 || EPI == EPI_EMBED));
-#endif
-#ifdef LDIT_BF16_STAGGER
-    // A/B build: all eight waves issue (half the pieces each); waves 0..3 right behind the hand-over, waves 4..7 - their SIMD
-    // partners - a step or two later: one wave of a SIMD multiplies while the other is held up by its pieces
-    constexpr bool STAGGER = SPLIT;
-    constexpr int LW = NWAVES;
-#else
-    constexpr bool STAGGER = false;
     constexpr int LW = SPLIT ? NWAVES / 2 : NWAVES;      // waves that issue
-#endif
     constexpr int NLW = ROWS / (8 * LW);                 // pieces per issuing wave and k-tile
     static_assert(ROWS % (8 * LW) == 0, "DMA pieces must split evenly over the issuing waves");
-    const bool loader = !SPLIT || STAGGER || wave < LW;  // wave-uniform
+    const bool loader = !SPLIT || wave < LW;             // wave-uniform
     unsigned src[NLW];   // element (bf16) offsets
 #pragma unroll
     for (int u = 0; u < NLW; ++u) {
@@ -246,18 +231,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         ka = __builtin_amdgcn_readfirstlane((unsigned)(((p.x.seg_a >> (4 * seg)) & 15u) * (unsigned)p.K + (unsigned)t * BKB));
         kw = __builtin_amdgcn_readfirstlane((unsigned)(((p.x.seg_w >> (4 * seg)) & 15u) * (unsigned)p.K + (unsigned)t * BKB));
     };
+    // pieces lo .. hi-1 of this wave's NLW, k-tile offsets (ka, kw), into `stage`
     auto issue_range = [&](int stage, unsigned ka, unsigned kw, int lo, int hi) {
-#ifdef LDIT_BF16_VADDR_DMA           // A/B build only: per-lane 64-bit source addresses through the builtin, as in rounds 1-2
-        char *base = smem + stage * (ROWS * ROWB);
-#pragma unroll
-        for (int u = 0; u < NLW; ++u) {
-            if (u < lo || u >= hi) continue;
-            const int piece = (wave % LW) + LW * u;
-            const bool isA = 8 * piece < BM;
-            const bf16_t *opnd = isA ? p.A : p.W;
-            glds16(opnd + (src[u] + (isA ? ka : kw)), base + piece * 1024);
-        }
-#else
         // the k-tile's column offset travels in the scalar base, the lane's row / chunk offset is the kernel constant src[u]
         const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(smem + stage * (ROWS * ROWB))));
         // (scalar arithmetic on kernel-argument pointers and the scalar tile offsets: nothing here comes fresh out of a v_readfirstlane)
@@ -268,15 +243,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
             const int piece = (wave % LW) + LW * u;
             glds16_sbase(8 * piece < BM ? abase : wbase, 2u * src[u], dst + piece * 1024);
         }
-#endif
     };
 
-#ifndef LDIT_BF16_MFMA32
-    // v_mfma_f32_16x16x32_bf16 build: the same LDS image, a 32 x 32 tile = 2 x 2 tiles of 16 x 16, lane (r16, q) supplies the 8
-    // consecutive k of chunk q (of the four of a 32-deep step) for row r16 - ONE ds_read_b128 per 16-row fragment and 32-deep step.
+    // v_mfma_f32_16x16x32_bf16: a 32 x 32 block = 2 x 2 tiles of 16 x 16, lane (r16, q) supplies the 8 consecutive k of chunk q (of
+    // the four of a 32-deep step) for row r16 - ONE ds_read_b128 per 16-row fragment and 32-deep step.
     // A k-tile is four HALF steps: (k32, half) = (0, a) (0, b) (1, a) (1, b); a half multiplies TM of the 2 TM activation
-    // fragments with all 2 TN weight fragments (16 MFMAs of 16 cycles for the 128 x 64 wave tile = the 8 x 32 cycles of a 16-deep
-    // step of the 32x32x16 build).  MI355X_MICROARCH.md, DVFS give-back item 7: this shape holds a higher clock on random data.
+    // fragments with all 2 TN weight fragments (16 MFMAs of 16 cycles for the 128 x 64 wave tile).  On random data this shape
+    // holds a higher clock than 32x32x16 accumulators (profiles/r04_bf16_gemm_stamps.txt: 1.60 - 1.71 GHz against 1.44 - 1.48).
     f32x4 acc[2 * TM][2 * TN];
 #pragma unroll
     for (int i = 0; i < 2 * TM; ++i)
@@ -307,42 +280,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
                 else acc[TM + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[TM + i][j], 0, 0, 0);
             }
     };
-#else
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 
-    const int c32 = lane & 31, h = lane >> 5;
-    const int sw = (c32 >> 1) & 7;
-    const int a_row = (wm * TM * 32 + c32) * ROWB, b_row = (BM + wn * TN * 32 + c32) * ROWB;
-    auto load_frags = [&](int stage, int s, bf16x8(&xa)[TM], bf16x8(&wb)[TN]) {
-        const char *base = smem + stage * (ROWS * ROWB) + ((s * 2 + h) ^ sw) * 16;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) xa[i] = *reinterpret_cast<const bf16x8 *>(base + a_row + i * 32 * ROWB);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) wb[j] = *reinterpret_cast<const bf16x8 *>(base + b_row + j * 32 * ROWB);
-    };
-    auto mfma_step = [&](const bf16x8(&xa)[TM], const bf16x8(&wb)[TN]) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-    };
-
-#endif
-
-    // Pinned pipeline (sched_group_barrier), four 16-deep steps per 64-deep k-tile:
-    //   step s multiplies fragments read during step s-1 while the fragments of step s+1 are read, ONE LDS read or DMA
-    //   piece per MFMA;  the hand-over barrier (tile kt+1 landed, stage cur released) sits in front of step 3's MFMAs;
-    //   the NLD DMA pieces of a tile are spread over step 3 of the previous iteration (right after the hand-over that
-    //   freed their stage) and steps 0 and 1, so the last of them still has ~2 steps of MFMA time to land.
+    // Pinned pipeline (sched_group_barrier), four half steps per 64-deep k-tile:
+    //   a half step multiplies fragments read during the one before while the fragments of the next are read, ONE LDS read or
+    //   DMA piece per MFMA;  the hand-over barrier (tile kt+1 landed, stage cur released) sits in front of (1, b)'s MFMAs;
+    //   the NP DMA pieces of a tile are spread over (1, b) of the previous iteration (right after the hand-over that freed
+    //   their stage) and (0, a) and (0, b), so the last of them still has about two half steps of MFMA time to land.
     constexpr int SG_MFMA = 0x8, SG_VMEM = 0x20, SG_DSR = 0x100;
-#ifndef LDIT_BF16_MFMA32
     constexpr int NM = 2 * TM * TN;                     // MFMAs per half step
     bf16x8 xaA[TM], xaB[TM], wbX[2 * TN], wbY[2 * TN];
 #ifdef LDIT_GEMM_STAMPS
@@ -364,14 +308,16 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         }
         if (NM - NR - ND > 0) __builtin_amdgcn_sched_group_barrier(SG_MFMA, NM - NR - ND, ID);
     };
-    auto kloop = [&](auto np_c, auto late_c) {
+    // the k-loop, instantiated per role: NP = DMA pieces this wave issues per k-tile (0 for the non-loaders of a SPLIT tile)
+    auto kloop = [&](auto np_c) {
     constexpr int NP = decltype(np_c)::value;
-    constexpr int LATE = decltype(late_c)::value;        // 0: pieces dealt as always; 1 / 2: all of them in half step (0, a) / (0, b)
-    constexpr int D3 = LATE ? 0 : (SPLIT ? NP : (NP + 2) / 3), D0 = LATE == 1 ? NP : LATE == 2 ? 0 : (SPLIT ? 0 : (NP - D3 + 1) / 2), D1 = NP - D3 - D0;
+    // pieces issued in half steps (1, b) / (0, a) / (0, b); a SPLIT loader issues all of them right behind the hand-over (twice
+    // the pieces: the last ones need the whole k-tile to land)
+    constexpr int D3 = SPLIT ? NP : (NP + 2) / 3, D0 = SPLIT ? 0 : (NP - D3 + 1) / 2, D1 = NP - D3 - D0;
     unsigned ka0, kw0, ka1, kw1, ka2, kw2;
     tile_off(0, ka0, kw0);
     tile_off(1, ka1, kw1);
-    asm volatile("s_nop 4" ::: "memory");
+    asm volatile("s_nop 4" ::: "memory");                 // the only place where a tile offset is used right after it was made scalar
     issue_range(0, ka0, kw0, 0, NP);
     issue_range(1, ka1, kw1, 0, D3);
     // tile 0 has landed (vmcnt counts down in issue order); the D3 pieces of tile 1 stay in flight under the first k-tile - the
@@ -406,7 +352,9 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         mfma_half(0, xaA, wbY);
         deal(std::integral_constant<int, TM>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
         __builtin_amdgcn_sched_barrier(0);
-        // ---- hand-over
+        // ---- hand-over: own DMA of tile kt+1 landed (vmcnt 0), own reads of stage cur done, then all waves.  The wait is
+        //      explicit: hipcc does NOT put a vmcnt wait in front of this barrier for LDS-DMA pieces issued behind the PREVIOUS
+        //      hand-over (a loader's pieces all are) - other waves would read a stage that has not landed
 #ifdef LDIT_GEMM_STAMPS
         {
             const unsigned long long h0 = __builtin_amdgcn_s_memtime();
@@ -430,128 +378,11 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
         deal(std::integral_constant<int, TM + 2 * TN>{}, std::integral_constant<int, (D3 < NM - TM - 2 * TN ? D3 : NM - TM - 2 * TN)>{}, std::integral_constant<int, 3>{});
     }
     };
-#else
-    constexpr int NM = TM * TN, NF = TM + TN;
-    static_assert(NF <= NM, "fewer MFMAs than fragment reads per step");
-    bf16x8 xa0[TM], wb0[TN], xa1[TM], wb1[TN];
-#ifdef LDIT_GEMM_STAMPS
-    unsigned long long st_vm = 0, st_bar = 0, st_loop0 = 0, st_real0 = 0;
-#endif
-    // the k-loop, instantiated per role: NP = DMA pieces this wave issues per k-tile (0 for the non-loaders of a SPLIT tile)
-    auto kloop = [&](auto np_c) {
-    constexpr int NP = decltype(np_c)::value;
-    // pieces issued in steps 3 / 0 / 1; a SPLIT loader issues all of them right behind the hand-over (twice the pieces: the last
-    // ones need the whole k-tile to land)
-    constexpr int D3 = SPLIT ? NP : (NP + 2) / 3, D0 = SPLIT ? 0 : (NP - D3 + 1) / 2, D1 = NP - D3 - D0;
-    unsigned ka0, kw0, ka1, kw1, ka2, kw2;
-    tile_off(0, ka0, kw0);
-    tile_off(1, ka1, kw1);
-    asm volatile("s_nop 4" ::: "memory");                 // the only place where a tile offset is used right after it was made scalar
-    issue_range(0, ka0, kw0, 0, NP);
-    issue_range(1, ka1, kw1, 0, D3);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // explicit: the first tile has landed before anybody reads it
-    __syncthreads();
-#ifdef LDIT_GEMM_STAMPS
-    st_loop0 = __builtin_amdgcn_s_memtime();
-    st_real0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    load_frags(0, 0, xa0, wb0);
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        tile_off(kt + 2, ka2, kw2);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- step 0
-        load_frags(cur, 1, xa1, wb1);
-        issue_range(cur ^ 1, ka1, kw1, D3, D3 + D0);
-        mfma_step(xa0, wb0);
-#pragma unroll
-        for (int g = 0; g < NF; ++g) {
-            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(SG_DSR, 1, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < D0; ++g) {
-            if (NF + g < NM) __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 0);
-        }
-        if (NM - NF - D0 > 0) __builtin_amdgcn_sched_group_barrier(SG_MFMA, NM - NF - D0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- step 1
-        load_frags(cur, 2, xa0, wb0);
-        issue_range(cur ^ 1, ka1, kw1, D3 + D0, NP);
-        mfma_step(xa1, wb1);
-#pragma unroll
-        for (int g = 0; g < NF; ++g) {
-            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 1);
-            __builtin_amdgcn_sched_group_barrier(SG_DSR, 1, 1);
-        }
-#pragma unroll
-        for (int g = 0; g < D1; ++g) {
-            if (NF + g < NM) __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 1);
-            __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 1);
-        }
-        if (NM - NF - D1 > 0) __builtin_amdgcn_sched_group_barrier(SG_MFMA, NM - NF - D1, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- step 2
-        load_frags(cur, 3, xa1, wb1);
-        mfma_step(xa0, wb0);
-#pragma unroll
-        for (int g = 0; g < NF; ++g) {
-            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 2);
-            __builtin_amdgcn_sched_group_barrier(SG_DSR, 1, 2);
-        }
-        if (NM - NF > 0) __builtin_amdgcn_sched_group_barrier(SG_MFMA, NM - NF, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- hand-over: own DMA of tile kt+1 landed (vmcnt 0), own reads of stage cur done, then all waves
-#ifdef LDIT_GEMM_STAMPS
-        {
-            const unsigned long long h0 = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            const unsigned long long h1 = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const unsigned long long h2 = __builtin_amdgcn_s_memtime();
-            st_vm += h1 - h0; st_bar += h2 - h1;
-        }
-#else
-        // explicit: hipcc does NOT put a vmcnt wait in front of this barrier for LDS-DMA pieces issued behind the PREVIOUS
-        // hand-over (a loader's pieces all are) - other waves would read a stage that has not landed
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#endif
-        // ---- step 3: MFMAs of the last fragments | first fragments of tile kt+1 | first DMA pieces of tile kt+2 -> stage cur
-        load_frags(cur ^ 1, 0, xa0, wb0);
-        issue_range(cur, ka2, kw2, 0, D3);
-        ka1 = ka2; kw1 = kw2;
-        mfma_step(xa1, wb1);
-#pragma unroll
-        for (int g = 0; g < NF; ++g) {
-            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 3);
-            __builtin_amdgcn_sched_group_barrier(SG_DSR, 1, 3);
-        }
-#pragma unroll
-        for (int g = 0; g < D3; ++g) {
-            if (NF + g < NM) __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 3);
-            __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 3);
-        }
-        if (NM - NF - D3 > 0) __builtin_amdgcn_sched_group_barrier(SG_MFMA, NM - NF - D3, 3);
-    }
-    };
-#endif
-#ifndef LDIT_BF16_MFMA32
-#ifndef LDIT_BF16_STAGGER_STEP
-#define LDIT_BF16_STAGGER_STEP 2
-#endif
-    if (STAGGER && wave >= NWAVES / 2) kloop(std::integral_constant<int, NLW>{}, std::integral_constant<int, LDIT_BF16_STAGGER_STEP>{});
-    else if (loader) kloop(std::integral_constant<int, NLW>{}, std::integral_constant<int, 0>{});
-    else kloop(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-#else
     if (loader) kloop(std::integral_constant<int, NLW>{});
     else kloop(std::integral_constant<int, 0>{});
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-fetches of the tail must not outlive the LDS allocation
 #ifdef LDIT_GEMM_STAMPS
-    asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[(L16 ? 2 : 1) * TM - 1][(L16 ? 2 : 1) * TN - 1][L16 ? 3 : 15]));
+    asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[2 * TM - 1][2 * TN - 1][3]));
     const unsigned long long st_loop1 = __builtin_amdgcn_s_memtime(), st_real1 = __builtin_amdgcn_s_memrealtime();
 #endif
 
@@ -577,20 +408,33 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_mfma(co
 #endif
 }
 
-template <int WM, int WN, int TM, int TN, int EPI>
-int launch_h(const GemmArgsH &a, hipStream_t stream)
+// One launcher for the row-major GEMM and the implicit-im2col convolution: the argument type follows CONV as the kernel's does.
+template <int WM, int WN, int TM, int TN, int EPI, bool CONV>
+int launch_h(const std::conditional_t<CONV, ConvArgsH, GemmArgsH> &a, hipStream_t stream)
 {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int lds = 2 * (BM + BN) * ROWB;
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    auto kern = gemm_bf16_mfma<WM, WN, TM, TN, EPI>;
+    const GemmArgsH &g = gemm_args(a);
+    const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+    auto kern = gemm_bf16_mfma<WM, WN, TM, TN, EPI, CONV>;
     LDIT_DYN_LDS(kern, lds);
-    // (+ one workgroup per 32 x 16 tile of a peeled tail riding in this launch)
-    const int tail_tiles = a.x.tail_rows > 0 ? ((a.N + 15) / 16) * ((a.x.tail_rows + 31) / 32) : 0;
-    const int tail_blocks = tail_tiles;
-    hipLaunchKernelGGL(kern, dim3(tiles * a.x.splits + tail_blocks), dim3(64 * WM * WN), lds, stream, a);
+    // + one workgroup per 32 x 16 tile of a peeled tail riding in this launch (a convolution has none: tail_rows stays 0, splits 1)
+    const int tail_blocks = g.x.tail_rows > 0 ? ((g.N + 15) / 16) * ((g.x.tail_rows + 31) / 32) : 0;
+    hipLaunchKernelGGL(kern, dim3(tiles * g.x.splits + tail_blocks), dim3(64 * WM * WN), lds, stream, a);
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
+}
+
+// a pick (2..5, pick_tile_h below) -> its <WM, WN, TM, TN> instantiation
+template <int EPI, bool CONV>
+int launch_pick(int pick, const std::conditional_t<CONV, ConvArgsH, GemmArgsH> &a, hipStream_t stream)
+{
+    switch (pick) {
+        case 3: return launch_h<2, 4, 4, 2, EPI, CONV>(a, stream);     // 256 x 256, 8 waves (2 per SIMD)
+        case 4: return launch_h<2, 4, 3, 2, EPI, CONV>(a, stream);     // 192 x 256
+        case 5: return launch_h<2, 4, 5, 2, EPI, CONV>(a, stream);     // 320 x 256
+        default: return launch_h<2, 2, 2, 2, EPI, CONV>(a, stream);    // 128 x 128, 4 waves
+    }
 }
 
 // ---- tail kernel: up to 64 rows (the ragged tail peeled off by launch_gemm_bf16_ex, or a whole problem that small) ----------
@@ -630,8 +474,9 @@ int pick_tile_h(const GemmArgsH &a)
     //   128 x 128 (two per CU, they overlap each other's prologue / epilogue):  rounds of 256 tiles, each  r[epi] + 7.6e-3 K,
     //   but never less than one tile's own latency  5 + 11.4e-3 K.
     // Measured and dropped (profiles/README.md): a four-stage and a five-stage counted-vmcnt ring, a 256 x 128 ring at two
-    // workgroups per CU, a barrier-phased ping-pong of the two waves per SIMD, a v_mfma_f32_16x16x32_bf16 build and a
-    // four-wave 256 x 256 tile - none beat this kernel on any shape; the 256 x 128 tile stays selectable for experiments.
+    // workgroups per CU, a barrier-phased ping-pong of the two waves per SIMD and a four-wave 256 x 256 tile - none beat this
+    // kernel on any shape.  (The v_mfma_f32_16x16x32_bf16 build that first stood in this list won in round 4, inside the models,
+    // and is the kernel above: profiles/r04_model_ab_mfma16.txt.)
     // (EPI_EMBED and EPI_F32 priced like the residual epilogue, EPI_GELU_BWD like the GELU one, EPI_BIAS_RELU like EPI_BIAS: the
     // same tile for the same shape)
     const double a256[9] = {19.0, 18.5, 25.0, 25.0, 25.0, 18.5, 25.0, 25.0, 19.0}, r128[9] = {5.2, 5.0, 7.7, 7.7, 7.7, 5.0, 7.7, 7.7, 5.2};
@@ -671,40 +516,17 @@ int launch_h_tiled(const GemmArgsH &a, hipStream_t stream)
     // 3.04 / 3.07 ms on the tile kernels alone, 1.49 / 2.24 / 2.77 ms with this rule; 6 144 waves: 1.49 / 2.42 / 3.83 ms).
     if (a.x.nseg > 1 && a.x.splits == 1 && !diag().bf16_tile_env && (long)((a.M + 31) / 32) * ((a.N + 31) / 32) <= diag().planes_tail_waves)
         return launch_tail<EPI>(a, stream);
-    switch (pick_tile_h<EPI>(a)) {
-        case 3: return launch_h<2, 4, 4, 2, EPI>(a, stream);     // 256 x 256, 8 waves (2 per SIMD)
-        case 4: return launch_h<2, 4, 3, 2, EPI>(a, stream);     // 192 x 256
-        case 5: return launch_h<2, 4, 5, 2, EPI>(a, stream);     // 320 x 256
-        default: return launch_h<2, 2, 2, 2, EPI>(a, stream);    // 128 x 128, 4 waves
-    }
+    return launch_pick<EPI, false>(pick_tile_h<EPI>(a), a, stream);
 }
 
 // ---- implicit-im2col 3x3 convolution on the padded bf16 map (gemm_bf16_mfma<..., CONV = true>) ------------------------------------
-template <int WM, int WN, int TM, int TN, int EPI>
-int launch_conv_h(const ConvArgsH &a, hipStream_t stream)
-{
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr int lds = 2 * (BM + BN) * ROWB;
-    const int tiles = ((a.g.M + BM - 1) / BM) * ((a.g.N + BN - 1) / BN);
-    auto kern = gemm_bf16_mfma<WM, WN, TM, TN, EPI, true>;
-    LDIT_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(64 * WM * WN), lds, stream, a);
-    LDIT_HIP_CHECK(hipGetLastError());
-    return LDIT_OK;
-}
-
 // Every size runs on a tile kernel (the ragged last row tile and ragged N through its clamped rows and checked stores; no peeled
 // tail, no one-wave kernel): a map of at most 64 pixels takes the smallest tile, every other one the row-major picker's.
 template <int EPI>
 int launch_conv_tiled(const ConvArgsH &a, hipStream_t stream)
 {
     const int pick = (a.g.M <= 64 && !diag().bf16_tile_env) ? 2 : pick_tile_h<EPI>(a.g);
-    switch (pick) {
-        case 3: return launch_conv_h<2, 4, 4, 2, EPI>(a, stream);
-        case 4: return launch_conv_h<2, 4, 3, 2, EPI>(a, stream);
-        case 5: return launch_conv_h<2, 4, 5, 2, EPI>(a, stream);
-        default: return launch_conv_h<2, 2, 2, 2, EPI>(a, stream);
-    }
+    return launch_pick<EPI, true>(pick, a, stream);
 }
 
 // fp32 -> bf16 (round to nearest even), n elements, 4 per thread

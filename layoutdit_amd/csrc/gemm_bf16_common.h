@@ -40,6 +40,15 @@ struct GemmArgsH {
 
 template <int EPI> constexpr bool f32_out() { return EPI == EPI_SCALE_RESID || EPI == EPI_F32 || EPI == EPI_EMBED; }
 
+// Workgroup -> (tile, K-split) number of a launch of `nblocks` of them, XCD-contiguous: consecutive workgroups go to the eight XCDs in
+// turn, so XCD x is given the contiguous run of numbers [x nblocks / 8, (x + 1) nblocks / 8) (the first nblocks % 8 runs one longer) -
+// neighbouring tiles, which share operand rows, then share an L2.  A bijection for every nblocks.
+__device__ __forceinline__ int xcd_contiguous_tile(int nblocks)
+{
+    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3, qq = nblocks >> 3, rr = nblocks & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+}
+
 // MODE 0: tile inside the matrix, 16-B / 8-B accesses unchecked; MODE 1: columns inside, rows past M skipped (the ragged
 // last row tile keeps its vector accesses - a lane owns a row, so the element-wise path does not coalesce and cost ~20 us);
 // MODE 2: element-wise with checks.

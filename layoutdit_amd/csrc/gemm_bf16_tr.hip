@@ -16,7 +16,7 @@
 // gemm_bf16.hip 2 % inside the models; same sums bit for bit; lane group q reads reduction rows 8 q .. 8 q + 7 of a 32-deep step for
 // one 16-column fragment, the two 32-byte halves of a granule swapped on rows with bit 3 set so the two groups of a 32-lane half -
 // rows 8 apart, same 16 columns - stay conflict-free) passed the same tests and measured 0.5 - 1.2 % SLOWER in the train step
-// (profiles/r04_tr_mfma16_ab.txt); it lived in this file as -DLDIT_TR_MFMA16 from commit 9cb824f to d318110.
+// (profiles/r04_tr_mfma16_ab.txt); it lived in this file behind a compile-time switch from commit 9cb824f to d318110.
 // Reduction rows past the end (tokens are not a multiple of 64) are fetched from a page of zeros: LDS-DMA has no predication.
 //
 // Main loop (round 4: the pipeline of gemm_bf16.hip; rounds 2-3 ran a simple issue-all / read / multiply / barrier loop that left the
@@ -54,11 +54,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
 
     const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
     const int ntiles = nbm * nbn, nblocks = ntiles * p.x.splits;
-    int tile;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3, qq = nblocks >> 3, rr = nblocks & 7;
-        tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-    }
+    int tile = xcd_contiguous_tile(nblocks);
     int nk = (p.K + BKB - 1) / BKB, kbeg = 0;
     if (EPI == EPI_F32 && p.x.splits > 1) {
         const int split = tile / ntiles, per = (nk + p.x.splits - 1) / p.x.splits, kt0 = split * per;
@@ -105,31 +101,26 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
         }
     }
     // every k-tile but a ragged last one: the tile's advance travels in a scalar base, the lane's offset is the kernel constant src[u]
-    // (glds16_sbase, lds_dma.h) - no vector address arithmetic per piece.  Pieces lo .. hi-1 of this wave's NLW.
+    // (glds16_sbase, lds_dma.h) - no vector address arithmetic per piece.
     // (k0 is scalar - kbeg was made so at its definition, far from here - so the bases are scalar-unit arithmetic on kernel-argument
     // pointers: no v_readfirstlane result reaches the DMA's scalar base within its five wait states, cdna guide 5.7 item 2)
-    auto issue_sbase = [&](int stage, int k0, int lo, int hi) {
+    auto issue_sbase = [&](int stage, int k0) {
         const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(smem + stage * STAGE)));
         const bf16_t *a_k = p.A + (unsigned)k0, *a_r = p.A + (size_t)k0 * (size_t)p.lda, *w_r = p.W + (size_t)k0 * (size_t)p.ldw;
 #pragma unroll
         for (int u = 0; u < NLW; ++u) {
-            if (u < lo || u >= hi) continue;
             const int piece = piece_of(u);
             const bool isA = 8 * piece < BM;
             glds16_sbase((!TA && isA) ? a_k : isA ? a_r : w_r, 2u * src[u], dst + piece * 1024);
         }
     };
     // (the 320-row tile has no register left for the three scalar bases' set-up)
-#ifndef LDIT_BF16_VADDR_DMA
     constexpr bool SBASE = TM < 5;
-#else
-    constexpr bool SBASE = false;
-#endif
     auto issue = [&](int stage, int k0) {                     // k0: first reduction index of the k-tile
         char *base = smem + stage * STAGE;
         const bool ragged = k0 + BKB > p.K;                   // block-uniform: only the last k-tile of the matrix
         if (SBASE && !ragged) {
-            issue_sbase(stage, k0, 0, NLW);
+            issue_sbase(stage, k0);
             return;
         }
 #pragma unroll
@@ -181,7 +172,6 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
         for (int j = 0; j < TN; ++j)
             tw_addr[j] = lds0 + A_BYTES + (8 * h + (i16 >> 2)) * BPRW + ((((wn * TN + j)) ^ swz) << 6) + inrow;
     }
-#ifndef LDIT_TR_DEALT_READS
     // two transposing reads: reduction rows 16 s + 8 h + {0..3} and + {4..7} (both offsets are immediates)
     auto tr_frag = [&](unsigned addr, auto off_c, auto bpr4_c) -> bf16x8 {
         union { s16x4 v[2]; bf16x8 f; } u;
@@ -189,33 +179,19 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
         asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u.v[1]) : "v"(addr), "n"(decltype(off_c)::value + decltype(bpr4_c)::value));
         return u.f;
     };
-#else
-    // (every LDS-DMA of this kernel is an asm statement, so hipcc sees plain LDS reads here: no vmcnt guard, its own counted lgkmcnt)
-    auto tr_frag = [&](unsigned addr, auto off_c, auto bpr4_c) -> bf16x8 {
-        union { s16x4 v[2]; bf16x8 f; } u;
-        typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
-        u.v[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(uintptr_t)(addr + (unsigned)decltype(off_c)::value));
-        u.v[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(uintptr_t)(addr + (unsigned)(decltype(off_c)::value + decltype(bpr4_c)::value)));
-        return u.f;
-    };
-#endif
     // (issued in the order the next step's MFMAs need them - wb[0], xa[0], wb[1], xa[1], xa[2] ... for MFMAs (0,0) (0,1) (1,0) ... -
     //  so the first MFMA behind a step boundary waits for the OLDEST reads of the previous step)
     auto load_frags = [&](int stage, auto s_c, bf16x8(&xa)[TM], bf16x8(&wb)[TN]) {
         constexpr int s = decltype(s_c)::value;
         const unsigned so = (unsigned)(stage * STAGE);
         const unsigned addr = (a0 + so) ^ (unsigned)(s << 5);
-        auto read_a = [&](int, auto i_c) {
+        auto read_a = [&](auto i_c) {
             constexpr int I = decltype(i_c)::value;
             if (TA) {
                 xa[I] = tr_frag(ta_addr[TA ? I : 0] + so, std::integral_constant<int, 16 * s * BM * 2>{}, std::integral_constant<int, 4 * BM * 2>{});
             } else {
-#ifndef LDIT_TR_DEALT_READS
                 const unsigned ad = addr;       // (an asm operand alone does not capture a variable of the enclosing lambda)
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[I]) : "v"(ad), "n"(I * 32 * ROWB));
-#else
-                xa[I] = *(const __attribute__((address_space(3))) bf16x8 *)(uintptr_t)(addr + (unsigned)(I * 32 * ROWB));
-#endif
             }
         };
         auto read_w = [&](auto j_c) {
@@ -224,12 +200,12 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
         };
         static_assert(TN == 2 && TM >= 2 && TM <= 5, "read order written out for two column fragments");
         read_w(std::integral_constant<int, 0>{});
-        read_a(0, std::integral_constant<int, 0>{});
+        read_a(std::integral_constant<int, 0>{});
         read_w(std::integral_constant<int, 1>{});
-        read_a(1, std::integral_constant<int, 1>{});
-        if constexpr (TM > 2) read_a(2, std::integral_constant<int, 2>{});
-        if constexpr (TM > 3) read_a(3, std::integral_constant<int, 3>{});
-        if constexpr (TM > 4) read_a(4, std::integral_constant<int, 4>{});
+        read_a(std::integral_constant<int, 1>{});
+        if constexpr (TM > 2) read_a(std::integral_constant<int, 2>{});
+        if constexpr (TM > 3) read_a(std::integral_constant<int, 3>{});
+        if constexpr (TM > 4) read_a(std::integral_constant<int, 4>{});
     };
     auto mfma_step = [&](const bf16x8(&xa)[TM], const bf16x8(&wb)[TN]) {
 #pragma unroll
@@ -239,29 +215,20 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
     };
 
-#ifndef LDIT_TR_DEALT_READS
-    // the hand-over step: a DMA-issuing wave's pieces of tile kt+2 go out in one burst in front of its MFMAs.  -DLDIT_TR_DEAL deals
-    // them between the MFMAs instead, pinned pair by pair (gemm_bf16.hip's arrangement): measured 0.7 % SLOWER in the train step on
-    // one box (profiles/r04_tr_pinned_order_ab.txt), kept for the A/B.  Either way the MFMAs stay outside every branch - an
-    // accumulator written on two paths costs the register allocator a copy of the tile (hundreds of spilled registers).
+    // the hand-over step: a DMA-issuing wave's pieces of tile kt+2 go out in one burst in front of its MFMAs.  Dealing them between
+    // the MFMAs instead, pinned pair by pair (gemm_bf16.hip's arrangement), measured 0.7 % SLOWER in the train step
+    // (profiles/r04_tr_pinned_order_ab.txt).  The MFMAs stay outside the branch - an accumulator written on two paths costs the
+    // register allocator a copy of the tile (hundreds of spilled registers).
     auto mfma_step_dma = [&](const bf16x8(&xa)[TM], const bf16x8(&wb)[TN], int stage, int k0) {
-        constexpr int NM = TM * TN, PPM = (NLW + NM - 1) / NM;
-#ifdef LDIT_TR_DEAL
-        const bool fast = SBASE && k0 + BKB <= p.K;           // block-uniform: every k-tile but a ragged last one
-#else
-        const bool fast = false;
-#endif
-        if (loader && !fast) issue(stage, k0);
+        if (loader) issue(stage, k0);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-                if (loader && fast) issue_sbase(stage, k0, (i * TN + j) * PPM, (i * TN + j + 1) * PPM);
                 __builtin_amdgcn_sched_barrier(0);
             }
     };
-#endif
     bf16x8 xa0[TM], wb0[TN], xa1[TM], wb1[TN];
     // k-tile kt of this block -> its first reduction index (past the end: the last tile again - fetched, never multiplied)
     auto k_of = [&](int kt) { return kbeg + (kt < nk ? kt : nk - 1) * BKB; };
@@ -278,67 +245,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
     constexpr std::integral_constant<int, 2> S2{};
     constexpr std::integral_constant<int, 3> S3{};
     load_frags(0, S0, xa0, wb0);
-#ifdef LDIT_TR_DEALT_READS
-    // Pinned pipeline, gemm_bf16.hip's: a step multiplies the fragments read during the previous step while the next step's are
-    // read - the LDS reads DEALT between the step's first MFMAs (sched_group_barrier), hipcc's own counted lgkmcnt in front of each
-    // MFMA that needs a fragment (it can count: every read is its own instruction, every LDS-DMA is asm and invisible to it).
-    // Rounds 2 - 4a had the transposing reads as asm statements with hand waits: the scheduler sank them behind the MFMAs, right in
-    // front of the wait (profiles/r04_tr_pinned_order_ab.txt); round 4b pinned reads | MFMAs | wait with sched_barrier - the burst
-    // of reads in front of every step's MFMAs (both waves of a SIMD leave the hand-over barrier together) left the k-loop 17 % slower
-    // per k than the forward GEMM's (scripts/tr_fit.py).  THIS build (-DLDIT_TR_DEALT_READS) closes that gap alone - dgrad 70 -> 62e-3
-    // us per k on the 320-row tile, 17.4 -> 16.0e-3 on N = 768 - and LOSES 0.7 - 0.8 % inside the train step on two boxes
-    // (profiles/r04_tr_pinned_order_ab.txt): the burst build stays the default, this one is kept for the A/B.
-    constexpr int SG_MFMA = 0x8, SG_DSR = 0x100;
-    // MFMAs and LDS reads per step; the reads are dealt over the FIRST HALF of the step's MFMAs (the second half covers the latency
-    // of the last ones: the next step's first MFMA needs fragments from the middle of the read order)
-#ifndef LDIT_TR_DEAL_SPAN
-#define LDIT_TR_DEAL_SPAN 2
-#endif
-    constexpr int NM = TM * TN, NR = (TA ? 2 * TM : TM) + 2 * TN, NMD = NM / LDIT_TR_DEAL_SPAN > 0 ? NM / LDIT_TR_DEAL_SPAN : 1, RPM = (NR + NMD - 1) / NMD;
-    auto deal = [&](auto id_c) {
-        constexpr int ID = decltype(id_c)::value;
-#pragma unroll
-        for (int g = 0; g < NM; ++g) {
-            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, ID);
-#pragma unroll
-            for (int r = 0; r < RPM; ++r)
-                if (g * RPM + r < NR) __builtin_amdgcn_sched_group_barrier(SG_DSR, 1, ID);
-        }
-    };
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        __builtin_amdgcn_sched_barrier(0);
-        load_frags(cur, S1, xa1, wb1);
-        mfma_step(xa0, wb0);
-        deal(S0);
-        __builtin_amdgcn_sched_barrier(0);
-        load_frags(cur, S2, xa0, wb0);
-        mfma_step(xa1, wb1);
-        deal(S1);
-        __builtin_amdgcn_sched_barrier(0);
-        load_frags(cur, S3, xa1, wb1);
-        mfma_step(xa0, wb0);
-        deal(S2);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- hand-over: own DMA of tile kt+1 landed (vmcnt 0: the pieces are asm, hipcc does not wait for them), own reads of
-        //      stage cur done (hipcc's lgkmcnt in front of the barrier), then all waves
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // ---- step 3: first fragments of tile kt+1 | the last fragments' MFMAs | DMA of tile kt+2 -> stage cur (free now)
-        //      (the pieces are asm statements with a memory clobber - no LDS read moves across them - so they follow the step's MFMAs
-        //       and reads in program order and go out while the MFMAs drain; they still have three steps to land)
-        load_frags(cur ^ 1, S0, xa0, wb0);
-        mfma_step(xa1, wb1);
-        deal(S3);
-        __builtin_amdgcn_sched_barrier(0);
-        if (loader) issue(cur, k_of(kt + 2));
-    }
-#else
     // Every LDS read of the loop is asm (hipcc would guard the transposing builtin against the in-flight LDS-DMA with vmcnt(0), and
     // would count its own ds_read_b128 against transposing reads it cannot see), so the order is pinned by hand, sched_barrier by
     // sched_barrier: a step ISSUES its reads, then its MFMAs (on the previous step's fragments), then waits for the reads.  Left to
     // the scheduler (rounds 2 - 4a) the reads sank behind the MFMAs, right in front of the wait, and every step exposed a full LDS
-    // latency that only the SIMD partner covered.
+    // latency that only the SIMD partner covered.  The forward GEMM's arrangement - compiler-visible reads dealt between the MFMAs by
+    // sched_group_barrier - took 9 - 12 % less time per k alone (scripts/tr_fit.py) and LOST 0.7 - 0.8 % inside the train step on
+    // two boxes (profiles/r04_tr_pinned_order_ab.txt): this burst order is the one loop of the file.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -373,8 +286,6 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_bf16_tr(cons
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-fetches of the tail must not outlive the LDS allocation
     __syncthreads();                                      // every wave is out of the k-loop: the stage memory becomes slab buffers
 
@@ -414,7 +325,6 @@ int tr_pick(long M, long N, int splits, bool ta)
 {
     const long t256 = (long)splits * ((M + 255) / 256) * ((N + 255) / 256);
     int pick = t256 >= 120 ? 3 : 2;
-#ifndef LDIT_TR_NO_TALL
     if (!ta && pick == 3) {
         double best = (double)((t256 + 255) / 256);
         for (int bm : {192, 320}) {
@@ -423,7 +333,6 @@ int tr_pick(long M, long N, int splits, bool ta)
             if (c < best) { best = c; pick = bm == 192 ? 4 : 5; }
         }
     }
-#endif
     // (wgrad form, round 4: a 256 x 128 eight-wave tile - one workgroup per CU, one DMA-issuing wave per SIMD - is selectable
     //  (LDIT_GEMM_BF16_TR_TILE=6).  Alone it beats the 128 x 128 tiles at the same split counts by 1 - 3 %; inside the train step it
     //  lost 5 % (75.6 vs ~70 us per call: profiles/r04_wgrad_tiles.txt), so two four-wave workgroups per CU stay the choice.)
