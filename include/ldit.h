@@ -829,6 +829,53 @@ int ldit_opt_advance(ldit_opt_state *state, double beta1, double beta2, float gr
 int ldit_adamw_multi_f32(const ldit_opt_segment *segs, int32_t S, const ldit_opt_state *state, double beta1, double beta2, float eps,
                          float weight_decay, float grad_mul, ldit_stream stream);
 
+/* -- global-norm clipping and per-segment hyper-parameters (additive: the three entry points above are unchanged) --
+ * torch.nn.utils.clip_grad_norm_ + AdamW with parameter groups, still without a synchronisation:
+ *   ldit_grads_check_norm_multi_f32 -> ldit_opt_advance -> ldit_clip_finish -> ldit_adamw_groups_multi_f32.
+ *
+ * The clip block (16 bytes of device memory, 4-byte aligned); the caller allocates and initialises it: max_norm = the bound
+ * (a device-side store changes it, no re-capture), the rest 0. */
+typedef struct ldit_clip_state {
+    float max_norm;          /* input: the bound on the global L2 norm of the UNSCALED gradients; +inf = never clip */
+    float total_norm;        /* output of ldit_clip_finish: that norm, of this step's gradients (non-finite on a skipped step) */
+    float clip_coef;         /* output: float(min(1, max_norm / (total_norm + 1e-6))), formed in double; not written on a skipped step */
+    int32_t clipped_steps;   /* unskipped steps whose clip_coef was below 1 */
+} ldit_clip_state;
+
+/* Per-segment hyper-parameters of ldit_adamw_groups_multi_f32 (8 bytes), a HOST array parallel to `segs`. */
+typedef struct ldit_opt_hyper {
+    float lr_scale;          /* the segment's learning rate is state->lr * lr_scale (>= 0) */
+    float weight_decay;      /* >= 0 */
+} ldit_opt_hyper;
+
+/* The number of partial sums ldit_grads_check_norm_multi_f32 writes for these segments: one per 1 024 elements of every segment,
+ * rounded up per segment.  Host arithmetic; -1 (and a message) for a null array, a negative count or a negative length. */
+int64_t ldit_grad_norm_partials(const ldit_opt_segment *segs, int32_t S);
+
+/* ldit_grads_check_multi_f32 and the sum of squares in ONE pass over the gradients.  Blocks and paths are the check's; every
+ * workgroup also writes the sum of g * g over its elements, accumulated in double (a finite fp32 square cannot overflow it), to
+ * partials[k], k counting the workgroups of all launches in segment order.  The reduction order inside a workgroup is fixed (the
+ * lanes of a wave by butterfly, the waves one after another): equal inputs give equal bits.  `partials` is 8-byte aligned device
+ * memory of partials_len doubles; partials_len < ldit_grad_norm_partials(segs, S) is refused before any launch.  A NaN or an
+ * infinity makes its partial non-finite.  No float atomics. */
+int ldit_grads_check_norm_multi_f32(const ldit_opt_segment *segs, int32_t S, ldit_opt_state *state, double *partials, int64_t partials_len,
+                                    ldit_stream stream);
+
+/* One workgroup, AFTER ldit_opt_advance (it reads this step's skip and inv_scale_used): the n partials are summed in double in a
+ * fixed order,  total_norm = float(sqrt(sum) * inv_scale_used)  and, unless the step is skipped,
+ * clip_coef = float(min(1, max_norm / (total_norm + 1e-6))) - torch.nn.utils.clip_grad_norm_'s formula on the two floats, formed
+ * in double and rounded once - and clipped_steps += 1 when clip_coef < 1.  On a skipped step (a NaN or an infinity made the norm
+ * non-finite) only total_norm is written.  n == 0: a norm of 0. */
+int ldit_clip_finish(const ldit_opt_state *state, ldit_clip_state *clip, const double *partials, int64_t n, ldit_stream stream);
+
+/* ldit_adamw_multi_f32 with the learning rate state->lr * hyper[s].lr_scale and the weight decay hyper[s].weight_decay for segment
+ * s, on g = grads * (clip->clip_coef * inv_scale_used), or grads * inv_scale_used when clip is NULL.  lr_scale == 1, equal
+ * weight_decay and clip_coef == 1 give ldit_adamw_multi_f32(grad_mul = 1) bit for bit.  lr_scale == 0 moves m and v and leaves p as
+ * it is (the decay factor is 1 - lr * weight_decay of the SCALED lr, so it is 1 as well).  48 segments per launch (their hyper-parameters
+ * ride beside them in the kernel arguments). */
+int ldit_adamw_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyper *hyper, int32_t S, const ldit_opt_state *state,
+                                const ldit_clip_state *clip, double beta1, double beta2, float eps, ldit_stream stream);
+
 /* ---- COCO box evaluation: matching, accumulation ----
  * The arithmetic of the reference's Evaluator.score() (ref evaluation/evaluator.py:219-286, which hands a JSON file to a per-image,
  * per-category host loop) on padded device tensors: no host round trip, no allocation, no float atomics, capturable, every output a

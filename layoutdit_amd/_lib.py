@@ -56,8 +56,20 @@ class LditOptState(C.Structure):
                 ("bc1", C.c_float), ("bc2_sqrt", C.c_float)]
 
 
+class LditClipState(C.Structure):
+    """Host-side picture of the clipping block (``ldit_clip_state``, 16 bytes): field order and sizes only."""
+    _fields_ = [("max_norm", C.c_float), ("total_norm", C.c_float), ("clip_coef", C.c_float), ("clipped_steps", C.c_int32)]
+
+
+class LditOptHyper(C.Structure):
+    """One segment's hyper-parameters for the grouped update (``ldit_opt_hyper``, 8 bytes)."""
+    _fields_ = [("lr_scale", C.c_float), ("weight_decay", C.c_float)]
+
+
 OPT_STATE_FIELDS = tuple(n for n, _ in LditOptState._fields_)       # index of a field = its 4-byte slot in the block
+CLIP_STATE_FIELDS = tuple(n for n, _ in LditClipState._fields_)
 OPT_MAX_SEGMENTS = 64                                               # segments per launch (csrc/optim_multi.hip)
+OPT_GROUP_SEGMENTS = 48                                             # of the grouped update, whose hyper-parameters ride beside them
 
 # name -> (restype, argtypes); every symbol include/ldit.h declares
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
@@ -165,6 +177,11 @@ SIGNATURES = {
     "ldit_grads_check_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, _vp]),
     "ldit_opt_advance": (C.c_int, [_vp, C.c_double, C.c_double, _f32, _f32, _i32, _vp]),
     "ldit_adamw_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, C.c_double, C.c_double, _f32, _f32, _f32, _vp]),
+    "ldit_grad_norm_partials": (_i64, [C.POINTER(LditOptSegment), _i32]),
+    "ldit_grads_check_norm_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), _i32, _vp, _vp, _i64, _vp]),
+    "ldit_clip_finish": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
+    "ldit_adamw_groups_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), C.POINTER(LditOptHyper), _i32, _vp, _vp, C.c_double, C.c_double, _f32,
+                                              _vp]),
     # COCO box evaluation
     "ldit_coco_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp]),
@@ -228,6 +245,14 @@ def box_loss_workspace_bytes(rows: int) -> int:
 def nms_workspace_bytes(problems: int, n: int) -> int:
     """Scratch bytes ``ldit_nms_batched_f32`` wants for ``problems`` x ``n`` candidates (host arithmetic, no launch)."""
     return int(load().ldit_nms_workspace_bytes(problems, n))
+
+
+def grad_norm_partials(segs, S: int) -> int:
+    """Partial sums ``ldit_grads_check_norm_multi_f32`` writes for a host array of ``S`` segments (host arithmetic, no launch)."""
+    n = int(load().ldit_grad_norm_partials(segs, S))
+    if n < 0:
+        raise LditError(LDIT_EINVAL, load().ldit_last_error().decode(errors="replace"))
+    return n
 
 
 def check(rc: int) -> None:

@@ -10,6 +10,10 @@
 //
 // Three launches, because each needs the one before it complete on the WHOLE parameter set: the update may not touch a single element
 // before every gradient element was seen finite, and the step count / bias corrections / loss scale change once per step, not per block.
+//
+// With global-norm clipping and parameter groups the sequence is check + sum of squares (one pass, one double
+// partial per workgroup), the state machine, ldit_clip_finish (one workgroup: the norm and the clip coefficient into the 16-byte
+// ldit_clip_state) and adamw_groups_multi_kernel: adamw_multi_kernel with a per-segment {lr_scale, weight_decay} beside the table.
 #include "api_internal.h"
 
 namespace ldit {
@@ -30,8 +34,22 @@ struct OptLaunch {
 };
 static_assert(sizeof(OptLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
 
+constexpr int GROUP_SEGS = 48;            // the grouped update: 48 x (48 + 8) bytes + the prefix table, under the same 3584
+struct GroupLaunch {
+    ldit_opt_segment seg[GROUP_SEGS];
+    int first_block[GROUP_SEGS + 1];
+    int n;
+    ldit_opt_hyper hyper[GROUP_SEGS];
+};
+static_assert(sizeof(GroupLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
+
+template <typename T> struct launch_cap;
+template <> struct launch_cap<OptLaunch> { static constexpr int value = OPT_SEGS; };
+template <> struct launch_cap<GroupLaunch> { static constexpr int value = GROUP_SEGS; };
+
 // the segment of this block: the last j with first_block[j] <= blk (every segment in a launch has at least one block)
-__device__ __forceinline__ int find_segment(const OptLaunch &a, int blk)
+template <typename T>
+__device__ __forceinline__ int find_segment(const T &a, int blk)
 {
     int lo = 0, hi = a.n - 1;
     while (lo < hi) {
@@ -78,6 +96,70 @@ __global__ void __launch_bounds__(256) grads_check_kernel(const OptLaunch a, ldi
     if (tid == 0 && flag) atomicOr(&st->found_inf, 1);
 }
 
+// ---- 1b. the same check and, in the same pass, this workgroup's sum of squares -----------------------------------------------------
+// The squares arrive loss-scaled (x 65 536 and more) and a finite fp32 square can overflow fp32, so a thread squares and adds in
+// double.  Lanes of a wave by the butterfly of layernorm.hip's wave_sum, the four waves through LDS one after another by thread 0:
+// a fixed order, so equal inputs give equal bits.  A NaN or an infinity makes the partial non-finite, which ldit_clip_finish passes on.
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ double sq(float x) { return (double)x * (double)x; }
+
+__global__ void __launch_bounds__(256) grads_check_norm_kernel(const OptLaunch a, ldit_opt_state *__restrict__ st, double *__restrict__ partials,
+                                                               int64_t launch_base)
+{
+    __shared__ int flag;
+    __shared__ double wave_part[4];
+    const int tid = threadIdx.x;
+    const int j = find_segment(a, (int)blockIdx.x);
+    const float *g = static_cast<const float *>(a.seg[j].g);
+    const int64_t n = a.seg[j].n;
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    bool bad = false;
+    double ss = 0.0;
+    if (quad_aligned(g)) {
+        const int64_t i = base + 4 * tid;
+        if (i + 4 <= n) {
+            const f32x4 G = *reinterpret_cast<const f32x4 *>(g + i);
+            bad = nonfinite(G[0]) || nonfinite(G[1]) || nonfinite(G[2]) || nonfinite(G[3]);
+            ss = (sq(G[0]) + sq(G[1])) + (sq(G[2]) + sq(G[3]));
+        } else {
+            for (int64_t e = i; e < n; ++e) {
+                const float x = g[e];
+                bad |= nonfinite(x);
+                ss += sq(x);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t e = base + tid + 256 * k;
+            if (e < n) {
+                const float x = g[e];
+                bad |= nonfinite(x);
+                ss += sq(x);
+            }
+        }
+    }
+    ss = wave_sum_f64(ss);
+    const bool wave_bad = __ballot(bad) != 0ull;     // by the whole wave, before the leaders part from it
+    if (tid == 0) flag = 0;
+    __syncthreads();
+    if ((tid & 63) == 0) {
+        wave_part[tid >> 6] = ss;
+        if (wave_bad) flag = 1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        partials[launch_base + blockIdx.x] = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
+        if (flag) atomicOr(&st->found_inf, 1);
+    }
+}
+
 // ---- 2. the state machine of torch.amp.GradScaler.step / update and of the optimizer's step count, one thread ------------------
 __global__ void opt_advance_kernel(ldit_opt_state *__restrict__ st, double b1, double b2, float growth, float backoff, int interval)
 {
@@ -121,26 +203,28 @@ __device__ __forceinline__ void adamw_element(float &P, const float G, float &Mo
     Vo = vo;
 }
 
-__global__ void __launch_bounds__(256) adamw_multi_kernel(const OptLaunch a, const ldit_opt_state *__restrict__ st, float b1, float omb1,
-                                                          float b2, float omb2, float eps, float wd, float grad_mul)
+// the constants of one segment's update from the block; lr is the segment's own learning rate (the block's, times its lr_scale)
+__device__ __forceinline__ AdamwConsts adamw_consts(const ldit_opt_state *__restrict__ st, double lr, float wd, float gs, float b1, float omb1,
+                                                    float b2, float omb2, float eps)
 {
-    if (st->skip) return;                            // a skipped step writes nothing at all
-    const int tid = threadIdx.x;
-    const int j = find_segment(a, (int)blockIdx.x);
-    float *p = static_cast<float *>(a.seg[j].p), *m = static_cast<float *>(a.seg[j].m), *v = static_cast<float *>(a.seg[j].v);
-    const float *g = static_cast<const float *>(a.seg[j].g);
-    bf16_t *mirror = static_cast<bf16_t *>(a.seg[j].bf16_mirror);
-    const int64_t n = a.seg[j].n;
-    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
-    const float lr = st->lr;
     AdamwConsts c;
     c.b1 = b1; c.omb1 = omb1; c.b2 = b2; c.omb2 = omb2; c.eps = eps;
     // lr and bc1 are floats in the block: their quotient is formed in double and rounded once, like torch's lr / (1 - beta1^t) on
     // Python floats - a float division rounds a second time and lands one ulp off that in about half of all cases
-    c.step = (float)((double)lr / (double)st->bc1);
-    c.decay = 1.0f - lr * wd;
+    c.step = (float)(lr / (double)st->bc1);
+    c.decay = 1.0f - (float)lr * wd;
     c.bc2_sqrt = st->bc2_sqrt;
-    c.gs = grad_mul * st->inv_scale_used;
+    c.gs = gs;
+    return c;
+}
+
+// this workgroup's 1024 elements of one segment, from element `base` on
+__device__ __forceinline__ void adamw_block(const ldit_opt_segment &sg, const int64_t base, const int tid, const AdamwConsts &c)
+{
+    float *p = static_cast<float *>(sg.p), *m = static_cast<float *>(sg.m), *v = static_cast<float *>(sg.v);
+    const float *g = static_cast<const float *>(sg.g);
+    bf16_t *mirror = static_cast<bf16_t *>(sg.bf16_mirror);
+    const int64_t n = sg.n;
     const bool vec = quad_aligned(p) && quad_aligned(g) && quad_aligned(m) && quad_aligned(v) &&
                      (reinterpret_cast<uintptr_t>(mirror) & 7u) == 0;
     if (vec) {
@@ -180,6 +264,56 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const OptLaunch a, con
     }
 }
 
+__global__ void __launch_bounds__(256) adamw_multi_kernel(const OptLaunch a, const ldit_opt_state *__restrict__ st, float b1, float omb1,
+                                                          float b2, float omb2, float eps, float wd, float grad_mul)
+{
+    if (st->skip) return;                            // a skipped step writes nothing at all
+    const int j = find_segment(a, (int)blockIdx.x);
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    const AdamwConsts c = adamw_consts(st, (double)st->lr, wd, grad_mul * st->inv_scale_used, b1, omb1, b2, omb2, eps);
+    adamw_block(a.seg[j], base, threadIdx.x, c);
+}
+
+// ---- 3b. the same update with the segment's own {lr_scale, weight_decay} and the clip coefficient in the gradient multiplier -------
+// lr * lr_scale is formed in double and enters the step size unrounded; with lr_scale == 1 it is the block's lr bit for bit, with
+// clip_coef == 1 (or no clip block) the multiplier is inv_scale_used bit for bit: then this IS adamw_multi_kernel(grad_mul = 1).
+__global__ void __launch_bounds__(256) adamw_groups_multi_kernel(const GroupLaunch a, const ldit_opt_state *__restrict__ st,
+                                                                 const ldit_clip_state *__restrict__ clip, float b1, float omb1, float b2,
+                                                                 float omb2, float eps)
+{
+    if (st->skip) return;
+    const int j = find_segment(a, (int)blockIdx.x);
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    const float gs = clip ? clip->clip_coef * st->inv_scale_used : st->inv_scale_used;
+    const AdamwConsts c = adamw_consts(st, (double)st->lr * (double)a.hyper[j].lr_scale, a.hyper[j].weight_decay, gs, b1, omb1, b2, omb2, eps);
+    adamw_block(a.seg[j], base, threadIdx.x, c);
+}
+
+// ---- 2b. the global norm and the clip coefficient, one workgroup, after the state machine ------------------------------------------
+// Thread t adds partials t, t + 256, ... in that order, then a tree over the 256 sums in LDS: a fixed order.
+__global__ void __launch_bounds__(256) clip_finish_kernel(const ldit_opt_state *__restrict__ st, ldit_clip_state *__restrict__ clip,
+                                                          const double *__restrict__ partials, int64_t n)
+{
+    __shared__ double part[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int64_t i = tid; i < n; i += 256) s += partials[i];
+    part[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) part[tid] += part[tid + w];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const float norm = (float)(sqrt(part[0]) * (double)st->inv_scale_used);
+    clip->total_norm = norm;
+    if (st->skip) return;                            // a skipped step: the (non-finite) norm and nothing else
+    // torch.nn.utils.clip_grad_norm_'s formula on the two floats, formed in double and rounded once
+    const float coef = (float)fmin(1.0, (double)clip->max_norm / ((double)norm + 1e-6));
+    clip->clip_coef = coef;
+    if (coef < 1.0f) clip->clipped_steps = clip->clipped_steps + 1;
+}
+
 #define LAUNCH_CHECKED(...)              \
     do {                                 \
         hipLaunchKernelGGL(__VA_ARGS__); \
@@ -208,32 +342,44 @@ int validate(const char *what, const ldit_opt_segment *segs, int32_t S, const vo
     return LDIT_OK;
 }
 
-// the launches of one entry point: segments in order, OPT_SEGS non-empty ones (and at most 2^31 - 1 blocks) per launch
-template <typename F>
+// the launches of one entry point: segments in order, the table's capacity of non-empty ones (and at most 2^31 - 1 blocks) per
+// launch.  launch(a, blocks, first) - `first` the host array's index of every slot of `a`, for what rides beside the segments.
+template <typename T, typename F>
 int for_each_launch(const ldit_opt_segment *segs, int32_t S, F &&launch)
 {
-    OptLaunch a;
+    constexpr int CAP = launch_cap<T>::value;
+    T a;
+    int32_t index[CAP];
     a.n = 0;
     int64_t blocks = 0;
     for (int32_t s = 0; s < S; ++s) {
         if (segs[s].n == 0) continue;
         const int64_t nb = (segs[s].n + OPT_BLOCK_ELEMS - 1) / OPT_BLOCK_ELEMS;
-        if (a.n == OPT_SEGS || blocks + nb > OPT_MAX_BLOCKS) {
+        if (a.n == CAP || blocks + nb > OPT_MAX_BLOCKS) {
             a.first_block[a.n] = (int)blocks;
-            if (int rc = launch(a, (unsigned)blocks)) return rc;
+            if (int rc = launch(a, (unsigned)blocks, index)) return rc;
             a.n = 0;
             blocks = 0;
         }
         a.seg[a.n] = segs[s];
         a.first_block[a.n] = (int)blocks;
+        index[a.n] = s;
         ++a.n;
         blocks += nb;
     }
     if (a.n > 0) {
         a.first_block[a.n] = (int)blocks;
-        if (int rc = launch(a, (unsigned)blocks)) return rc;
+        if (int rc = launch(a, (unsigned)blocks, index)) return rc;
     }
     return LDIT_OK;
+}
+
+// one partial per workgroup of the check, over validated segments
+int64_t count_partials(const ldit_opt_segment *segs, int32_t S)
+{
+    int64_t total = 0;
+    for (int32_t s = 0; s < S; ++s) total += (segs[s].n + OPT_BLOCK_ELEMS - 1) / OPT_BLOCK_ELEMS;
+    return total;
 }
 
 int need_device()
@@ -256,7 +402,7 @@ int ldit_grads_check_multi_f32(const ldit_opt_segment *segs, int32_t S, ldit_opt
     LDIT_TRY(validate("grads_check_multi", segs, S, state, false));
     LDIT_TRY(need_device());
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return for_each_launch(segs, S, [&](const OptLaunch &a, unsigned blocks) -> int {
+    return for_each_launch<OptLaunch>(segs, S, [&](const OptLaunch &a, unsigned blocks, const int32_t *) -> int {
         LAUNCH_CHECKED(grads_check_kernel, dim3(blocks), dim3(256), 0, stream, a, state);
         return LDIT_OK;
     });
@@ -284,8 +430,70 @@ int ldit_adamw_multi_f32(const ldit_opt_segment *segs, int32_t S, const ldit_opt
     const float b1 = (float)beta1, omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
     LDIT_TRY(need_device());
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return for_each_launch(segs, S, [&](const OptLaunch &a, unsigned blocks) -> int {
+    return for_each_launch<OptLaunch>(segs, S, [&](const OptLaunch &a, unsigned blocks, const int32_t *) -> int {
         LAUNCH_CHECKED(adamw_multi_kernel, dim3(blocks), dim3(256), 0, stream, a, state, b1, omb1, b2, omb2, eps, weight_decay, grad_mul);
+        return LDIT_OK;
+    });
+}
+
+int64_t ldit_grad_norm_partials(const ldit_opt_segment *segs, int32_t S)
+{
+    if (S < 0) return fail(LDIT_EINVAL, "grad_norm_partials: negative segment count %d", S), -1;
+    if (S > 0 && !segs) return fail(LDIT_EINVAL, "grad_norm_partials: null segment array"), -1;
+    for (int32_t s = 0; s < S; ++s)
+        if (segs[s].n < 0) return fail(LDIT_EINVAL, "grad_norm_partials: segment %d has negative length %lld", s, (long long)segs[s].n), -1;
+    return count_partials(segs, S);
+}
+
+int ldit_grads_check_norm_multi_f32(const ldit_opt_segment *segs, int32_t S, ldit_opt_state *state, double *partials, int64_t partials_len,
+                                    ldit_stream stream_)
+{
+    LDIT_TRY(validate("grads_check_norm_multi", segs, S, state, false));
+    if (partials_len < 0) return fail(LDIT_EINVAL, "grads_check_norm_multi: negative partials_len %lld", (long long)partials_len);
+    const int64_t need = count_partials(segs, S);
+    if (partials_len < need)
+        return fail(LDIT_EINVAL, "grads_check_norm_multi: %lld partials for segments that need %lld", (long long)partials_len, (long long)need);
+    if (need > 0 && !partials) return fail(LDIT_EINVAL, "grads_check_norm_multi: null partials buffer");
+    if (reinterpret_cast<uintptr_t>(partials) & 7u) return fail(LDIT_EINVAL, "grads_check_norm_multi: partials must be 8-byte aligned");
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int64_t base = 0;
+    return for_each_launch<OptLaunch>(segs, S, [&](const OptLaunch &a, unsigned blocks, const int32_t *) -> int {
+        LAUNCH_CHECKED(grads_check_norm_kernel, dim3(blocks), dim3(256), 0, stream, a, state, partials, base);
+        base += blocks;
+        return LDIT_OK;
+    });
+}
+
+int ldit_clip_finish(const ldit_opt_state *state, ldit_clip_state *clip, const double *partials, int64_t n, ldit_stream stream)
+{
+    if (!state || !aligned4(state)) return fail(LDIT_EINVAL, "clip_finish: null or misaligned state block");
+    if (!clip || !aligned4(clip)) return fail(LDIT_EINVAL, "clip_finish: null or misaligned clip block");
+    if (n < 0) return fail(LDIT_EINVAL, "clip_finish: negative number of partials %lld", (long long)n);
+    if (n > 0 && !partials) return fail(LDIT_EINVAL, "clip_finish: null partials buffer");
+    if (reinterpret_cast<uintptr_t>(partials) & 7u) return fail(LDIT_EINVAL, "clip_finish: partials must be 8-byte aligned");
+    LDIT_TRY(need_device());
+    LAUNCH_CHECKED(clip_finish_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), state, clip, partials, n);
+    return LDIT_OK;
+}
+
+int ldit_adamw_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyper *hyper, int32_t S, const ldit_opt_state *state,
+                                const ldit_clip_state *clip, double beta1, double beta2, float eps, ldit_stream stream_)
+{
+    LDIT_TRY(validate("adamw_groups_multi", segs, S, state, true));
+    if (S > 0 && !hyper) return fail(LDIT_EINVAL, "adamw_groups_multi: null hyper-parameter array");
+    for (int32_t s = 0; s < S; ++s)
+        if (!(hyper[s].lr_scale >= 0.0f) || !(hyper[s].weight_decay >= 0.0f))
+            return fail(LDIT_EINVAL, "adamw_groups_multi: segment %d: lr_scale and weight_decay must be >= 0", s);
+    if (clip && !aligned4(clip)) return fail(LDIT_EINVAL, "adamw_groups_multi: clip block must be 4-byte aligned");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LDIT_EINVAL, "adamw_groups_multi: betas must lie in [0, 1)");
+    const float b1 = (float)beta1, omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return for_each_launch<GroupLaunch>(segs, S, [&](GroupLaunch &a, unsigned blocks, const int32_t *index) -> int {
+        for (int k = 0; k < a.n; ++k) a.hyper[k] = hyper[index[k]];
+        for (int k = a.n; k < GROUP_SEGS; ++k) a.hyper[k] = ldit_opt_hyper{0.0f, 0.0f};
+        LAUNCH_CHECKED(adamw_groups_multi_kernel, dim3(blocks), dim3(256), 0, stream, a, state, clip, b1, omb1, b2, omb2, eps);
         return LDIT_OK;
     });
 }

@@ -10,12 +10,18 @@ rate live in one 40-byte device block (``ldit_opt_state``): between ``backward()
 ``torch.optim.AdamW`` + ``torch.amp.GradScaler`` on the same model launch a group of kernels per parameter tensor and read
 ``found_inf`` back once per iteration.
 
-One parameter group, no gradient clipping, no data parallelism.  PyTorch is plumbing: it owns the memory, the
-stream and autograd's graph; the arithmetic of the update is the library's.
+Optional, and with the same property: ``max_grad_norm`` clips the global gradient norm
+(``torch.nn.utils.clip_grad_norm_``), ``param_groups`` give tensors their own learning-rate scale and weight decay
+(:func:`detector_param_groups`: no decay on biases, norms, LayerScale and the tokens; a layer-wise decayed rate across the encoder),
+``warmup_iters`` ramps the rate up linearly.  The norm, the clip coefficient and the count of clipped steps live in a second,
+16-byte device block (``ldit_clip_state``); one more small launch, one pass over the gradients as before.
+
+No data parallelism.  PyTorch is plumbing: it owns the memory, the stream and autograd's graph; the arithmetic of
+the update is the library's.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -24,6 +30,67 @@ from . import _lib, ops
 _FIELD = {n: i for i, n in enumerate(_lib.OPT_STATE_FIELDS)}
 _INT_FIELDS = ("found_inf", "skip", "step", "growth_tracker", "skipped_steps")
 _FLOAT_FIELDS = ("scale", "inv_scale_used", "lr", "bc1", "bc2_sqrt")
+_CLIP = {n: i for i, n in enumerate(_lib.CLIP_STATE_FIELDS)}
+_ENCODER = "model.backbone.backbone.dit."
+
+
+def warmup_lr(lr: float, it: int, warmup_iters: int, warmup_factor: float) -> float:
+    """The learning rate of iteration ``it`` (0-based): a line from ``lr * warmup_factor`` at 0 to ``lr`` at ``warmup_iters``."""
+    if it >= warmup_iters:
+        return lr
+    return lr * (warmup_factor + (1.0 - warmup_factor) * it / warmup_iters)
+
+
+def resolve_param_groups(model, param_groups: Sequence[dict], weight_decay: float = 0.0) -> Dict[str, Tuple[float, float]]:
+    """``param_groups`` (a list of ``{"params": names or parameters, "lr_scale": float, "weight_decay": float}``) as parameter name ->
+    ``(lr_scale, weight_decay)``; ``weight_decay`` is what a group without one takes.  Refused with a ``ValueError``: a name or a
+    tensor that is no parameter of ``model``, a parameter named twice, a negative value."""
+    by_id = {id(p): n for n, p in model.named_parameters()}
+    names = set(by_id.values())
+    hyper: Dict[str, Tuple[float, float]] = {}
+    for gi, group in enumerate(param_groups):
+        if not isinstance(group, dict) or "params" not in group:
+            raise ValueError(f"param_groups[{gi}] is not a dict with a 'params' entry")
+        scale, wd = float(group.get("lr_scale", 1.0)), float(group.get("weight_decay", weight_decay))
+        if not scale >= 0.0 or not wd >= 0.0:
+            raise ValueError(f"param_groups[{gi}]: negative lr_scale or weight_decay ({scale}, {wd})")
+        members: Iterable[Union[str, torch.Tensor]] = group["params"]
+        if isinstance(members, (str, torch.Tensor)):
+            members = [members]
+        for q in members:
+            name = q if isinstance(q, str) else by_id.get(id(q))
+            if name is None or name not in names:
+                raise ValueError(f"param_groups[{gi}] names an unknown parameter ({q if isinstance(q, str) else 'a tensor'})")
+            if name in hyper:
+                raise ValueError(f"parameter {name} is named in two groups")
+            hyper[name] = (scale, wd)
+    return hyper
+
+
+def detector_param_groups(model, layer_decay: Optional[float] = None, no_decay: bool = True, weight_decay: float = 0.05) -> List[dict]:
+    """The usual groups for fine-tuning a DiT / BEiT backbone under a detector, as ``param_groups`` for :class:`DetectorTrainStep`:
+    lists of parameter NAMES, every parameter of ``model.named_parameters()`` in exactly one.
+
+    ``no_decay``: weight decay 0 for every 1-d parameter (biases, LayerNorm, LayerScale) and for ``cls_token`` and
+    ``position_embeddings``.  ``layer_decay``: inside the encoder ``lr_scale = layer_decay ** (L + 1 - k)`` for layer ``k = 1 .. L``
+    (``encoder.layer.{k - 1}``) and ``k = 0`` for the embeddings; everything else - the rest of the encoder, FPN, RPN, box head - 1."""
+    if layer_decay is not None and not 0.0 < float(layer_decay) <= 1.0:
+        raise ValueError("detector_param_groups: layer_decay must lie in (0, 1]")
+    if not float(weight_decay) >= 0.0:
+        raise ValueError("detector_param_groups: weight_decay must be >= 0")
+    L = model.model.backbone.backbone.dit.config.num_hidden_layers
+    groups: Dict[Tuple[float, float], List[str]] = {}
+    for name, p in model.named_parameters():
+        scale = 1.0
+        if layer_decay is not None and name.startswith(_ENCODER):
+            rest = name[len(_ENCODER):]
+            if rest.startswith("embeddings."):
+                scale = float(layer_decay) ** (L + 1)
+            elif rest.startswith("encoder.layer."):
+                scale = float(layer_decay) ** (L - int(rest.split(".")[2]))
+        plain = no_decay and (p.dim() <= 1 or name.endswith(("cls_token", "position_embeddings")))
+        groups.setdefault((scale, 0.0 if plain else float(weight_decay)), []).append(name)
+    return [{"params": names, "lr_scale": s, "weight_decay": w} for (s, w), names in groups.items()]
 
 
 class DetectorTrainStep:
@@ -31,11 +98,18 @@ class DetectorTrainStep:
     optimizer half alone, on the gradients the parameters currently hold.
 
     ``loss_scaling=False`` keeps the scale at 1 (the loss is not multiplied); a step whose gradients hold a NaN or an infinity is
-    still skipped and counted.  ``step_size=None`` keeps the learning rate constant; otherwise :meth:`epoch_end` is ``StepLR``."""
+    still skipped and counted.  ``step_size=None`` keeps the learning rate constant; otherwise :meth:`epoch_end` is ``StepLR``.
+
+    ``max_grad_norm``: the gradients are multiplied by ``min(1, max_grad_norm / (norm + 1e-6))``, ``norm`` the L2 norm of all unscaled
+    gradients (of the parameters' own elements; nothing else of the encoder's flat block enters).  ``param_groups``: a list of
+    ``{"params": names or parameters, "lr_scale": float, "weight_decay": float}``; a parameter no group names has ``lr_scale`` 1 and
+    the constructor's ``weight_decay``.  ``warmup_iters``: for that many first calls of :meth:`step` the learning rate is
+    :func:`warmup_lr`.  With all four left alone the step is the three launches it always was."""
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 0.0, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  step_size: Optional[int] = None, gamma: float = 0.1, init_scale: float = 65536.0, growth_factor: float = 2.0,
-                 backoff_factor: float = 0.5, growth_interval: int = 2000, loss_scaling: bool = True):
+                 backoff_factor: float = 0.5, growth_interval: int = 2000, loss_scaling: bool = True, max_grad_norm: Optional[float] = None,
+                 param_groups: Optional[Sequence[dict]] = None, warmup_iters: int = 0, warmup_factor: float = 1e-3):
         from .modeling.detector import LayoutDetectionModel
         if not isinstance(model, LayoutDetectionModel):
             raise TypeError("DetectorTrainStep: expected a LayoutDetectionModel (the encoder alone trains with TrainStep)")
@@ -54,7 +128,12 @@ class DetectorTrainStep:
             raise ValueError("DetectorTrainStep: every parameter must live on one GPU (libldit_hip has no CPU path) - call .to(device) first")
         if step_size is not None and int(step_size) < 1:
             raise ValueError("DetectorTrainStep: step_size must be a positive number of epochs")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("DetectorTrainStep: max_grad_norm must be positive (None: no clipping)")
+        if int(warmup_iters) < 0 or not 0.0 <= float(warmup_factor) <= 1.0:
+            raise ValueError("DetectorTrainStep: warmup_iters must be >= 0 and warmup_factor lie in [0, 1]")
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.warmup_iters, self.warmup_factor, self.iters = int(warmup_iters), float(warmup_factor), 0
         self.step_size, self.gamma = None if step_size is None else int(step_size), float(gamma)
         self.loss_scaling = bool(loss_scaling)
         self.growth_factor, self.backoff_factor = (float(growth_factor), float(backoff_factor)) if self.loss_scaling else (1.0, 1.0)
@@ -66,6 +145,16 @@ class DetectorTrainStep:
         self._mom: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}        # parameter name -> (exp_avg, exp_avg_sq)
         self._pending: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}    # loaded moments of parameters not seen yet
         self._enc = None                                                     # (FlatState, flat exp_avg, flat exp_avg_sq)
+        # parameter name -> (lr_scale, weight_decay), or None: one group, the three launches of section 21
+        self._hyper = None if param_groups is None else resolve_param_groups(model, param_groups, self.weight_decay)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip = None if max_grad_norm is None else ops.new_clip_state(self.device, self.max_grad_norm)
+        self._partials: Optional[torch.Tensor] = None                        # one float64 per 1 024 gradient elements, made with the moments
+        self._partials_key = None
+        self._grouped = self._hyper is not None or self._clip is not None
+
+    def _hyper_of(self, name: str) -> Tuple[float, float]:
+        return (1.0, self.weight_decay) if self._hyper is None else self._hyper.get(name, (1.0, self.weight_decay))
 
     # ---- the iteration ----------------------------------------------------------------------------------------------------------------
     def step(self, images: List[torch.Tensor], targets: List[Dict[str, torch.Tensor]],
@@ -74,6 +163,9 @@ class DetectorTrainStep:
         unscaled, detached losses.  From the backward on there is no host synchronisation; the loss scale enters the graph as a device
         tensor.  (The input transform's host bookkeeping is ``model.losses``'s own.)"""
         self._require_train_mode()
+        if self.warmup_iters and self.iters <= self.warmup_iters:           # the last of these fills writes the full rate
+            self._write_lr()
+        self.iters += 1
         for p in self.model.parameters():
             p.grad = None
         losses = self.model.losses(images, targets, generator=generator)
@@ -90,12 +182,34 @@ class DetectorTrainStep:
         state machine, AdamW - or nothing, if the check fired.  No synchronisation; capturable once every moment exists (after one
         eager call).  A replayed graph moves the weights behind this object's back: call :meth:`invalidate_caches` after replays."""
         self._require_train_mode()
-        params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current = self._segments()
-        if params:
-            ops.grads_check_multi(grads, self._state)
-        ops.opt_advance(self._state, self.betas, self.growth_factor, self.backoff_factor, self.growth_interval)
-        if params:
-            ops.adamw_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, self.betas, self.eps, self.weight_decay, 1.0, mirrors)
+        params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current, hyper = self._segments()
+        if not self._grouped:
+            if params:
+                ops.grads_check_multi(grads, self._state)
+            ops.opt_advance(self._state, self.betas, self.growth_factor, self.backoff_factor, self.growth_interval)
+            if params:
+                ops.adamw_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, self.betas, self.eps, self.weight_decay, 1.0, mirrors)
+        else:
+            # check (+ sum of squares) -> state machine -> (norm, clip coefficient) -> update: each needs its predecessor complete
+            # over the WHOLE parameter set, like the three launches above
+            n = 0
+            if self._clip is not None:
+                key = tuple(g.numel() for g in grads)
+                if self._partials is None or key != self._partials_key:
+                    need = max(ops.grad_norm_partials(grads), 1)
+                    if self._partials is None or self._partials.numel() < need:
+                        self._partials = torch.empty(need, dtype=torch.float64, device=self.device)
+                    self._partials_key = key
+                if params:
+                    n = ops.grads_check_norm_multi(grads, self._state, self._partials)
+            elif params:
+                ops.grads_check_multi(grads, self._state)
+            ops.opt_advance(self._state, self.betas, self.growth_factor, self.backoff_factor, self.growth_interval)
+            if self._clip is not None:
+                ops.clip_finish(self._state, self._clip, self._partials, n)
+            if params:
+                ops.adamw_groups_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, [h[0] for h in hyper], [h[1] for h in hyper],
+                                       self._clip, self.betas, self.eps, mirrors)
         self.invalidate_caches(_mirror_current=current)
 
     def invalidate_caches(self, _mirror_current: bool = False) -> None:
@@ -132,7 +246,11 @@ class DetectorTrainStep:
         self.epochs += 1
         if self.step_size is not None and self.epochs % self.step_size == 0:
             self.lr *= self.gamma
-            self._state_f[_FIELD["lr"]].fill_(self.lr)
+            self._write_lr()
+
+    def _write_lr(self) -> None:
+        """The learning rate of the next iteration into the device block (a fill: no synchronisation)."""
+        self._state_f[_FIELD["lr"]].fill_(warmup_lr(self.lr, self.iters, self.warmup_iters, self.warmup_factor))
 
     # ---- segments -----------------------------------------------------------------------------------------------------------------------
     def _require_train_mode(self) -> None:
@@ -176,26 +294,47 @@ class DetectorTrainStep:
     def _segments(self):
         """Lists of (param, grad, exp_avg, exp_avg_sq, mirror) over every parameter that holds a gradient, the encoder's flat state
         (or None) and whether its training mirror is current.  At the position table's own grid, with the gradients autograd's views
-        of one flat block, the whole encoder is a single segment with its bf16 mirror attached."""
+        of one flat block, the whole encoder is a single segment with its bf16 mirror attached.
+
+        With clipping or groups (``hyper``: one ``(lr_scale, weight_decay)`` per segment, else None) the block never enters whole: the
+        gradient block is ``torch.empty_like`` and the backward promises the named slots only, so the key-bias third of every layer
+        (no parameter: BEiT's key has no bias) may hold whatever the allocator left, which a norm must not see.  The encoder then
+        enters as runs of neighbouring named slots with equal hyper-parameters, mirror slices at the matching offsets: the norm
+        covers the parameters' own elements and nothing else."""
         params, grads, exp_avgs, exp_avg_sqs, mirrors = [], [], [], [], []
+        hyper = [] if self._grouped else None
         st = getattr(self.encoder, "_flat_state", None)
         if st is not None and not st.intact():
             st = None                                     # re-homed since (.to() / assign): plain parameters until the next forward
-        in_flat, current = {}, False
+        in_flat, current, taken = {}, False, set()
         if st is not None:
             self._bind_encoder(st)
             in_flat = {id(p): (off, p) for _, p, off, _ in st.named}
             current = not st._dirty and st._packed_version == st.version()
             mirror = st.packed[: 2 * st.numel].view(torch.bfloat16)
             g = st.grads
-            whole = st.native and g.dtype == torch.float32 and g.is_contiguous() and all(
+            whole = not self._grouped and st.native and g.dtype == torch.float32 and g.is_contiguous() and all(
                 p.grad is not None and p.grad.dtype == torch.float32 and p.grad.data_ptr() == g.data_ptr() + 4 * off for off, p in in_flat.values())
             if whole:
                 params.append(st.params), grads.append(g), exp_avgs.append(self._enc[1]), exp_avg_sqs.append(self._enc[2]), mirrors.append(mirror)
+            elif self._grouped and g.dtype == torch.float32 and g.is_contiguous():
+                runs = []                                 # [first offset, end offset, (lr_scale, weight_decay)] over slots whose gradient is autograd's view
+                for off, p in sorted(in_flat.values(), key=lambda e: e[0]):
+                    if p.grad is None or p.grad.dtype != torch.float32 or p.grad.data_ptr() != g.data_ptr() + 4 * off:
+                        continue
+                    h = self._hyper_of(self._names[id(p)])
+                    if runs and runs[-1][1] == off and runs[-1][2] == h:
+                        runs[-1][1] = off + p.numel()
+                    else:
+                        runs.append([off, off + p.numel(), h])
+                    taken.add(id(p))
+                for a, b, h in runs:
+                    params.append(st.params[a:b]), grads.append(g[a:b]), exp_avgs.append(self._enc[1][a:b]), exp_avg_sqs.append(self._enc[2][a:b])
+                    mirrors.append(mirror[a:b]), hyper.append(h)
         else:
             whole = False
         for name, p in self.model.named_parameters():
-            if p.grad is None or (whole and id(p) in in_flat):
+            if p.grad is None or (whole and id(p) in in_flat) or id(p) in taken:
                 continue
             g = p.grad
             if g.dtype != torch.float32 or g.device != p.device:
@@ -207,7 +346,9 @@ class DetectorTrainStep:
                 mirrors.append(mirror[off: off + p.numel()])
             else:
                 mirrors.append(None)
-        return params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current
+            if hyper is not None:
+                hyper.append(self._hyper_of(name))
+        return params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current, hyper
 
     # ---- state ------------------------------------------------------------------------------------------------------------------------------
     def _read_state(self) -> Dict[str, float]:
@@ -232,13 +373,32 @@ class DetectorTrainStep:
         """Steps skipped because a gradient was not finite.  Synchronises."""
         return self._read_state()["skipped_steps"]
 
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """The global L2 norm of the last step's unscaled gradients, before clipping: a 0-dim view of the device block (no
+        synchronisation; non-finite after a skipped step).  Needs ``max_grad_norm``."""
+        if self._clip is None:
+            raise RuntimeError("DetectorTrainStep.grad_norm: built without max_grad_norm, no norm is formed")
+        return self._clip[_CLIP["total_norm"]]
+
+    @property
+    def clipped_steps(self) -> int:
+        """Steps taken whose clip coefficient was below 1.  Synchronises."""
+        if self._clip is None:
+            raise RuntimeError("DetectorTrainStep.clipped_steps: built without max_grad_norm")
+        return int(self._clip.cpu().view(torch.int32)[_CLIP["clipped_steps"]])
+
     def state_dict(self) -> dict:
         """Everything a resumed run needs: the device block's fields, both moments keyed by the model's parameter names, the host-side
         schedule.  Synchronises."""
         moments = {n: (m.detach().clone(), v.detach().clone()) for n, (m, v) in self._mom.items()}
         moments.update({n: (m.clone(), v.clone()) for n, (m, v) in self._pending.items() if n not in moments})
-        return {"state": self._read_state(), "exp_avg": {n: mv[0] for n, mv in moments.items()},
-                "exp_avg_sq": {n: mv[1] for n, mv in moments.items()}, "lr": self.lr, "epochs": self.epochs}
+        out = {"state": self._read_state(), "exp_avg": {n: mv[0] for n, mv in moments.items()},
+               "exp_avg_sq": {n: mv[1] for n, mv in moments.items()}, "lr": self.lr, "epochs": self.epochs, "iters": self.iters}
+        if self._clip is not None:
+            host = self._clip.cpu()
+            out["clip"] = {n: (int(host.view(torch.int32)[i]) if n == "clipped_steps" else float(host[i])) for n, i in _CLIP.items()}
+        return out
 
     def load_state_dict(self, sd: dict) -> None:
         names = set(self._names.values())
@@ -253,6 +413,16 @@ class DetectorTrainStep:
             hf[_FIELD[n]] = float(sd["state"][n])
         self._state.copy_(host)
         self.lr, self.epochs = float(sd["lr"]), int(sd["epochs"])
+        # a dictionary written before warmup existed has no count: every apply() was one iteration, taken or skipped
+        self.iters = int(sd["iters"]) if "iters" in sd else int(sd["state"]["step"]) + int(sd["state"]["skipped_steps"])
+        if self._clip is not None and "clip" in sd:
+            host = torch.zeros(len(_CLIP), dtype=torch.float32)
+            for n, i in _CLIP.items():
+                if n == "clipped_steps":
+                    host.view(torch.int32)[i] = int(sd["clip"][n])
+                else:
+                    host[i] = float(sd["clip"][n])
+            self._clip.copy_(host)
         self._pending = {n: (sd["exp_avg"][n].detach().to(self.device, torch.float32), sd["exp_avg_sq"][n].detach().to(self.device, torch.float32))
                          for n in sd["exp_avg"]}
         with torch.no_grad():

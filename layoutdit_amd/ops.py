@@ -1205,6 +1205,87 @@ def adamw_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], e
             float(weight_decay), float(grad_mul))
 
 
+# -- global-norm clipping and per-segment hyper-parameters: check + norm -> opt_advance -> clip_finish -> adamw_groups_multi --
+OPT_GROUP_SEGMENTS = _lib.OPT_GROUP_SEGMENTS
+
+
+def new_clip_state(device, max_norm: float = float("inf")) -> torch.Tensor:
+    """A fresh ``ldit_clip_state`` block on ``device`` as a float32 tensor of four 4-byte slots in ``_lib.CLIP_STATE_FIELDS`` order
+    (``clipped_steps`` is read through ``.view(torch.int32)``): ``max_norm`` as given, everything else zero."""
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("max_norm must be positive")
+    host = torch.zeros(len(_lib.CLIP_STATE_FIELDS), dtype=torch.float32)
+    host[_lib.CLIP_STATE_FIELDS.index("max_norm")] = max_norm
+    return host.to(device)
+
+
+def _req_clip_state(clip: torch.Tensor) -> torch.Tensor:
+    if not isinstance(clip, torch.Tensor) or clip.dtype != torch.float32 or clip.numel() != len(_lib.CLIP_STATE_FIELDS) or not clip.is_contiguous():
+        raise ValueError(f"clip: expected the contiguous float32 block of {len(_lib.CLIP_STATE_FIELDS)} slots that new_clip_state makes")
+    return clip
+
+
+def _req_partials(partials: torch.Tensor) -> torch.Tensor:
+    if not isinstance(partials, torch.Tensor) or partials.dtype != torch.float64 or partials.dim() != 1 or not partials.is_contiguous():
+        raise ValueError("partials: expected a contiguous 1-d float64 tensor")
+    return partials
+
+
+def grad_norm_partials(grads: Sequence[torch.Tensor]) -> int:
+    """The number of float64 partial sums ``grads_check_norm_multi`` writes for these tensors (host arithmetic, no launch)."""
+    segs, S, _ = _opt_segments(None, grads, None, None, None)
+    return _lib.grad_norm_partials(segs, S)
+
+
+def grads_check_norm_multi(grads: Sequence[torch.Tensor], state: torch.Tensor, partials: torch.Tensor) -> int:
+    """``grads_check_multi`` and, in the same pass, one float64 sum of squares per 1 024 elements of every tensor into the front of
+    ``partials``.  Returns how many were written (what ``clip_finish`` is to be given).  No synchronisation."""
+    lib = _lib.load()
+    state, partials = _req_opt_state(state), _req_partials(partials)
+    segs, S, used = _opt_segments(None, grads, None, None, None)
+    need = _lib.grad_norm_partials(segs, S)
+    if partials.numel() < need:
+        raise ValueError(f"partials: {partials.numel()} elements, these gradients need {need}")
+    _launch(_device(state, partials, *used), lib.ldit_grads_check_norm_multi_f32, segs, S, _ptr(state), _ptr(partials), partials.numel())
+    return need
+
+
+def clip_finish(state: torch.Tensor, clip: torch.Tensor, partials: torch.Tensor, n: int) -> None:
+    """After ``opt_advance``: ``clip.total_norm`` = the global L2 norm of the unscaled gradients from the first ``n`` partials and,
+    unless the step is skipped, ``clip.clip_coef = min(1, max_norm / (total_norm + 1e-6))``.  One workgroup, no synchronisation."""
+    lib = _lib.load()
+    state, clip, partials = _req_opt_state(state), _req_clip_state(clip), _req_partials(partials)
+    n = int(n)
+    if n < 0 or n > partials.numel():
+        raise ValueError(f"n = {n} partials of a buffer of {partials.numel()}")
+    _launch(_device(state, clip, partials), lib.ldit_clip_finish, _ptr(state), _ptr(clip), _ptr(partials), n)
+
+
+def adamw_groups_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+                       exp_avg_sqs: Sequence[torch.Tensor], state: torch.Tensor, lr_scales: Sequence[float], weight_decays: Sequence[float],
+                       clip: Optional[torch.Tensor] = None, betas=(0.9, 0.999), eps: float = 1e-8,
+                       mirrors: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """``adamw_multi`` with the learning rate ``state.lr * lr_scales[i]`` and the weight decay ``weight_decays[i]`` for tensor ``i``, on
+    gradients multiplied by ``clip.clip_coef`` as well (``clip`` None: by the inverse loss scale alone), in
+    ``ceil(S / OPT_GROUP_SEGMENTS)`` launches.  No synchronisation."""
+    lib = _lib.load()
+    state = _req_opt_state(state)
+    if clip is not None:
+        clip = _req_clip_state(clip)
+    segs, S, used = _opt_segments(params, grads, exp_avgs, exp_avg_sqs, mirrors)
+    lr_scales, weight_decays = [float(x) for x in lr_scales], [float(x) for x in weight_decays]
+    if len(lr_scales) != S or len(weight_decays) != S:
+        raise ValueError(f"lr_scales / weight_decays: {len(lr_scales)} / {len(weight_decays)} entries for {S} segments")
+    hyper = (_lib.LditOptHyper * max(S, 1))()
+    for i, (h, s, w) in enumerate(zip(hyper, lr_scales, weight_decays)):
+        if not s >= 0.0 or not w >= 0.0:
+            raise ValueError(f"segment {i}: lr_scale and weight_decay must be >= 0")
+        h.lr_scale, h.weight_decay = s, w
+    _launch(_device(state, clip, *used), lib.ldit_adamw_groups_multi_f32, segs, hyper, S, _ptr(state), _ptr(clip), float(betas[0]),
+            float(betas[1]), float(eps))
+
+
 # ---- COCO box evaluation (include/ldit.h "COCO box evaluation"; csrc/coco_eval.hip) -----------------------------------------------------
 COCO_MAX_DETS, COCO_MAX_GT, COCO_MAX_CLASSES = 128, 128, 64      # per image: detection slots, GT boxes; categories
 COCO_MAX_SLOTS = 1 << 24                                         # capacity * slots per image the total-order key has room for

@@ -462,4 +462,4 @@ class TrainStep:
         return taps
 
 
-from .detector_training import DetectorTrainStep  # noqa: E402,F401  (the whole detector's step, next to the encoder's)
+from .detector_training import DetectorTrainStep, detector_param_groups  # noqa: E402,F401  (the whole detector's step, next to the encoder's)
