@@ -416,6 +416,26 @@ int ldit_colsum_f32(const void *x, int64_t M, int64_t N, int64_t ldx, void *out,
 /* out[n] = max_m |x[m * ldx + n]|: per-channel activation ranges for the fp8 build's calibration (the SmoothQuant-style fold of
  * DiTEncoder.calibrate_fp8: per-channel factors move LayerNorm-output outliers into the next GEMM's weight columns). Same scratch. */
 int ldit_colamax_f32(const void *x, int64_t M, int64_t N, int64_t ldx, void *out, void *scratch, size_t scratch_bytes, ldit_stream stream);
+/* What stands between two layers of the detector's backward under grad_dtype="bf16", in one pass over dy (and act): the ReLU's
+ * backward, the bf16 copy that the dgrad and the wgrad GEMM both read, and the bias gradient.  With w = (act > 0 ? dy : 0) - a
+ * SELECTION (torch's threshold_backward): a non-finite dy under a masked position gives 0, and act = +0, -0 or NaN masks -
+ *   out    = bf16(w), ldit_cast_f32_bf16's conversion (to nearest even, non-finite kept)
+ *   colsum = the column sums of w, bit for bit ldit_colsum_f32 on w (its device code: 512-row blocks, four accumulators per
+ *            block, sequential second stage; no atomics)
+ * act NULL: w = dy.  colsum NULL: no sums, scratch unused (may be NULL); else scratch: ldit_colsum_scratch_bytes(M, N) bytes.
+ * Nothing is allocated; capturable; bit-reproducible.
+ *   ldit_relu_bwd_bf16:          dy, act fp32 [M, N], out bf16 [M, N], row strides lddy, ldact, ldout >= N elements, any M, N >= 1
+ *                                (four columns per thread where N, the strides and the addresses allow, else one).
+ *   ldit_relu_bwd_pad_nhwc_bf16: dy, act fp32 [B, H, W, C], out bf16 [B, H+2, W+2, C] = the zero-padded map that
+ *                                ldit_pad_nhwc_f32_bf16 writes for w (every element written, border included), colsum over
+ *                                the M = B*H*W pixel rows; C % 4 == 0.
+ * LDIT_EINVAL: null dy / out, colsum without scratch, empty problem, a stride below N, C % 4, misaligned operand (plain form:
+ * the element size; padded form: 16 bytes, out 8).  LDIT_EWORKSPACE: scratch too small.  LDIT_EUNSUPPORTED: 2^31 rows or
+ * columns or more, a padded map of 2^33 elements or more. */
+int ldit_relu_bwd_bf16(const void *dy, int64_t lddy, const void *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                       void *colsum, void *scratch, size_t scratch_bytes, ldit_stream stream);
+int ldit_relu_bwd_pad_nhwc_bf16(const void *dy, const void *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, void *colsum,
+                                void *scratch, size_t scratch_bytes, ldit_stream stream);
 
 /* ==== train step (BASELINE.json configs[2]: ViT-B/16 bs=64 bf16 forward + backward + AdamW) =============
  * Replaces, for the encoder, what the reference's loop runs through torch.autograd and torch.optim:

@@ -9,7 +9,9 @@
 //   laterals                    = ldit_linear_f32 (dgrad, on the transposed weight) / the same bf16 wgrad form
 // Here:  (1) the adjoint of fpn_merge_nhwc (misc.hip): bilinear rescale of the lateral tokens + nearest top-down add,
 //        (2) fp32 NHWC -> zero-padded bf16 NHWC copies for (wgrad),
-//        (3) column sums (bias gradients), two stages, fixed order - no atomics anywhere, every result bit-reproducible.
+//        (3) column sums (bias gradients), two stages, fixed order - no atomics anywhere, every result bit-reproducible,
+//        (4) for grad_dtype="bf16" of the detector: a ReLU's backward, (2) or the plain bf16 copy, and stage 1 of (3) as one pass
+//            over dy and the activation - the copy is the operand of the layer's dgrad AND wgrad GEMM.
 #include "ldit_common.h"
 
 namespace ldit {
@@ -128,7 +130,45 @@ __global__ void __launch_bounds__(256) pad_nhwc_bf16(const float *__restrict__ s
 constexpr int CS_ROWS = 512;
 
 // ABSMAX = false: column sums; true: column maxima of |x| (fp8 calibration: per-channel activation ranges)
-template <bool ABSMAX> __device__ __forceinline__ float cs_op(float acc, float v) { return ABSMAX ? fmaxf(acc, fabsf(v)) : acc + v; }
+template <bool ABSMAX, typename T> __device__ __forceinline__ T cs_op(T acc, T v)
+{
+    if constexpr (ABSMAX) return fmaxf(acc, fabsf(v));
+    else return acc + v;
+}
+
+// R consecutive rows from m on (R a multiple of 4, or 1): their terms into the four accumulators in row order - row m + r into
+// s[r % 4] - with all R loads issued before the first store
+template <bool ABSMAX, int R, typename T, typename Row, typename Sink> __device__ __forceinline__ void cs_rows(Row row, Sink sink, long m, T (&s)[4])
+{
+    T v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = row(m + r);
+#pragma unroll
+    for (int r = 0; r < R; ++r) sink(m + r, v[r]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) s[r & 3] = cs_op<ABSMAX>(s[r & 3], v[r]);
+}
+
+// One row block of a column sum, in the ONE order every column sum of this file has.  `row(m)` is called once per row m of
+// [m0, m1), ascending, and yields that row's term - of one column (T = float) or of four adjacent ones (T = f32x4, each component
+// its own column); `sink(m, term)` follows it for whoever also wants the term stored.  Four accumulators take rows m0 + 4 i + j
+// (j = 0..3), the rows left over at the end go to the first, and the block's sum is (s0 + s1) + (s2 + s3): a fixed function of
+// (M, row block).  U groups of four rows are in flight at a time - U moves loads, never a sum.
+template <bool ABSMAX, int U, typename T, typename Row, typename Sink> __device__ __forceinline__ T cs_block(Row row, Sink sink, long m0, long m1)
+{
+    T s[4] = {};
+    long m = m0;
+    if constexpr (U > 1)
+        for (; m + 4 * U - 1 < m1; m += 4 * U) cs_rows<ABSMAX, 4 * U>(row, sink, m, s);
+    for (; m + 3 < m1; m += 4) cs_rows<ABSMAX, 4>(row, sink, m, s);
+    for (; m < m1; ++m) {
+        const T v = row(m);
+        sink(m, v);
+        s[0] = cs_op<ABSMAX>(s[0], v);
+    }
+    if constexpr (ABSMAX) return fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+    else return (s[0] + s[1]) + (s[2] + s[3]);
+}
 
 // stage 1: part[blockIdx.x][n] = sum of rows [blockIdx.x * CS_ROWS, +CS_ROWS) of x[:, n]; a thread owns a column
 template <bool ABSMAX>
@@ -137,16 +177,82 @@ __global__ void __launch_bounds__(256) colsum_stage1(const float *__restrict__ x
     const int n = blockIdx.y * 256 + threadIdx.x;
     if (n >= N) return;
     const long m0 = (long)blockIdx.x * CS_ROWS, m1 = m0 + CS_ROWS < M ? m0 + CS_ROWS : M;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    long m = m0;
-    for (; m + 3 < m1; m += 4) {             // four rows in flight; the summation order is a fixed function of (M, row block)
-        s0 = cs_op<ABSMAX>(s0, x[m * ld + n]);
-        s1 = cs_op<ABSMAX>(s1, x[(m + 1) * ld + n]);
-        s2 = cs_op<ABSMAX>(s2, x[(m + 2) * ld + n]);
-        s3 = cs_op<ABSMAX>(s3, x[(m + 3) * ld + n]);
+    part[(long)blockIdx.x * N + n] = cs_block<ABSMAX, 1, float>([&](long m) { return x[m * ld + n]; }, [](long, float) {}, m0, m1);
+}
+
+// ---- ReLU backward + bf16 copy + stage 1 of the column sum, one pass over dy and act (grad_dtype="bf16" of the detector) ----------
+constexpr int RB_GROUPS = 4;                                         // 16 rows of dy (and act) in flight per thread
+template <int V> struct cols_t { typedef float f; };                 // the V adjacent columns of a thread
+template <> struct cols_t<4> { typedef f32x4 f; };
+
+// w = act > 0 ? dy : 0 - a selection (threshold_backward): a masked non-finite dy is 0, act = +-0 or NaN masks.  ACT = false: w = dy
+template <int V, bool ACT> __device__ __forceinline__ typename cols_t<V>::f relu_bwd_load(const float *__restrict__ dy, const float *__restrict__ act)
+{
+    typedef typename cols_t<V>::f F;
+    F v = *reinterpret_cast<const F *>(dy);
+    if constexpr (ACT) {
+        const F a = *reinterpret_cast<const F *>(act);
+        if constexpr (V == 4) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = a[e] > 0.f ? v[e] : 0.f;
+        } else {
+            v = a > 0.f ? v : 0.f;
+        }
     }
-    for (; m < m1; ++m) s0 = cs_op<ABSMAX>(s0, x[m * ld + n]);
-    part[(long)blockIdx.x * N + n] = ABSMAX ? fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)) : (s0 + s1) + (s2 + s3);
+    return v;
+}
+
+template <int V> __device__ __forceinline__ void store_bf16(__bf16 *__restrict__ dst, typename cols_t<V>::f v)
+{
+    if constexpr (V == 4) *reinterpret_cast<bf16x4_t *>(dst) = bf16x4_t{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+    else *dst = (__bf16)v;
+}
+
+// out[m, n] = bf16(w[m, n]); part[blockIdx.x][n] (part != nullptr) = colsum_stage1's partial of w: the grid of colsum_stage1 with V
+// columns per thread and blockDim.x threads per block
+template <int V, bool ACT>
+__global__ void __launch_bounds__(256) relu_bwd_bf16(const float *__restrict__ dy, const float *__restrict__ act, __bf16 *__restrict__ out,
+                                                     float *__restrict__ part, long M, int N, long lddy, long ldact, long ldout)
+{
+    typedef typename cols_t<V>::f F;
+    const long n = ((long)blockIdx.y * blockDim.x + threadIdx.x) * V;
+    if (n >= N) return;
+    const long m0 = (long)blockIdx.x * CS_ROWS, m1 = m0 + CS_ROWS < M ? m0 + CS_ROWS : M;
+    const F s = cs_block<false, RB_GROUPS, F>([&](long m) { return relu_bwd_load<V, ACT>(dy + m * lddy + n, act + m * ldact + n); },
+                                   [&](long m, F v) { store_bf16<V>(out + m * ldout + n, v); }, m0, m1);
+    if (part) *reinterpret_cast<F *>(part + (long)blockIdx.x * N + n) = s;
+}
+
+// The same into the zero-padded map of pad_nhwc_bf16, out bf16 [B, H+2, W+2, C]: row m = (b, y, x) of dy lands on pixel
+// (b, y+1, x+1), and the thread that writes an interior pixel at the map's edge also writes the border pixels beside it (a corner
+// goes with the corner pixel) - every element of out is written exactly once.
+template <bool ACT>
+__global__ void __launch_bounds__(256) relu_bwd_pad_nhwc_bf16(const float *__restrict__ dy, const float *__restrict__ act,
+                                                              __bf16 *__restrict__ out, float *__restrict__ part, int M, int H, int W, int C)
+{
+    const int c = (blockIdx.y * blockDim.x + threadIdx.x) * 4;
+    if (c >= C) return;
+    const long m0 = (long)blockIdx.x * CS_ROWS, m1 = m0 + CS_ROWS < M ? m0 + CS_ROWS : (long)M;
+    const long rs = (long)(W + 2) * C;                               // one padded row
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 s = cs_block<false, RB_GROUPS, f32x4>([&](long m) { return relu_bwd_load<4, ACT>(dy + m * C + c, act + m * C + c); },
+                                           [&](long m, f32x4 v) {
+        const int x = (int)m % W, t = (int)m / W, y = t % H, b = t / H;                   // (uniform over the workgroup)
+        __bf16 *o = out + (((long)b * (H + 2) + y + 1) * (W + 2) + x + 1) * C + c;
+        store_bf16<4>(o, v);
+        if (x == 0) store_bf16<4>(o - C, zero);
+        if (x == W - 1) store_bf16<4>(o + C, zero);
+        if (y == 0) {
+            store_bf16<4>(o - rs, zero);
+            if (x == 0) store_bf16<4>(o - rs - C, zero);
+            if (x == W - 1) store_bf16<4>(o - rs + C, zero);
+        }
+        if (y == H - 1) {
+            store_bf16<4>(o + rs, zero);
+            if (x == 0) store_bf16<4>(o + rs - C, zero);
+            if (x == W - 1) store_bf16<4>(o + rs + C, zero);
+        } }, m0, m1);
+    if (part) *reinterpret_cast<f32x4 *>(part + (long)blockIdx.x * C + c) = s;
 }
 
 template <bool ABSMAX>
@@ -217,6 +323,65 @@ int launch_colsum_f32(const float *x, int64_t M, int N, int64_t ld, float *out, 
     }
     LDIT_HIP_CHECK(hipGetLastError());
     return LDIT_OK;
+}
+
+// threads per block for `cols` column groups: whole waves, at most 256
+static unsigned relu_bwd_threads(long cols) { return cols > 128 ? 256u : cols > 64 ? 128u : 64u; }
+
+static int relu_bwd_stage2(float *colsum, float *scratch, int64_t M, int N, hipStream_t stream)
+{
+    if (colsum) hipLaunchKernelGGL(colsum_stage2<false>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, scratch, colsum,
+                                   (int)((M + CS_ROWS - 1) / CS_ROWS), N);
+    LDIT_HIP_CHECK(hipGetLastError());
+    return LDIT_OK;
+}
+
+int launch_relu_bwd_bf16(const float *dy, int64_t lddy, const float *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                         float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    if (M <= 0 || N <= 0 || lddy < N || ldout < N || (act && ldact < N)) return fail(LDIT_EINVAL, "relu_bwd_bf16: bad geometry");
+    if (!dy || !out || (colsum && !scratch)) return fail(LDIT_EINVAL, "relu_bwd_bf16: null operand");
+    const auto addr = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((addr(dy) & 3u) || (addr(act) & 3u) || (addr(out) & 1u) || (addr(colsum) & 3u) || (addr(scratch) & 3u))
+        return fail(LDIT_EINVAL, "relu_bwd_bf16: misaligned operand");
+    if (M >= (1ll << 31) || N >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "relu_bwd_bf16: 2^31 rows or columns or more");
+    if (colsum && scratch_bytes < colsum_scratch_bytes(M, N))
+        return fail(LDIT_EWORKSPACE, "relu_bwd_bf16: scratch %zu bytes < required %zu", scratch_bytes, colsum_scratch_bytes(M, N));
+    const unsigned P = (unsigned)((M + CS_ROWS - 1) / CS_ROWS);
+    float *part = colsum ? scratch : nullptr;
+    __bf16 *o = static_cast<__bf16 *>(out);
+    // four columns per thread where every row of every operand starts on a vector boundary
+    const bool vec = !(N & 3) && !(lddy & 3) && !(ldout & 3) && (!act || !(ldact & 3)) && aligned16(dy) && (!act || aligned16(act)) &&
+                     !(addr(out) & 7u) && (!part || aligned16(part));
+    const int64_t cols = vec ? N / 4 : N;
+    const unsigned th = relu_bwd_threads(cols);
+    const dim3 grid(P, (unsigned)((cols + th - 1) / th));
+    if (grid.y > 65535u) return fail(LDIT_EUNSUPPORTED, "relu_bwd_bf16: too many columns");
+    auto kernel = vec ? (act ? relu_bwd_bf16<4, true> : relu_bwd_bf16<4, false>) : (act ? relu_bwd_bf16<1, true> : relu_bwd_bf16<1, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(th), 0, stream, dy, act, o, part, (long)M, (int)N, (long)lddy, (long)ldact, (long)ldout);
+    return relu_bwd_stage2(colsum, scratch, M, (int)N, stream);
+}
+
+int launch_relu_bwd_pad_nhwc_bf16(const float *dy, const float *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, float *colsum,
+                                  float *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return fail(LDIT_EINVAL, "relu_bwd_pad_nhwc_bf16: bad geometry");
+    if (!dy || !out || (colsum && !scratch)) return fail(LDIT_EINVAL, "relu_bwd_pad_nhwc_bf16: null operand");
+    if (!aligned16(dy) || (act && !aligned16(act)) || (reinterpret_cast<uintptr_t>(out) & 7u) || (colsum && (!aligned16(scratch) || (reinterpret_cast<uintptr_t>(colsum) & 3u))))
+        return fail(LDIT_EINVAL, "relu_bwd_pad_nhwc_bf16: misaligned operand");
+    const int64_t lim = 1ll << 31;
+    // (each factor first: the products below stay inside 64 bits)
+    if (B >= lim || H >= lim || W >= lim || C >= lim || B * H >= lim || B * H * W >= lim || (B * (H + 2)) * (W + 2) >= lim ||
+        (B * (H + 2)) * (W + 2) * C >= (1ll << 33))
+        return fail(LDIT_EUNSUPPORTED, "relu_bwd_pad_nhwc_bf16: 2^31 pixel rows or a padded map of 2^33 elements or more");
+    const int64_t M = B * H * W;
+    if (colsum && scratch_bytes < colsum_scratch_bytes(M, C))
+        return fail(LDIT_EWORKSPACE, "relu_bwd_pad_nhwc_bf16: scratch %zu bytes < required %zu", scratch_bytes, colsum_scratch_bytes(M, C));
+    const unsigned P = (unsigned)((M + CS_ROWS - 1) / CS_ROWS), th = relu_bwd_threads(C / 4);
+    if ((C / 4 + th - 1) / th > 65535) return fail(LDIT_EUNSUPPORTED, "relu_bwd_pad_nhwc_bf16: too many channels");
+    hipLaunchKernelGGL(act ? relu_bwd_pad_nhwc_bf16<true> : relu_bwd_pad_nhwc_bf16<false>, dim3(P, (unsigned)((C / 4 + th - 1) / th)), dim3(th), 0, stream, dy, act, static_cast<__bf16 *>(out),
+                       colsum ? scratch : nullptr, (int)M, (int)H, (int)W, (int)C);
+    return relu_bwd_stage2(colsum, scratch, M, (int)C, stream);
 }
 
 }  // namespace ldit

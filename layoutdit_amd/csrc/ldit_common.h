@@ -294,6 +294,11 @@ int launch_pad_nhwc_bf16(const float *src, void *dst, int B, int H, int W, int C
 size_t colsum_scratch_bytes(int64_t M, int64_t N);
 int launch_colsum_f32(const float *x, int64_t M, int N, int64_t ld, float *out, float *scratch, size_t scratch_bytes, bool absmax,
                       hipStream_t stream);
+// ReLU backward + bf16 copy (+ column sums) in one pass; `pad`: out is the zero-padded map of launch_pad_nhwc_bf16 (M = B H W, N = C)
+int launch_relu_bwd_bf16(const float *dy, int64_t lddy, const float *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                         float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream);
+int launch_relu_bwd_pad_nhwc_bf16(const float *dy, const float *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, float *colsum,
+                                  float *scratch, size_t scratch_bytes, hipStream_t stream);
 int launch_gemm_bf16(const void *A, int lda, const void *W, const float *bias, void *Y, int ldy, int M, int N, int K, int epi,
                      const float *lam, const float *R, float *Y2, hipStream_t stream);
 int launch_gemm_bf16_ex(const void *A, int lda, const void *W, const float *bias, void *Y, int ldy, int M, int N, int K, int epi,

@@ -231,14 +231,17 @@ class DetectorTrainStep:
         self.encoder._pos_cache.clear()
         for mod in self.model.modules():
             if isinstance(mod, DiTWithFPN):
-                for c in mod._cache + mod._cache_bf16:
-                    c.clear()
+                for c in mod._cache + mod._cache_bf16 + mod._cache_dgrad["conv"] + mod._cache_dgrad["lat"]:
+                    c.clear()                             # (the last two: the dgrad operands of grad_dtype="bf16")
             elif isinstance(mod, RPNHead):
                 mod._packed.clear()
                 mod._packed_bf16.clear()                  # the bf16 neck's operands likewise
+                mod._dgrad_bf16.clear()                   # ... and the 3x3's bf16 dgrad operand
             elif isinstance(mod, (TwoMLPHead, FastRCNNPredictor)):
                 mod._packed.clear()
                 mod._packed_bf16.clear()                  # the bf16 head's operands are keyed on versions like the fp32 re-layouts
+                if isinstance(mod, TwoMLPHead):
+                    mod._dgrad_bf16.clear()               # fc6's and fc7's bf16 dgrad operands
 
     def epoch_end(self) -> None:
         """``StepLR(step_size, gamma).step()``: after every ``step_size`` calls the learning rate is multiplied by ``gamma``; the new

@@ -29,11 +29,16 @@ convolutions of the path that wants no gradient onto the bf16 matrix pipe: per l
 zero-padded bf16 map (``ldit_pad_nhwc_f32_bf16``) and ``ldit_conv3x3_nhwc_bf16`` - the implicit-im2col mode of the bf16 MFMA GEMM,
 fp32 accumulation, bf16 operand rounding - writes the fp32 NHWC result, so every consumer sees the tensors it sees today.  Laterals
 and merges stay fp32, parameters stay fp32, the ``state_dict`` does not depend on the option and :class:`_FPNFn` ignores it.
+
+``grad_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_grad_dtype`) concerns :class:`_FPNFn`'s backward alone: the dgrad GEMMs
+of the four 3x3 convolutions and of the four laterals run on the bf16 MFMA GEMM, on the bf16 copy of the incoming gradient that the
+wgrad reads (``grad_ops.conv3x3_bwd`` / ``linear_bwd``).  No forward reads the option.
 """
 from __future__ import annotations
 
 import math
 from collections import OrderedDict
+from functools import partial
 from typing import Optional
 
 import torch
@@ -42,7 +47,8 @@ import torch.nn as nn
 from .. import _lib, ops
 from ..config import DiTConfig
 from .dit_backbone import DiTBackbone
-from .grad_ops import ParamCache, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, linear_bwd, param_key
+from .grad_ops import (ParamCache, check_grad_dtype, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, conv3x3_dgrad_bf16, linear_bwd,
+                       linear_dgrad_bf16, param_key)
 
 
 class _Conv(nn.Sequential):
@@ -84,11 +90,13 @@ def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, c
 
 class _FPNFn(torch.autograd.Function):
     """p2..p5 = FPN(taps) with gradients for the taps and for every FPN parameter.
-    apply(geom, t0..t3, lw0, lb0, .. lw3, lb3, cw0, cb0, .. cw3, cb3) -> (p2, p3, p4, p5) as [B, 256, h, w] channels-last views."""
+    apply(geom, t0..t3, lw0, lb0, .. lw3, lb3, cw0, cb0, .. cw3, cb3) -> (p2, p3, p4, p5) as [B, 256, h, w] channels-last views.
+    ``geom``: ``(gh, gw, scales)`` or ``(gh, gw, scales, grad_dtype, dgrad)`` - the stage's option and its cached
+    :meth:`DiTWithFPN._dgrad_operands_bf16` as a callable ``dgrad(kind, i)``; the forward does not read them."""
 
     @staticmethod
     def forward(ctx, geom, *args):
-        gh, gw, scales = geom
+        gh, gw, scales = geom[:3]
         toks = [_f32c(t.detach()) for t in args[0:4]]
         lw = [args[4 + 2 * i].detach() for i in range(4)]
         lb = [args[5 + 2 * i].detach() for i in range(4)]
@@ -103,7 +111,9 @@ class _FPNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dps):
-        gh, gw, scales = ctx.geom
+        gh, gw, scales = ctx.geom[:3]
+        grad_dtype, dgrad = ctx.geom[3:] if len(ctx.geom) > 3 else ("f32", None)
+        operand = (lambda kind, i: None) if dgrad is None else (lambda kind, i: partial(dgrad, kind, i))
         if ctx.inners is None:
             raise RuntimeError("DiTWithFPN: backward through the FPN a second time (its saved maps are freed after the first)")
         toks, inners, lw, cw = ctx.toks, ctx.inners, ctx.lw, ctx.cw
@@ -119,7 +129,8 @@ class _FPNFn(torch.autograd.Function):
                 dy = dp.permute(0, 2, 3, 1)
                 dy = dy.float() if dy.dtype != torch.float32 else dy
                 dy = dy.contiguous()                                  # NHWC [B, h, w, Ch]; a no-op for channels-last gradients
-                d_inner[i], g_cw[i], g_cb[i] = conv3x3_bwd(dy, inners[i], cw[i], True, need[12 + 2 * i], need[13 + 2 * i])
+                d_inner[i], g_cw[i], g_cb[i] = conv3x3_bwd(dy, inners[i], cw[i], True, need[12 + 2 * i], need[13 + 2 * i], grad_dtype,
+                                                           dgrad_w=operand("conv", i))
             else:
                 d_inner[i] = torch.zeros_like(inners[i])
             if i > 0:
@@ -130,7 +141,7 @@ class _FPNFn(torch.autograd.Function):
             d_lat = ops.fpn_merge_bwd(d_inner[i], gh, gw, scales[i])                     # [B, T, Ch], CLS row zero
             d_inner[i] = None
             g_x, g_w, g_lb[i] = linear_bwd(d_lat.view(B * T, Ch), toks[i].view(B * T, Cc), lw[i].reshape(Ch, Cc), need[i],
-                                           need[4 + 2 * i], need[5 + 2 * i])
+                                           need[4 + 2 * i], need[5 + 2 * i], grad_dtype, dgrad_w=operand("lat", i))
             g_tok[i] = g_x.view(B, T, Cc) if need[i] else None
             g_lw[i] = g_w.view(Ch, Cc, 1, 1) if need[4 + 2 * i] else None
         grads = [None] + g_tok
@@ -149,14 +160,32 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 
 class DiTWithFPN(nn.Module):
     def __init__(self, pretrained: bool = False, config: Optional[DiTConfig] = None, checkpoint: Optional[str] = None,
-                 compute_dtype: str = "f32", qat: bool = False, neck_dtype: str = "f32"):
+                 compute_dtype: str = "f32", qat: bool = False, neck_dtype: str = "f32", grad_dtype: str = "f32"):
         super().__init__()
         self.neck_dtype = check_neck_dtype(neck_dtype)
+        self.grad_dtype = check_grad_dtype(grad_dtype)
         self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype, qat=qat)
         self.fpn = _FPNParams([self.backbone.hidden_size] * 4, 256)
         self.out_channels = 256
         self._cache = [ParamCache() for _ in range(4)]
         self._cache_bf16 = [ParamCache() for _ in range(4)]
+        self._cache_dgrad = {kind: [ParamCache() for _ in range(4)] for kind in ("conv", "lat")}
+
+    def set_grad_dtype(self, grad_dtype: str) -> "DiTWithFPN":
+        """``"f32"`` or ``"bf16"``: the matrix pipe of the FPN's eight input-gradient GEMMs in the backward from now on (four 3x3
+        output convolutions, four laterals; ``grad_ops.conv3x3_bwd`` / ``linear_bwd``).  Forward, parameters and ``state_dict`` do not
+        depend on it; the encoder below has its own ``compute_dtype``."""
+        self.grad_dtype = check_grad_dtype(grad_dtype)
+        return self
+
+    def _dgrad_operands_bf16(self, kind: str, i: int) -> torch.Tensor:
+        """The weight operand of a dgrad GEMM under ``grad_dtype="bf16"``, re-made when the parameter changes: ``"conv"`` - level i's
+        3x3 weight flipped, in/out-swapped, bf16; ``"lat"`` - its lateral weight transposed [C, 256], bf16."""
+        if kind == "conv":
+            w = self.fpn.layer_blocks[i][0].weight
+            return self._cache_dgrad[kind][i].get(param_key(w), lambda: conv3x3_dgrad_bf16(w))
+        w = self.fpn.inner_blocks[i][0].weight
+        return self._cache_dgrad[kind][i].get(param_key(w), lambda: linear_dgrad_bf16(w.reshape(w.shape[0], w.shape[1])))
 
     def set_neck_dtype(self, neck_dtype: str) -> "DiTWithFPN":
         """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where no gradient is wanted, on the same
@@ -192,7 +221,7 @@ class DiTWithFPN(nn.Module):
                 args += [m.weight, m.bias]
             for m in conv:
                 args += [m.weight, m.bias]
-            results = list(_FPNFn.apply((gh, gw, tuple(bb.scales)), *args))
+            results = list(_FPNFn.apply((gh, gw, tuple(bb.scales), self.grad_dtype, self._dgrad_operands_bf16), *args))
         else:
             Cc = bb.hidden_size
             bf16_conv = self.neck_dtype == "bf16"

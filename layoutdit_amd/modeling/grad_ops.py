@@ -3,9 +3,11 @@ and of a linear layer on the library's kernels, two layers stacked into one GEMM
 stage keeps ONE ``autograd.Function`` (the order in which autograd sums a shared parameter's gradients is part of the bits)."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
-from .. import ops
+from .. import _lib, ops
 
 
 def flip_ihwo(w: torch.Tensor) -> torch.Tensor:
@@ -13,18 +15,60 @@ def flip_ihwo(w: torch.Tensor) -> torch.Tensor:
     return w.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
 
 
-def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.Tensor, need_x: bool, need_w: bool, need_b: bool):
+GRAD_DTYPES = ("f32", "bf16")
+BF16_K = 64                    # the k-tile of the bf16 GEMM: a reduction length it takes is a multiple of it
+
+
+def check_grad_dtype(grad_dtype: str) -> str:
+    """The option of the FPN, the RPN head, the box head and the detector that holds them: the matrix pipe of the input-gradient
+    (dgrad) GEMMs of their backward."""
+    if grad_dtype not in GRAD_DTYPES:
+        raise ValueError(f"grad_dtype {grad_dtype!r}: the detector's backward is built for {' and '.join(repr(d) for d in GRAD_DTYPES)}")
+    return grad_dtype
+
+
+def conv3x3_dgrad_bf16(weight_oihw: torch.Tensor) -> torch.Tensor:
+    """The bf16 operand of a 3x3 convolution's dgrad under ``grad_dtype="bf16"``: :func:`flip_ihwo` rounded to bf16."""
+    return ops.cast_bf16(flip_ihwo(weight_oihw))
+
+
+def linear_dgrad_bf16(weight: torch.Tensor) -> torch.Tensor:
+    """The bf16 operand of a linear layer's dgrad under ``grad_dtype="bf16"``: the transposed weight [K, N] rounded to bf16."""
+    return ops.cast_bf16(weight.detach().t().contiguous())
+
+
+def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.Tensor, need_x: bool, need_w: bool, need_b: bool,
+                grad_dtype: str = "f32", act: Optional[torch.Tensor] = None, dgrad_w=None):
     """Gradients of ``y = conv3x3(x, weight, padding=1) + bias`` on NHWC fp32 maps: ``(g_x NHWC, g_w OIHW, g_b)``, ``None`` and no
     launch for one that is not needed.  ``g_x``: the forward's implicit-im2col fp32 GEMM on the flipped weight.  ``g_w``: one bf16
     MFMA GEMM per tap (fp32 accumulation, bf16 operand rounding) on the zero-padded maps as reduction-major operands
-    [B (h+2)(w+2), C] - a tap is a constant row offset into the padded input, kept inside the buffer by ``slack`` zero rows."""
+    [B (h+2)(w+2), C] - a tap is a constant row offset into the padded input, kept inside the buffer by ``slack`` zero rows.
+
+    ``act`` (same shape as ``dy``): ``dy`` is first masked by the ReLU whose output ``act`` is - ``where(act > 0, dy, 0)``.
+
+    ``grad_dtype="bf16"`` with ``Cout % 64 == 0``: ONE launch (``ldit_relu_bwd_pad_nhwc_bf16``) masks ``dy``, writes its zero-padded
+    bf16 copy and sums ``g_b``; that copy is the operand of the wgrad taps - ``g_w`` and ``g_b`` have the bits of the ``"f32"``
+    setting - and of ``g_x = ldit_conv3x3_nhwc_bf16(copy, dgrad_w)``: bf16 operand rounding, fp32 accumulation, fp32 result.
+    ``dgrad_w``: a callable returning the cached :func:`conv3x3_dgrad_bf16` of the weight (made here without one).  A ``Cout`` that
+    is no multiple of 64 - the bf16 GEMM's k-tile - stays on the fp32 GEMM: every launch of the ``"f32"`` setting."""
     B, h, w, Cout = dy_nhwc.shape
-    g_x = ops.conv3x3_nhwc(dy_nhwc, flip_ihwo(weight_oihw)) if need_x else None
-    g_b = ops.colsum(dy_nhwc.view(B * h * w, Cout)) if need_b else None
+    bf16 = check_grad_dtype(grad_dtype) == "bf16" and Cout % BF16_K == 0
+    if bf16:
+        dy_p, g_b = ops.relu_bwd_pad_nhwc_bf16(dy_nhwc, act, want_colsum=need_b)
+        g_x = None
+        if need_x:
+            w16 = dgrad_w() if dgrad_w is not None else conv3x3_dgrad_bf16(weight_oihw)
+            g_x = ops.conv3x3_nhwc_bf16(dy_p, B, h, w, w16, None, _lib.EPI_F32).view(B, h, w, -1)
+    else:
+        if act is not None:
+            dy_nhwc = torch.where(act > 0, dy_nhwc, 0.0)
+        g_x = ops.conv3x3_nhwc(dy_nhwc, flip_ihwo(weight_oihw)) if need_x else None
+        g_b = ops.colsum(dy_nhwc.view(B * h * w, Cout)) if need_b else None
     g_w = None
     if need_w:
         slack = w + 3
-        dy_p = ops.pad_nhwc_bf16(dy_nhwc)
+        if not bf16:
+            dy_p = ops.pad_nhwc_bf16(dy_nhwc)
         x_p = ops.pad_nhwc_bf16(x_nhwc, slack_rows=slack)
         K = dy_p.shape[0]
         taps = []
@@ -36,12 +80,31 @@ def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.
     return g_x, g_w, g_b
 
 
-def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: bool, need_w: bool, need_b: bool):
+def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: bool, need_w: bool, need_b: bool,
+               grad_dtype: str = "f32", act: Optional[torch.Tensor] = None, dgrad_w=None):
     """Gradients of ``y = x @ weight.T + bias``: ``(g_x, g_w, g_b)``, ``None`` and no launch for one that is not needed.  ``g_x``:
     ``ldit_linear_f32`` on the transposed weight; ``g_w``: a bf16 MFMA GEMM on reduction-major operands (fp32 accumulation, bf16
     operand rounding); ``g_b``: ``ldit_colsum_f32``.  ``dy`` [M, N], N % 32 == 0 (the K of the fp32 GEMM), ``x`` [M, K], ``weight``
     [<= N, K]: where ``dy`` ends in zero padding columns that the weight has no rows for, the transposed weight is zero-extended
-    to N columns, and ``g_w`` and ``g_b`` have N rows."""
+    to N columns, and ``g_w`` and ``g_b`` have N rows.
+
+    ``act`` (same shape as ``dy``): ``dy`` is first masked by the ReLU whose output ``act`` is - ``where(act > 0, dy, 0)``.
+
+    ``grad_dtype="bf16"`` with ``N % 64 == 0`` and a weight of N rows: ONE launch (``ldit_relu_bwd_bf16``) masks ``dy``, writes its
+    bf16 copy and sums ``g_b``; that copy is the operand of the wgrad - ``g_w`` and ``g_b`` have the bits of the ``"f32"`` setting -
+    and of ``g_x = ldit_linear_bf16_ex(copy, dgrad_w)`` with ``LDIT_EPI_F32``, any M: bf16 operand rounding, fp32 accumulation, fp32
+    result.  ``dgrad_w``: a callable returning the cached :func:`linear_dgrad_bf16` of the weight (made here without one).  A
+    reduction length N that is no multiple of 64 - the bf16 GEMM's k-tile; the 32 padded columns of the box predictor and of the
+    RPN head's 1x1 pair, a few GFLOP - stays on the fp32 GEMM: every launch of the ``"f32"`` setting."""
+    if check_grad_dtype(grad_dtype) == "bf16" and dy.shape[1] % BF16_K == 0 and weight.shape[0] == dy.shape[1]:
+        dy16, g_b = ops.relu_bwd_bf16(dy, act, want_colsum=need_b)
+        g_x = None
+        if need_x:
+            g_x = ops.linear_bf16(dy16, dgrad_w() if dgrad_w is not None else linear_dgrad_bf16(weight), None, _lib.EPI_F32)
+        g_w = ops.wgrad_bf16(dy16, ops.cast_bf16(x), dy.shape[0]) if need_w else None
+        return g_x, g_w, g_b
+    if act is not None:
+        dy = torch.where(act > 0, dy, 0.0)
     g_x = None
     if need_x:
         if weight.shape[0] == dy.shape[1]:

@@ -34,6 +34,11 @@ bf16: RoIAlign rounds its fp32 rows to bf16 at the store (``ldit_roi_align_level
 predictor on the same GEMM with an fp32 result.  The parameters stay fp32 (the ``state_dict`` does not depend on the option); their
 bf16 copies are cached beside the fp32 re-layouts.  Train mode and every path that wants a gradient stay fp32 whatever the option
 says.
+
+``grad_dtype="bf16"`` (default ``"f32"``; :meth:`RoIHeads.set_grad_dtype`, :meth:`TwoMLPHead.set_grad_dtype`) concerns
+:class:`_TwoMLPHeadFn`'s backward alone: per layer one launch masks the incoming gradient by the ReLU, writes its bf16 copy and sums
+the bias gradient, and fc7's and fc6's dgrad run on the bf16 MFMA GEMM on that copy (``grad_ops.linear_bwd``).
+The predictor's dgrad (32 padded columns), RoIAlign's backward and the losses stay fp32.
 """
 from __future__ import annotations
 
@@ -43,7 +48,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .grad_ops import ParamCache, linear_bwd, param_key, stack_rows
+from .grad_ops import ParamCache, check_grad_dtype, linear_bwd, linear_dgrad_bf16, param_key, stack_rows
 
 
 HEAD_DTYPES = ("f32", "bf16")
@@ -120,10 +125,12 @@ class MultiScaleRoIAlign(nn.Module):
 
 class _TwoMLPHeadFn(torch.autograd.Function):
     """:class:`TwoMLPHead` with gradients for the pooled rows and the four parameters.
-    apply(pooled [M, P, P, C], fc6.weight, fc6.bias, fc7.weight, fc7.bias) -> [M, representation_size]."""
+    apply(pooled [M, P, P, C], fc6.weight, fc6.bias, fc7.weight, fc7.bias, grad) -> [M, representation_size].  ``grad``:
+    ``(grad_dtype, operands)``, the head's option and its cached :meth:`TwoMLPHead.dgrad_operands_bf16` as a callable; the forward
+    does not read it."""
 
     @staticmethod
-    def forward(ctx, pooled, w6, b6, w7, b7):
+    def forward(ctx, pooled, w6, b6, w7, b7, grad=("f32", None)):
         M, ph, pw, Cc = pooled.shape
         x0 = pooled.detach().reshape(M, ph * pw * Cc)
         w6p = w6.detach().view(w6.shape[0], Cc, ph, pw).permute(0, 2, 3, 1).reshape(w6.shape[0], -1).contiguous()      # (ph, pw, c) columns
@@ -133,6 +140,7 @@ class _TwoMLPHeadFn(torch.autograd.Function):
         torch.relu_(h7)
         ctx.saved = (x0, w6p, h6, w7.detach(), h7)
         ctx.pooled_shape = (M, ph, pw, Cc)
+        ctx.grad = grad
         return h7.clone()                                             # the saved activation is the ReLU mask: keep it private
 
     @staticmethod
@@ -143,14 +151,21 @@ class _TwoMLPHeadFn(torch.autograd.Function):
         ctx.saved = None
         M, ph, pw, Cc = ctx.pooled_shape
         need = ctx.needs_input_grad
-        d7 = d7.contiguous() * (h7 > 0)                               # ReLU mask
-        d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4])
-        d6.mul_(h6 > 0)
-        g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2])
+        grad_dtype, operands = ctx.grad
+        if grad_dtype == "bf16":
+            # each ReLU mask is applied by the launch that makes the layer's bf16 copy of dy and its bias gradient
+            w6_16, w7_16 = (None, None) if operands is None else ((lambda: operands()[0]), (lambda: operands()[1]))
+            d6, g_w7, g_b7 = linear_bwd(d7.contiguous(), h6, w7.contiguous(), True, need[3], need[4], grad_dtype, act=h7, dgrad_w=w7_16)
+            g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2], grad_dtype, act=h6, dgrad_w=w6_16)
+        else:
+            d7 = d7.contiguous() * (h7 > 0)                           # ReLU mask
+            d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4])
+            d6.mul_(h6 > 0)
+            g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2])
         g_w6 = None
         if g_w6p is not None:                                         # back to torchvision's (c, ph, pw) columns
             g_w6 = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
-        return (g_x.view(M, ph, pw, Cc) if g_x is not None else None), g_w6, g_b6, g_w7, g_b7
+        return (g_x.view(M, ph, pw, Cc) if g_x is not None else None), g_w6, g_b6, g_w7, g_b7, None
 
 
 class _PredictorFn(torch.autograd.Function):
@@ -205,11 +220,24 @@ def _wants_grad(module: nn.Module, x: torch.Tensor) -> bool:
 class TwoMLPHead(nn.Module):
     """torchvision's ``TwoMLPHead(in_channels, representation_size)``: ``fc6``, ``fc7``, a ReLU after each."""
 
-    def __init__(self, in_channels: int = 256 * 7 * 7, representation_size: int = 1024):
+    def __init__(self, in_channels: int = 256 * 7 * 7, representation_size: int = 1024, grad_dtype: str = "f32"):
         super().__init__()
+        self.grad_dtype = check_grad_dtype(grad_dtype)
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
-        self._packed, self._packed_bf16 = ParamCache(), ParamCache()
+        self._packed, self._packed_bf16, self._dgrad_bf16 = ParamCache(), ParamCache(), ParamCache()
+
+    def set_grad_dtype(self, grad_dtype: str) -> "TwoMLPHead":
+        """``"f32"`` or ``"bf16"``: the matrix pipe of the two input-gradient GEMMs of the backward from now on (``grad_ops.linear_bwd``).
+        Forward, parameters and ``state_dict`` do not depend on it."""
+        self.grad_dtype = check_grad_dtype(grad_dtype)
+        return self
+
+    def dgrad_operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The weight operands of the two dgrad GEMMs under ``grad_dtype="bf16"``: :meth:`fc6_weight_hwc` and ``fc7.weight``, each
+        transposed and rounded to bf16, re-made when a parameter changes."""
+        return self._dgrad_bf16.get((param_key(self.fc6.weight, self.fc7.weight), channels, ph, pw),
+                                    lambda: (linear_dgrad_bf16(self.fc6_weight_hwc(channels, ph, pw)), linear_dgrad_bf16(self.fc7.weight)))
 
     def fc6_weight_hwc(self, channels: int, ph: int, pw: int) -> torch.Tensor:
         """``fc6.weight`` with its columns re-ordered from torchvision's ``flatten(start_dim=1)`` of (c, ph, pw) to (ph, pw, c) - the
@@ -246,7 +274,8 @@ class TwoMLPHead(nn.Module):
             raise ValueError(f"TwoMLPHead: pooled rows of {ph} x {pw} x {Cc} do not match fc6's {self.fc6.weight.shape[1]} inputs")
         if _wants_grad(self, pooled):
             # gradients are wanted: the differentiable node (the eval path below and its cache are untouched)
-            return _TwoMLPHeadFn.apply(pooled, self.fc6.weight, self.fc6.bias, self.fc7.weight, self.fc7.bias)
+            return _TwoMLPHeadFn.apply(pooled, self.fc6.weight, self.fc6.bias, self.fc7.weight, self.fc7.bias,
+                                       (self.grad_dtype, lambda: self.dgrad_operands_bf16(Cc, ph, pw)))
         x = ops.linear(pooled.reshape(M, ph * pw * Cc), self.fc6_weight_hwc(Cc, ph, pw), self.fc6.bias.detach())
         torch.relu_(x)
         x = ops.linear(x, self.fc7.weight.detach(), self.fc7.bias.detach())
@@ -298,10 +327,13 @@ class RoIHeads(nn.Module):
     def __init__(self, box_roi_pool: MultiScaleRoIAlign, box_head: TwoMLPHead, box_predictor: FastRCNNPredictor,
                  bbox_reg_weights: Optional[Sequence[float]] = None, score_thresh: float = 0.05, nms_thresh: float = 0.5,
                  detections_per_img: int = 100, min_size: float = 1e-2, fg_iou_thresh: float = 0.5, bg_iou_thresh: float = 0.5,
-                 batch_size_per_image: int = 512, positive_fraction: float = 0.25, head_dtype: str = "f32"):
+                 batch_size_per_image: int = 512, positive_fraction: float = 0.25, head_dtype: str = "f32",
+                 grad_dtype: Optional[str] = None):
         super().__init__()
         self.head_dtype = _check_head_dtype(head_dtype)
         self.box_roi_pool, self.box_head, self.box_predictor = box_roi_pool, box_head, box_predictor
+        if grad_dtype is not None:                                    # None: the box head keeps the setting it was built with
+            self.set_grad_dtype(grad_dtype)
         self.bbox_reg_weights = tuple(float(w) for w in (bbox_reg_weights or (10.0, 10.0, 5.0, 5.0)))
         self.score_thresh, self.nms_thresh, self.min_size = float(score_thresh), float(nms_thresh), float(min_size)
         self.detections_per_img = int(detections_per_img)
@@ -322,6 +354,16 @@ class RoIHeads(nn.Module):
     def set_head_dtype(self, head_dtype: str) -> "RoIHeads":
         """``"f32"`` or ``"bf16"``: how the eval-mode head runs from now on.  The parameters are untouched."""
         self.head_dtype = _check_head_dtype(head_dtype)
+        return self
+
+    @property
+    def grad_dtype(self) -> str:
+        """The box head's setting (:meth:`TwoMLPHead.set_grad_dtype`): fc6's and fc7's dgrad GEMMs.  RoIAlign's backward, the
+        predictor (32 padded columns: below the bf16 GEMM's k-tile) and the losses are fp32 under either."""
+        return self.box_head.grad_dtype
+
+    def set_grad_dtype(self, grad_dtype: str) -> "RoIHeads":
+        self.box_head.set_grad_dtype(check_grad_dtype(grad_dtype))
         return self
 
     def _wants_grad(self, features) -> bool:

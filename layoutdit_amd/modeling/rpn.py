@@ -29,6 +29,11 @@ fp32 logits and deltas in the layout above.  Parameters stay fp32; :class:`_RPNH
 torchvision is not installed offline: the semantics are restated from its documented behaviour (``tests/rpn_oracle.py``,
 ``tests/rpn_train_oracle.py``) - parity unpinned with respect to torchvision itself, as for the FPN.  Parameter names follow
 torchvision, so detector checkpoints load (``rpn.head.conv.0.0.weight`` ...).
+
+``grad_dtype="bf16"`` (default ``"f32"``; :meth:`RPNHead.set_grad_dtype`) concerns :class:`_RPNHeadLevelFn`'s backward alone: one launch
+masks the 1x1 pair's input gradient by the ReLU, writes its zero-padded bf16 copy and sums the 3x3's bias gradient, and the 3x3's
+dgrad runs on the bf16 MFMA GEMM on that copy (``grad_ops.conv3x3_bwd``).  The 1x1 pair's own dgrad (32 padded
+columns) stays on the fp32 GEMM.
 """
 from __future__ import annotations
 
@@ -39,7 +44,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .grad_ops import ParamCache, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, linear_bwd, param_key, stack_rows
+from .grad_ops import (ParamCache, check_grad_dtype, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, conv3x3_dgrad_bf16, linear_bwd, param_key,
+                       stack_rows)
 
 
 class AnchorGenerator(nn.Module):
@@ -127,13 +133,16 @@ def _level_forward_bf16(x, operands_bf16, A: int):
 class _RPNHeadLevelFn(torch.autograd.Function):
     """One level of :class:`RPNHead` with gradients for the map and all six parameters.  ``operands`` is the head's cached
     :meth:`RPNHead._operands` - the same weights as the GEMMs read them, no gradient of their own.
-    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box, operands) -> (logits [B, h w A], deltas [B, h w A, 4])."""
+    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box, operands, grad) -> (logits [B, h w A], deltas [B, h w A, 4]).
+    ``grad``: ``(grad_dtype, dgrad_w)``, the head's option and its cached :meth:`RPNHead._dgrad_operand_bf16` as a callable; the
+    forward does not read it."""
 
     @staticmethod
-    def forward(ctx, x, w3, b3, wc, bc, wb, bb, operands):
+    def forward(ctx, x, w3, b3, wc, bc, wb, bb, operands, grad=("f32", None)):
         xn, t, out = _level_forward(x, operands, wc.shape[0])
         ctx.saved = (xn, t, w3.detach(), operands[2])
         ctx.A = wc.shape[0]
+        ctx.grad = grad
         return out
 
     @staticmethod
@@ -154,12 +163,18 @@ class _RPNHeadLevelFn(torch.autograd.Function):
             dy[:, :A] = d_logits.reshape(M, A)
         if d_deltas is not None:
             dy[:, A:5 * A] = d_deltas.reshape(M, 4 * A)
-        dt, g1, gb = linear_bwd(dy, t.view(M, Cc), w1, True, need[3] or need[5], need[4] or need[6])   # [M, C], [K, C], [K]
-        dt.mul_(t.view(M, Cc) > 0)                                                        # ReLU mask
-        g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2])
+        grad_dtype, dgrad_w = ctx.grad
+        # (K = 32 is below the bf16 GEMM's k-tile: this dgrad is the fp32 GEMM under either setting)
+        dt, g1, gb = linear_bwd(dy, t.view(M, Cc), w1, True, need[3] or need[5], need[4] or need[6], grad_dtype)   # [M, C], [K, C], [K]
+        if grad_dtype == "bf16":
+            # the ReLU mask is applied by the launch that makes the padded bf16 copy of dt and the bias gradient
+            g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2], grad_dtype, act=t, dgrad_w=dgrad_w)
+        else:
+            dt.mul_(t.view(M, Cc) > 0)                                                    # ReLU mask
+            g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2])
         return (g_x.permute(0, 3, 1, 2) if need[0] else None, g_w3, g_b3,
                 g1[:A].reshape(A, Cc, 1, 1) if need[3] else None, gb[:A] if need[4] else None,
-                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None)
+                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None, None)
 
 
 class _RPNLossFn(torch.autograd.Function):
@@ -181,9 +196,10 @@ class _RPNLossFn(torch.autograd.Function):
 class RPNHead(nn.Module):
     """torchvision's ``RPNHead(in_channels, num_anchors)``: ``conv.0.0`` (3x3 + ReLU), ``cls_logits`` and ``bbox_pred`` (1x1)."""
 
-    def __init__(self, in_channels: int = 256, num_anchors: int = 3, neck_dtype: str = "f32"):
+    def __init__(self, in_channels: int = 256, num_anchors: int = 3, neck_dtype: str = "f32", grad_dtype: str = "f32"):
         super().__init__()
         self.neck_dtype = check_neck_dtype(neck_dtype)
+        self.grad_dtype = check_grad_dtype(grad_dtype)
         self.conv = nn.Sequential(_ConvRelu(in_channels))
         self.cls_logits = nn.Conv2d(in_channels, num_anchors, kernel_size=1)
         self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1)
@@ -192,7 +208,20 @@ class RPNHead(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.normal_(m.weight, std=0.01)
                 nn.init.constant_(m.bias, 0)
-        self._packed, self._packed_bf16 = ParamCache(), ParamCache()
+        self._packed, self._packed_bf16, self._dgrad_bf16 = ParamCache(), ParamCache(), ParamCache()
+
+    def set_grad_dtype(self, grad_dtype: str) -> "RPNHead":
+        """``"f32"`` or ``"bf16"``: the matrix pipe of the 3x3 convolution's input-gradient GEMM in the backward from now on
+        (``grad_ops.conv3x3_bwd``; the 1x1 pair's 32 padded columns keep theirs on the fp32 GEMM).  Forward, parameters and
+        ``state_dict`` do not depend on it."""
+        self.grad_dtype = check_grad_dtype(grad_dtype)
+        return self
+
+    def _dgrad_operand_bf16(self) -> torch.Tensor:
+        """The weight operand of the 3x3 convolution's dgrad under ``grad_dtype="bf16"`` (flipped, in/out-swapped, bf16), re-made
+        when the parameter changes."""
+        w3 = self.conv[0][0].weight
+        return self._dgrad_bf16.get(param_key(w3), lambda: conv3x3_dgrad_bf16(w3))
 
     def set_neck_dtype(self, neck_dtype: str) -> "RPNHead":
         """``"f32"`` or ``"bf16"``: how the head runs from now on where no gradient is wanted, on the same weights."""
@@ -227,7 +256,7 @@ class RPNHead(nn.Module):
             raise ValueError(f"RPNHead: expected float32 features, got {x.dtype}")
         if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             # gradients are wanted: one differentiable node per level, on the operands of the eval path below
-            return _RPNHeadLevelFn.apply(x, *self._params(), self._operands())
+            return _RPNHeadLevelFn.apply(x, *self._params(), self._operands(), (self.grad_dtype, self._dgrad_operand_bf16))
         if self.neck_dtype == "bf16":
             return _level_forward_bf16(x, self._operands_bf16(), self.num_anchors)
         return _level_forward(x, self._operands(), self.num_anchors)[2]

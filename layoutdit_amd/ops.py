@@ -696,6 +696,46 @@ def colamax(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _colsum_buffers(M: int, N: int, device, want: bool):
+    """``(colsum, scratch, scratch_bytes)`` of a fused column sum over an [M, N] matrix; all ``None`` / 0 when it is not wanted."""
+    if not want:
+        return None, None, 0
+    need = ((M + 511) // 512) * N * 4                  # = ldit_colsum_scratch_bytes(M, N): one partial row per 512 rows
+    return (torch.empty(N, device=device, dtype=torch.float32), torch.empty(max(need, 16), device=device, dtype=torch.uint8), need)
+
+
+def _req_act(act: Optional[torch.Tensor], dy: torch.Tensor) -> Optional[torch.Tensor]:
+    if act is not None and tuple(_req(act, "act").shape) != tuple(dy.shape):
+        raise ValueError(f"act {tuple(act.shape)} does not match dy {tuple(dy.shape)}")
+    return act
+
+
+def relu_bwd_bf16(dy: torch.Tensor, act: Optional[torch.Tensor] = None, want_colsum: bool = True):
+    """One pass between two layers of a backward: with ``w = torch.where(act > 0, dy, 0)`` (``w = dy`` without ``act``) returns
+    ``(cast_bf16(w), colsum(w))`` bit for bit, the sum ``None`` where it is not wanted.  ``dy``, ``act``: contiguous fp32 [M, N]."""
+    lib = _lib.load()
+    dy = _req(dy, "dy")
+    act = _req_act(act, dy)
+    M, N = dy.shape
+    out = torch.empty((M, N), device=dy.device, dtype=torch.bfloat16)
+    cs, scratch, need = _colsum_buffers(M, N, dy.device, want_colsum)
+    _launch(_device(dy, act), lib.ldit_relu_bwd_bf16, _ptr(dy), N, _ptr(act), N, _ptr(out), N, M, N, _ptr(cs), _ptr(scratch), need)
+    return out, cs
+
+
+def relu_bwd_pad_nhwc_bf16(dy: torch.Tensor, act: Optional[torch.Tensor] = None, want_colsum: bool = True):
+    """:func:`relu_bwd_bf16` on an NHWC map ``dy`` [B, H, W, C] with the copy in the zero-padded layout: returns
+    ``(pad_nhwc_bf16(w), colsum(w.view(-1, C)))`` bit for bit - bf16 ``[B (H+2) (W+2), C]`` (no slack rows) and fp32 [C] or ``None``."""
+    lib = _lib.load()
+    dy = _req(dy, "dy")
+    act = _req_act(act, dy)
+    B, H, W, Cc = dy.shape
+    out = torch.empty((B * (H + 2) * (W + 2), Cc), device=dy.device, dtype=torch.bfloat16)
+    cs, scratch, need = _colsum_buffers(B * H * W, Cc, dy.device, want_colsum)
+    _launch(_device(dy, act), lib.ldit_relu_bwd_pad_nhwc_bf16, _ptr(dy), _ptr(act), _ptr(out), B, H, W, Cc, _ptr(cs), _ptr(scratch), need)
+    return out, cs
+
+
 def _splits_for(K: int, M: int, N: int) -> int:
     """K-splits of a wgrad GEMM with an [M, N] output - the rule of csrc/api_train.hip pick_splits: enough 128 x 128 tiles for the
     machine (~512 / output tiles, at most 8), every split non-empty."""

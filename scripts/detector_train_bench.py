@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Time of the detector's training iteration, split into its three calls - LayoutDetectionModel.losses(), backward() of the summed
+loss, DetectorTrainStep.apply() - for grad_dtype "f32" and "bf16" (DESIGN section 30), alternating in ONE process on ONE set of
+weights: ViT-B/16 detector, bf16 encoder, 224 x 224, bs=64, synthetic pages and targets from a seed, drop_path_rate = 0.  HIP events
+around each call (host work of the call included), every shape warmed up in both settings first, median / min / max of --runs
+iterations per setting.  The weights move by one AdamW step per timed iteration (lr 1e-6), for both settings alike.
+--count N [--phases losses|iteration]: no timing and no file - N iterations (or their losses() alone) in the FIRST setting, for a
+kernel trace of the process from outside: launches per call are differences between two such traces (scripts/README.md).
+Needs a GPU: without one it fails.  Writes one JSON object (--out, default profiles/detector_train_bench.json)."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from layoutdit_amd import config as cfgs, synth  # noqa: E402
+from layoutdit_amd.modeling import LayoutDetectionModel  # noqa: E402
+from layoutdit_amd.training import DetectorTrainStep  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--config", default="vit_base", choices=["vit_micro", "vit_tiny", "vit_base"])
+ap.add_argument("--batch", type=int, default=64)
+ap.add_argument("--runs", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--seed", type=int, default=7)
+ap.add_argument("--settings", default="f32,bf16", help="comma-separated grad_dtype settings, timed alternately in this order")
+ap.add_argument("--count", type=int, default=0, help="no timing, nothing written: this many iterations of --phases in the first setting")
+ap.add_argument("--phases", default="iteration", choices=["losses", "iteration"])
+ap.add_argument("--commit", default=None, help="recorded as the tree's commit (default: git rev-parse of the checkout, if it is one)")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detector_train_bench.json"))
+args = ap.parse_args()
+if args.runs < 20 and not args.count:
+    ap.error("--runs: at least 20 iterations per setting")
+if not torch.cuda.is_available():
+    sys.exit("detector_train_bench: no GPU found (the detector has no CPU path)")
+
+dev = "cuda:0"
+settings = args.settings.split(",")
+cfg = getattr(cfgs, args.config)()
+cfg.drop_path_rate = 0.0
+torch.manual_seed(0)
+model = LayoutDetectionModel(config=cfg, compute_dtype="bf16")
+model.model.backbone.backbone.dit.load_numpy(synth.synth_weights(cfg, seed=4))
+model = model.to(dev).train()
+step = DetectorTrainStep(model, lr=1e-6)
+
+pages = synth.synth_images(args.batch, 224, 224, seed=args.seed, kind="doc")
+images = [torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in pages]
+rng = np.random.RandomState(args.seed)
+targets = []
+for _ in range(args.batch):
+    n = int(rng.randint(1, 9))
+    x0, y0 = rng.uniform(0, 150, size=n), rng.uniform(0, 150, size=n)
+    w, h = rng.uniform(16, 72, size=n), rng.uniform(16, 72, size=n)
+    boxes = np.stack([x0, y0, np.minimum(x0 + w, 223.0), np.minimum(y0 + h, 223.0)], axis=1).astype(np.float32)
+    targets.append({"boxes": torch.from_numpy(boxes).to(dev), "labels": torch.from_numpy(rng.randint(1, 6, size=n).astype(np.int64)).to(dev)})
+
+
+def iteration(setting: str, timed: bool, losses_only: bool = False):
+    model.set_grad_dtype(setting)
+    for p in model.parameters():
+        p.grad = None
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timed else None
+    if timed:
+        ev[0].record()
+    losses = model.losses(images, targets, generator=gen)
+    total = sum(losses.values())
+    if losses_only:
+        return None, float(total.detach())
+    if timed:
+        ev[1].record()
+    total.backward()
+    if timed:
+        ev[2].record()
+    step.apply()
+    if timed:
+        ev[3].record()
+        ev[3].synchronize()
+        return [ev[i].elapsed_time(ev[i + 1]) for i in range(3)], float(total.detach())
+    return None, float(total.detach())
+
+
+if args.count:
+    for _ in range(args.count):
+        iteration(settings[0], False, losses_only=args.phases == "losses")
+    torch.cuda.synchronize()
+    sys.exit(0)
+for _ in range(args.warmup):                       # every shape, every cache and every moment, in both settings
+    for s in settings:
+        iteration(s, False)
+torch.cuda.synchronize()
+samples = {s: [] for s in settings}
+finite = True
+for _ in range(args.runs):
+    for s in settings:
+        t, total = iteration(s, True)
+        samples[s].append(t)
+        finite = finite and bool(np.isfinite(total))
+torch.cuda.synchronize()
+
+
+def stats(v):
+    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+
+ms = {s: {name: stats([t[i] for t in samples[s]]) for i, name in enumerate(("losses", "backward", "apply"))} for s in settings}
+commit = args.commit
+try:
+    commit = commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True, timeout=10).stdout.strip() or None
+except (OSError, subprocess.SubprocessError):
+    pass
+res = {
+    "workload": {"config": args.config, "encoder": "bf16", "batch": args.batch, "image": [224, 224], "seed": args.seed, "drop_path_rate": 0.0,
+                 "gt_boxes": int(sum(len(t["labels"]) for t in targets)), "sampled_rows_per_image": model.model.roi_heads.batch_size_per_image,
+                 "optimizer": "DetectorTrainStep(lr=1e-6), one step per timed iteration"},
+    "settings": settings, "order": "alternating, one iteration of each setting in turn, one process, one set of weights",
+    "runs": args.runs, "warmup": args.warmup, "timer": "HIP events around each call, host work of the call included",
+    "ms": ms, "all_losses_finite": finite, "steps": step.steps, "skipped_steps": step.skipped_steps,
+    "launches": None,                                  # from kernel traces of --count runs, where they were made (scripts/README.md)
+    "device": torch.cuda.get_device_name(0), "commit": commit, "box": "one MI355X box", "repeats": "one run",
+}
+if len(settings) == 2:
+    a, b = (ms[s]["backward"] for s in settings)
+    res["backward_difference"] = {"median_ms": round(a["median_ms"] - b["median_ms"], 3),
+                                  "spread_ms": {s: round(ms[s]["backward"]["max_ms"] - ms[s]["backward"]["min_ms"], 3) for s in settings},
+                                  "separated": bool(b["max_ms"] < a["min_ms"])}
+print(json.dumps(res))
+with open(args.out, "w") as f:
+    json.dump(res, f, indent=1)
+    f.write("\n")
