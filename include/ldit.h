@@ -552,6 +552,25 @@ int ldit_attention_bwd_bf16(const void *Q, const void *K, const void *V, const v
 size_t ldit_layernorm_bwd_scratch_bytes(int64_t rows, int64_t C);
 int ldit_layernorm_bwd_f32(const void *dy, const void *x, const void *gamma, void *dh, int64_t rows, int64_t C, float eps,
                            void *dgamma, void *dbeta, void *scratch, size_t scratch_bytes, ldit_stream stream);
+/* LayerNorm backward fused with the LayerScale / residual backward of the branch below it, as the train step launches it between the
+ * MLP and the attention branch of a layer.  With dh' = dh + d/dx (the LayerNorm backward above, dh a += destination, in place):
+ *   dz[r][c] = bf16(dh'[r][c] rs[r] lam[c]) ; dlam[c] = sum_r dh'[r][c] rs[r] z[r][c] ; dzbias[c] = sum_r dh'[r][c] rs[r] lam[c]
+ * (dzbias sums the unrounded fp32 products, not the bf16 dz), rs = rowscale (fp32 [rows]) or 1 when rowscale is null.
+ * dy, x, dh: fp32 [rows, C], gamma, lam: fp32 [C], 16-byte aligned; z (in), dz (out): bf16 [rows, C], 8-byte aligned; C % 4 == 0,
+ * C <= 4096.  dgamma, dbeta, dlam, dzbias: fp32 [C], 16-byte aligned, overwritten (not +=).  scratch: 16-byte aligned,
+ * ldit_layernorm_bwd_resid_scratch_bytes, contents irrelevant before and undefined after.  Additive to ABI 6. */
+size_t ldit_layernorm_bwd_resid_scratch_bytes(int64_t rows, int64_t C);
+int ldit_layernorm_bwd_resid_f32(const void *dy, const void *x, const void *gamma, const void *z, const void *lam, const void *rowscale,
+                                 void *dh, void *dz, int64_t rows, int64_t C, float eps, void *dgamma, void *dbeta, void *dlam,
+                                 void *dzbias, void *scratch, size_t scratch_bytes, ldit_stream stream);
+/* LayerScale / residual backward on its own (the MLP branch's): h_out = h_in + rs lam (.) z  =>
+ *   dz[r][c] = bf16(dh[r][c] rs[r] lam[c]) ; dlam[c] = sum_r dh[r][c] rs[r] z[r][c] ; dbias[c] = sum_r dh[r][c] rs[r] lam[c]
+ * dh is only read (it passes unchanged to the residual branch).  dh: fp32 [rows, C], lam: fp32 [C], dz: bf16 [rows, C] out, all
+ * 16-byte aligned; z: bf16 [rows, C], 8-byte aligned; rowscale: fp32 [rows] or null; C % 64 == 0.  dlam, dbias: fp32 [C], 16-byte
+ * aligned, overwritten.  scratch: 16-byte aligned, ldit_resid_bwd_scratch_bytes.  Additive to ABI 6. */
+size_t ldit_resid_bwd_scratch_bytes(int64_t rows, int64_t C);
+int ldit_resid_bwd_bf16(const void *dh, const void *z, const void *lam, const void *rowscale, void *dz, int64_t rows, int64_t C,
+                        void *dlam, void *dbias, void *scratch, size_t scratch_bytes, ldit_stream stream);
 /* ldit_linear_bf16 with the train step's extras: Ypre (bf16 [M,N], stride ldy) receives X W^T + b before GELU / LayerScale;
  * (LDIT_EPI_BIAS_GELU: gelu'(X W^T + b) instead); rowscale (fp32 [M]) multiplies lam per row; aux (bf16 [M,N], stride
  * ldaux) is the factor LDIT_EPI_GELU_BWD multiplies the accumulator with (= that saved gelu');

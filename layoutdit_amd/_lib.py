@@ -153,6 +153,11 @@ SIGNATURES = {
                                           _i64, _f32, _vp]),
     "ldit_layernorm_bwd_scratch_bytes": (_sz, [_i64, _i64]),
     "ldit_layernorm_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "ldit_layernorm_bwd_resid_scratch_bytes": (_sz, [_i64, _i64]),
+    "ldit_layernorm_bwd_resid_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _sz,
+                                               _vp]),
+    "ldit_resid_bwd_scratch_bytes": (_sz, [_i64, _i64]),
+    "ldit_resid_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ldit_linear_bf16_ex": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                       _i32, _vp]),
     "ldit_reduce_slabs_f32": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),

@@ -615,6 +615,68 @@ int ldit_layernorm_bwd_f32(const void *dy, const void *x, const void *gamma, voi
     return launch_reduce_jobs(jobs, stream);
 }
 
+// partial rows of the fused LayerNorm + LayerScale backward: the count the launcher's grid has (train_ops.hip)
+static int layernorm_bwd_resid_part_rows(int64_t rows, int64_t C)
+{
+    return C <= 1024 ? layernorm_bwd_resid_blocks(rows) : layernorm_bwd_blocks(rows);
+}
+
+size_t ldit_layernorm_bwd_resid_scratch_bytes(int64_t rows, int64_t C)
+{
+    if (rows <= 0 || C <= 0) return 0;
+    return (size_t)4 * layernorm_bwd_resid_part_rows(rows, C) * (size_t)C * 4;
+}
+
+int ldit_layernorm_bwd_resid_f32(const void *dy, const void *x, const void *gamma, const void *z, const void *lam, const void *rowscale,
+                                 void *dh, void *dz, int64_t rows, int64_t C, float eps, void *dgamma, void *dbeta, void *dlam,
+                                 void *dzbias, void *scratch, size_t scratch_bytes, ldit_stream stream_)
+{
+    if (rows <= 0 || C <= 0 || C > 4096) return fail(LDIT_EINVAL, "layernorm_bwd_resid: bad shape");
+    if (!dgamma || !dbeta || !dlam || !dzbias || !scratch || !aligned16(scratch)) return fail(LDIT_EINVAL, "layernorm_bwd_resid: null operand or misaligned scratch");
+    if (!aligned16(dy) || !aligned16(x) || !aligned16(gamma) || !aligned16(dh))
+        return fail(LDIT_EINVAL, "layernorm_bwd_resid: dy, x, gamma, dh must be 16-byte aligned");
+    if (scratch_bytes < ldit_layernorm_bwd_resid_scratch_bytes(rows, C)) return fail(LDIT_EWORKSPACE, "layernorm_bwd_resid: scratch too small");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int blocks = layernorm_bwd_resid_part_rows(rows, C);
+    const size_t pn = (size_t)blocks * C;
+    float *pg = static_cast<float *>(scratch), *pb = pg + pn, *pl = pb + pn, *pz = pl + pn;
+    LDIT_TRY(launch_layernorm_bwd_resid(static_cast<const float *>(dy), static_cast<const float *>(x), static_cast<const float *>(gamma),
+                                        static_cast<float *>(dh), rows, (int)C, eps, pg, pb, z, static_cast<const float *>(lam),
+                                        static_cast<const float *>(rowscale), dz, pl, pz, stream));
+    ReduceJobs jobs;
+    jobs.add(pg, static_cast<float *>(dgamma), C, blocks, C);
+    jobs.add(pb, static_cast<float *>(dbeta), C, blocks, C);
+    jobs.add(pl, static_cast<float *>(dlam), C, blocks, C);
+    jobs.add(pz, static_cast<float *>(dzbias), C, blocks, C);
+    return launch_reduce_jobs(jobs, stream);
+}
+
+size_t ldit_resid_bwd_scratch_bytes(int64_t rows, int64_t C)
+{
+    if (rows <= 0 || C <= 0) return 0;
+    return (size_t)2 * (size_t)((rows + 63) / 64) * (size_t)C * 4;
+}
+
+int ldit_resid_bwd_bf16(const void *dh, const void *z, const void *lam, const void *rowscale, void *dz, int64_t rows, int64_t C,
+                        void *dlam, void *dbias, void *scratch, size_t scratch_bytes, ldit_stream stream_)
+{
+    if (rows <= 0 || C <= 0 || rows + 63 >= (1ll << 31) || C >= (1ll << 31)) return fail(LDIT_EINVAL, "resid_bwd: bad shape");
+    if (C % 64) return fail(LDIT_EUNSUPPORTED, "resid_bwd: C=%lld must be a multiple of 64", (long long)C);
+    if (!dh || !z || !lam || !dz || !dlam || !dbias || !scratch || !aligned16(scratch)) return fail(LDIT_EINVAL, "resid_bwd: null operand or misaligned scratch");
+    if (!aligned16(dh) || !aligned16(lam) || !aligned16(dz) || (reinterpret_cast<uintptr_t>(z) & 7u))
+        return fail(LDIT_EINVAL, "resid_bwd: dh, lam, dz must be 16-byte aligned, z 8-byte aligned");
+    if (scratch_bytes < ldit_resid_bwd_scratch_bytes(rows, C)) return fail(LDIT_EWORKSPACE, "resid_bwd: scratch too small");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int Mp = (int)((rows + 63) / 64 * 64), blocks = Mp / 64;
+    float *pl = static_cast<float *>(scratch), *pb = pl + (size_t)blocks * C;
+    LDIT_TRY(launch_resid_bwd(static_cast<const float *>(dh), z, static_cast<const float *>(lam), static_cast<const float *>(rowscale), dz,
+                              nullptr, (int)rows, (int)C, Mp, pl, pb, stream));
+    ReduceJobs jobs;
+    jobs.add(pl, static_cast<float *>(dlam), C, blocks, C);
+    jobs.add(pb, static_cast<float *>(dbias), C, blocks, C);
+    return launch_reduce_jobs(jobs, stream);
+}
+
 int ldit_linear_bf16_ex(const void *X, int64_t lda, const void *W, const void *bias, void *Y, int64_t ldy, int64_t M, int64_t N,
                         int64_t K, int32_t epilogue, const void *lam, const void *R, void *Y2, void *Ypre, const void *rowscale,
                         const void *aux, int64_t ldaux, int32_t splits, ldit_stream stream)

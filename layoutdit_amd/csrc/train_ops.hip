@@ -277,6 +277,9 @@ __global__ void __launch_bounds__(64 * NWV) layernorm_bwd_rows(const float *__re
                 v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
                 d[u] = f32x4{0.f, 0.f, 0.f, 0.f};
                 acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                // RES: gamma is loaded under idx < nvec only, and the statistics loop below multiplies d by it on EVERY lane:
+                // 0 * (whatever the register held) is NaN for a NaN / Inf pattern, and wave_sum hands it to the whole row
+                if (RES) gg[u] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
         const float mu = wave_sum(s) * inv_c;

@@ -26,7 +26,7 @@ torch = pytest.importorskip("torch")
 from layoutdit_amd import _lib, ops                                   # noqa: E402
 from tests import attention_cases as ac                              # noqa: E402
 from tests.test_gpu_split_fp32 import OUT                             # noqa: E402  (the suite's directory for measured margins)
-from tests.test_mxfp8_format import e4m3_bits, mx_dequant, mx_exponent, mx_quant_ref   # noqa: E402
+from tests.mx_checks import check_mx_pack                            # noqa: E402
 
 DEV = "cuda:0"
 BF = torch.bfloat16
@@ -215,37 +215,9 @@ def _fp32_grade_gates(name, got, ref, v, gate, shifted_case):
     _gate(name, got, ref.o, bound, tensor_gate, shifted_case)
 
 
-# ---- mxfp8: the codes against the host MX pack ---------------------------------------------------------------------------------
+# ---- mxfp8: the codes against the host MX pack (tests/mx_checks.py, shared with the LayerNorm edges) --------------------------------
 def _check_mx_pack(name, codes, scales, ob, od, exact):
-    """od is the exact dequantisation of (codes, scales).  exact (the selecting cases: o is bf16-exact in fp32 already): codes and
-    scales EQUAL the host MX pack of ob.  Otherwise the kernel quantises its fp32 o, of which ob is the bf16 rounding (attention_flash.hip,
-    OUT_MX epilogue: amax and pack_fp8x4 read o[dt][e], Ob stores (bf16)o[dt][e]), so the pack of ob is a SECOND rounding of o and may
-    differ from the codes wherever ob landed on an e4m3 tie (1 in 16 bf16 values is one).  What must hold: the block's scale byte is
-    the scale rule's byte for an amax inside ob's bf16 rounding interval, and each code lies between the e4m3 roundings of the two
-    ends of its element's interval [|ob| - h, |ob| + h], h = half a bf16 ulp of ob, with ob's sign."""
-    rows = codes.shape[0]
-    obn = ob.float().numpy().reshape(rows, -1)
-    assert np.array_equal(od.float().numpy().reshape(rows, -1).astype(np.float64), mx_dequant(codes, scales)), name
-    rc, rs, finite = mx_quant_ref(obn)
-    assert finite.all()
-    same = float((rc == codes).mean())
-    print(f"{name}: codes equal to the host pack of ob: {same:.4f} of the elements, scales: {float((rs == scales).mean()):.4f}")
-    MARGINS[name + "/fraction_of_codes_equal_to_pack_of_ob"] = min(MARGINS.get(name + "/fraction_of_codes_equal_to_pack_of_ob", 1.0), same)
-    if exact:
-        assert np.array_equal(rc, codes) and np.array_equal(rs, scales), name
-        return
-    a = np.abs(obn.astype(np.float64))
-    _, E = np.frexp(np.where(a > 0, a, 1.0))
-    hulp = np.where(a > 0, np.ldexp(1.0, E - 9), 0.0)                        # a = m 2^E, m in [0.5, 1): bf16 ulp 2^(E-8)
-    lo, hi = np.maximum(a - hulp, 0.0), a + hulp
-    blo, bhi = (x.reshape(rows, -1, 32).max(-1) for x in (lo, hi))
-    e = scales.astype(np.int64) - 127
-    assert ((mx_exponent(blo) <= e) & (e <= mx_exponent(bhi))).all(), name
-    inv = np.repeat(np.ldexp(1.0, -e), 32, axis=1)
-    clo, chi = e4m3_bits(np.minimum(lo * inv, 448.0)) & 0x7F, e4m3_bits(np.minimum(hi * inv, 448.0)) & 0x7F
-    mag = codes & 0x7F
-    assert ((clo <= mag) & (mag <= chi)).all(), name
-    assert (((codes >> 7) == np.signbit(obn)) | (mag == 0)).all(), name
+    check_mx_pack(name, codes, scales, ob.float().numpy(), od.float().numpy(), exact, MARGINS)
 
 
 # ================================================================================================================ exact selection

@@ -34,8 +34,8 @@ Padding rows about which the header is silent (the twin run asserts only that th
                              decode to the box (0, 0, 0, 0) because fmaxf / fminf drop a NaN operand in the clamp to the image.
 Every other padding row has a documented value (-1, zeros, -inf, ABSENT) and is compared with the oracle.
 
-Coverage: every entry of include/ldit.h that takes a device pointer (70).  "here": this module, with the shapes; "fresh": through
-the whole path in tests/test_gpu_fresh_memory.py; "exempt": with the reason (7 of 70).
+Coverage: every entry of include/ldit.h that takes a device pointer (72).  "here": this module, with the shapes; "fresh": through
+the whole path in tests/test_gpu_fresh_memory.py; "exempt": with the reason (7 of 72).
   entry                          where   shapes / reason
   ldit_linear_f32                here    tiles 0..7 + auto + persistent panel; M 17..321 around each tile height, N 50 / 96 / 200 / 257, K 64 / 96
   ldit_linear_bf16               here    tiles 1..5 + auto; M 37 / 528 / 1040, the peeled tail at 16400 x 1024 (riding and own launch); K 64 / 192
@@ -59,6 +59,8 @@ the whole path in tests/test_gpu_fresh_memory.py; "exempt": with the reason (7 o
   ldit_layernorm_mxfp8           here    the same
   ldit_layernorm_mxfp8_train     here    the same
   ldit_layernorm_bwd_f32         here    the same; dh a += destination; scratch 0x00 / 0xFF
+  ldit_layernorm_bwd_resid_f32   here    the same, with and without rowscale; dh a += destination; scratch 0x00 / 0xFF
+  ldit_resid_bwd_bf16            here    the same, with and without rowscale; dh an input; scratch 0x00 / 0xFF
   ldit_colsum_f32                here    M 1 / 5 / 65 / 513, ldx > N; scratch 0x00 / 0xFF
   ldit_colamax_f32               here    the same
   ldit_split_f32_planes          here    rows 1 / 5 / 65, lds > cols
@@ -913,6 +915,76 @@ def test_layernorm_bwd_f32(rows, Cc):
     assert _rel(res.clean["dh"], dh0.double() + xt.grad) < 2e-5
     assert _rel(res.clean["dg"], gt.grad) < 2e-5 and _rel(res.clean["db"], bt.grad) < 2e-5
     _done(res, "dh", "dg", "db")
+
+
+def _resid_ref(dh, z, lam, rs):
+    gr = dh.double() * (1.0 if rs is None else rs.double()[:, None])
+    return gr * lam.double(), (gr * z.double()).sum(0), (gr * lam.double()).sum(0)
+
+
+def _resid_inputs(rows, Cc, rowscale):
+    z, lam = _bf(912, rows, Cc), _f32(913, Cc).abs() * 0.3 + 0.05
+    rs = ((torch.arange(rows) % 3 != 1).float() / 0.9) if rowscale else None
+    return z, lam, rs
+
+
+@pytest.mark.parametrize("rows,Cc", LN_SHAPES)
+@pytest.mark.parametrize("rowscale", [False, True])
+def test_layernorm_bwd_resid_f32(rows, Cc, rowscale):
+    """The fused LayerNorm + LayerScale backward: dh is a documented += destination, dz and the four vectors are overwritten, the
+    scratch is 0x00 / 0xFF.  C = 64 and 192 leave lanes of the wave without a vector (the gamma registers of those lanes)."""
+    lib = _lib.load()
+    x, g, _ = _ln_inputs(rows, Cc)
+    dy, dh0 = _f32(910, rows, Cc), _f32(911, rows, Cc)
+    z, lam, rs = _resid_inputs(rows, Cc, rowscale)
+    need = int(lib.ldit_layernorm_bwd_resid_scratch_bytes(rows, Cc))
+    s = {"dy": In(dy), "x": In(x), "g": In(g), "z": In(z), "lam": In(lam), "dh": Out((rows, Cc), F32, init=dh0),
+         "dz": Out((rows, Cc), BF), "dg": Out((Cc,), F32), "db": Out((Cc,), F32), "dlam": Out((Cc,), F32), "dzb": Out((Cc,), F32),
+         "scratch": Scratch(need)}
+    if rowscale:
+        s["rs"] = In(rs)
+
+    def call(t):
+        _lib.check(lib.ldit_layernorm_bwd_resid_f32(_p(t["dy"]), _p(t["x"]), _p(t["g"]), _p(t["z"]), _p(t["lam"]), _p(t.get("rs")),
+                                                    _p(t["dh"]), _p(t["dz"]), rows, Cc, 1e-12, _p(t["dg"]), _p(t["db"]), _p(t["dlam"]),
+                                                    _p(t["dzb"]), _p(t["scratch"]), need, _s()))
+
+    res = _twin(s, call)
+    xt, gt = x.double().requires_grad_(True), g.double().requires_grad_(True)
+    bt = torch.zeros(Cc, dtype=torch.float64, requires_grad=True)
+    (F.layer_norm(xt, (Cc,), gt, bt, 1e-12) * dy.double()).sum().backward()
+    dh_ref = dh0.double() + xt.grad
+    rdz, rdlam, rdzb = _resid_ref(dh_ref, z, lam, rs)
+    # test_gpu_train.py::test_layernorm_backward (fp32 outputs); dz is one bf16 rounding of an fp32-grade value
+    assert _rel(res.clean["dh"], dh_ref) < 2e-5
+    assert _rel(res.clean["dg"], gt.grad) < 2e-5 and _rel(res.clean["db"], bt.grad) < 2e-5
+    assert _rel(res.clean["dlam"], rdlam) < 2e-5 and _rel(res.clean["dzb"], rdzb) < 2e-5
+    assert _rel(res.clean["dz"], rdz) < 3e-3
+    _done(res, "dh", "dz", "dg", "db", "dlam", "dzb")
+
+
+@pytest.mark.parametrize("rows,Cc", LN_SHAPES)
+@pytest.mark.parametrize("rowscale", [False, True])
+def test_resid_bwd_bf16(rows, Cc, rowscale):
+    """The LayerScale / residual backward on its own: dh is only read; the scratch is 0x00 / 0xFF."""
+    lib = _lib.load()
+    dh = _f32(914, rows, Cc)
+    z, lam, rs = _resid_inputs(rows, Cc, rowscale)
+    need = int(lib.ldit_resid_bwd_scratch_bytes(rows, Cc))
+    s = {"dh": In(dh), "z": In(z), "lam": In(lam), "dz": Out((rows, Cc), BF), "dlam": Out((Cc,), F32), "db": Out((Cc,), F32),
+         "scratch": Scratch(need)}
+    if rowscale:
+        s["rs"] = In(rs)
+
+    def call(t):
+        _lib.check(lib.ldit_resid_bwd_bf16(_p(t["dh"]), _p(t["z"]), _p(t["lam"]), _p(t.get("rs")), _p(t["dz"]), rows, Cc, _p(t["dlam"]),
+                                           _p(t["db"]), _p(t["scratch"]), need, _s()))
+
+    res = _twin(s, call)
+    rdz, rdlam, rdb = _resid_ref(dh, z, lam, rs)
+    assert _rel(res.clean["dlam"], rdlam) < 2e-5 and _rel(res.clean["db"], rdb) < 2e-5
+    assert _rel(res.clean["dz"], rdz) < 3e-3
+    _done(res, "dz", "dlam", "db")
 
 
 @pytest.mark.parametrize("M,N", [(1, 64), (5, 192), (65, 64), (513, 96)])
