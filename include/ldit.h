@@ -436,6 +436,14 @@ int ldit_relu_bwd_bf16(const void *dy, int64_t lddy, const void *act, int64_t ld
                        void *colsum, void *scratch, size_t scratch_bytes, ldit_stream stream);
 int ldit_relu_bwd_pad_nhwc_bf16(const void *dy, const void *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, void *colsum,
                                 void *scratch, size_t scratch_bytes, ldit_stream stream);
+/* The two with act as bf16 - the activation as a forward under train_dtype="bf16" of the detector saves it - so no fp32 copy of it is
+ * made first.  A bf16 widens exactly: out and colsum are bit for bit those of the entry points above on the widened act.  Same
+ * arguments, results and refusals; only act's element type (ldact counts bf16 elements) and alignment differ: 2 bytes in the plain
+ * form (8 for its four-column path), 8 in the padded form. */
+int ldit_relu_bwd_bf16_act16(const void *dy, int64_t lddy, const void *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                             void *colsum, void *scratch, size_t scratch_bytes, ldit_stream stream);
+int ldit_relu_bwd_pad_nhwc_bf16_act16(const void *dy, const void *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, void *colsum,
+                                      void *scratch, size_t scratch_bytes, ldit_stream stream);
 
 /* ==== train step (BASELINE.json configs[2]: ViT-B/16 bs=64 bf16 forward + backward + AdamW) =============
  * Replaces, for the encoder, what the reference's loop runs through torch.autograd and torch.optim:

@@ -132,6 +132,8 @@ SIGNATURES = {
     "ldit_colamax_f32": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "ldit_relu_bwd_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "ldit_relu_bwd_pad_nhwc_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "ldit_relu_bwd_bf16_act16": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "ldit_relu_bwd_pad_nhwc_bf16_act16": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     # train step
     "ldit_flat_param_bytes": (_sz, [C.POINTER(LditCfg)]),
     "ldit_flat_param_layout": (C.c_int, [C.POINTER(LditCfg), C.POINTER(_i64), _i32]),

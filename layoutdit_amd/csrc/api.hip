@@ -968,6 +968,20 @@ int ldit_relu_bwd_pad_nhwc_bf16(const void *dy, const void *act, void *out, int6
                                          static_cast<hipStream_t>(stream));
 }
 
+int ldit_relu_bwd_bf16_act16(const void *dy, int64_t lddy, const void *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                             void *colsum, void *scratch, size_t scratch_bytes, ldit_stream stream)
+{
+    return launch_relu_bwd_bf16_act16(static_cast<const float *>(dy), lddy, act, ldact, out, ldout, M, N, static_cast<float *>(colsum),
+                                      static_cast<float *>(scratch), scratch_bytes, static_cast<hipStream_t>(stream));
+}
+
+int ldit_relu_bwd_pad_nhwc_bf16_act16(const void *dy, const void *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, void *colsum,
+                                      void *scratch, size_t scratch_bytes, ldit_stream stream)
+{
+    return launch_relu_bwd_pad_nhwc_bf16_act16(static_cast<const float *>(dy), act, out, B, H, W, C, static_cast<float *>(colsum),
+                                               static_cast<float *>(scratch), scratch_bytes, static_cast<hipStream_t>(stream));
+}
+
 int ldit_cast_f16_f32(const void *src, void *dst, int64_t n, ldit_stream stream)
 {
     if (n < 0 || (n && (!src || !dst))) return fail(LDIT_EINVAL, "cast: null operand");

@@ -11,7 +11,8 @@
 //        (2) fp32 NHWC -> zero-padded bf16 NHWC copies for (wgrad),
 //        (3) column sums (bias gradients), two stages, fixed order - no atomics anywhere, every result bit-reproducible,
 //        (4) for grad_dtype="bf16" of the detector: a ReLU's backward, (2) or the plain bf16 copy, and stage 1 of (3) as one pass
-//            over dy and the activation - the copy is the operand of the layer's dgrad AND wgrad GEMM.
+//            over dy and the activation - the copy is the operand of the layer's dgrad AND wgrad GEMM.  The activation is fp32
+//            or, for train_dtype="bf16" of the detector, the bf16 tensor its forward saved (the *_act16 entry points).
 #include "ldit_common.h"
 
 namespace ldit {
@@ -185,18 +186,23 @@ constexpr int RB_GROUPS = 4;                                         // 16 rows 
 template <int V> struct cols_t { typedef float f; };                 // the V adjacent columns of a thread
 template <> struct cols_t<4> { typedef f32x4 f; };
 
-// w = act > 0 ? dy : 0 - a selection (threshold_backward): a masked non-finite dy is 0, act = +-0 or NaN masks.  ACT = false: w = dy
-template <int V, bool ACT> __device__ __forceinline__ typename cols_t<V>::f relu_bwd_load(const float *__restrict__ dy, const float *__restrict__ act)
+template <typename A, int V> struct act_cols_t { typedef typename cols_t<V>::f t; };    // V adjacent elements of the activation
+template <> struct act_cols_t<__bf16, 1> { typedef __bf16 t; };
+template <> struct act_cols_t<__bf16, 4> { typedef bf16x4_t t; };                         // one 8-byte load
+
+// w = act > 0 ? dy : 0 - a selection (threshold_backward): a masked non-finite dy is 0, act = +-0 or NaN masks.  ACT = false: w = dy.
+// A: the activation's element type, float or __bf16 - a bf16 widens exactly (subnormals kept), so the mask is that of its fp32 copy
+template <int V, bool ACT, typename A> __device__ __forceinline__ typename cols_t<V>::f relu_bwd_load(const float *__restrict__ dy, const A *__restrict__ act)
 {
     typedef typename cols_t<V>::f F;
     F v = *reinterpret_cast<const F *>(dy);
     if constexpr (ACT) {
-        const F a = *reinterpret_cast<const F *>(act);
+        const auto a = *reinterpret_cast<const typename act_cols_t<A, V>::t *>(act);
         if constexpr (V == 4) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = a[e] > 0.f ? v[e] : 0.f;
+            for (int e = 0; e < 4; ++e) v[e] = (float)a[e] > 0.f ? v[e] : 0.f;
         } else {
-            v = a > 0.f ? v : 0.f;
+            v = (float)a > 0.f ? v : 0.f;
         }
     }
     return v;
@@ -210,15 +216,15 @@ template <int V> __device__ __forceinline__ void store_bf16(__bf16 *__restrict__
 
 // out[m, n] = bf16(w[m, n]); part[blockIdx.x][n] (part != nullptr) = colsum_stage1's partial of w: the grid of colsum_stage1 with V
 // columns per thread and blockDim.x threads per block
-template <int V, bool ACT>
-__global__ void __launch_bounds__(256) relu_bwd_bf16(const float *__restrict__ dy, const float *__restrict__ act, __bf16 *__restrict__ out,
+template <int V, bool ACT, typename A>
+__global__ void __launch_bounds__(256) relu_bwd_bf16(const float *__restrict__ dy, const A *__restrict__ act, __bf16 *__restrict__ out,
                                                      float *__restrict__ part, long M, int N, long lddy, long ldact, long ldout)
 {
     typedef typename cols_t<V>::f F;
     const long n = ((long)blockIdx.y * blockDim.x + threadIdx.x) * V;
     if (n >= N) return;
     const long m0 = (long)blockIdx.x * CS_ROWS, m1 = m0 + CS_ROWS < M ? m0 + CS_ROWS : M;
-    const F s = cs_block<false, RB_GROUPS, F>([&](long m) { return relu_bwd_load<V, ACT>(dy + m * lddy + n, act + m * ldact + n); },
+    const F s = cs_block<false, RB_GROUPS, F>([&](long m) { return relu_bwd_load<V, ACT, A>(dy + m * lddy + n, act + m * ldact + n); },
                                    [&](long m, F v) { store_bf16<V>(out + m * ldout + n, v); }, m0, m1);
     if (part) *reinterpret_cast<F *>(part + (long)blockIdx.x * N + n) = s;
 }
@@ -226,8 +232,8 @@ __global__ void __launch_bounds__(256) relu_bwd_bf16(const float *__restrict__ d
 // The same into the zero-padded map of pad_nhwc_bf16, out bf16 [B, H+2, W+2, C]: row m = (b, y, x) of dy lands on pixel
 // (b, y+1, x+1), and the thread that writes an interior pixel at the map's edge also writes the border pixels beside it (a corner
 // goes with the corner pixel) - every element of out is written exactly once.
-template <bool ACT>
-__global__ void __launch_bounds__(256) relu_bwd_pad_nhwc_bf16(const float *__restrict__ dy, const float *__restrict__ act,
+template <bool ACT, typename A>
+__global__ void __launch_bounds__(256) relu_bwd_pad_nhwc_bf16(const float *__restrict__ dy, const A *__restrict__ act,
                                                               __bf16 *__restrict__ out, float *__restrict__ part, int M, int H, int W, int C)
 {
     const int c = (blockIdx.y * blockDim.x + threadIdx.x) * 4;
@@ -235,7 +241,7 @@ __global__ void __launch_bounds__(256) relu_bwd_pad_nhwc_bf16(const float *__res
     const long m0 = (long)blockIdx.x * CS_ROWS, m1 = m0 + CS_ROWS < M ? m0 + CS_ROWS : (long)M;
     const long rs = (long)(W + 2) * C;                               // one padded row
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 s = cs_block<false, RB_GROUPS, f32x4>([&](long m) { return relu_bwd_load<4, ACT>(dy + m * C + c, act + m * C + c); },
+    const f32x4 s = cs_block<false, RB_GROUPS, f32x4>([&](long m) { return relu_bwd_load<4, ACT, A>(dy + m * C + c, act + m * C + c); },
                                            [&](long m, f32x4 v) {
         const int x = (int)m % W, t = (int)m / W, y = t % H, b = t / H;                   // (uniform over the workgroup)
         __bf16 *o = out + (((long)b * (H + 2) + y + 1) * (W + 2) + x + 1) * C + c;
@@ -336,52 +342,83 @@ static int relu_bwd_stage2(float *colsum, float *scratch, int64_t M, int N, hipS
     return LDIT_OK;
 }
 
-int launch_relu_bwd_bf16(const float *dy, int64_t lddy, const float *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
-                         float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream)
+// A: the activation's element type (float: the entry points of grad_dtype="bf16"; __bf16: their *_act16 forms); `name` heads the messages
+template <typename A>
+static int relu_bwd_bf16_any(const char *name, const float *dy, int64_t lddy, const A *act, int64_t ldact, void *out, int64_t ldout, int64_t M,
+                             int64_t N, float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream)
 {
-    if (M <= 0 || N <= 0 || lddy < N || ldout < N || (act && ldact < N)) return fail(LDIT_EINVAL, "relu_bwd_bf16: bad geometry");
-    if (!dy || !out || (colsum && !scratch)) return fail(LDIT_EINVAL, "relu_bwd_bf16: null operand");
+    if (M <= 0 || N <= 0 || lddy < N || ldout < N || (act && ldact < N)) return fail(LDIT_EINVAL, "%s: bad geometry", name);
+    if (!dy || !out || (colsum && !scratch)) return fail(LDIT_EINVAL, "%s: null operand", name);
     const auto addr = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
-    if ((addr(dy) & 3u) || (addr(act) & 3u) || (addr(out) & 1u) || (addr(colsum) & 3u) || (addr(scratch) & 3u))
-        return fail(LDIT_EINVAL, "relu_bwd_bf16: misaligned operand");
-    if (M >= (1ll << 31) || N >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "relu_bwd_bf16: 2^31 rows or columns or more");
+    if ((addr(dy) & 3u) || (addr(act) & (sizeof(A) - 1)) || (addr(out) & 1u) || (addr(colsum) & 3u) || (addr(scratch) & 3u))
+        return fail(LDIT_EINVAL, "%s: misaligned operand", name);
+    if (M >= (1ll << 31) || N >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "%s: 2^31 rows or columns or more", name);
     if (colsum && scratch_bytes < colsum_scratch_bytes(M, N))
-        return fail(LDIT_EWORKSPACE, "relu_bwd_bf16: scratch %zu bytes < required %zu", scratch_bytes, colsum_scratch_bytes(M, N));
+        return fail(LDIT_EWORKSPACE, "%s: scratch %zu bytes < required %zu", name, scratch_bytes, colsum_scratch_bytes(M, N));
     const unsigned P = (unsigned)((M + CS_ROWS - 1) / CS_ROWS);
     float *part = colsum ? scratch : nullptr;
     __bf16 *o = static_cast<__bf16 *>(out);
-    // four columns per thread where every row of every operand starts on a vector boundary
-    const bool vec = !(N & 3) && !(lddy & 3) && !(ldout & 3) && (!act || !(ldact & 3)) && aligned16(dy) && (!act || aligned16(act)) &&
+    // four columns per thread where every row of every operand starts on a vector boundary (act: four of its elements)
+    const bool vec = !(N & 3) && !(lddy & 3) && !(ldout & 3) && (!act || !(ldact & 3)) && aligned16(dy) && !(addr(act) & (4 * sizeof(A) - 1)) &&
                      !(addr(out) & 7u) && (!part || aligned16(part));
     const int64_t cols = vec ? N / 4 : N;
     const unsigned th = relu_bwd_threads(cols);
     const dim3 grid(P, (unsigned)((cols + th - 1) / th));
-    if (grid.y > 65535u) return fail(LDIT_EUNSUPPORTED, "relu_bwd_bf16: too many columns");
-    auto kernel = vec ? (act ? relu_bwd_bf16<4, true> : relu_bwd_bf16<4, false>) : (act ? relu_bwd_bf16<1, true> : relu_bwd_bf16<1, false>);
+    if (grid.y > 65535u) return fail(LDIT_EUNSUPPORTED, "%s: too many columns", name);
+    auto kernel = vec ? (act ? relu_bwd_bf16<4, true, A> : relu_bwd_bf16<4, false, A>) : (act ? relu_bwd_bf16<1, true, A> : relu_bwd_bf16<1, false, A>);
     hipLaunchKernelGGL(kernel, grid, dim3(th), 0, stream, dy, act, o, part, (long)M, (int)N, (long)lddy, (long)ldact, (long)ldout);
     return relu_bwd_stage2(colsum, scratch, M, (int)N, stream);
+}
+
+template <typename A>
+static int relu_bwd_pad_nhwc_bf16_any(const char *name, const float *dy, const A *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C,
+                                      float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return fail(LDIT_EINVAL, "%s: bad geometry", name);
+    if (!dy || !out || (colsum && !scratch)) return fail(LDIT_EINVAL, "%s: null operand", name);
+    if (!aligned16(dy) || (reinterpret_cast<uintptr_t>(act) & (4 * sizeof(A) - 1)) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
+        (colsum && (!aligned16(scratch) || (reinterpret_cast<uintptr_t>(colsum) & 3u))))
+        return fail(LDIT_EINVAL, "%s: misaligned operand", name);
+    const int64_t lim = 1ll << 31;
+    // (each factor first: the products below stay inside 64 bits)
+    if (B >= lim || H >= lim || W >= lim || C >= lim || B * H >= lim || B * H * W >= lim || (B * (H + 2)) * (W + 2) >= lim ||
+        (B * (H + 2)) * (W + 2) * C >= (1ll << 33))
+        return fail(LDIT_EUNSUPPORTED, "%s: 2^31 pixel rows or a padded map of 2^33 elements or more", name);
+    const int64_t M = B * H * W;
+    if (colsum && scratch_bytes < colsum_scratch_bytes(M, C))
+        return fail(LDIT_EWORKSPACE, "%s: scratch %zu bytes < required %zu", name, scratch_bytes, colsum_scratch_bytes(M, C));
+    const unsigned P = (unsigned)((M + CS_ROWS - 1) / CS_ROWS), th = relu_bwd_threads(C / 4);
+    if ((C / 4 + th - 1) / th > 65535) return fail(LDIT_EUNSUPPORTED, "%s: too many channels", name);
+    auto kernel = act ? relu_bwd_pad_nhwc_bf16<true, A> : relu_bwd_pad_nhwc_bf16<false, A>;
+    hipLaunchKernelGGL(kernel, dim3(P, (unsigned)((C / 4 + th - 1) / th)), dim3(th), 0, stream, dy, act, static_cast<__bf16 *>(out),
+                       colsum ? scratch : nullptr, (int)M, (int)H, (int)W, (int)C);
+    return relu_bwd_stage2(colsum, scratch, M, (int)C, stream);
+}
+
+int launch_relu_bwd_bf16(const float *dy, int64_t lddy, const float *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                         float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    return relu_bwd_bf16_any("relu_bwd_bf16", dy, lddy, act, ldact, out, ldout, M, N, colsum, scratch, scratch_bytes, stream);
 }
 
 int launch_relu_bwd_pad_nhwc_bf16(const float *dy, const float *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, float *colsum,
                                   float *scratch, size_t scratch_bytes, hipStream_t stream)
 {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return fail(LDIT_EINVAL, "relu_bwd_pad_nhwc_bf16: bad geometry");
-    if (!dy || !out || (colsum && !scratch)) return fail(LDIT_EINVAL, "relu_bwd_pad_nhwc_bf16: null operand");
-    if (!aligned16(dy) || (act && !aligned16(act)) || (reinterpret_cast<uintptr_t>(out) & 7u) || (colsum && (!aligned16(scratch) || (reinterpret_cast<uintptr_t>(colsum) & 3u))))
-        return fail(LDIT_EINVAL, "relu_bwd_pad_nhwc_bf16: misaligned operand");
-    const int64_t lim = 1ll << 31;
-    // (each factor first: the products below stay inside 64 bits)
-    if (B >= lim || H >= lim || W >= lim || C >= lim || B * H >= lim || B * H * W >= lim || (B * (H + 2)) * (W + 2) >= lim ||
-        (B * (H + 2)) * (W + 2) * C >= (1ll << 33))
-        return fail(LDIT_EUNSUPPORTED, "relu_bwd_pad_nhwc_bf16: 2^31 pixel rows or a padded map of 2^33 elements or more");
-    const int64_t M = B * H * W;
-    if (colsum && scratch_bytes < colsum_scratch_bytes(M, C))
-        return fail(LDIT_EWORKSPACE, "relu_bwd_pad_nhwc_bf16: scratch %zu bytes < required %zu", scratch_bytes, colsum_scratch_bytes(M, C));
-    const unsigned P = (unsigned)((M + CS_ROWS - 1) / CS_ROWS), th = relu_bwd_threads(C / 4);
-    if ((C / 4 + th - 1) / th > 65535) return fail(LDIT_EUNSUPPORTED, "relu_bwd_pad_nhwc_bf16: too many channels");
-    hipLaunchKernelGGL(act ? relu_bwd_pad_nhwc_bf16<true> : relu_bwd_pad_nhwc_bf16<false>, dim3(P, (unsigned)((C / 4 + th - 1) / th)), dim3(th), 0, stream, dy, act, static_cast<__bf16 *>(out),
-                       colsum ? scratch : nullptr, (int)M, (int)H, (int)W, (int)C);
-    return relu_bwd_stage2(colsum, scratch, M, (int)C, stream);
+    return relu_bwd_pad_nhwc_bf16_any("relu_bwd_pad_nhwc_bf16", dy, act, out, B, H, W, C, colsum, scratch, scratch_bytes, stream);
+}
+
+int launch_relu_bwd_bf16_act16(const float *dy, int64_t lddy, const void *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                               float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    return relu_bwd_bf16_any("relu_bwd_bf16_act16", dy, lddy, static_cast<const __bf16 *>(act), ldact, out, ldout, M, N, colsum, scratch,
+                             scratch_bytes, stream);
+}
+
+int launch_relu_bwd_pad_nhwc_bf16_act16(const float *dy, const void *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, float *colsum,
+                                        float *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    return relu_bwd_pad_nhwc_bf16_any("relu_bwd_pad_nhwc_bf16_act16", dy, static_cast<const __bf16 *>(act), out, B, H, W, C, colsum, scratch,
+                                      scratch_bytes, stream);
 }
 
 }  // namespace ldit

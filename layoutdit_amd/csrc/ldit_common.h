@@ -299,6 +299,11 @@ int launch_relu_bwd_bf16(const float *dy, int64_t lddy, const float *act, int64_
                          float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream);
 int launch_relu_bwd_pad_nhwc_bf16(const float *dy, const float *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, float *colsum,
                                   float *scratch, size_t scratch_bytes, hipStream_t stream);
+// the same with a bf16 `act` (the activation as a bf16 forward saved it): only its element type and alignment differ
+int launch_relu_bwd_bf16_act16(const float *dy, int64_t lddy, const void *act, int64_t ldact, void *out, int64_t ldout, int64_t M, int64_t N,
+                               float *colsum, float *scratch, size_t scratch_bytes, hipStream_t stream);
+int launch_relu_bwd_pad_nhwc_bf16_act16(const float *dy, const void *act, void *out, int64_t B, int64_t H, int64_t W, int64_t C, float *colsum,
+                                        float *scratch, size_t scratch_bytes, hipStream_t stream);
 int launch_gemm_bf16(const void *A, int lda, const void *W, const float *bias, void *Y, int ldy, int M, int N, int K, int epi,
                      const float *lam, const float *R, float *Y2, hipStream_t stream);
 int launch_gemm_bf16_ex(const void *A, int lda, const void *W, const float *bias, void *Y, int ldy, int M, int N, int K, int epi,

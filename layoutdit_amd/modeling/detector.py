@@ -21,7 +21,7 @@ import torch.nn as nn
 from ..config import DiTConfig
 from .detector_input import DetectorInputTransform
 from .dit_fpn import DiTWithFPN
-from .grad_ops import check_grad_dtype, check_neck_dtype
+from .grad_ops import check_grad_dtype, check_neck_dtype, check_train_dtype
 from .roi_heads import FastRCNNPredictor, MultiScaleRoIAlign, RoIHeads, TwoMLPHead, _check_head_dtype, _nhwc_f32
 from .rpn import AnchorGenerator, RegionProposalNetwork, RPNHead
 
@@ -33,21 +33,23 @@ class _FasterRCNN(nn.Module):
     (``transform`` holds no parameter)."""
 
     def __init__(self, backbone: DiTWithFPN, num_classes: int, anchor_generator: AnchorGenerator, fixed_size=(224, 224),
-                 head_dtype: str = "f32", neck_dtype: str = "f32", grad_dtype: str = "f32"):
+                 head_dtype: str = "f32", neck_dtype: str = "f32", grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
         self.transform = DetectorInputTransform(fixed_size=tuple(fixed_size), image_mean=(0.5, 0.5, 0.5), image_std=(0.5, 0.5, 0.5))
         self.backbone = backbone
         c = backbone.out_channels
         self.rpn = RegionProposalNetwork(anchor_generator, RPNHead(c, anchor_generator.num_anchors_per_location()[0], neck_dtype=neck_dtype,
-                                                                           grad_dtype=grad_dtype))
+                                                                           grad_dtype=grad_dtype, train_dtype=train_dtype))
         pool = MultiScaleRoIAlign(FEATMAP_NAMES, output_size=7, sampling_ratio=2)
-        self.roi_heads = RoIHeads(pool, TwoMLPHead(c * 7 * 7, 1024, grad_dtype=grad_dtype), FastRCNNPredictor(1024, num_classes), head_dtype=head_dtype)
+        self.roi_heads = RoIHeads(pool, TwoMLPHead(c * 7 * 7, 1024, grad_dtype=grad_dtype, train_dtype=train_dtype),
+                                  FastRCNNPredictor(1024, num_classes), head_dtype=head_dtype)
 
 
 class LayoutDetectionModel(nn.Module):
     def __init__(self, num_classes: int = 5, anchor_sizes=((32,), (64,), (128,), (256,), (512,)),
                  aspect_ratios=((0.5, 1.0, 2.0),) * 5, config: Optional[DiTConfig] = None, compute_dtype: str = "f32",
-                 fixed_size: Tuple[int, int] = (224, 224), head_dtype: str = "f32", neck_dtype: str = "f32", grad_dtype: str = "f32"):
+                 fixed_size: Tuple[int, int] = (224, 224), head_dtype: str = "f32", neck_dtype: str = "f32", grad_dtype: str = "f32",
+                 train_dtype: str = "f32"):
         """``num_classes`` counts the foreground classes (the reference adds the background itself, ref model.py:47); the anchor
         defaults are the reference's ``ModelConfig``.  ``compute_dtype`` selects the encoder build; the box head is fp32 in every build
         unless ``head_dtype="bf16"`` (eval mode only: bf16 pooled rows and bf16 GEMMs with fp32 accumulation behind the fp32 maps; the
@@ -58,16 +60,23 @@ class LayoutDetectionModel(nn.Module):
         (the encoder's own check).  ``grad_dtype="bf16"`` (default ``"f32"``) concerns the backward alone: the input-gradient GEMMs of the
         FPN, the RPN head and the box head run on the bf16 MFMA GEMM (bf16 operand rounding, fp32 accumulation - what every weight
         gradient of the detector has under either setting); every forward, hence every loss, sampled anchor and proposal, keeps its
-        bits, and eval mode and ``no_grad`` never read it."""
+        bits, and eval mode and ``no_grad`` never read it.  ``train_dtype="bf16"`` (default ``"f32"``) concerns the forward where a
+        gradient is wanted - ``losses`` / ``rpn_losses`` in train mode: the FPN's and the RPN head's 3x3 convolutions, the RPN head's
+        1x1 pair, fc6, fc7 and the box predictor run as ``neck_dtype`` / ``head_dtype="bf16"`` run them in eval mode (bf16 operand
+        rounding, fp32 accumulation), and the backward reads the bf16 tensors that forward saved; eval mode and ``no_grad`` never read
+        it, and it is independent of the other three options."""
         super().__init__()
         _check_head_dtype(head_dtype)
         check_neck_dtype(neck_dtype)
         check_grad_dtype(grad_dtype)
+        check_train_dtype(train_dtype)
         if len(set(len(s) * len(r) for s, r in zip(anchor_sizes, aspect_ratios))) != 1:
             raise ValueError("LayoutDetectionModel: every level must have the same number of anchors per location (one RPN head)")
-        backbone = DiTWithFPN(pretrained=False, config=config, compute_dtype=compute_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype)
+        backbone = DiTWithFPN(pretrained=False, config=config, compute_dtype=compute_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype,
+                              train_dtype=train_dtype)
         self.model = _FasterRCNN(backbone, int(num_classes) + 1, AnchorGenerator(sizes=anchor_sizes, aspect_ratios=aspect_ratios),
-                                 fixed_size=fixed_size, head_dtype=head_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype)
+                                 fixed_size=fixed_size, head_dtype=head_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype,
+                                 train_dtype=train_dtype)
 
     @property
     def head_dtype(self) -> str:
@@ -101,6 +110,19 @@ class LayoutDetectionModel(nn.Module):
         self.model.backbone.set_grad_dtype(grad_dtype)
         self.model.rpn.head.set_grad_dtype(grad_dtype)
         self.model.roi_heads.set_grad_dtype(grad_dtype)
+        return self
+
+    @property
+    def train_dtype(self) -> str:
+        return self.model.backbone.train_dtype
+
+    def set_train_dtype(self, train_dtype: str) -> "LayoutDetectionModel":
+        """``"f32"`` or ``"bf16"``: the matrix pipe of the FPN's, the RPN head's and the box head's forward from now on where a gradient
+        is wanted, on the same weights.  Eval mode and ``no_grad`` do not change."""
+        check_train_dtype(train_dtype)                                # refused before any stage changes
+        self.model.backbone.set_train_dtype(train_dtype)
+        self.model.rpn.head.set_train_dtype(train_dtype)
+        self.model.roi_heads.set_train_dtype(train_dtype)
         return self
 
     def forward_padded(self, batch: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -33,6 +33,12 @@ and merges stay fp32, parameters stay fp32, the ``state_dict`` does not depend o
 ``grad_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_grad_dtype`) concerns :class:`_FPNFn`'s backward alone: the dgrad GEMMs
 of the four 3x3 convolutions and of the four laterals run on the bf16 MFMA GEMM, on the bf16 copy of the incoming gradient that the
 wgrad reads (``grad_ops.conv3x3_bwd`` / ``linear_bwd``).  No forward reads the option.
+
+``train_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_train_dtype`) concerns :class:`_FPNFn`'s forward alone, the path that
+wants a gradient: its four 3x3 output convolutions run as the eval path under ``neck_dtype="bf16"`` runs them - the same kernel on the
+same cached bf16 weights, bit-equal maps - on a zero-padded bf16 copy of each merged map that carries the slack rows of the wgrad
+taps, so the backward reads that one buffer again and neither saves the fp32 merged maps nor pads them a second time (DESIGN section
+32).  Laterals and merges stay fp32.  Eval mode and ``no_grad`` never read it.
 """
 from __future__ import annotations
 
@@ -47,8 +53,8 @@ import torch.nn as nn
 from .. import _lib, ops
 from ..config import DiTConfig
 from .dit_backbone import DiTBackbone
-from .grad_ops import (ParamCache, check_grad_dtype, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, conv3x3_dgrad_bf16, linear_bwd,
-                       linear_dgrad_bf16, param_key)
+from .grad_ops import (BF16_K, ParamCache, check_grad_dtype, check_neck_dtype, check_train_dtype, conv3x3_bf16, conv3x3_bwd,
+                       conv3x3_dgrad_bf16, linear_bwd, linear_dgrad_bf16, padded_middle, param_key)
 
 
 class _Conv(nn.Sequential):
@@ -70,21 +76,30 @@ class _FPNParams(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
 
-def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool, bf16_conv: bool = False):
+def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool, bf16_conv: bool = False,
+                 train_w16=None):
     """The stage on fp32 contiguous token tensors [B, 1+P, C]; returns NHWC outputs (coarsest last) and, for the backward,
     the four merged maps.  ``bf16_conv`` (the eval path under ``neck_dtype="bf16"``): ``conv_w_ohwi`` holds bf16 copies and the 3x3
-    convolutions run on the bf16 MFMA GEMM - laterals, merges and the fp32 NHWC results are what they are without it."""
+    convolutions run on the bf16 MFMA GEMM - laterals, merges and the fp32 NHWC results are what they are without it.
+    ``train_w16`` (:class:`_FPNFn` under ``train_dtype="bf16"``): a callable giving level i's cached bf16 weight; a level whose channel
+    count the bf16 GEMM takes runs that same convolution on the slack-padded bf16 copy of its merged map, and that copy is what is
+    kept for the backward in the map's place."""
     B, T, Cc = toks[0].shape
     lats = [ops.linear(toks[i].reshape(B * T, Cc), lat_w[i], lat_b[i]).view(B, T, -1) for i in range(4)]
     inner, outs, inners = None, [None] * 4, [None] * 4
     for i in (3, 2, 1, 0):                                            # coarsest first (top-down)
         inner = ops.fpn_merge(lats[i], gh, gw, bb_scales[i], top=inner)
-        if bf16_conv:
+        kept = inner
+        if train_w16 is not None and inner.shape[3] % BF16_K == 0:
+            Bi, h, w, _ = inner.shape
+            kept = ops.pad_nhwc_bf16(inner, slack_rows=w + 3)
+            outs[i] = ops.conv3x3_nhwc_bf16(padded_middle(kept, Bi, h, w), Bi, h, w, train_w16(i), conv_b[i], _lib.EPI_F32).view(Bi, h, w, -1)
+        elif bf16_conv:
             outs[i] = conv3x3_bf16(inner, conv_w_ohwi[i], conv_b[i], _lib.EPI_F32).view(*inner.shape[:3], -1)
         else:
             outs[i] = ops.conv3x3_nhwc(inner, conv_w_ohwi[i], conv_b[i])
         if keep_inner:
-            inners[i] = inner
+            inners[i] = kept
     return outs, inners
 
 
@@ -92,27 +107,32 @@ class _FPNFn(torch.autograd.Function):
     """p2..p5 = FPN(taps) with gradients for the taps and for every FPN parameter.
     apply(geom, t0..t3, lw0, lb0, .. lw3, lb3, cw0, cb0, .. cw3, cb3) -> (p2, p3, p4, p5) as [B, 256, h, w] channels-last views.
     ``geom``: ``(gh, gw, scales)`` or ``(gh, gw, scales, grad_dtype, dgrad)`` - the stage's option and its cached
-    :meth:`DiTWithFPN._dgrad_operands_bf16` as a callable ``dgrad(kind, i)``; the forward does not read them."""
+    :meth:`DiTWithFPN._dgrad_operands_bf16` as a callable ``dgrad(kind, i)``; the forward does not read them.  Two more entries,
+    ``(.., train_dtype, conv16)``, are the forward's option and the cached :meth:`DiTWithFPN._ohwi_bf16` as a callable ``conv16(i)``."""
 
     @staticmethod
     def forward(ctx, geom, *args):
         gh, gw, scales = geom[:3]
+        train_w16 = geom[6] if len(geom) > 5 and check_train_dtype(geom[5]) == "bf16" else None
         toks = [_f32c(t.detach()) for t in args[0:4]]
         lw = [args[4 + 2 * i].detach() for i in range(4)]
         lb = [args[5 + 2 * i].detach() for i in range(4)]
         cw = [args[12 + 2 * i].detach() for i in range(4)]
         cb = [args[13 + 2 * i].detach() for i in range(4)]
         Ch, Cc = lw[0].shape[0], toks[0].shape[2]
+        bf16 = [train_w16 is not None and w.shape[1] % BF16_K == 0 for w in cw]       # (such a level reads no fp32 re-layout)
         outs, inners = _fpn_forward(scales, gh, gw, toks, [w.reshape(Ch, Cc) for w in lw], lb,
-                                    [w.permute(0, 2, 3, 1).contiguous() for w in cw], cb, keep_inner=True)
+                                    [None if b else w.permute(0, 2, 3, 1).contiguous() for w, b in zip(cw, bf16)], cb, keep_inner=True,
+                                    train_w16=train_w16)
         ctx.geom = geom
+        ctx.shapes = [tuple(o.shape) for o in outs]                   # of the merged maps too: the 3x3 keeps the channel count
         ctx.toks, ctx.inners, ctx.lw, ctx.cw = toks, inners, lw, cw
         return tuple(o.permute(0, 3, 1, 2) for o in outs)
 
     @staticmethod
     def backward(ctx, *dps):
         gh, gw, scales = ctx.geom[:3]
-        grad_dtype, dgrad = ctx.geom[3:] if len(ctx.geom) > 3 else ("f32", None)
+        grad_dtype, dgrad = ctx.geom[3:5] if len(ctx.geom) > 3 else ("f32", None)
         operand = (lambda kind, i: None) if dgrad is None else (lambda kind, i: partial(dgrad, kind, i))
         if ctx.inners is None:
             raise RuntimeError("DiTWithFPN: backward through the FPN a second time (its saved maps are freed after the first)")
@@ -132,7 +152,7 @@ class _FPNFn(torch.autograd.Function):
                 d_inner[i], g_cw[i], g_cb[i] = conv3x3_bwd(dy, inners[i], cw[i], True, need[12 + 2 * i], need[13 + 2 * i], grad_dtype,
                                                            dgrad_w=operand("conv", i))
             else:
-                d_inner[i] = torch.zeros_like(inners[i])
+                d_inner[i] = torch.zeros(ctx.shapes[i], device=toks[0].device, dtype=torch.float32)
             if i > 0:
                 ops.fpn_merge_bwd(d_inner[i - 1], gh, gw, scales[i - 1], d_top=d_inner[i], want_lat=False)
             inners[i] = None
@@ -160,10 +180,11 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 
 class DiTWithFPN(nn.Module):
     def __init__(self, pretrained: bool = False, config: Optional[DiTConfig] = None, checkpoint: Optional[str] = None,
-                 compute_dtype: str = "f32", qat: bool = False, neck_dtype: str = "f32", grad_dtype: str = "f32"):
+                 compute_dtype: str = "f32", qat: bool = False, neck_dtype: str = "f32", grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
         self.neck_dtype = check_neck_dtype(neck_dtype)
         self.grad_dtype = check_grad_dtype(grad_dtype)
+        self.train_dtype = check_train_dtype(train_dtype)
         self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype, qat=qat)
         self.fpn = _FPNParams([self.backbone.hidden_size] * 4, 256)
         self.out_channels = 256
@@ -176,6 +197,13 @@ class DiTWithFPN(nn.Module):
         output convolutions, four laterals; ``grad_ops.conv3x3_bwd`` / ``linear_bwd``).  Forward, parameters and ``state_dict`` do not
         depend on it; the encoder below has its own ``compute_dtype``."""
         self.grad_dtype = check_grad_dtype(grad_dtype)
+        return self
+
+    def set_train_dtype(self, train_dtype: str) -> "DiTWithFPN":
+        """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where a gradient IS wanted (:class:`_FPNFn`'s
+        forward), on the same weights - ``"bf16"``: as ``neck_dtype="bf16"`` runs them where none is.  Parameters and ``state_dict`` do
+        not depend on it; eval mode and ``no_grad`` never read it."""
+        self.train_dtype = check_train_dtype(train_dtype)
         return self
 
     def _dgrad_operands_bf16(self, kind: str, i: int) -> torch.Tensor:
@@ -221,7 +249,8 @@ class DiTWithFPN(nn.Module):
                 args += [m.weight, m.bias]
             for m in conv:
                 args += [m.weight, m.bias]
-            results = list(_FPNFn.apply((gh, gw, tuple(bb.scales), self.grad_dtype, self._dgrad_operands_bf16), *args))
+            results = list(_FPNFn.apply((gh, gw, tuple(bb.scales), self.grad_dtype, self._dgrad_operands_bf16, self.train_dtype,
+                                         self._ohwi_bf16), *args))
         else:
             Cc = bb.hidden_size
             bf16_conv = self.neck_dtype == "bf16"

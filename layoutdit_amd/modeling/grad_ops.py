@@ -27,6 +27,23 @@ def check_grad_dtype(grad_dtype: str) -> str:
     return grad_dtype
 
 
+TRAIN_DTYPES = ("f32", "bf16")
+
+
+def check_train_dtype(train_dtype: str) -> str:
+    """The option of the FPN, the RPN head, the box head and the detector that holds them: the matrix pipe of their forward where a
+    gradient is wanted (the GEMMs that ``neck_dtype`` / ``head_dtype`` move where none is)."""
+    if train_dtype not in TRAIN_DTYPES:
+        raise ValueError(f"train_dtype {train_dtype!r}: the detector's training forward is built for {' and '.join(repr(d) for d in TRAIN_DTYPES)}")
+    return train_dtype
+
+
+def padded_middle(x_p: torch.Tensor, B: int, h: int, w: int) -> torch.Tensor:
+    """The padded map ``[B (h+2) (w+2), C]`` inside ``ops.pad_nhwc_bf16(x, slack_rows=w + 3)`` - what ``ops.conv3x3_nhwc_bf16`` reads;
+    the whole buffer is what the nine wgrad taps of :func:`conv3x3_bwd` read."""
+    return x_p[w + 3:w + 3 + B * (h + 2) * (w + 2)]
+
+
 def conv3x3_dgrad_bf16(weight_oihw: torch.Tensor) -> torch.Tensor:
     """The bf16 operand of a 3x3 convolution's dgrad under ``grad_dtype="bf16"``: :func:`flip_ihwo` rounded to bf16."""
     return ops.cast_bf16(flip_ihwo(weight_oihw))
@@ -50,8 +67,14 @@ def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.
     bf16 copy and sums ``g_b``; that copy is the operand of the wgrad taps - ``g_w`` and ``g_b`` have the bits of the ``"f32"``
     setting - and of ``g_x = ldit_conv3x3_nhwc_bf16(copy, dgrad_w)``: bf16 operand rounding, fp32 accumulation, fp32 result.
     ``dgrad_w``: a callable returning the cached :func:`conv3x3_dgrad_bf16` of the weight (made here without one).  A ``Cout`` that
-    is no multiple of 64 - the bf16 GEMM's k-tile - stays on the fp32 GEMM: every launch of the ``"f32"`` setting."""
+    is no multiple of 64 - the bf16 GEMM's k-tile - stays on the fp32 GEMM: every launch of the ``"f32"`` setting.
+
+    What a forward under ``train_dtype="bf16"`` saved is read as it stands: a bf16 ``x_nhwc`` is the slack-padded copy
+    ``ops.pad_nhwc_bf16(x, slack_rows=w + 3)`` the forward convolved (no pad launch here), a bf16 ``act`` is the mask without an fp32
+    copy of it.  Every gradient has the bits of the call on their fp32 widenings."""
     B, h, w, Cout = dy_nhwc.shape
+    if act is not None:
+        act = act.view(dy_nhwc.shape)
     bf16 = check_grad_dtype(grad_dtype) == "bf16" and Cout % BF16_K == 0
     if bf16:
         dy_p, g_b = ops.relu_bwd_pad_nhwc_bf16(dy_nhwc, act, want_colsum=need_b)
@@ -69,14 +92,16 @@ def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.
         slack = w + 3
         if not bf16:
             dy_p = ops.pad_nhwc_bf16(dy_nhwc)
-        x_p = ops.pad_nhwc_bf16(x_nhwc, slack_rows=slack)
+        x_p = x_nhwc if x_nhwc.dtype == torch.bfloat16 else ops.pad_nhwc_bf16(x_nhwc, slack_rows=slack)
         K = dy_p.shape[0]
+        if x_p.dim() != 2 or x_p.shape[0] != K + 2 * slack:
+            raise ValueError(f"conv3x3_bwd: a bf16 x {tuple(x_p.shape)} is not the padded copy [{K} + 2 * {slack}, Cin] of the convolution's input")
         taps = []
         for ky in range(3):
             for kx in range(3):
                 shift = (ky - 1) * (w + 2) + (kx - 1)
                 taps.append(ops.wgrad_bf16(dy_p, x_p, K, w_row_offset=slack + shift))      # [co, ci]
-        g_w = torch.stack(taps, dim=2).view(Cout, x_nhwc.shape[3], 3, 3)                    # [co, ci, ky, kx] (layout plumbing)
+        g_w = torch.stack(taps, dim=2).view(Cout, x_p.shape[1], 3, 3)                        # [co, ci, ky, kx] (layout plumbing)
     return g_x, g_w, g_b
 
 
@@ -95,13 +120,17 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: 
     and of ``g_x = ldit_linear_bf16_ex(copy, dgrad_w)`` with ``LDIT_EPI_F32``, any M: bf16 operand rounding, fp32 accumulation, fp32
     result.  ``dgrad_w``: a callable returning the cached :func:`linear_dgrad_bf16` of the weight (made here without one).  A
     reduction length N that is no multiple of 64 - the bf16 GEMM's k-tile; the 32 padded columns of the box predictor and of the
-    RPN head's 1x1 pair, a few GFLOP - stays on the fp32 GEMM: every launch of the ``"f32"`` setting."""
+    RPN head's 1x1 pair, a few GFLOP - stays on the fp32 GEMM: every launch of the ``"f32"`` setting.
+
+    A bf16 ``x`` (the layer's input as a forward under ``train_dtype="bf16"`` saved it) is the wgrad's operand as it stands - no cast
+    launch - and a bf16 ``act`` the mask without an fp32 copy of it: every gradient has the bits of the call on their fp32 widenings."""
+    x16 = (lambda: x) if x.dtype == torch.bfloat16 else (lambda: ops.cast_bf16(x))
     if check_grad_dtype(grad_dtype) == "bf16" and dy.shape[1] % BF16_K == 0 and weight.shape[0] == dy.shape[1]:
         dy16, g_b = ops.relu_bwd_bf16(dy, act, want_colsum=need_b)
         g_x = None
         if need_x:
             g_x = ops.linear_bf16(dy16, dgrad_w() if dgrad_w is not None else linear_dgrad_bf16(weight), None, _lib.EPI_F32)
-        g_w = ops.wgrad_bf16(dy16, ops.cast_bf16(x), dy.shape[0]) if need_w else None
+        g_w = ops.wgrad_bf16(dy16, x16(), dy.shape[0]) if need_w else None
         return g_x, g_w, g_b
     if act is not None:
         dy = torch.where(act > 0, dy, 0.0)
@@ -113,7 +142,7 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: 
             wt = torch.zeros((weight.shape[1], dy.shape[1]), device=dy.device, dtype=torch.float32)
             wt[:, :weight.shape[0]] = weight.t()
         g_x = ops.linear(dy, wt)
-    g_w = ops.wgrad_bf16(ops.cast_bf16(dy), ops.cast_bf16(x), dy.shape[0]) if need_w else None
+    g_w = ops.wgrad_bf16(ops.cast_bf16(dy), x16(), dy.shape[0]) if need_w else None
     g_b = ops.colsum(dy) if need_b else None
     return g_x, g_w, g_b
 

@@ -39,6 +39,14 @@ says.
 :class:`_TwoMLPHeadFn`'s backward alone: per layer one launch masks the incoming gradient by the ReLU, writes its bf16 copy and sums
 the bias gradient, and fc7's and fc6's dgrad run on the bf16 MFMA GEMM on that copy (``grad_ops.linear_bwd``).
 The predictor's dgrad (32 padded columns), RoIAlign's backward and the losses stay fp32.
+
+``train_dtype="bf16"`` (default ``"f32"``; :meth:`RoIHeads.set_train_dtype`, :meth:`TwoMLPHead.set_train_dtype`) concerns the forward of
+:meth:`RoIHeads.head_padded` where a gradient is wanted: it runs the launches of ``head_dtype="bf16"`` on the same cached operands -
+bit-equal fp32 logits and deltas - as ONE node, :class:`_BoxHeadBF16Fn`, from the fp32 maps to the fp32 result.  One node, because
+autograd converts a gradient to the dtype of the forward output it belongs to: bf16 rows handed from a RoIAlign node to a head node
+would have fc6's fp32 input gradient rounded to bf16 on the way back.  The bf16 rows and activations it saves are the wgrad
+operands and ReLU masks of its backward as they stand.  A head with a reduction length that is no multiple of
+64 keeps the three nodes and every launch of ``"f32"``; so does a :class:`TwoMLPHead` called on its own (fp32 rows in, fp32 out).
 """
 from __future__ import annotations
 
@@ -48,7 +56,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .grad_ops import ParamCache, check_grad_dtype, linear_bwd, linear_dgrad_bf16, param_key, stack_rows
+from .grad_ops import BF16_K, ParamCache, check_grad_dtype, check_train_dtype, linear_bwd, linear_dgrad_bf16, param_key, stack_rows
 
 
 HEAD_DTYPES = ("f32", "bf16")
@@ -194,6 +202,62 @@ class _PredictorFn(torch.autograd.Function):
                 g_b[NC:5 * NC] if need[4] else None)
 
 
+class _BoxHeadBF16Fn(torch.autograd.Function):
+    """The box head under ``train_dtype="bf16"``, RoIAlign -> fc6 -> fc7 -> predictor as one node: fp32 maps and the eight parameters in,
+    fp32 ``[M, 5 NC (+ pad)]`` out, every bf16 tensor inside.  The forward is ``head_dtype="bf16"``'s - ``ldit_roi_align_levels_bf16``,
+    :meth:`TwoMLPHead.forward_bf16`, :meth:`FastRCNNPredictor.forward_stacked_bf16` on the modules' cached operands.  The backward is
+    ``grad_ops.linear_bwd`` per layer on the saved bf16 rows and activations (wgrad operands and ReLU masks as they stand), then
+    :class:`_RoIAlignLevelsFn`'s one gather launch on the fp32 ``g_x`` of fc6's dgrad.
+    apply(roi_heads, boxes, count, image_size, *maps (5), fc6.weight, fc6.bias, fc7.weight, fc7.bias, cls_score.weight, .bias,
+    bbox_pred.weight, .bias) -> [B R, 5 NC (+ pad)]."""
+
+    @staticmethod
+    def forward(ctx, heads, boxes, count, image_size, *args):
+        maps, pool, head, pred = args[:-8], heads.box_roi_pool, heads.box_head, heads.box_predictor
+        x0, levels = ops.roi_align_levels([_nhwc_f32(f.detach()) for f in maps], boxes, count, image_size, pool.output_size,
+                                          pool.sampling_ratio, pool.canonical_scale, pool.canonical_level, return_levels=True,
+                                          out_dtype=torch.bfloat16)
+        M, ph, pw, Cc = x0.shape
+        w6_16, w7_16 = head.operands_bf16(Cc, ph, pw)
+        h6 = ops.linear_bf16(x0.view(M, ph * pw * Cc), w6_16, head.fc6.bias.detach(), _lib.EPI_BIAS_RELU)
+        h7 = ops.linear_bf16(h6, w7_16, head.fc7.bias.detach(), _lib.EPI_BIAS_RELU)
+        y = pred.forward_stacked_bf16(h7)
+        ctx.saved = (boxes, count, levels, x0, h6, h7, head.fc6_weight_hwc(Cc, ph, pw), args[-6].detach(), pred._operands()[0])
+        ctx.geometry = ([tuple(f.shape[-2:]) for f in maps], tuple(image_size), pool.output_size, pool.sampling_ratio)
+        ctx.grad = (head.grad_dtype, lambda: head.dgrad_operands_bf16(Cc, ph, pw))
+        ctx.NC = pred.num_classes
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.saved is None:
+            raise RuntimeError("RoIHeads: backward through the box head a second time (its saved activations are freed after the first)")
+        boxes, count, levels, x0, h6, h7, w6p, w7, wp = ctx.saved
+        ctx.saved = None
+        shapes, image_size, output_size, sampling_ratio = ctx.geometry
+        grad_dtype, operands = ctx.grad
+        M, ph, pw, Cc = x0.shape
+        NC, nmaps = ctx.NC, len(shapes)
+        need = ctx.needs_input_grad[4:]                               # maps, then (w6, b6, w7, b7, wc, bc, wb, bb)
+        need_maps, np_ = any(need[:nmaps]), need[nmaps:]
+        # the predictor's row zero-padded to 32 columns, the K of its fp32 dgrad GEMM (below the bf16 GEMM's k-tile under either grad_dtype)
+        K = (dy.shape[1] + 31) // 32 * 32
+        dy32 = torch.zeros((M, K), device=dy.device, dtype=torch.float32)
+        dy32[:, :dy.shape[1]] = dy
+        d7, g_wp, g_bp = linear_bwd(dy32, h7, wp, True, np_[4] or np_[6], np_[5] or np_[7], grad_dtype)
+        d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, np_[2], np_[3], grad_dtype, act=h7, dgrad_w=lambda: operands()[1])
+        g_x, g_w6p, g_b6 = linear_bwd(d6, x0.view(M, ph * pw * Cc), w6p, need_maps, np_[0], np_[1], grad_dtype, act=h6,
+                                      dgrad_w=lambda: operands()[0])
+        g_w6 = None
+        if g_w6p is not None:                                         # back to torchvision's (c, ph, pw) columns
+            g_w6 = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
+        g_maps = (None,) * nmaps
+        if need_maps:
+            g_maps = tuple(ops.roi_align_levels_bwd(g_x.view(M, ph, pw, Cc), boxes, count, levels, shapes, image_size, output_size, sampling_ratio))
+        return (None,) * 4 + g_maps + (g_w6, g_b6, g_w7, g_b7, g_wp[:NC] if np_[4] else None, g_bp[:NC] if np_[5] else None,
+                                       g_wp[NC:5 * NC] if np_[6] else None, g_bp[NC:5 * NC] if np_[7] else None)
+
+
 class _BoxLossFn(torch.autograd.Function):
     """``ldit_box_loss_f32`` as a differentiable node: the kernel has already written both gradients for unit upstream into their
     column ranges of one buffer, the backward scales each range by its upstream scalar."""
@@ -220,9 +284,10 @@ def _wants_grad(module: nn.Module, x: torch.Tensor) -> bool:
 class TwoMLPHead(nn.Module):
     """torchvision's ``TwoMLPHead(in_channels, representation_size)``: ``fc6``, ``fc7``, a ReLU after each."""
 
-    def __init__(self, in_channels: int = 256 * 7 * 7, representation_size: int = 1024, grad_dtype: str = "f32"):
+    def __init__(self, in_channels: int = 256 * 7 * 7, representation_size: int = 1024, grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
         self.grad_dtype = check_grad_dtype(grad_dtype)
+        self.train_dtype = check_train_dtype(train_dtype)
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
         self._packed, self._packed_bf16, self._dgrad_bf16 = ParamCache(), ParamCache(), ParamCache()
@@ -231,6 +296,13 @@ class TwoMLPHead(nn.Module):
         """``"f32"`` or ``"bf16"``: the matrix pipe of the two input-gradient GEMMs of the backward from now on (``grad_ops.linear_bwd``).
         Forward, parameters and ``state_dict`` do not depend on it."""
         self.grad_dtype = check_grad_dtype(grad_dtype)
+        return self
+
+    def set_train_dtype(self, train_dtype: str) -> "TwoMLPHead":
+        """``"f32"`` or ``"bf16"``: how :meth:`RoIHeads.head_padded` runs this head from now on where a gradient IS wanted -
+        ``"bf16"``: the launches of ``head_dtype="bf16"`` inside :class:`_BoxHeadBF16Fn`.  :meth:`forward` on its own (fp32 rows in,
+        fp32 out), parameters and ``state_dict`` do not depend on it; eval mode and ``no_grad`` never read it."""
+        self.train_dtype = check_train_dtype(train_dtype)
         return self
 
     def dgrad_operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -328,12 +400,14 @@ class RoIHeads(nn.Module):
                  bbox_reg_weights: Optional[Sequence[float]] = None, score_thresh: float = 0.05, nms_thresh: float = 0.5,
                  detections_per_img: int = 100, min_size: float = 1e-2, fg_iou_thresh: float = 0.5, bg_iou_thresh: float = 0.5,
                  batch_size_per_image: int = 512, positive_fraction: float = 0.25, head_dtype: str = "f32",
-                 grad_dtype: Optional[str] = None):
+                 grad_dtype: Optional[str] = None, train_dtype: Optional[str] = None):
         super().__init__()
         self.head_dtype = _check_head_dtype(head_dtype)
         self.box_roi_pool, self.box_head, self.box_predictor = box_roi_pool, box_head, box_predictor
         if grad_dtype is not None:                                    # None: the box head keeps the setting it was built with
             self.set_grad_dtype(grad_dtype)
+        if train_dtype is not None:                                   # (alike)
+            self.set_train_dtype(train_dtype)
         self.bbox_reg_weights = tuple(float(w) for w in (bbox_reg_weights or (10.0, 10.0, 5.0, 5.0)))
         self.score_thresh, self.nms_thresh, self.min_size = float(score_thresh), float(nms_thresh), float(min_size)
         self.detections_per_img = int(detections_per_img)
@@ -348,8 +422,24 @@ class RoIHeads(nn.Module):
         if self.head_dtype == "bf16" and not self.training and not self._wants_grad(features):
             pooled = self.box_roi_pool(features, proposals, count, image_size, out_dtype=torch.bfloat16)
             return self.box_predictor.forward_stacked_bf16(self.box_head.forward_bf16(pooled))
+        if self.train_dtype == "bf16" and self._trains_bf16(features):
+            feats = [features[n] for n in self.box_roi_pool.featmap_names] if isinstance(features, dict) else list(features)
+            head, pred = self.box_head, self.box_predictor
+            return _BoxHeadBF16Fn.apply(self, proposals.detach(), count, tuple(image_size), *feats, head.fc6.weight, head.fc6.bias,
+                                        head.fc7.weight, head.fc7.bias, pred.cls_score.weight, pred.cls_score.bias, pred.bbox_pred.weight,
+                                        pred.bbox_pred.bias)
         pooled = self.box_roi_pool(features, proposals, count, image_size)
         return self.box_predictor.forward_stacked(self.box_head(pooled))
+
+    def _trains_bf16(self, features) -> bool:
+        """Whether this call is the one ``train_dtype="bf16"`` concerns: train mode, a gradient wanted by a map or a parameter, and
+        three reduction lengths the bf16 GEMM takes (else: every launch of ``"f32"``)."""
+        head, pred = self.box_head, self.box_predictor
+        if not (self.training and head.training and pred.training and torch.is_grad_enabled()):
+            return False
+        if not (self._wants_grad(features) or any(p.requires_grad for m in (head, pred) for p in m.parameters())):
+            return False
+        return head.fc6.in_features % BF16_K == 0 and head.fc6.out_features % BF16_K == 0 and head.fc7.out_features % BF16_K == 0
 
     def set_head_dtype(self, head_dtype: str) -> "RoIHeads":
         """``"f32"`` or ``"bf16"``: how the eval-mode head runs from now on.  The parameters are untouched."""
@@ -364,6 +454,16 @@ class RoIHeads(nn.Module):
 
     def set_grad_dtype(self, grad_dtype: str) -> "RoIHeads":
         self.box_head.set_grad_dtype(check_grad_dtype(grad_dtype))
+        return self
+
+    @property
+    def train_dtype(self) -> str:
+        """The box head's setting (:meth:`TwoMLPHead.set_train_dtype`): under ``"bf16"`` :meth:`head_padded` runs RoIAlign, fc6, fc7 and
+        the predictor as one bf16 node where a gradient is wanted."""
+        return self.box_head.train_dtype
+
+    def set_train_dtype(self, train_dtype: str) -> "RoIHeads":
+        self.box_head.set_train_dtype(check_train_dtype(train_dtype))
         return self
 
     def _wants_grad(self, features) -> bool:

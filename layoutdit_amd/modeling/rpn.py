@@ -34,6 +34,12 @@ torchvision, so detector checkpoints load (``rpn.head.conv.0.0.weight`` ...).
 masks the 1x1 pair's input gradient by the ReLU, writes its zero-padded bf16 copy and sums the 3x3's bias gradient, and the 3x3's
 dgrad runs on the bf16 MFMA GEMM on that copy (``grad_ops.conv3x3_bwd``).  The 1x1 pair's own dgrad (32 padded
 columns) stays on the fp32 GEMM.
+
+``train_dtype="bf16"`` (default ``"f32"``; :meth:`RPNHead.set_train_dtype`) concerns :class:`_RPNHeadLevelFn`'s forward alone, the branch
+that wants a gradient: it runs the launches of ``neck_dtype="bf16"`` on the same cached operands - bit-equal logits and deltas - with
+the map's zero-padded bf16 copy made once with the slack rows of the wgrad taps.  That copy and the bf16 activation are what the
+backward reads again: the 3x3's wgrad operand, the ReLU mask and the 1x1 pair's wgrad operand as they stand.  A
+channel count that is no multiple of 64 keeps every launch of ``"f32"``.  Eval mode and ``no_grad`` never read it.
 """
 from __future__ import annotations
 
@@ -44,8 +50,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .grad_ops import (ParamCache, check_grad_dtype, check_neck_dtype, conv3x3_bf16, conv3x3_bwd, conv3x3_dgrad_bf16, linear_bwd, param_key,
-                       stack_rows)
+from .grad_ops import (BF16_K, ParamCache, check_grad_dtype, check_neck_dtype, check_train_dtype, conv3x3_bf16, conv3x3_bwd,
+                       conv3x3_dgrad_bf16, linear_bwd, padded_middle, param_key, stack_rows)
 
 
 class AnchorGenerator(nn.Module):
@@ -135,13 +141,27 @@ class _RPNHeadLevelFn(torch.autograd.Function):
     :meth:`RPNHead._operands` - the same weights as the GEMMs read them, no gradient of their own.
     apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box, operands, grad) -> (logits [B, h w A], deltas [B, h w A, 4]).
     ``grad``: ``(grad_dtype, dgrad_w)``, the head's option and its cached :meth:`RPNHead._dgrad_operand_bf16` as a callable; the
-    forward does not read it."""
+    forward does not read it.  ``train``: ``(train_dtype, operands_bf16)``, the forward's option and the head's cached
+    :meth:`RPNHead._operands_bf16` as a callable.  Under ``"bf16"``, with a channel count the bf16 GEMM takes, the forward is
+    :func:`_level_forward_bf16`'s launches on a padded copy that has the wgrad's slack rows, and what is saved in the place of the NHWC
+    map and the fp32 activation are that copy and the bf16 activation."""
 
     @staticmethod
-    def forward(ctx, x, w3, b3, wc, bc, wb, bb, operands, grad=("f32", None)):
-        xn, t, out = _level_forward(x, operands, wc.shape[0])
-        ctx.saved = (xn, t, w3.detach(), operands[2])
-        ctx.A = wc.shape[0]
+    def forward(ctx, x, w3, b3, wc, bc, wb, bb, operands, grad=("f32", None), train=("f32", None)):
+        A = wc.shape[0]
+        B, Cc, h, w = x.shape
+        if check_train_dtype(train[0]) == "bf16" and Cc % BF16_K == 0:
+            w3_16, b3_, w1_16, b1 = train[1]()
+            x_p = ops.pad_nhwc_bf16(x.detach().permute(0, 2, 3, 1).contiguous(), slack_rows=w + 3)
+            t = ops.conv3x3_nhwc_bf16(padded_middle(x_p, B, h, w), B, h, w, w3_16, b3_, _lib.EPI_BIAS_RELU)      # bf16 [B h w, C]
+            y = ops.linear_bf16(t, w1_16, b1, _lib.EPI_F32)
+            out = (y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4))
+            ctx.saved = (x_p, t, w3.detach(), operands[2])
+        else:
+            xn, t, out = _level_forward(x, operands, A)
+            ctx.saved = (xn, t, w3.detach(), operands[2])
+        ctx.shape = (B, h, w, Cc)
+        ctx.A = A
         ctx.grad = grad
         return out
 
@@ -152,7 +172,7 @@ class _RPNHeadLevelFn(torch.autograd.Function):
         xn, t, w3, w1 = ctx.saved
         ctx.saved = None
         A = ctx.A
-        B, h, w, Cc = xn.shape
+        B, h, w, Cc = ctx.shape
         M = B * h * w
         need = ctx.needs_input_grad
         # the gradient of the pixel rows [M, logits | deltas | zero padding]: 32 columns, the K the fp32 GEMM wants (and a multiple
@@ -168,13 +188,13 @@ class _RPNHeadLevelFn(torch.autograd.Function):
         dt, g1, gb = linear_bwd(dy, t.view(M, Cc), w1, True, need[3] or need[5], need[4] or need[6], grad_dtype)   # [M, C], [K, C], [K]
         if grad_dtype == "bf16":
             # the ReLU mask is applied by the launch that makes the padded bf16 copy of dt and the bias gradient
-            g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2], grad_dtype, act=t, dgrad_w=dgrad_w)
+            g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2], grad_dtype, act=t.view(B, h, w, Cc), dgrad_w=dgrad_w)
         else:
             dt.mul_(t.view(M, Cc) > 0)                                                    # ReLU mask
             g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2])
         return (g_x.permute(0, 3, 1, 2) if need[0] else None, g_w3, g_b3,
                 g1[:A].reshape(A, Cc, 1, 1) if need[3] else None, gb[:A] if need[4] else None,
-                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None, None)
+                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None, None, None)
 
 
 class _RPNLossFn(torch.autograd.Function):
@@ -196,10 +216,11 @@ class _RPNLossFn(torch.autograd.Function):
 class RPNHead(nn.Module):
     """torchvision's ``RPNHead(in_channels, num_anchors)``: ``conv.0.0`` (3x3 + ReLU), ``cls_logits`` and ``bbox_pred`` (1x1)."""
 
-    def __init__(self, in_channels: int = 256, num_anchors: int = 3, neck_dtype: str = "f32", grad_dtype: str = "f32"):
+    def __init__(self, in_channels: int = 256, num_anchors: int = 3, neck_dtype: str = "f32", grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
         self.neck_dtype = check_neck_dtype(neck_dtype)
         self.grad_dtype = check_grad_dtype(grad_dtype)
+        self.train_dtype = check_train_dtype(train_dtype)
         self.conv = nn.Sequential(_ConvRelu(in_channels))
         self.cls_logits = nn.Conv2d(in_channels, num_anchors, kernel_size=1)
         self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1)
@@ -215,6 +236,13 @@ class RPNHead(nn.Module):
         (``grad_ops.conv3x3_bwd``; the 1x1 pair's 32 padded columns keep theirs on the fp32 GEMM).  Forward, parameters and
         ``state_dict`` do not depend on it."""
         self.grad_dtype = check_grad_dtype(grad_dtype)
+        return self
+
+    def set_train_dtype(self, train_dtype: str) -> "RPNHead":
+        """``"f32"`` or ``"bf16"``: how the head's forward runs from now on where a gradient IS wanted (:class:`_RPNHeadLevelFn`), on the
+        same weights - ``"bf16"``: the launches of ``neck_dtype="bf16"``.  Parameters and ``state_dict`` do not depend on it; eval mode
+        and ``no_grad`` never read it."""
+        self.train_dtype = check_train_dtype(train_dtype)
         return self
 
     def _dgrad_operand_bf16(self) -> torch.Tensor:
@@ -256,7 +284,8 @@ class RPNHead(nn.Module):
             raise ValueError(f"RPNHead: expected float32 features, got {x.dtype}")
         if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             # gradients are wanted: one differentiable node per level, on the operands of the eval path below
-            return _RPNHeadLevelFn.apply(x, *self._params(), self._operands(), (self.grad_dtype, self._dgrad_operand_bf16))
+            return _RPNHeadLevelFn.apply(x, *self._params(), self._operands(), (self.grad_dtype, self._dgrad_operand_bf16),
+                                         (self.train_dtype, self._operands_bf16))
         if self.neck_dtype == "bf16":
             return _level_forward_bf16(x, self._operands_bf16(), self.num_anchors)
         return _level_forward(x, self._operands(), self.num_anchors)[2]

@@ -705,34 +705,50 @@ def _colsum_buffers(M: int, N: int, device, want: bool):
 
 
 def _req_act(act: Optional[torch.Tensor], dy: torch.Tensor) -> Optional[torch.Tensor]:
-    if act is not None and tuple(_req(act, "act").shape) != tuple(dy.shape):
+    """``act`` of a ReLU backward: a contiguous GPU tensor of ``dy``'s shape, fp32 or - as a bf16 forward saved it - bf16."""
+    if act is None:
+        return None
+    if isinstance(act, torch.Tensor) and act.dtype == torch.bfloat16:
+        if not act.is_cuda or not act.is_contiguous():
+            raise ValueError("act: expected a contiguous GPU tensor")
+    else:
+        _req(act, "act")
+    if tuple(act.shape) != tuple(dy.shape):
         raise ValueError(f"act {tuple(act.shape)} does not match dy {tuple(dy.shape)}")
     return act
 
 
+def _act16(act: Optional[torch.Tensor]) -> bool:
+    return act is not None and act.dtype == torch.bfloat16
+
+
 def relu_bwd_bf16(dy: torch.Tensor, act: Optional[torch.Tensor] = None, want_colsum: bool = True):
     """One pass between two layers of a backward: with ``w = torch.where(act > 0, dy, 0)`` (``w = dy`` without ``act``) returns
-    ``(cast_bf16(w), colsum(w))`` bit for bit, the sum ``None`` where it is not wanted.  ``dy``, ``act``: contiguous fp32 [M, N]."""
+    ``(cast_bf16(w), colsum(w))`` bit for bit, the sum ``None`` where it is not wanted.  ``dy``: contiguous fp32 [M, N]; ``act``:
+    the same, or bf16 (``ldit_relu_bwd_bf16_act16``: no fp32 copy of it is made, the results are those on ``act.float()``)."""
     lib = _lib.load()
     dy = _req(dy, "dy")
     act = _req_act(act, dy)
     M, N = dy.shape
     out = torch.empty((M, N), device=dy.device, dtype=torch.bfloat16)
     cs, scratch, need = _colsum_buffers(M, N, dy.device, want_colsum)
-    _launch(_device(dy, act), lib.ldit_relu_bwd_bf16, _ptr(dy), N, _ptr(act), N, _ptr(out), N, M, N, _ptr(cs), _ptr(scratch), need)
+    entry = getattr(lib, "ldit_relu_bwd_bf16_act16" if _act16(act) else "ldit_relu_bwd_bf16")                  # one signature
+    _launch(_device(dy, act), entry, _ptr(dy), N, _ptr(act), N, _ptr(out), N, M, N, _ptr(cs), _ptr(scratch), need)
     return out, cs
 
 
 def relu_bwd_pad_nhwc_bf16(dy: torch.Tensor, act: Optional[torch.Tensor] = None, want_colsum: bool = True):
     """:func:`relu_bwd_bf16` on an NHWC map ``dy`` [B, H, W, C] with the copy in the zero-padded layout: returns
-    ``(pad_nhwc_bf16(w), colsum(w.view(-1, C)))`` bit for bit - bf16 ``[B (H+2) (W+2), C]`` (no slack rows) and fp32 [C] or ``None``."""
+    ``(pad_nhwc_bf16(w), colsum(w.view(-1, C)))`` bit for bit - bf16 ``[B (H+2) (W+2), C]`` (no slack rows) and fp32 [C] or ``None``.
+    A bf16 ``act`` goes to ``ldit_relu_bwd_pad_nhwc_bf16_act16``."""
     lib = _lib.load()
     dy = _req(dy, "dy")
     act = _req_act(act, dy)
     B, H, W, Cc = dy.shape
     out = torch.empty((B * (H + 2) * (W + 2), Cc), device=dy.device, dtype=torch.bfloat16)
     cs, scratch, need = _colsum_buffers(B * H * W, Cc, dy.device, want_colsum)
-    _launch(_device(dy, act), lib.ldit_relu_bwd_pad_nhwc_bf16, _ptr(dy), _ptr(act), _ptr(out), B, H, W, Cc, _ptr(cs), _ptr(scratch), need)
+    entry = getattr(lib, "ldit_relu_bwd_pad_nhwc_bf16_act16" if _act16(act) else "ldit_relu_bwd_pad_nhwc_bf16")
+    _launch(_device(dy, act), entry, _ptr(dy), _ptr(act), _ptr(out), B, H, W, Cc, _ptr(cs), _ptr(scratch), need)
     return out, cs
 
 

@@ -6,6 +6,8 @@ around each call (host work of the call included), every shape warmed up in both
 iterations per setting.  The weights move by one AdamW step per timed iteration (lr 1e-6), for both settings alike.
 --count N [--phases losses|iteration]: no timing and no file - N iterations (or their losses() alone) in the FIRST setting, for a
 kernel trace of the process from outside: launches per call are differences between two such traces (scripts/README.md).
+--train-dtype f32,bf16: the settings that alternate are train_dtype's instead, under one --grad-dtype (default
+bf16); peak allocated memory of an iteration is recorded per setting, and the file is profiles/detector_train_bench_train_bf16.json.
 Needs a GPU: without one it fails.  Writes one JSON object (--out, default profiles/detector_train_bench.json)."""
 import argparse
 import json
@@ -30,18 +32,21 @@ ap.add_argument("--runs", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--settings", default="f32,bf16", help="comma-separated grad_dtype settings, timed alternately in this order")
+ap.add_argument("--train-dtype", default=None, help="comma-separated train_dtype settings: these alternate instead, under --grad-dtype")
+ap.add_argument("--grad-dtype", default="bf16", help="the one grad_dtype of a --train-dtype run")
 ap.add_argument("--count", type=int, default=0, help="no timing, nothing written: this many iterations of --phases in the first setting")
 ap.add_argument("--phases", default="iteration", choices=["losses", "iteration"])
 ap.add_argument("--commit", default=None, help="recorded as the tree's commit (default: git rev-parse of the checkout, if it is one)")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detector_train_bench.json"))
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+args.out = args.out or os.path.join(ROOT, "profiles", "detector_train_bench_train_bf16.json" if args.train_dtype else "detector_train_bench.json")
 if args.runs < 20 and not args.count:
     ap.error("--runs: at least 20 iterations per setting")
 if not torch.cuda.is_available():
     sys.exit("detector_train_bench: no GPU found (the detector has no CPU path)")
 
 dev = "cuda:0"
-settings = args.settings.split(",")
+settings = (args.train_dtype or args.settings).split(",")
 cfg = getattr(cfgs, args.config)()
 cfg.drop_path_rate = 0.0
 torch.manual_seed(0)
@@ -63,7 +68,10 @@ for _ in range(args.batch):
 
 
 def iteration(setting: str, timed: bool, losses_only: bool = False):
-    model.set_grad_dtype(setting)
+    if args.train_dtype:
+        model.set_grad_dtype(args.grad_dtype).set_train_dtype(setting)
+    else:
+        model.set_grad_dtype(setting)
     for p in model.parameters():
         p.grad = None
     gen = torch.Generator(device=dev)
@@ -98,10 +106,14 @@ for _ in range(args.warmup):                       # every shape, every cache an
         iteration(s, False)
 torch.cuda.synchronize()
 samples = {s: [] for s in settings}
+peak = {s: 0 for s in settings}
 finite = True
 for _ in range(args.runs):
     for s in settings:
+        if args.train_dtype:
+            torch.cuda.reset_peak_memory_stats()
         t, total = iteration(s, True)
+        peak[s] = max(peak[s], torch.cuda.max_memory_allocated())
         samples[s].append(t)
         finite = finite and bool(np.isfinite(total))
 torch.cuda.synchronize()
@@ -132,6 +144,14 @@ if len(settings) == 2:
     res["backward_difference"] = {"median_ms": round(a["median_ms"] - b["median_ms"], 3),
                                   "spread_ms": {s: round(ms[s]["backward"]["max_ms"] - ms[s]["backward"]["min_ms"], 3) for s in settings},
                                   "separated": bool(b["max_ms"] < a["min_ms"])}
+if args.train_dtype:
+    res["option"], res["grad_dtype"] = "train_dtype", args.grad_dtype
+    res["peak_allocated_mb"] = {s: round(peak[s] / 2 ** 20, 1) for s in settings}
+    if len(settings) == 2:
+        a, b = (ms[s]["losses"] for s in settings)
+        res["losses_difference"] = {"median_ms": round(a["median_ms"] - b["median_ms"], 3),
+                                    "spread_ms": {s: round(ms[s]["losses"]["max_ms"] - ms[s]["losses"]["min_ms"], 3) for s in settings},
+                                    "separated": bool(b["max_ms"] < a["min_ms"])}
 print(json.dumps(res))
 with open(args.out, "w") as f:
     json.dump(res, f, indent=1)
