@@ -214,12 +214,10 @@ class DetectorTrainStep:
 
     def invalidate_caches(self, _mirror_current: bool = False) -> None:
         """The update goes through raw pointers, so no tensor version moves and every copy of the weights keyed on versions is stale:
-        the encoder's packed inference block and resampled position tables, the FPN's re-laid 3x3 weights, the RPN head's and the box
-        head's stacked / re-ordered matrices and their bf16 copies.  The training mirror of the encoder was refreshed by the update itself where it was
+        the encoder's packed inference block and resampled position tables, every stage's ``OperandCache`` (re-laid, stacked and
+        re-ordered matrices, their bf16 copies, the dgrad operands).  The training mirror of the encoder was refreshed by the update itself where it was
         current before (``_mirror_current``); otherwise the next forward rebuilds it."""
-        from .modeling.dit_fpn import DiTWithFPN
-        from .modeling.roi_heads import FastRCNNPredictor, TwoMLPHead
-        from .modeling.rpn import RPNHead
+        from .modeling.grad_ops import OperandCache
         st = getattr(self.encoder, "_flat_state", None)
         if st is not None:
             if _mirror_current and st.native:
@@ -229,19 +227,10 @@ class DetectorTrainStep:
                 st.mark_dirty()                           # another grid: the position slot is re-derived from its parameter
         self.encoder._packed_key = None
         self.encoder._pos_cache.clear()
-        for mod in self.model.modules():
-            if isinstance(mod, DiTWithFPN):
-                for c in mod._cache + mod._cache_bf16 + mod._cache_dgrad["conv"] + mod._cache_dgrad["lat"]:
-                    c.clear()                             # (the last two: the dgrad operands of grad_dtype="bf16")
-            elif isinstance(mod, RPNHead):
-                mod._packed.clear()
-                mod._packed_bf16.clear()                  # the bf16 neck's operands likewise
-                mod._dgrad_bf16.clear()                   # ... and the 3x3's bf16 dgrad operand
-            elif isinstance(mod, (TwoMLPHead, FastRCNNPredictor)):
-                mod._packed.clear()
-                mod._packed_bf16.clear()                  # the bf16 head's operands are keyed on versions like the fp32 re-layouts
-                if isinstance(mod, TwoMLPHead):
-                    mod._dgrad_bf16.clear()               # fc6's and fc7's bf16 dgrad operands
+        for mod in self.model.modules():                  # every stage keeps its derived weights in one cache, under one name
+            cache = getattr(mod, "_operand_cache", None)
+            if isinstance(cache, OperandCache):
+                cache.clear()
 
     def epoch_end(self) -> None:
         """``StepLR(step_size, gamma).step()``: after every ``step_size`` calls the learning rate is multiplied by ``gamma``; the new

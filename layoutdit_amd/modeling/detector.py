@@ -21,8 +21,8 @@ import torch.nn as nn
 from ..config import DiTConfig
 from .detector_input import DetectorInputTransform
 from .dit_fpn import DiTWithFPN
-from .grad_ops import check_grad_dtype, check_neck_dtype, check_train_dtype
-from .roi_heads import FastRCNNPredictor, MultiScaleRoIAlign, RoIHeads, TwoMLPHead, _check_head_dtype, _nhwc_f32
+from .grad_ops import check_dtype
+from .roi_heads import FastRCNNPredictor, MultiScaleRoIAlign, RoIHeads, TwoMLPHead, _nhwc_f32
 from .rpn import AnchorGenerator, RegionProposalNetwork, RPNHead
 
 FEATMAP_NAMES = ("p2", "p3", "p4", "p5", "pool")
@@ -66,10 +66,8 @@ class LayoutDetectionModel(nn.Module):
         rounding, fp32 accumulation), and the backward reads the bf16 tensors that forward saved; eval mode and ``no_grad`` never read
         it, and it is independent of the other three options."""
         super().__init__()
-        _check_head_dtype(head_dtype)
-        check_neck_dtype(neck_dtype)
-        check_grad_dtype(grad_dtype)
-        check_train_dtype(train_dtype)
+        for option, value in (("head_dtype", head_dtype), ("neck_dtype", neck_dtype), ("grad_dtype", grad_dtype), ("train_dtype", train_dtype)):
+            check_dtype(option, value)
         if len(set(len(s) * len(r) for s, r in zip(anchor_sizes, aspect_ratios))) != 1:
             raise ValueError("LayoutDetectionModel: every level must have the same number of anchors per location (one RPN head)")
         backbone = DiTWithFPN(pretrained=False, config=config, compute_dtype=compute_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype,
@@ -78,14 +76,19 @@ class LayoutDetectionModel(nn.Module):
                                  fixed_size=fixed_size, head_dtype=head_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype,
                                  train_dtype=train_dtype)
 
+    def _set(self, option: str, value: str, *stages) -> "LayoutDetectionModel":
+        check_dtype(option, value)                                    # refused before any stage changes
+        for stage in stages:
+            getattr(stage, "set_" + option)(value)
+        return self
+
     @property
     def head_dtype(self) -> str:
         return self.model.roi_heads.head_dtype
 
     def set_head_dtype(self, head_dtype: str) -> "LayoutDetectionModel":
         """``"f32"`` or ``"bf16"``: how the box head of ``forward`` / ``forward_padded`` runs from now on, on the same weights."""
-        self.model.roi_heads.set_head_dtype(head_dtype)
-        return self
+        return self._set("head_dtype", head_dtype, self.model.roi_heads)
 
     @property
     def neck_dtype(self) -> str:
@@ -94,10 +97,7 @@ class LayoutDetectionModel(nn.Module):
     def set_neck_dtype(self, neck_dtype: str) -> "LayoutDetectionModel":
         """``"f32"`` or ``"bf16"``: how the FPN's and the RPN head's convolutions of ``forward`` / ``forward_padded`` run from now on,
         on the same weights."""
-        check_neck_dtype(neck_dtype)                                  # refused before either stage changes
-        self.model.backbone.set_neck_dtype(neck_dtype)
-        self.model.rpn.head.set_neck_dtype(neck_dtype)
-        return self
+        return self._set("neck_dtype", neck_dtype, self.model.backbone, self.model.rpn.head)
 
     @property
     def grad_dtype(self) -> str:
@@ -106,11 +106,7 @@ class LayoutDetectionModel(nn.Module):
     def set_grad_dtype(self, grad_dtype: str) -> "LayoutDetectionModel":
         """``"f32"`` or ``"bf16"``: the matrix pipe of the dgrad GEMMs of the FPN's, the RPN head's and the box head's backward from now
         on, on the same weights.  No forward changes."""
-        check_grad_dtype(grad_dtype)                                  # refused before any stage changes
-        self.model.backbone.set_grad_dtype(grad_dtype)
-        self.model.rpn.head.set_grad_dtype(grad_dtype)
-        self.model.roi_heads.set_grad_dtype(grad_dtype)
-        return self
+        return self._set("grad_dtype", grad_dtype, self.model.backbone, self.model.rpn.head, self.model.roi_heads)
 
     @property
     def train_dtype(self) -> str:
@@ -119,11 +115,7 @@ class LayoutDetectionModel(nn.Module):
     def set_train_dtype(self, train_dtype: str) -> "LayoutDetectionModel":
         """``"f32"`` or ``"bf16"``: the matrix pipe of the FPN's, the RPN head's and the box head's forward from now on where a gradient
         is wanted, on the same weights.  Eval mode and ``no_grad`` do not change."""
-        check_train_dtype(train_dtype)                                # refused before any stage changes
-        self.model.backbone.set_train_dtype(train_dtype)
-        self.model.rpn.head.set_train_dtype(train_dtype)
-        self.model.roi_heads.set_train_dtype(train_dtype)
-        return self
+        return self._set("train_dtype", train_dtype, self.model.backbone, self.model.rpn.head, self.model.roi_heads)
 
     def forward_padded(self, batch: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """``batch`` [B, 3, H, W] (already transformed) -> ``(boxes [B, D, 4], scores [B, D], labels int32 [B, D], count int32 [B])``

@@ -24,21 +24,11 @@ GEMMs on reduction-major operands with fp32 accumulation, so gradients of the FP
 encoder's), the merge adjoint and the bias column sums in ``csrc/fpn_bwd.hip``.  Gradients reach the four taps, hence the
 encoder (``layoutdit_amd.training``).  Oracle: autograd of ``oracle/fpn_oracle_torch.py`` (parity unpinned, as above).
 
-``neck_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_neck_dtype` switches one set of weights) moves the four 3x3 output
-convolutions of the path that wants no gradient onto the bf16 matrix pipe: per level the merged fp32 map is copied once into a
-zero-padded bf16 map (``ldit_pad_nhwc_f32_bf16``) and ``ldit_conv3x3_nhwc_bf16`` - the implicit-im2col mode of the bf16 MFMA GEMM,
-fp32 accumulation, bf16 operand rounding - writes the fp32 NHWC result, so every consumer sees the tensors it sees today.  Laterals
-and merges stay fp32, parameters stay fp32, the ``state_dict`` does not depend on the option and :class:`_FPNFn` ignores it.
-
-``grad_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_grad_dtype`) concerns :class:`_FPNFn`'s backward alone: the dgrad GEMMs
-of the four 3x3 convolutions and of the four laterals run on the bf16 MFMA GEMM, on the bf16 copy of the incoming gradient that the
-wgrad reads (``grad_ops.conv3x3_bwd`` / ``linear_bwd``).  No forward reads the option.
-
-``train_dtype="bf16"`` (default ``"f32"``; :meth:`DiTWithFPN.set_train_dtype`) concerns :class:`_FPNFn`'s forward alone, the path that
-wants a gradient: its four 3x3 output convolutions run as the eval path under ``neck_dtype="bf16"`` runs them - the same kernel on the
-same cached bf16 weights, bit-equal maps - on a zero-padded bf16 copy of each merged map that carries the slack rows of the wgrad
-taps, so the backward reads that one buffer again and neither saves the fp32 merged maps nor pads them a second time (DESIGN section
-32).  Laterals and merges stay fp32.  Eval mode and ``no_grad`` never read it.
+The dtype options are ``grad_ops.py``'s.  What is particular to this stage: ``neck_dtype`` and ``train_dtype`` concern the four 3x3
+output convolutions - per level the merged fp32 map is copied once into a zero-padded bf16 map and ``ldit_conv3x3_nhwc_bf16``
+writes the fp32 NHWC result, so every consumer sees the tensors it sees today; under ``train_dtype`` that copy carries the slack
+rows of the wgrad taps and is what :class:`_FPNFn` saves in the merged map's place.  ``grad_dtype`` concerns the eight dgrad GEMMs of
+:class:`_FPNFn`'s backward, 3x3s and laterals.  Laterals and merges stay fp32 in every forward.
 """
 from __future__ import annotations
 
@@ -53,8 +43,8 @@ import torch.nn as nn
 from .. import _lib, ops
 from ..config import DiTConfig
 from .dit_backbone import DiTBackbone
-from .grad_ops import (BF16_K, ParamCache, check_grad_dtype, check_neck_dtype, check_train_dtype, conv3x3_bf16, conv3x3_bwd,
-                       conv3x3_dgrad_bf16, linear_bwd, linear_dgrad_bf16, padded_middle, param_key)
+from .grad_ops import (BF16_K, OperandCache, check_dtype, conv3x3_bwd, conv3x3_dgrad_bf16, conv3x3_fwd_bf16, dtype_setter, linear_bwd,
+                       linear_dgrad_bf16)
 
 
 class _Conv(nn.Sequential):
@@ -76,26 +66,19 @@ class _FPNParams(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
 
-def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool, bf16_conv: bool = False,
-                 train_w16=None):
-    """The stage on fp32 contiguous token tensors [B, 1+P, C]; returns NHWC outputs (coarsest last) and, for the backward,
-    the four merged maps.  ``bf16_conv`` (the eval path under ``neck_dtype="bf16"``): ``conv_w_ohwi`` holds bf16 copies and the 3x3
-    convolutions run on the bf16 MFMA GEMM - laterals, merges and the fp32 NHWC results are what they are without it.
-    ``train_w16`` (:class:`_FPNFn` under ``train_dtype="bf16"``): a callable giving level i's cached bf16 weight; a level whose channel
-    count the bf16 GEMM takes runs that same convolution on the slack-padded bf16 copy of its merged map, and that copy is what is
-    kept for the backward in the map's place."""
+def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, conv_b, keep_inner: bool):
+    """The stage on fp32 contiguous token tensors [B, 1+P, C]; returns NHWC outputs (coarsest last) and, with ``keep_inner``, what the
+    backward reads of the four merged maps.  A level whose ``conv_w_ohwi`` is a bf16 copy runs its 3x3 on the bf16 MFMA GEMM
+    (``grad_ops.conv3x3_fwd_bf16``) and keeps the slack-padded bf16 copy of its map in the map's place; laterals, merges and the fp32
+    NHWC results are what they are without it."""
     B, T, Cc = toks[0].shape
     lats = [ops.linear(toks[i].reshape(B * T, Cc), lat_w[i], lat_b[i]).view(B, T, -1) for i in range(4)]
     inner, outs, inners = None, [None] * 4, [None] * 4
     for i in (3, 2, 1, 0):                                            # coarsest first (top-down)
-        inner = ops.fpn_merge(lats[i], gh, gw, bb_scales[i], top=inner)
-        kept = inner
-        if train_w16 is not None and inner.shape[3] % BF16_K == 0:
-            Bi, h, w, _ = inner.shape
-            kept = ops.pad_nhwc_bf16(inner, slack_rows=w + 3)
-            outs[i] = ops.conv3x3_nhwc_bf16(padded_middle(kept, Bi, h, w), Bi, h, w, train_w16(i), conv_b[i], _lib.EPI_F32).view(Bi, h, w, -1)
-        elif bf16_conv:
-            outs[i] = conv3x3_bf16(inner, conv_w_ohwi[i], conv_b[i], _lib.EPI_F32).view(*inner.shape[:3], -1)
+        inner = kept = ops.fpn_merge(lats[i], gh, gw, bb_scales[i], top=inner)
+        if conv_w_ohwi[i].dtype == torch.bfloat16:
+            rows, kept = conv3x3_fwd_bf16(inner, conv_w_ohwi[i], conv_b[i], _lib.EPI_F32, slack=keep_inner)
+            outs[i] = rows.view(*inner.shape[:3], -1)
         else:
             outs[i] = ops.conv3x3_nhwc(inner, conv_w_ohwi[i], conv_b[i])
         if keep_inner:
@@ -105,42 +88,38 @@ def _fpn_forward(bb_scales, gh: int, gw: int, toks, lat_w, lat_b, conv_w_ohwi, c
 
 class _FPNFn(torch.autograd.Function):
     """p2..p5 = FPN(taps) with gradients for the taps and for every FPN parameter.
-    apply(geom, t0..t3, lw0, lb0, .. lw3, lb3, cw0, cb0, .. cw3, cb3) -> (p2, p3, p4, p5) as [B, 256, h, w] channels-last views.
-    ``geom``: ``(gh, gw, scales)`` or ``(gh, gw, scales, grad_dtype, dgrad)`` - the stage's option and its cached
-    :meth:`DiTWithFPN._dgrad_operands_bf16` as a callable ``dgrad(kind, i)``; the forward does not read them.  Two more entries,
-    ``(.., train_dtype, conv16)``, are the forward's option and the cached :meth:`DiTWithFPN._ohwi_bf16` as a callable ``conv16(i)``."""
+    apply(stage, gh, gw, t0..t3, lw0, lb0, .. lw3, lb3, cw0, cb0, .. cw3, cb3) -> (p2, p3, p4, p5) as [B, 256, h, w] channels-last views.
+    ``stage``: the :class:`DiTWithFPN` whose parameters these are.  The forward reads its ``train_dtype`` (``"bf16"``: a level the bf16
+    GEMM takes runs on the cached :meth:`DiTWithFPN._ohwi_bf16`) and its ``grad_dtype``, which it keeps on ``ctx``: a setter called
+    between forward and backward does not change that backward.  The backward takes its dgrad operands from the stage's cache."""
 
     @staticmethod
-    def forward(ctx, geom, *args):
-        gh, gw, scales = geom[:3]
-        train_w16 = geom[6] if len(geom) > 5 and check_train_dtype(geom[5]) == "bf16" else None
+    def forward(ctx, stage, gh, gw, *args):
         toks = [_f32c(t.detach()) for t in args[0:4]]
         lw = [args[4 + 2 * i].detach() for i in range(4)]
         lb = [args[5 + 2 * i].detach() for i in range(4)]
         cw = [args[12 + 2 * i].detach() for i in range(4)]
         cb = [args[13 + 2 * i].detach() for i in range(4)]
         Ch, Cc = lw[0].shape[0], toks[0].shape[2]
-        bf16 = [train_w16 is not None and w.shape[1] % BF16_K == 0 for w in cw]       # (such a level reads no fp32 re-layout)
-        outs, inners = _fpn_forward(scales, gh, gw, toks, [w.reshape(Ch, Cc) for w in lw], lb,
-                                    [None if b else w.permute(0, 2, 3, 1).contiguous() for w, b in zip(cw, bf16)], cb, keep_inner=True,
-                                    train_w16=train_w16)
-        ctx.geom = geom
+        bf16 = check_dtype("train_dtype", stage.train_dtype) == "bf16"
+        conv_w = [stage._ohwi_bf16(i) if bf16 and w.shape[1] % BF16_K == 0 else w.permute(0, 2, 3, 1).contiguous() for i, w in enumerate(cw)]
+        outs, inners = _fpn_forward(stage.backbone.scales, gh, gw, toks, [w.reshape(Ch, Cc) for w in lw], lb, conv_w, cb, keep_inner=True)
+        ctx.stage, ctx.grid, ctx.grad_dtype = stage, (gh, gw), check_dtype("grad_dtype", stage.grad_dtype)
         ctx.shapes = [tuple(o.shape) for o in outs]                   # of the merged maps too: the 3x3 keeps the channel count
         ctx.toks, ctx.inners, ctx.lw, ctx.cw = toks, inners, lw, cw
         return tuple(o.permute(0, 3, 1, 2) for o in outs)
 
     @staticmethod
     def backward(ctx, *dps):
-        gh, gw, scales = ctx.geom[:3]
-        grad_dtype, dgrad = ctx.geom[3:5] if len(ctx.geom) > 3 else ("f32", None)
-        operand = (lambda kind, i: None) if dgrad is None else (lambda kind, i: partial(dgrad, kind, i))
+        (gh, gw), scales, grad_dtype = ctx.grid, ctx.stage.backbone.scales, ctx.grad_dtype
+        operand = lambda kind, i: partial(ctx.stage._dgrad_operands_bf16, kind, i)          # noqa: E731
         if ctx.inners is None:
             raise RuntimeError("DiTWithFPN: backward through the FPN a second time (its saved maps are freed after the first)")
         toks, inners, lw, cw = ctx.toks, ctx.inners, ctx.lw, ctx.cw
         ctx.inners = None
         B, T, Cc = toks[0].shape
         Ch = lw[0].shape[0]
-        need = ctx.needs_input_grad[1:]                              # lines up with ``args``: t0..t3, (lw, lb) x 4, (cw, cb) x 4
+        need = ctx.needs_input_grad[3:]                              # lines up with ``args``: t0..t3, (lw, lb) x 4, (cw, cb) x 4
         d_inner = [None] * 4
         g_cw, g_cb = [None] * 4, [None] * 4
         for i in range(4):                                            # finest first: the top-down adjoint flows fine -> coarse
@@ -164,7 +143,7 @@ class _FPNFn(torch.autograd.Function):
                                            need[4 + 2 * i], need[5 + 2 * i], grad_dtype, dgrad_w=operand("lat", i))
             g_tok[i] = g_x.view(B, T, Cc) if need[i] else None
             g_lw[i] = g_w.view(Ch, Cc, 1, 1) if need[4 + 2 * i] else None
-        grads = [None] + g_tok
+        grads = [None] * 3 + g_tok
         for i in range(4):
             grads += [g_lw[i], g_lb[i]]
         for i in range(4):
@@ -182,54 +161,36 @@ class DiTWithFPN(nn.Module):
     def __init__(self, pretrained: bool = False, config: Optional[DiTConfig] = None, checkpoint: Optional[str] = None,
                  compute_dtype: str = "f32", qat: bool = False, neck_dtype: str = "f32", grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
-        self.neck_dtype = check_neck_dtype(neck_dtype)
-        self.grad_dtype = check_grad_dtype(grad_dtype)
-        self.train_dtype = check_train_dtype(train_dtype)
+        self.neck_dtype = check_dtype("neck_dtype", neck_dtype)
+        self.grad_dtype = check_dtype("grad_dtype", grad_dtype)
+        self.train_dtype = check_dtype("train_dtype", train_dtype)
         self.backbone = DiTBackbone(pretrained=pretrained, config=config, checkpoint=checkpoint, compute_dtype=compute_dtype, qat=qat)
         self.fpn = _FPNParams([self.backbone.hidden_size] * 4, 256)
         self.out_channels = 256
-        self._cache = [ParamCache() for _ in range(4)]
-        self._cache_bf16 = [ParamCache() for _ in range(4)]
-        self._cache_dgrad = {kind: [ParamCache() for _ in range(4)] for kind in ("conv", "lat")}
+        self._operand_cache = OperandCache()
 
-    def set_grad_dtype(self, grad_dtype: str) -> "DiTWithFPN":
-        """``"f32"`` or ``"bf16"``: the matrix pipe of the FPN's eight input-gradient GEMMs in the backward from now on (four 3x3
-        output convolutions, four laterals; ``grad_ops.conv3x3_bwd`` / ``linear_bwd``).  Forward, parameters and ``state_dict`` do not
-        depend on it; the encoder below has its own ``compute_dtype``."""
-        self.grad_dtype = check_grad_dtype(grad_dtype)
-        return self
-
-    def set_train_dtype(self, train_dtype: str) -> "DiTWithFPN":
-        """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where a gradient IS wanted (:class:`_FPNFn`'s
-        forward), on the same weights - ``"bf16"``: as ``neck_dtype="bf16"`` runs them where none is.  Parameters and ``state_dict`` do
-        not depend on it; eval mode and ``no_grad`` never read it."""
-        self.train_dtype = check_train_dtype(train_dtype)
-        return self
-
-    def _dgrad_operands_bf16(self, kind: str, i: int) -> torch.Tensor:
-        """The weight operand of a dgrad GEMM under ``grad_dtype="bf16"``, re-made when the parameter changes: ``"conv"`` - level i's
-        3x3 weight flipped, in/out-swapped, bf16; ``"lat"`` - its lateral weight transposed [C, 256], bf16."""
-        if kind == "conv":
-            w = self.fpn.layer_blocks[i][0].weight
-            return self._cache_dgrad[kind][i].get(param_key(w), lambda: conv3x3_dgrad_bf16(w))
-        w = self.fpn.inner_blocks[i][0].weight
-        return self._cache_dgrad[kind][i].get(param_key(w), lambda: linear_dgrad_bf16(w.reshape(w.shape[0], w.shape[1])))
-
-    def set_neck_dtype(self, neck_dtype: str) -> "DiTWithFPN":
-        """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where no gradient is wanted, on the same
-        weights."""
-        self.neck_dtype = check_neck_dtype(neck_dtype)
-        return self
+    set_neck_dtype = dtype_setter("neck_dtype", """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where no
+        gradient is wanted, on the same weights.""")
+    set_grad_dtype = dtype_setter("grad_dtype", """``"f32"`` or ``"bf16"``: the matrix pipe of the FPN's eight input-gradient GEMMs in the
+        backward from now on (four 3x3 output convolutions, four laterals).  The encoder below has its own ``compute_dtype``.""")
+    set_train_dtype = dtype_setter("train_dtype", """``"f32"`` or ``"bf16"``: how the four 3x3 output convolutions run from now on where a
+        gradient IS wanted (:class:`_FPNFn`'s forward) - ``"bf16"``: as ``neck_dtype="bf16"`` runs them where none is.""")
 
     def _ohwi(self, i: int) -> torch.Tensor:
         """3x3 weight of level i as [Cout, 3, 3, Cin] (GEMM operand layout), re-laid when the parameter changes."""
         w = self.fpn.layer_blocks[i][0].weight
-        return self._cache[i].get(param_key(w), lambda: w.detach().permute(0, 2, 3, 1).contiguous())
+        return self._operand_cache.get(("ohwi", i), (w,), lambda: w.detach().permute(0, 2, 3, 1).contiguous())
 
     def _ohwi_bf16(self, i: int) -> torch.Tensor:
-        """The bf16 copy of :meth:`_ohwi` (``neck_dtype="bf16"``), cached beside it under the same key."""
-        w = self.fpn.layer_blocks[i][0].weight
-        return self._cache_bf16[i].get(param_key(w), lambda: ops.cast_bf16(self._ohwi(i)))
+        """The bf16 copy of :meth:`_ohwi` (``neck_dtype`` / ``train_dtype="bf16"``), cached beside it under the same key."""
+        return self._operand_cache.get(("ohwi_bf16", i), (self.fpn.layer_blocks[i][0].weight,), lambda: ops.cast_bf16(self._ohwi(i)))
+
+    def _dgrad_operands_bf16(self, kind: str, i: int) -> torch.Tensor:
+        """The weight operand of a dgrad GEMM under ``grad_dtype="bf16"``, re-made when the parameter changes: ``"conv"`` - level i's
+        3x3 weight flipped, in/out-swapped, bf16; ``"lat"`` - its lateral weight transposed [C, 256], bf16."""
+        w = (self.fpn.layer_blocks if kind == "conv" else self.fpn.inner_blocks)[i][0].weight
+        return self._operand_cache.get(("dgrad", kind, i), (w,), lambda: conv3x3_dgrad_bf16(w) if kind == "conv"
+                                       else linear_dgrad_bf16(w.reshape(w.shape[0], w.shape[1])))
 
     def forward(self, x: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
         bb = self.backbone
@@ -249,15 +210,14 @@ class DiTWithFPN(nn.Module):
                 args += [m.weight, m.bias]
             for m in conv:
                 args += [m.weight, m.bias]
-            results = list(_FPNFn.apply((gh, gw, tuple(bb.scales), self.grad_dtype, self._dgrad_operands_bf16, self.train_dtype,
-                                         self._ohwi_bf16), *args))
+            results = list(_FPNFn.apply(self, gh, gw, *args))
         else:
             Cc = bb.hidden_size
             bf16_conv = self.neck_dtype == "bf16"
             outs, _ = _fpn_forward(bb.scales, gh, gw, [_f32c(t.detach()) for t in toks],
                                    [m.weight.detach().reshape(256, Cc) for m in lat], [m.bias.detach() for m in lat],
                                    [self._ohwi_bf16(i) if bf16_conv else self._ohwi(i) for i in range(4)],
-                                   [m.bias.detach() for m in conv], keep_inner=False, bf16_conv=bf16_conv)
+                                   [m.bias.detach() for m in conv], keep_inner=False)
             results = [o.permute(0, 3, 1, 2) for o in outs]          # [B, 256, h, w], channels-last memory
         feats = OrderedDict((f"p{i + 2}", r) for i, r in enumerate(results))
         feats["pool"] = results[3][:, :, ::2, ::2]                    # LastLevelMaxPool: max_pool2d(kernel 1, stride 2)

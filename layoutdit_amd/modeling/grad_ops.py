@@ -1,6 +1,23 @@
 """What the detector's differentiable stages (``dit_fpn.py``, ``rpn.py``, ``roi_heads.py``) share: the backward of a 3x3 convolution
-and of a linear layer on the library's kernels, two layers stacked into one GEMM operand, and the cache of a re-laid operand.  Each
-stage keeps ONE ``autograd.Function`` (the order in which autograd sums a shared parameter's gradients is part of the bits)."""
+and of a linear layer on the library's kernels, the bf16 3x3 forward, two layers stacked into one GEMM operand, and the cache of
+re-laid operands.  Each stage keeps ONE ``autograd.Function`` (the order in which autograd sums a shared parameter's gradients is
+part of the bits).
+
+The four dtype options of the stages and of the detector that holds them, each ``"f32"`` (the default) or ``"bf16"``
+(:func:`check_dtype`), each a constructor argument, a property and a ``set_*`` method returning ``self``.  None touches a parameter
+or the ``state_dict``; a bf16 copy of a weight lives in the module's :class:`OperandCache` beside its fp32 re-layout.
+
+* ``neck_dtype`` (FPN, RPN head) and ``head_dtype`` (box head) - the path that wants NO gradient: the 3x3 convolutions
+  (:func:`conv3x3_fwd_bf16`) and the linear layers on the bf16 MFMA GEMM, fp32 accumulation, bf16 operand rounding, fp32 results.
+* ``train_dtype`` - the forward that WANTS a gradient: the launches of ``neck_dtype`` / ``head_dtype="bf16"`` on the same cached
+  operands (bit-equal results), saving the bf16 tensors the backward reads again as they stand.  Eval mode and
+  ``no_grad`` never read it.
+* ``grad_dtype`` - the backward alone: the input-gradient (dgrad) GEMMs of :func:`conv3x3_bwd` / :func:`linear_bwd` on the bf16
+  copy of the incoming gradient that the wgrad reads.  No forward reads it.
+
+A stage's autograd node takes the stage module itself, reads ``train_dtype`` and ``grad_dtype`` in its forward and keeps them on
+``ctx`` - a setter called between forward and backward does not change that backward - and takes the dgrad operands from the
+module's cache.  A reduction length that is no multiple of :data:`BF16_K` keeps every fp32 launch under any option."""
 from __future__ import annotations
 
 from typing import Optional
@@ -15,27 +32,24 @@ def flip_ihwo(w: torch.Tensor) -> torch.Tensor:
     return w.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
 
 
-GRAD_DTYPES = ("f32", "bf16")
+DTYPES = ("f32", "bf16")
 BF16_K = 64                    # the k-tile of the bf16 GEMM: a reduction length it takes is a multiple of it
 
 
-def check_grad_dtype(grad_dtype: str) -> str:
-    """The option of the FPN, the RPN head, the box head and the detector that holds them: the matrix pipe of the input-gradient
-    (dgrad) GEMMs of their backward."""
-    if grad_dtype not in GRAD_DTYPES:
-        raise ValueError(f"grad_dtype {grad_dtype!r}: the detector's backward is built for {' and '.join(repr(d) for d in GRAD_DTYPES)}")
-    return grad_dtype
+def check_dtype(option: str, value: str) -> str:
+    """``value`` if it is one ``option`` (``neck_dtype``, ``head_dtype``, ``grad_dtype``, ``train_dtype``) can take."""
+    if value not in DTYPES:
+        raise ValueError(f"{option} {value!r}: the detector's stages are built for {' and '.join(repr(d) for d in DTYPES)}")
+    return value
 
 
-TRAIN_DTYPES = ("f32", "bf16")
-
-
-def check_train_dtype(train_dtype: str) -> str:
-    """The option of the FPN, the RPN head, the box head and the detector that holds them: the matrix pipe of their forward where a
-    gradient is wanted (the GEMMs that ``neck_dtype`` / ``head_dtype`` move where none is)."""
-    if train_dtype not in TRAIN_DTYPES:
-        raise ValueError(f"train_dtype {train_dtype!r}: the detector's training forward is built for {' and '.join(repr(d) for d in TRAIN_DTYPES)}")
-    return train_dtype
+def dtype_setter(option: str, doc: str):
+    """The ``set_<option>`` method of a stage that keeps ``option`` as a plain attribute: validates, assigns, returns ``self``."""
+    def setter(self, value: str):
+        setattr(self, option, check_dtype(option, value))
+        return self
+    setter.__name__, setter.__doc__ = f"set_{option}", doc
+    return setter
 
 
 def padded_middle(x_p: torch.Tensor, B: int, h: int, w: int) -> torch.Tensor:
@@ -61,7 +75,9 @@ def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.
     MFMA GEMM per tap (fp32 accumulation, bf16 operand rounding) on the zero-padded maps as reduction-major operands
     [B (h+2)(w+2), C] - a tap is a constant row offset into the padded input, kept inside the buffer by ``slack`` zero rows.
 
-    ``act`` (same shape as ``dy``): ``dy`` is first masked by the ReLU whose output ``act`` is - ``where(act > 0, dy, 0)``.
+    ``act`` (same shape as ``dy``): ``dy`` is first masked by the ReLU whose output ``act`` is.  The fused launch of ``"bf16"``
+    selects, ``where(act > 0, dy, 0)``; the fp32 GEMM's arm multiplies, ``dy * (act > 0)`` - what the default configuration has
+    always done: equal for a finite ``dy`` but for the sign of a zero, and a non-finite ``dy`` at a masked position gives NaN there.
 
     ``grad_dtype="bf16"`` with ``Cout % 64 == 0``: ONE launch (``ldit_relu_bwd_pad_nhwc_bf16``) masks ``dy``, writes its zero-padded
     bf16 copy and sums ``g_b``; that copy is the operand of the wgrad taps - ``g_w`` and ``g_b`` have the bits of the ``"f32"``
@@ -75,7 +91,7 @@ def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.
     B, h, w, Cout = dy_nhwc.shape
     if act is not None:
         act = act.view(dy_nhwc.shape)
-    bf16 = check_grad_dtype(grad_dtype) == "bf16" and Cout % BF16_K == 0
+    bf16 = check_dtype("grad_dtype", grad_dtype) == "bf16" and Cout % BF16_K == 0
     if bf16:
         dy_p, g_b = ops.relu_bwd_pad_nhwc_bf16(dy_nhwc, act, want_colsum=need_b)
         g_x = None
@@ -84,7 +100,7 @@ def conv3x3_bwd(dy_nhwc: torch.Tensor, x_nhwc: torch.Tensor, weight_oihw: torch.
             g_x = ops.conv3x3_nhwc_bf16(dy_p, B, h, w, w16, None, _lib.EPI_F32).view(B, h, w, -1)
     else:
         if act is not None:
-            dy_nhwc = torch.where(act > 0, dy_nhwc, 0.0)
+            dy_nhwc = dy_nhwc * (act > 0)
         g_x = ops.conv3x3_nhwc(dy_nhwc, flip_ihwo(weight_oihw)) if need_x else None
         g_b = ops.colsum(dy_nhwc.view(B * h * w, Cout)) if need_b else None
     g_w = None
@@ -113,7 +129,9 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: 
     [<= N, K]: where ``dy`` ends in zero padding columns that the weight has no rows for, the transposed weight is zero-extended
     to N columns, and ``g_w`` and ``g_b`` have N rows.
 
-    ``act`` (same shape as ``dy``): ``dy`` is first masked by the ReLU whose output ``act`` is - ``where(act > 0, dy, 0)``.
+    ``act`` (same shape as ``dy``): ``dy`` is first masked by the ReLU whose output ``act`` is.  The fused launch of ``"bf16"``
+    selects, ``where(act > 0, dy, 0)``; the fp32 GEMM's arm multiplies, ``dy * (act > 0)`` - what the default configuration has
+    always done: equal for a finite ``dy`` but for the sign of a zero, and a non-finite ``dy`` at a masked position gives NaN there.
 
     ``grad_dtype="bf16"`` with ``N % 64 == 0`` and a weight of N rows: ONE launch (``ldit_relu_bwd_bf16``) masks ``dy``, writes its
     bf16 copy and sums ``g_b``; that copy is the operand of the wgrad - ``g_w`` and ``g_b`` have the bits of the ``"f32"`` setting -
@@ -125,7 +143,7 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: 
     A bf16 ``x`` (the layer's input as a forward under ``train_dtype="bf16"`` saved it) is the wgrad's operand as it stands - no cast
     launch - and a bf16 ``act`` the mask without an fp32 copy of it: every gradient has the bits of the call on their fp32 widenings."""
     x16 = (lambda: x) if x.dtype == torch.bfloat16 else (lambda: ops.cast_bf16(x))
-    if check_grad_dtype(grad_dtype) == "bf16" and dy.shape[1] % BF16_K == 0 and weight.shape[0] == dy.shape[1]:
+    if check_dtype("grad_dtype", grad_dtype) == "bf16" and dy.shape[1] % BF16_K == 0 and weight.shape[0] == dy.shape[1]:
         dy16, g_b = ops.relu_bwd_bf16(dy, act, want_colsum=need_b)
         g_x = None
         if need_x:
@@ -133,7 +151,7 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, need_x: 
         g_w = ops.wgrad_bf16(dy16, x16(), dy.shape[0]) if need_w else None
         return g_x, g_w, g_b
     if act is not None:
-        dy = torch.where(act > 0, dy, 0.0)
+        dy = dy * (act > 0)
     g_x = None
     if need_x:
         if weight.shape[0] == dy.shape[1]:
@@ -160,22 +178,27 @@ def stack_rows(weights, biases, multiple: int):
     return w, b
 
 
-NECK_DTYPES = ("f32", "bf16")
-
-
-def check_neck_dtype(neck_dtype: str) -> str:
-    """The option of the FPN, the RPN head and the detector that holds them: how their 3x3 convolutions run where no gradient is
-    wanted."""
-    if neck_dtype not in NECK_DTYPES:
-        raise ValueError(f"neck_dtype {neck_dtype!r}: the FPN and the RPN head are built for {' and '.join(repr(d) for d in NECK_DTYPES)}")
-    return neck_dtype
-
-
-def conv3x3_bf16(x_nhwc: torch.Tensor, weight_ohwi_bf16: torch.Tensor, bias, epilogue: int) -> torch.Tensor:
-    """The eval-mode bf16 3x3 convolution of an fp32 NHWC map: one launch for its zero-padded bf16 copy, one for the implicit-im2col
-    bf16 MFMA GEMM on it.  Returns the pixel rows ``[B h w, Cout]`` (fp32 for ``EPI_F32``, else bf16)."""
+def conv3x3_fwd_bf16(x_nhwc: torch.Tensor, weight_ohwi_bf16: torch.Tensor, bias, epilogue: int, slack: bool = False):
+    """The bf16 3x3 convolution of an fp32 NHWC map: one launch for its zero-padded bf16 copy, one for the implicit-im2col bf16 MFMA
+    GEMM on it.  Returns the pixel rows ``[B h w, Cout]`` (fp32 for ``EPI_F32``, else bf16) and the copy; with ``slack`` the copy
+    carries the ``w + 3`` zero rows at either end that the wgrad taps of :func:`conv3x3_bwd` want - what a training forward saves."""
     B, h, w, _ = x_nhwc.shape
-    return ops.conv3x3_nhwc_bf16(ops.pad_nhwc_bf16(x_nhwc), B, h, w, weight_ohwi_bf16, bias, epilogue)
+    x_p = ops.pad_nhwc_bf16(x_nhwc, slack_rows=w + 3 if slack else 0)
+    rows = ops.conv3x3_nhwc_bf16(padded_middle(x_p, B, h, w) if slack else x_p, B, h, w, weight_ohwi_bf16, bias, epilogue)
+    return rows, x_p
+
+
+def pad_grad_row(blocks, M: int, device) -> torch.Tensor:
+    """Column blocks ``(width, gradient or None)`` side by side as fp32 ``[M, K]``, K their width rounded up to 32 - the K the fp32
+    dgrad GEMM wants, a multiple of 8 for the bf16 wgrad; a missing block and the padding are zero."""
+    K = (sum(n for n, _ in blocks) + 31) // 32 * 32
+    dy = torch.zeros((M, K), device=device, dtype=torch.float32)
+    col = 0
+    for n, d in blocks:
+        if d is not None:
+            dy[:, col:col + n] = d.reshape(M, n)
+        col += n
+    return dy
 
 
 def param_key(*params: torch.Tensor) -> tuple:
@@ -185,7 +208,7 @@ def param_key(*params: torch.Tensor) -> tuple:
 
 class ParamCache:
     """One value derived from parameters under one key (:func:`param_key` of them and whatever else it depends on), rebuilt when
-    the key changes.  ``clear()`` after an update that moves no version counter."""
+    the key changes: one entry of an :class:`OperandCache`."""
 
     def __init__(self):
         self.key = self.value = None
@@ -197,3 +220,22 @@ class ParamCache:
 
     def clear(self) -> None:
         self.key = self.value = None
+
+
+class OperandCache:
+    """A module's values derived from its parameters, by name: each entry is a :class:`ParamCache` keyed on :func:`param_key` of its
+    parameters and whatever else it depends on, and is rebuilt alone when that key changes.  ``clear()`` after an update that moves
+    no version counter."""
+
+    def __init__(self):
+        self._entries = {}
+
+    def get(self, name, params, build, *extra):
+        return self._entries.setdefault(name, ParamCache()).get((param_key(*params), *extra), build)
+
+    def filled(self, name=None) -> bool:
+        """Whether the entry ``name`` - without one: any entry - holds a value."""
+        return any(e.value is not None for n, e in self._entries.items() if name is None or n == name)
+
+    def clear(self) -> None:
+        self._entries.clear()

@@ -28,25 +28,14 @@ installed offline: the semantics are restated from its documented behaviour (``t
 respect to torchvision itself, as for the FPN and the RPN.  Parameter names follow torchvision, so detector checkpoints load
 (``roi_heads.box_head.fc6.weight`` ...).
 
-``head_dtype="bf16"`` (default ``"f32"``; :meth:`RoIHeads.set_head_dtype` switches one set of weights) runs the eval-mode head in
-bf16: RoIAlign rounds its fp32 rows to bf16 at the store (``ldit_roi_align_levels_bf16`` - half the bytes written and read back),
-``fc6`` and ``fc7`` run on the bf16 MFMA GEMM with the ReLU in its epilogue (``LDIT_EPI_BIAS_RELU``: no ``relu_`` launch), the
-predictor on the same GEMM with an fp32 result.  The parameters stay fp32 (the ``state_dict`` does not depend on the option); their
-bf16 copies are cached beside the fp32 re-layouts.  Train mode and every path that wants a gradient stay fp32 whatever the option
-says.
-
-``grad_dtype="bf16"`` (default ``"f32"``; :meth:`RoIHeads.set_grad_dtype`, :meth:`TwoMLPHead.set_grad_dtype`) concerns
-:class:`_TwoMLPHeadFn`'s backward alone: per layer one launch masks the incoming gradient by the ReLU, writes its bf16 copy and sums
-the bias gradient, and fc7's and fc6's dgrad run on the bf16 MFMA GEMM on that copy (``grad_ops.linear_bwd``).
-The predictor's dgrad (32 padded columns), RoIAlign's backward and the losses stay fp32.
-
-``train_dtype="bf16"`` (default ``"f32"``; :meth:`RoIHeads.set_train_dtype`, :meth:`TwoMLPHead.set_train_dtype`) concerns the forward of
-:meth:`RoIHeads.head_padded` where a gradient is wanted: it runs the launches of ``head_dtype="bf16"`` on the same cached operands -
-bit-equal fp32 logits and deltas - as ONE node, :class:`_BoxHeadBF16Fn`, from the fp32 maps to the fp32 result.  One node, because
-autograd converts a gradient to the dtype of the forward output it belongs to: bf16 rows handed from a RoIAlign node to a head node
-would have fc6's fp32 input gradient rounded to bf16 on the way back.  The bf16 rows and activations it saves are the wgrad
-operands and ReLU masks of its backward as they stand.  A head with a reduction length that is no multiple of
-64 keeps the three nodes and every launch of ``"f32"``; so does a :class:`TwoMLPHead` called on its own (fp32 rows in, fp32 out).
+The dtype options are ``grad_ops.py``'s.  What is particular to this stage: under ``head_dtype="bf16"`` RoIAlign rounds its fp32 rows
+to bf16 at the store (``ldit_roi_align_levels_bf16`` - half the bytes written and read back), ``fc6`` and ``fc7`` have the ReLU in the
+GEMM's epilogue (no ``relu_`` launch) and the predictor stores its fp32 value unrounded.  ``train_dtype="bf16"`` runs those launches
+where :meth:`RoIHeads.head_padded` wants a gradient as ONE node, :class:`_BoxHeadBF16Fn`, from the fp32 maps to the fp32 result - one
+node, because autograd converts a gradient to the dtype of the forward output it belongs to: bf16 rows handed from a RoIAlign node to
+a head node would have fc6's fp32 input gradient rounded to bf16 on the way back.  A head with a reduction length that is no multiple
+of 64 keeps the three nodes and every launch of ``"f32"``; so does a :class:`TwoMLPHead` called on its own (fp32 rows in, fp32 out).
+``grad_dtype`` concerns fc6's and fc7's dgrad; the predictor's (32 padded columns), RoIAlign's backward and the losses stay fp32.
 """
 from __future__ import annotations
 
@@ -56,16 +45,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .grad_ops import BF16_K, ParamCache, check_grad_dtype, check_train_dtype, linear_bwd, linear_dgrad_bf16, param_key, stack_rows
-
-
-HEAD_DTYPES = ("f32", "bf16")
-
-
-def _check_head_dtype(head_dtype: str) -> str:
-    if head_dtype not in HEAD_DTYPES:
-        raise ValueError(f"head_dtype {head_dtype!r}: the box head is built for {' and '.join(repr(d) for d in HEAD_DTYPES)}")
-    return head_dtype
+from .grad_ops import BF16_K, OperandCache, check_dtype, dtype_setter, linear_bwd, linear_dgrad_bf16, pad_grad_row, stack_rows
 
 
 def _nhwc_f32(f: torch.Tensor) -> torch.Tensor:
@@ -131,14 +111,36 @@ class MultiScaleRoIAlign(nn.Module):
                                     self.sampling_ratio, self.canonical_scale, self.canonical_level)
 
 
+def _mlp_bwd(d7, x0, h6, h7, w6p, w7, pooled_shape, need, grad_dtype: str, head: "TwoMLPHead"):
+    """fc7 then fc6 of a :class:`TwoMLPHead` backwards: ``d7`` the gradient of the head's output before its ReLU mask, ``x0`` [M, K] the
+    pooled rows, ``h6`` / ``h7`` the two activations (the masks), ``w6p`` fc6's weight in the rows' (ph, pw, c) column order; ``need``:
+    (pooled rows, fc6.weight, fc6.bias, fc7.weight, fc7.bias).  Returns those five gradients, fc6's weight gradient permuted back to
+    torchvision's (c, ph, pw) columns and the rows' in ``pooled_shape``."""
+    M, ph, pw, Cc = pooled_shape
+    operands = lambda i: (lambda: head.dgrad_operands_bf16(Cc, ph, pw)[i])                # noqa: E731
+    d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4], grad_dtype, act=h7, dgrad_w=operands(1))
+    g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2], grad_dtype, act=h6, dgrad_w=operands(0))
+    if g_w6p is not None:
+        g_w6p = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
+    return (g_x.view(M, ph, pw, Cc) if g_x is not None else None), g_w6p, g_b6, g_w7, g_b7
+
+
+def _predictor_bwd(dy, x, w, NC: int, need, grad_dtype: str = "f32"):
+    """The stacked predictor GEMM backwards: ``dy`` [M, a multiple of 32 columns], ``w`` the stacked weight; ``need``: (input,
+    cls_score.weight, .bias, bbox_pred.weight, .bias).  Returns those five gradients, the stacked ones split back into the layers'."""
+    g_x, g_w, g_b = linear_bwd(dy, x, w, need[0], need[1] or need[3], need[2] or need[4], grad_dtype)
+    return (g_x, g_w[:NC] if need[1] else None, g_b[:NC] if need[2] else None, g_w[NC:5 * NC] if need[3] else None,
+            g_b[NC:5 * NC] if need[4] else None)
+
+
 class _TwoMLPHeadFn(torch.autograd.Function):
     """:class:`TwoMLPHead` with gradients for the pooled rows and the four parameters.
-    apply(pooled [M, P, P, C], fc6.weight, fc6.bias, fc7.weight, fc7.bias, grad) -> [M, representation_size].  ``grad``:
-    ``(grad_dtype, operands)``, the head's option and its cached :meth:`TwoMLPHead.dgrad_operands_bf16` as a callable; the forward
-    does not read it."""
+    apply(pooled [M, P, P, C], fc6.weight, fc6.bias, fc7.weight, fc7.bias, head) -> [M, representation_size].  ``head``: the
+    :class:`TwoMLPHead` whose parameters these are; the forward reads its ``grad_dtype`` and keeps it on ``ctx`` - a setter called
+    between forward and backward does not change that backward - and the backward takes the dgrad operands from its cache."""
 
     @staticmethod
-    def forward(ctx, pooled, w6, b6, w7, b7, grad=("f32", None)):
+    def forward(ctx, pooled, w6, b6, w7, b7, head):
         M, ph, pw, Cc = pooled.shape
         x0 = pooled.detach().reshape(M, ph * pw * Cc)
         w6p = w6.detach().view(w6.shape[0], Cc, ph, pw).permute(0, 2, 3, 1).reshape(w6.shape[0], -1).contiguous()      # (ph, pw, c) columns
@@ -146,34 +148,17 @@ class _TwoMLPHeadFn(torch.autograd.Function):
         torch.relu_(h6)
         h7 = ops.linear(h6, w7.detach().contiguous(), b7.detach())
         torch.relu_(h7)
-        ctx.saved = (x0, w6p, h6, w7.detach(), h7)
+        ctx.saved = (x0, h6, h7, w6p, w7.detach())
         ctx.pooled_shape = (M, ph, pw, Cc)
-        ctx.grad = grad
+        ctx.head, ctx.grad_dtype = head, check_dtype("grad_dtype", head.grad_dtype)
         return h7.clone()                                             # the saved activation is the ReLU mask: keep it private
 
     @staticmethod
     def backward(ctx, d7):
         if ctx.saved is None:
             raise RuntimeError("TwoMLPHead: backward a second time (its saved activations are freed after the first)")
-        x0, w6p, h6, w7, h7 = ctx.saved
-        ctx.saved = None
-        M, ph, pw, Cc = ctx.pooled_shape
-        need = ctx.needs_input_grad
-        grad_dtype, operands = ctx.grad
-        if grad_dtype == "bf16":
-            # each ReLU mask is applied by the launch that makes the layer's bf16 copy of dy and its bias gradient
-            w6_16, w7_16 = (None, None) if operands is None else ((lambda: operands()[0]), (lambda: operands()[1]))
-            d6, g_w7, g_b7 = linear_bwd(d7.contiguous(), h6, w7.contiguous(), True, need[3], need[4], grad_dtype, act=h7, dgrad_w=w7_16)
-            g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2], grad_dtype, act=h6, dgrad_w=w6_16)
-        else:
-            d7 = d7.contiguous() * (h7 > 0)                           # ReLU mask
-            d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, need[3], need[4])
-            d6.mul_(h6 > 0)
-            g_x, g_w6p, g_b6 = linear_bwd(d6, x0, w6p, need[0], need[1], need[2])
-        g_w6 = None
-        if g_w6p is not None:                                         # back to torchvision's (c, ph, pw) columns
-            g_w6 = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
-        return (g_x.view(M, ph, pw, Cc) if g_x is not None else None), g_w6, g_b6, g_w7, g_b7, None
+        saved, ctx.saved = ctx.saved, None
+        return _mlp_bwd(d7.contiguous(), *saved, ctx.pooled_shape, ctx.needs_input_grad, ctx.grad_dtype, ctx.head) + (None,)
 
 
 class _PredictorFn(torch.autograd.Function):
@@ -194,20 +179,18 @@ class _PredictorFn(torch.autograd.Function):
     def backward(ctx, dy):
         if ctx.saved is None:
             raise RuntimeError("FastRCNNPredictor: backward a second time (its saved input is freed after the first)")
-        x, w = ctx.saved
-        ctx.saved = None
-        NC, need = ctx.NC, ctx.needs_input_grad
-        g_x, g_w, g_b = linear_bwd(dy.contiguous(), x, w, need[0], need[1] or need[3], need[2] or need[4])
-        return (g_x, g_w[:NC] if need[1] else None, g_b[:NC] if need[2] else None, g_w[NC:5 * NC] if need[3] else None,
-                g_b[NC:5 * NC] if need[4] else None)
+        (x, w), ctx.saved = ctx.saved, None
+        return _predictor_bwd(dy.contiguous(), x, w, ctx.NC, ctx.needs_input_grad)
 
 
 class _BoxHeadBF16Fn(torch.autograd.Function):
     """The box head under ``train_dtype="bf16"``, RoIAlign -> fc6 -> fc7 -> predictor as one node: fp32 maps and the eight parameters in,
     fp32 ``[M, 5 NC (+ pad)]`` out, every bf16 tensor inside.  The forward is ``head_dtype="bf16"``'s - ``ldit_roi_align_levels_bf16``,
-    :meth:`TwoMLPHead.forward_bf16`, :meth:`FastRCNNPredictor.forward_stacked_bf16` on the modules' cached operands.  The backward is
-    ``grad_ops.linear_bwd`` per layer on the saved bf16 rows and activations (wgrad operands and ReLU masks as they stand), then
-    :class:`_RoIAlignLevelsFn`'s one gather launch on the fp32 ``g_x`` of fc6's dgrad.
+    :meth:`TwoMLPHead.layers_bf16`, :meth:`FastRCNNPredictor.forward_stacked_bf16` on the modules' cached operands.  The backward is
+    the fp32 head's, :func:`_predictor_bwd` and :func:`_mlp_bwd`, on the saved bf16 rows and activations (wgrad operands and ReLU masks
+    as they stand), then :class:`_RoIAlignLevelsFn`'s one gather launch on the fp32 ``g_x`` of fc6's dgrad.  The box head's
+    ``grad_dtype`` is read in the forward and kept on ``ctx``: a setter called between forward and backward does not change that
+    backward.
     apply(roi_heads, boxes, count, image_size, *maps (5), fc6.weight, fc6.bias, fc7.weight, fc7.bias, cls_score.weight, .bias,
     bbox_pred.weight, .bias) -> [B R, 5 NC (+ pad)]."""
 
@@ -218,13 +201,11 @@ class _BoxHeadBF16Fn(torch.autograd.Function):
                                           pool.sampling_ratio, pool.canonical_scale, pool.canonical_level, return_levels=True,
                                           out_dtype=torch.bfloat16)
         M, ph, pw, Cc = x0.shape
-        w6_16, w7_16 = head.operands_bf16(Cc, ph, pw)
-        h6 = ops.linear_bf16(x0.view(M, ph * pw * Cc), w6_16, head.fc6.bias.detach(), _lib.EPI_BIAS_RELU)
-        h7 = ops.linear_bf16(h6, w7_16, head.fc7.bias.detach(), _lib.EPI_BIAS_RELU)
+        h6, h7 = head.layers_bf16(x0)
         y = pred.forward_stacked_bf16(h7)
         ctx.saved = (boxes, count, levels, x0, h6, h7, head.fc6_weight_hwc(Cc, ph, pw), args[-6].detach(), pred._operands()[0])
         ctx.geometry = ([tuple(f.shape[-2:]) for f in maps], tuple(image_size), pool.output_size, pool.sampling_ratio)
-        ctx.grad = (head.grad_dtype, lambda: head.dgrad_operands_bf16(Cc, ph, pw))
+        ctx.head, ctx.grad_dtype = head, check_dtype("grad_dtype", head.grad_dtype)
         ctx.NC = pred.num_classes
         return y
 
@@ -235,27 +216,17 @@ class _BoxHeadBF16Fn(torch.autograd.Function):
         boxes, count, levels, x0, h6, h7, w6p, w7, wp = ctx.saved
         ctx.saved = None
         shapes, image_size, output_size, sampling_ratio = ctx.geometry
-        grad_dtype, operands = ctx.grad
         M, ph, pw, Cc = x0.shape
-        NC, nmaps = ctx.NC, len(shapes)
+        nmaps = len(shapes)
         need = ctx.needs_input_grad[4:]                               # maps, then (w6, b6, w7, b7, wc, bc, wb, bb)
         need_maps, np_ = any(need[:nmaps]), need[nmaps:]
-        # the predictor's row zero-padded to 32 columns, the K of its fp32 dgrad GEMM (below the bf16 GEMM's k-tile under either grad_dtype)
-        K = (dy.shape[1] + 31) // 32 * 32
-        dy32 = torch.zeros((M, K), device=dy.device, dtype=torch.float32)
-        dy32[:, :dy.shape[1]] = dy
-        d7, g_wp, g_bp = linear_bwd(dy32, h7, wp, True, np_[4] or np_[6], np_[5] or np_[7], grad_dtype)
-        d6, g_w7, g_b7 = linear_bwd(d7, h6, w7.contiguous(), True, np_[2], np_[3], grad_dtype, act=h7, dgrad_w=lambda: operands()[1])
-        g_x, g_w6p, g_b6 = linear_bwd(d6, x0.view(M, ph * pw * Cc), w6p, need_maps, np_[0], np_[1], grad_dtype, act=h6,
-                                      dgrad_w=lambda: operands()[0])
-        g_w6 = None
-        if g_w6p is not None:                                         # back to torchvision's (c, ph, pw) columns
-            g_w6 = g_w6p.view(-1, ph, pw, Cc).permute(0, 3, 1, 2).reshape(g_w6p.shape[0], -1)
+        # (the predictor's 32 columns are below the bf16 GEMM's k-tile: its dgrad is the fp32 GEMM under either grad_dtype)
+        d7, *g_pred = _predictor_bwd(pad_grad_row(((dy.shape[1], dy),), M, dy.device), h7, wp, ctx.NC, (True,) + np_[4:], ctx.grad_dtype)
+        g_x, *g_mlp = _mlp_bwd(d7, x0.view(M, ph * pw * Cc), h6, h7, w6p, w7, (M, ph, pw, Cc), (need_maps,) + np_[:4], ctx.grad_dtype, ctx.head)
         g_maps = (None,) * nmaps
         if need_maps:
-            g_maps = tuple(ops.roi_align_levels_bwd(g_x.view(M, ph, pw, Cc), boxes, count, levels, shapes, image_size, output_size, sampling_ratio))
-        return (None,) * 4 + g_maps + (g_w6, g_b6, g_w7, g_b7, g_wp[:NC] if np_[4] else None, g_bp[:NC] if np_[5] else None,
-                                       g_wp[NC:5 * NC] if np_[6] else None, g_bp[NC:5 * NC] if np_[7] else None)
+            g_maps = tuple(ops.roi_align_levels_bwd(g_x, boxes, count, levels, shapes, image_size, output_size, sampling_ratio))
+        return (None,) * 4 + g_maps + tuple(g_mlp) + tuple(g_pred)
 
 
 class _BoxLossFn(torch.autograd.Function):
@@ -286,30 +257,17 @@ class TwoMLPHead(nn.Module):
 
     def __init__(self, in_channels: int = 256 * 7 * 7, representation_size: int = 1024, grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
-        self.grad_dtype = check_grad_dtype(grad_dtype)
-        self.train_dtype = check_train_dtype(train_dtype)
+        self.grad_dtype = check_dtype("grad_dtype", grad_dtype)
+        self.train_dtype = check_dtype("train_dtype", train_dtype)
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
-        self._packed, self._packed_bf16, self._dgrad_bf16 = ParamCache(), ParamCache(), ParamCache()
+        self._operand_cache = OperandCache()
 
-    def set_grad_dtype(self, grad_dtype: str) -> "TwoMLPHead":
-        """``"f32"`` or ``"bf16"``: the matrix pipe of the two input-gradient GEMMs of the backward from now on (``grad_ops.linear_bwd``).
-        Forward, parameters and ``state_dict`` do not depend on it."""
-        self.grad_dtype = check_grad_dtype(grad_dtype)
-        return self
-
-    def set_train_dtype(self, train_dtype: str) -> "TwoMLPHead":
-        """``"f32"`` or ``"bf16"``: how :meth:`RoIHeads.head_padded` runs this head from now on where a gradient IS wanted -
-        ``"bf16"``: the launches of ``head_dtype="bf16"`` inside :class:`_BoxHeadBF16Fn`.  :meth:`forward` on its own (fp32 rows in,
-        fp32 out), parameters and ``state_dict`` do not depend on it; eval mode and ``no_grad`` never read it."""
-        self.train_dtype = check_train_dtype(train_dtype)
-        return self
-
-    def dgrad_operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The weight operands of the two dgrad GEMMs under ``grad_dtype="bf16"``: :meth:`fc6_weight_hwc` and ``fc7.weight``, each
-        transposed and rounded to bf16, re-made when a parameter changes."""
-        return self._dgrad_bf16.get((param_key(self.fc6.weight, self.fc7.weight), channels, ph, pw),
-                                    lambda: (linear_dgrad_bf16(self.fc6_weight_hwc(channels, ph, pw)), linear_dgrad_bf16(self.fc7.weight)))
+    set_grad_dtype = dtype_setter("grad_dtype", """``"f32"`` or ``"bf16"``: the matrix pipe of the two input-gradient GEMMs of the backward
+        from now on (``grad_ops.linear_bwd``).""")
+    set_train_dtype = dtype_setter("train_dtype", """``"f32"`` or ``"bf16"``: how :meth:`RoIHeads.head_padded` runs this head from now on
+        where a gradient IS wanted - ``"bf16"``: the launches of ``head_dtype="bf16"`` inside :class:`_BoxHeadBF16Fn`.  :meth:`forward`
+        on its own (fp32 rows in, fp32 out) does not depend on it.""")
 
     def fc6_weight_hwc(self, channels: int, ph: int, pw: int) -> torch.Tensor:
         """``fc6.weight`` with its columns re-ordered from torchvision's ``flatten(start_dim=1)`` of (c, ph, pw) to (ph, pw, c) - the
@@ -317,25 +275,36 @@ class TwoMLPHead(nn.Module):
         w = self.fc6.weight
         if channels * ph * pw != w.shape[1]:
             raise ValueError(f"TwoMLPHead: pooled rows of {ph} x {pw} x {channels} do not match fc6's {w.shape[1]} inputs")
-        return self._packed.get((param_key(w), channels, ph, pw), lambda: w.detach().view(w.shape[0], channels, ph, pw)
-                                .permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
+        return self._operand_cache.get("fc6_hwc", (w,), lambda: w.detach().view(w.shape[0], channels, ph, pw).permute(0, 2, 3, 1)
+                                       .reshape(w.shape[0], -1).contiguous(), channels, ph, pw)
 
     def operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The bf16 GEMM's weight operands: :meth:`fc6_weight_hwc` and ``fc7.weight`` rounded to bf16, re-made when a parameter
         changes."""
-        return self._packed_bf16.get((param_key(self.fc6.weight, self.fc7.weight), channels, ph, pw),
-                                     lambda: (ops.cast_bf16(self.fc6_weight_hwc(channels, ph, pw)),
-                                              ops.cast_bf16(self.fc7.weight.detach().contiguous())))
+        return self._operand_cache.get("bf16", (self.fc6.weight, self.fc7.weight),
+                                       lambda: (ops.cast_bf16(self.fc6_weight_hwc(channels, ph, pw)),
+                                                ops.cast_bf16(self.fc7.weight.detach().contiguous())), channels, ph, pw)
 
-    def forward_bf16(self, pooled: torch.Tensor) -> torch.Tensor:
-        """``pooled`` bf16 [M, P, P, C] -> bf16 [M, representation_size]: both layers on the bf16 GEMM, the ReLU in its epilogue.
-        No gradient."""
+    def dgrad_operands_bf16(self, channels: int, ph: int, pw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The weight operands of the two dgrad GEMMs under ``grad_dtype="bf16"``: :meth:`fc6_weight_hwc` and ``fc7.weight``, each
+        transposed and rounded to bf16, re-made when a parameter changes."""
+        return self._operand_cache.get("dgrad", (self.fc6.weight, self.fc7.weight),
+                                       lambda: (linear_dgrad_bf16(self.fc6_weight_hwc(channels, ph, pw)), linear_dgrad_bf16(self.fc7.weight)),
+                                       channels, ph, pw)
+
+    def layers_bf16(self, pooled: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``pooled`` bf16 [M, P, P, C] -> both activations, bf16 [M, representation_size] each: fc6 and fc7 on the bf16 GEMM, the ReLU
+        in its epilogue.  No gradient."""
         if pooled.dim() != 4 or pooled.dtype != torch.bfloat16:
             raise ValueError(f"TwoMLPHead: expected bfloat16 pooled rows [M, P, P, C], got {pooled.dtype} {tuple(pooled.shape)}")
         M, ph, pw, Cc = pooled.shape
         w6, w7 = self.operands_bf16(Cc, ph, pw)
-        x = ops.linear_bf16(pooled.reshape(M, ph * pw * Cc), w6, self.fc6.bias.detach(), _lib.EPI_BIAS_RELU)
-        return ops.linear_bf16(x, w7, self.fc7.bias.detach(), _lib.EPI_BIAS_RELU)
+        h6 = ops.linear_bf16(pooled.reshape(M, ph * pw * Cc), w6, self.fc6.bias.detach(), _lib.EPI_BIAS_RELU)
+        return h6, ops.linear_bf16(h6, w7, self.fc7.bias.detach(), _lib.EPI_BIAS_RELU)
+
+    def forward_bf16(self, pooled: torch.Tensor) -> torch.Tensor:
+        """:meth:`layers_bf16`'s second activation: the head's bf16 output."""
+        return self.layers_bf16(pooled)[1]
 
     def forward(self, pooled: torch.Tensor) -> torch.Tensor:
         """``pooled`` [M, P, P, C] (channels innermost) -> [M, representation_size]."""
@@ -346,8 +315,7 @@ class TwoMLPHead(nn.Module):
             raise ValueError(f"TwoMLPHead: pooled rows of {ph} x {pw} x {Cc} do not match fc6's {self.fc6.weight.shape[1]} inputs")
         if _wants_grad(self, pooled):
             # gradients are wanted: the differentiable node (the eval path below and its cache are untouched)
-            return _TwoMLPHeadFn.apply(pooled, self.fc6.weight, self.fc6.bias, self.fc7.weight, self.fc7.bias,
-                                       (self.grad_dtype, lambda: self.dgrad_operands_bf16(Cc, ph, pw)))
+            return _TwoMLPHeadFn.apply(pooled, self.fc6.weight, self.fc6.bias, self.fc7.weight, self.fc7.bias, self)
         x = ops.linear(pooled.reshape(M, ph * pw * Cc), self.fc6_weight_hwc(Cc, ph, pw), self.fc6.bias.detach())
         torch.relu_(x)
         x = ops.linear(x, self.fc7.weight.detach(), self.fc7.bias.detach())
@@ -363,18 +331,18 @@ class FastRCNNPredictor(nn.Module):
         self.cls_score = nn.Linear(in_channels, num_classes)
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
         self.num_classes = int(num_classes)
-        self._packed, self._packed_bf16 = ParamCache(), ParamCache()
+        self._operand_cache = OperandCache()
 
     def _operands(self):
         """Both layers as one [5 NC (padded to a multiple of 4), in_channels] matrix, re-laid when a parameter changes."""
         wc, bc, wb, bb = self.cls_score.weight, self.cls_score.bias, self.bbox_pred.weight, self.bbox_pred.bias
-        return self._packed.get(param_key(wc, bc, wb, bb), lambda: stack_rows((wc, wb), (bc, bb), 4))
+        return self._operand_cache.get("f32", (wc, bc, wb, bb), lambda: stack_rows((wc, wb), (bc, bb), 4))
 
     def forward_stacked_bf16(self, x: torch.Tensor) -> torch.Tensor:
         """bf16 [M, in_channels] -> fp32 [M, 5 NC (+ pad)] on the bf16 GEMM: the stacked weight rounded to bf16 (re-made when a
         parameter changes), fp32 bias, the accumulator stored unrounded; the padding columns are zero.  No gradient."""
         w, b = self._operands()
-        w16 = self._packed_bf16.get(param_key(self.cls_score.weight, self.bbox_pred.weight), lambda: ops.cast_bf16(w))
+        w16 = self._operand_cache.get("bf16", (self.cls_score.weight, self.bbox_pred.weight), lambda: ops.cast_bf16(w))
         return ops.linear_bf16(x, w16, b, _lib.EPI_F32)
 
     def forward_stacked(self, x: torch.Tensor) -> torch.Tensor:
@@ -402,7 +370,7 @@ class RoIHeads(nn.Module):
                  batch_size_per_image: int = 512, positive_fraction: float = 0.25, head_dtype: str = "f32",
                  grad_dtype: Optional[str] = None, train_dtype: Optional[str] = None):
         super().__init__()
-        self.head_dtype = _check_head_dtype(head_dtype)
+        self.head_dtype = check_dtype("head_dtype", head_dtype)
         self.box_roi_pool, self.box_head, self.box_predictor = box_roi_pool, box_head, box_predictor
         if grad_dtype is not None:                                    # None: the box head keeps the setting it was built with
             self.set_grad_dtype(grad_dtype)
@@ -441,10 +409,7 @@ class RoIHeads(nn.Module):
             return False
         return head.fc6.in_features % BF16_K == 0 and head.fc6.out_features % BF16_K == 0 and head.fc7.out_features % BF16_K == 0
 
-    def set_head_dtype(self, head_dtype: str) -> "RoIHeads":
-        """``"f32"`` or ``"bf16"``: how the eval-mode head runs from now on.  The parameters are untouched."""
-        self.head_dtype = _check_head_dtype(head_dtype)
-        return self
+    set_head_dtype = dtype_setter("head_dtype", """``"f32"`` or ``"bf16"``: how the eval-mode head runs from now on.""")
 
     @property
     def grad_dtype(self) -> str:
@@ -453,7 +418,7 @@ class RoIHeads(nn.Module):
         return self.box_head.grad_dtype
 
     def set_grad_dtype(self, grad_dtype: str) -> "RoIHeads":
-        self.box_head.set_grad_dtype(check_grad_dtype(grad_dtype))
+        self.box_head.set_grad_dtype(grad_dtype)
         return self
 
     @property
@@ -463,7 +428,7 @@ class RoIHeads(nn.Module):
         return self.box_head.train_dtype
 
     def set_train_dtype(self, train_dtype: str) -> "RoIHeads":
-        self.box_head.set_train_dtype(check_train_dtype(train_dtype))
+        self.box_head.set_train_dtype(train_dtype)
         return self
 
     def _wants_grad(self, features) -> bool:

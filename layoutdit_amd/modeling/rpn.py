@@ -21,25 +21,15 @@ GEMM's 32), ``conv3x3_bwd`` for the 3x3 (the same implicit-im2col GEMM on the fl
 MFMA GEMMs on reduction-major operands with fp32 accumulation (they carry bf16 operand rounding, like the encoder's), the biases
 ``ldit_colsum_f32``.  ``train()`` mode WITHOUT targets stays refused.
 
-``neck_dtype="bf16"`` (default ``"f32"``; :meth:`RPNHead.set_neck_dtype`) runs the head's non-differentiable branch on the bf16 matrix
-pipe: per level one zero-padded bf16 copy of the map, the 3x3 as ``ldit_conv3x3_nhwc_bf16`` with bias and ReLU in the GEMM's epilogue
-(bf16 activation rows; no ``relu_`` launch, no fp32 activation), the 1x1 pair as one bf16 GEMM whose fp32 value is stored unrounded -
-fp32 logits and deltas in the layout above.  Parameters stay fp32; :class:`_RPNHeadLevelFn` and the losses ignore the option.
-
 torchvision is not installed offline: the semantics are restated from its documented behaviour (``tests/rpn_oracle.py``,
 ``tests/rpn_train_oracle.py``) - parity unpinned with respect to torchvision itself, as for the FPN.  Parameter names follow
 torchvision, so detector checkpoints load (``rpn.head.conv.0.0.weight`` ...).
 
-``grad_dtype="bf16"`` (default ``"f32"``; :meth:`RPNHead.set_grad_dtype`) concerns :class:`_RPNHeadLevelFn`'s backward alone: one launch
-masks the 1x1 pair's input gradient by the ReLU, writes its zero-padded bf16 copy and sums the 3x3's bias gradient, and the 3x3's
-dgrad runs on the bf16 MFMA GEMM on that copy (``grad_ops.conv3x3_bwd``).  The 1x1 pair's own dgrad (32 padded
-columns) stays on the fp32 GEMM.
-
-``train_dtype="bf16"`` (default ``"f32"``; :meth:`RPNHead.set_train_dtype`) concerns :class:`_RPNHeadLevelFn`'s forward alone, the branch
-that wants a gradient: it runs the launches of ``neck_dtype="bf16"`` on the same cached operands - bit-equal logits and deltas - with
-the map's zero-padded bf16 copy made once with the slack rows of the wgrad taps.  That copy and the bf16 activation are what the
-backward reads again: the 3x3's wgrad operand, the ReLU mask and the 1x1 pair's wgrad operand as they stand.  A
-channel count that is no multiple of 64 keeps every launch of ``"f32"``.  Eval mode and ``no_grad`` never read it.
+The dtype options are ``grad_ops.py``'s.  What is particular to this head: under ``neck_dtype`` / ``train_dtype="bf16"`` the 3x3 has
+bias and ReLU in the GEMM's epilogue (bf16 activation rows; no ``relu_`` launch, no fp32 activation) and the 1x1 pair is one bf16
+GEMM whose fp32 value is stored unrounded; what :class:`_RPNHeadLevelFn` then saves are the map's slack-padded bf16 copy and the bf16
+activation - the 3x3's wgrad operand, the ReLU mask and the 1x1 pair's wgrad operand as they stand.  ``grad_dtype`` concerns the 3x3's
+dgrad; the 1x1 pair's own (32 padded columns) stays on the fp32 GEMM.
 """
 from __future__ import annotations
 
@@ -50,8 +40,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .grad_ops import (BF16_K, ParamCache, check_grad_dtype, check_neck_dtype, check_train_dtype, conv3x3_bf16, conv3x3_bwd,
-                       conv3x3_dgrad_bf16, linear_bwd, padded_middle, param_key, stack_rows)
+from .grad_ops import (BF16_K, OperandCache, check_dtype, conv3x3_bwd, conv3x3_dgrad_bf16, conv3x3_fwd_bf16, dtype_setter, linear_bwd,
+                       pad_grad_row, stack_rows)
 
 
 class AnchorGenerator(nn.Module):
@@ -113,56 +103,40 @@ class _ConvRelu(nn.Sequential):
         super().__init__(nn.Conv2d(c, c, kernel_size=3, padding=1), nn.ReLU(inplace=True))
 
 
-def _level_forward(x, operands, A: int):
-    """One level on :meth:`RPNHead._operands`: the NHWC map, the 3x3's activation and ``(logits [B, h w A], deltas [B, h w A, 4])``."""
+def _level_forward(x, operands, A: int, slack: bool = False):
+    """One level on :meth:`RPNHead._operands` or, on the bf16 matrix pipe, :meth:`RPNHead._operands_bf16` (the 3x3 with bias and ReLU in
+    the GEMM's epilogue, the 1x1 pair as one bf16 GEMM with its fp32 value stored unrounded).  Returns ``(logits [B, h w A], deltas
+    [B, h w A, 4])`` and what a backward reads: the NHWC map - under bf16 its zero-padded bf16 copy, with the wgrad's ``slack`` rows
+    where asked - and the 3x3's activation rows."""
     w3, b3, w1, b1 = operands
     B, Cc, h, w = x.shape
     xn = x.detach().permute(0, 2, 3, 1).contiguous()                                      # NHWC; free for channels-last maps
-    t = ops.conv3x3_nhwc(xn, w3, b3)
-    torch.relu_(t)
-    y = ops.linear(t.view(B * h * w, Cc), w1, b1)                      # [B h w, 5 A (+ pad)]: logits | deltas per pixel row
-    return xn, t, (y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4))
-
-
-def _level_forward_bf16(x, operands_bf16, A: int):
-    """:func:`_level_forward` under ``neck_dtype="bf16"``, on :meth:`RPNHead._operands_bf16`: the zero-padded bf16 copy of the map,
-    the 3x3 on the bf16 MFMA GEMM with bias and ReLU in its epilogue (bf16 activation rows, no ``relu_`` launch, no fp32 activation),
-    the 1x1 pair as one bf16 GEMM with its fp32 value stored unrounded.  Same results layout."""
-    w3, b3, w1, b1 = operands_bf16
-    B, _, h, w = x.shape
-    xn = x.detach().permute(0, 2, 3, 1).contiguous()
-    t = conv3x3_bf16(xn, w3, b3, _lib.EPI_BIAS_RELU)                                      # bf16 [B h w, C]
-    y = ops.linear_bf16(t, w1, b1, _lib.EPI_F32)                                          # fp32 [B h w, 5 A (+ pad)]
-    return y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4)
+    if w3.dtype == torch.bfloat16:
+        t, xn = conv3x3_fwd_bf16(xn, w3, b3, _lib.EPI_BIAS_RELU, slack=slack)             # bf16 [B h w, C]
+        y = ops.linear_bf16(t, w1, b1, _lib.EPI_F32)                                      # fp32 [B h w, 5 A (+ pad)]
+    else:
+        t = ops.conv3x3_nhwc(xn, w3, b3).view(B * h * w, Cc)
+        torch.relu_(t)
+        y = ops.linear(t, w1, b1)                                      # [B h w, 5 A (+ pad)]: logits | deltas per pixel row
+    return (y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4)), xn, t
 
 
 class _RPNHeadLevelFn(torch.autograd.Function):
-    """One level of :class:`RPNHead` with gradients for the map and all six parameters.  ``operands`` is the head's cached
-    :meth:`RPNHead._operands` - the same weights as the GEMMs read them, no gradient of their own.
-    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box, operands, grad) -> (logits [B, h w A], deltas [B, h w A, 4]).
-    ``grad``: ``(grad_dtype, dgrad_w)``, the head's option and its cached :meth:`RPNHead._dgrad_operand_bf16` as a callable; the
-    forward does not read it.  ``train``: ``(train_dtype, operands_bf16)``, the forward's option and the head's cached
-    :meth:`RPNHead._operands_bf16` as a callable.  Under ``"bf16"``, with a channel count the bf16 GEMM takes, the forward is
-    :func:`_level_forward_bf16`'s launches on a padded copy that has the wgrad's slack rows, and what is saved in the place of the NHWC
-    map and the fp32 activation are that copy and the bf16 activation."""
+    """One level of :class:`RPNHead` with gradients for the map and all six parameters.
+    apply(x [B, C, h, w], w3, b3, w_cls, b_cls, w_box, b_box, head) -> (logits [B, h w A], deltas [B, h w A, 4]).
+    ``head``: the :class:`RPNHead` whose parameters these are.  The forward is :func:`_level_forward` on its cached operands - the bf16
+    ones under ``train_dtype="bf16"`` with a channel count the bf16 GEMM takes - and reads both options there, keeping ``grad_dtype`` on
+    ``ctx``: a setter called between forward and backward does not change that backward.  The backward takes the 3x3's dgrad operand
+    from the head's cache."""
 
     @staticmethod
-    def forward(ctx, x, w3, b3, wc, bc, wb, bb, operands, grad=("f32", None), train=("f32", None)):
-        A = wc.shape[0]
+    def forward(ctx, x, w3, b3, wc, bc, wb, bb, head):
         B, Cc, h, w = x.shape
-        if check_train_dtype(train[0]) == "bf16" and Cc % BF16_K == 0:
-            w3_16, b3_, w1_16, b1 = train[1]()
-            x_p = ops.pad_nhwc_bf16(x.detach().permute(0, 2, 3, 1).contiguous(), slack_rows=w + 3)
-            t = ops.conv3x3_nhwc_bf16(padded_middle(x_p, B, h, w), B, h, w, w3_16, b3_, _lib.EPI_BIAS_RELU)      # bf16 [B h w, C]
-            y = ops.linear_bf16(t, w1_16, b1, _lib.EPI_F32)
-            out = (y[:, :A].reshape(B, h * w * A), y[:, A:5 * A].reshape(B, h * w * A, 4))
-            ctx.saved = (x_p, t, w3.detach(), operands[2])
-        else:
-            xn, t, out = _level_forward(x, operands, A)
-            ctx.saved = (xn, t, w3.detach(), operands[2])
+        bf16 = check_dtype("train_dtype", head.train_dtype) == "bf16" and Cc % BF16_K == 0
+        out, xn, t = _level_forward(x, head._operands_bf16() if bf16 else head._operands(), head.num_anchors, slack=True)
+        ctx.saved = (xn, t, w3.detach(), head._operands()[2])
         ctx.shape = (B, h, w, Cc)
-        ctx.A = A
-        ctx.grad = grad
+        ctx.head, ctx.grad_dtype = head, check_dtype("grad_dtype", head.grad_dtype)
         return out
 
     @staticmethod
@@ -171,30 +145,18 @@ class _RPNHeadLevelFn(torch.autograd.Function):
             raise RuntimeError("RPNHead: backward through a level a second time (its saved maps are freed after the first)")
         xn, t, w3, w1 = ctx.saved
         ctx.saved = None
-        A = ctx.A
+        A, grad_dtype = ctx.head.num_anchors, ctx.grad_dtype
         B, h, w, Cc = ctx.shape
         M = B * h * w
         need = ctx.needs_input_grad
-        # the gradient of the pixel rows [M, logits | deltas | zero padding]: 32 columns, the K the fp32 GEMM wants (and a multiple
-        # of 8, which the bf16 wgrad wants)
-        K = (5 * A + 31) // 32 * 32
-        dy = torch.zeros((M, K), device=xn.device, dtype=torch.float32)
-        if d_logits is not None:
-            dy[:, :A] = d_logits.reshape(M, A)
-        if d_deltas is not None:
-            dy[:, A:5 * A] = d_deltas.reshape(M, 4 * A)
-        grad_dtype, dgrad_w = ctx.grad
+        dy = pad_grad_row(((A, d_logits), (4 * A, d_deltas)), M, xn.device)   # the gradient of the pixel rows [M, logits | deltas | 0]
         # (K = 32 is below the bf16 GEMM's k-tile: this dgrad is the fp32 GEMM under either setting)
-        dt, g1, gb = linear_bwd(dy, t.view(M, Cc), w1, True, need[3] or need[5], need[4] or need[6], grad_dtype)   # [M, C], [K, C], [K]
-        if grad_dtype == "bf16":
-            # the ReLU mask is applied by the launch that makes the padded bf16 copy of dt and the bias gradient
-            g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2], grad_dtype, act=t.view(B, h, w, Cc), dgrad_w=dgrad_w)
-        else:
-            dt.mul_(t.view(M, Cc) > 0)                                                    # ReLU mask
-            g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2])
+        dt, g1, gb = linear_bwd(dy, t, w1, True, need[3] or need[5], need[4] or need[6], grad_dtype)                # [M, C], [K, C], [K]
+        g_x, g_w3, g_b3 = conv3x3_bwd(dt.view(B, h, w, Cc), xn, w3, need[0], need[1], need[2], grad_dtype, act=t,
+                                      dgrad_w=ctx.head._dgrad_operand_bf16)
         return (g_x.permute(0, 3, 1, 2) if need[0] else None, g_w3, g_b3,
                 g1[:A].reshape(A, Cc, 1, 1) if need[3] else None, gb[:A] if need[4] else None,
-                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None, None, None)
+                g1[A:5 * A].reshape(4 * A, Cc, 1, 1) if need[5] else None, gb[A:5 * A] if need[6] else None, None)
 
 
 class _RPNLossFn(torch.autograd.Function):
@@ -218,9 +180,9 @@ class RPNHead(nn.Module):
 
     def __init__(self, in_channels: int = 256, num_anchors: int = 3, neck_dtype: str = "f32", grad_dtype: str = "f32", train_dtype: str = "f32"):
         super().__init__()
-        self.neck_dtype = check_neck_dtype(neck_dtype)
-        self.grad_dtype = check_grad_dtype(grad_dtype)
-        self.train_dtype = check_train_dtype(train_dtype)
+        self.neck_dtype = check_dtype("neck_dtype", neck_dtype)
+        self.grad_dtype = check_dtype("grad_dtype", grad_dtype)
+        self.train_dtype = check_dtype("train_dtype", train_dtype)
         self.conv = nn.Sequential(_ConvRelu(in_channels))
         self.cls_logits = nn.Conv2d(in_channels, num_anchors, kernel_size=1)
         self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1)
@@ -229,32 +191,14 @@ class RPNHead(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.normal_(m.weight, std=0.01)
                 nn.init.constant_(m.bias, 0)
-        self._packed, self._packed_bf16, self._dgrad_bf16 = ParamCache(), ParamCache(), ParamCache()
+        self._operand_cache = OperandCache()
 
-    def set_grad_dtype(self, grad_dtype: str) -> "RPNHead":
-        """``"f32"`` or ``"bf16"``: the matrix pipe of the 3x3 convolution's input-gradient GEMM in the backward from now on
-        (``grad_ops.conv3x3_bwd``; the 1x1 pair's 32 padded columns keep theirs on the fp32 GEMM).  Forward, parameters and
-        ``state_dict`` do not depend on it."""
-        self.grad_dtype = check_grad_dtype(grad_dtype)
-        return self
-
-    def set_train_dtype(self, train_dtype: str) -> "RPNHead":
-        """``"f32"`` or ``"bf16"``: how the head's forward runs from now on where a gradient IS wanted (:class:`_RPNHeadLevelFn`), on the
-        same weights - ``"bf16"``: the launches of ``neck_dtype="bf16"``.  Parameters and ``state_dict`` do not depend on it; eval mode
-        and ``no_grad`` never read it."""
-        self.train_dtype = check_train_dtype(train_dtype)
-        return self
-
-    def _dgrad_operand_bf16(self) -> torch.Tensor:
-        """The weight operand of the 3x3 convolution's dgrad under ``grad_dtype="bf16"`` (flipped, in/out-swapped, bf16), re-made
-        when the parameter changes."""
-        w3 = self.conv[0][0].weight
-        return self._dgrad_bf16.get(param_key(w3), lambda: conv3x3_dgrad_bf16(w3))
-
-    def set_neck_dtype(self, neck_dtype: str) -> "RPNHead":
-        """``"f32"`` or ``"bf16"``: how the head runs from now on where no gradient is wanted, on the same weights."""
-        self.neck_dtype = check_neck_dtype(neck_dtype)
-        return self
+    set_neck_dtype = dtype_setter("neck_dtype", """``"f32"`` or ``"bf16"``: how the head runs from now on where no gradient is wanted, on
+        the same weights.""")
+    set_grad_dtype = dtype_setter("grad_dtype", """``"f32"`` or ``"bf16"``: the matrix pipe of the 3x3 convolution's input-gradient GEMM
+        in the backward from now on (the 1x1 pair's 32 padded columns keep theirs on the fp32 GEMM).""")
+    set_train_dtype = dtype_setter("train_dtype", """``"f32"`` or ``"bf16"``: how the head's forward runs from now on where a gradient IS
+        wanted (:class:`_RPNHeadLevelFn`) - ``"bf16"``: the launches of ``neck_dtype="bf16"``.""")
 
     def _params(self):
         return (self.conv[0][0].weight, self.conv[0][0].bias, self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight,
@@ -264,16 +208,22 @@ class RPNHead(nn.Module):
         """``(w3, b3, w1, b1)``: the 3x3 weight as [Cout, 3, 3, Cin] with its bias, and both 1x1 convolutions as one [5 A (padded
         to a multiple of 4), C] matrix with theirs, re-laid when a parameter changes."""
         w3, b3, wc, bc, wb, bb = ps = self._params()
-        return self._packed.get(param_key(*ps), lambda: (w3.detach().permute(0, 2, 3, 1).contiguous(), b3.detach(),
-                                                         *stack_rows((wc.flatten(1), wb.flatten(1)), (bc, bb), 4)))
+        return self._operand_cache.get("f32", ps, lambda: (w3.detach().permute(0, 2, 3, 1).contiguous(), b3.detach(),
+                                                           *stack_rows((wc.flatten(1), wb.flatten(1)), (bc, bb), 4)))
 
     def _operands_bf16(self):
-        """:meth:`_operands` with both matrices as bf16 copies (``neck_dtype="bf16"``; the biases stay fp32, the stacked matrix's
-        zero padding rows stay zero), cached beside them under the same key."""
+        """:meth:`_operands` with both matrices as bf16 copies (``neck_dtype`` / ``train_dtype="bf16"``; the biases stay fp32, the
+        stacked matrix's zero padding rows stay zero), cached beside them under the same key."""
         def build():
             w3, b3, w1, b1 = self._operands()
             return ops.cast_bf16(w3), b3, ops.cast_bf16(w1), b1
-        return self._packed_bf16.get(param_key(*self._params()), build)
+        return self._operand_cache.get("bf16", self._params(), build)
+
+    def _dgrad_operand_bf16(self) -> torch.Tensor:
+        """The weight operand of the 3x3 convolution's dgrad under ``grad_dtype="bf16"`` (flipped, in/out-swapped, bf16), re-made
+        when the parameter changes."""
+        w3 = self.conv[0][0].weight
+        return self._operand_cache.get("dgrad", (w3,), lambda: conv3x3_dgrad_bf16(w3))
 
     def forward_level(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """One map ``[B, C, h, w]`` (any memory layout; channels-last costs no copy) -> objectness logits ``[B, h w A]`` and box
@@ -284,11 +234,8 @@ class RPNHead(nn.Module):
             raise ValueError(f"RPNHead: expected float32 features, got {x.dtype}")
         if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             # gradients are wanted: one differentiable node per level, on the operands of the eval path below
-            return _RPNHeadLevelFn.apply(x, *self._params(), self._operands(), (self.grad_dtype, self._dgrad_operand_bf16),
-                                         (self.train_dtype, self._operands_bf16))
-        if self.neck_dtype == "bf16":
-            return _level_forward_bf16(x, self._operands_bf16(), self.num_anchors)
-        return _level_forward(x, self._operands(), self.num_anchors)[2]
+            return _RPNHeadLevelFn.apply(x, *self._params(), self)
+        return _level_forward(x, self._operands_bf16() if self.neck_dtype == "bf16" else self._operands(), self.num_anchors)[0]
 
     def forward(self, features: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         """All levels: logits ``[B, Ntot]`` and deltas ``[B, Ntot, 4]``, levels concatenated in the order given."""

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from layoutdit_amd import _lib, config as cfgs, ops, synth  # noqa: E402
 from layoutdit_amd.modeling import LayoutDetectionModel  # noqa: E402
 from layoutdit_amd.modeling.dit_fpn import _f32c, _fpn_forward  # noqa: E402
-from layoutdit_amd.modeling.grad_ops import conv3x3_bf16  # noqa: E402
+from layoutdit_amd.modeling.grad_ops import conv3x3_fwd_bf16  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64)
@@ -51,7 +51,7 @@ def neck(toks, bf16):
     conv = [fpn.fpn.layer_blocks[i][0] for i in range(4)]
     outs, _ = _fpn_forward(bb.scales, gh, gw, toks, [m.weight.detach().reshape(256, bb.hidden_size) for m in lat],
                            [m.bias.detach() for m in lat], [fpn._ohwi_bf16(i) if bf16 else fpn._ohwi(i) for i in range(4)],
-                           [m.bias.detach() for m in conv], keep_inner=False, bf16_conv=bf16)
+                           [m.bias.detach() for m in conv], keep_inner=False)   # a bf16 weight copy selects the bf16 3x3
     maps = [o.permute(0, 3, 1, 2) for o in outs]
     maps.append(maps[3][:, :, ::2, ::2])
     return head(maps)
@@ -81,7 +81,7 @@ with torch.no_grad():
 
     steps = {
         "fpn_conv3x3": lambda: [ops.conv3x3_nhwc(inners[i], w32[i], cb[i]) for i in range(4)],
-        "bf16/fpn_conv3x3": lambda: [conv3x3_bf16(inners[i], w16[i], cb[i], _lib.EPI_F32) for i in range(4)],
+        "bf16/fpn_conv3x3": lambda: [conv3x3_fwd_bf16(inners[i], w16[i], cb[i], _lib.EPI_F32)[0] for i in range(4)],
         "bf16/fpn_pad_only": lambda: [ops.pad_nhwc_bf16(inners[i]) for i in range(4)],
         "rpn_head": with_neck("f32", lambda: head(maps)),
         "bf16/rpn_head": with_neck("bf16", lambda: head(maps)),

@@ -217,7 +217,8 @@ def test_bf16_head_gemms_match_float64_linears():
         x6 = ops.linear_bf16(p16.reshape(M, -1), w6, head.fc6.bias.detach(), _lib.EPI_BIAS_RELU)
         x7 = head.forward_bf16(p16)
         y = pred.forward_stacked_bf16(x7)
-        wp = pred._packed_bf16.value
+        assert pred._operand_cache.filled("bf16")
+        wp = pred._operand_cache.get("bf16", (pred.cls_score.weight, pred.bbox_pred.weight), None)  # the entry itself: nothing to build
         assert torch.equal(x7, ops.linear_bf16(x6, w7, head.fc7.bias.detach(), _lib.EPI_BIAS_RELU))
     assert x7.dtype == BF and y.dtype == torch.float32 and tuple(y.shape) == (M, 32)
     _stage_gate("fc6", x6, p16.reshape(M, -1), w6, head.fc6.bias.detach(), 12544, True)
@@ -452,7 +453,7 @@ def test_train_step_invalidates_the_bf16_operands(train_batch):
 
     before = [t.clone() for t in model.eval().forward_padded(x)]                                    # fills the bf16 caches with the old weights
     y_before = head_out(model)
-    assert rh.box_head._packed_bf16.value is not None and rh.box_predictor._packed_bf16.value is not None
+    assert rh.box_head._operand_cache.filled("bf16") and rh.box_predictor._operand_cache.filled("bf16")
     model.train()
     step = DetectorTrainStep(model, lr=1e-3, init_scale=1024.0)
     step.step(*train_batch, generator=_seeded(2))

@@ -445,11 +445,11 @@ def test_twenty_steps_in_bf16_setting_lower_the_loss(batch):
         if i < 2:
             fc6_grads.append(head.fc6.bias.grad.detach().clone())
             # after apply() the cached dgrad operand is gone; the next backward re-makes it from the weights as they are now
-            assert head._dgrad_bf16.value is None and model.model.rpn.head._dgrad_bf16.value is None
-            assert all(c.value is None for cs in model.model.backbone._cache_dgrad.values() for c in cs)
+            m = model.model
+            assert not any(s._operand_cache.filled() for s in (head, m.roi_heads.box_predictor, m.rpn.head, m.backbone))
             fresh = head.dgrad_operands_bf16(256, 7, 7)[1]
             stale += int(not torch.equal(fresh, ops.cast_bf16(head.fc7.weight.detach().t().contiguous())))
-            head._dgrad_bf16.clear()
+            head._operand_cache.clear()
     totals = [float(sum(v.item() for v in h.values())) for h in history]
     print("summed loss over 20 steps, bf16 setting:", [round(v, 4) for v in totals], "steps", step.steps, "skipped", step.skipped_steps)
     assert all(np.isfinite(v.item()) for h in history for v in h.values())

@@ -111,3 +111,40 @@ def test_rpn_head_level_reads_the_cached_operands_of_the_current_weights():
     assert torch.equal(second[0], want[0]) and torch.equal(second[1], want[1])
     with torch.no_grad():                                         # the eval path reads the same operands
         assert torch.equal(head.eval().forward_level(x)[0], second[0])
+
+
+def _masked(seed, *shape, dtype=torch.float32):
+    """``dy``, a ReLU output ``act`` of that shape (about half of it zero, element [0, .., 0] among them) and ``dy`` with one NaN at
+    that masked position."""
+    dy, act = _rand(seed, *shape).to(DEV), torch.relu(_rand(seed + 1, *shape)).to(DEV).to(dtype)
+    act.view(-1)[0] = 0
+    poisoned = dy.clone()
+    poisoned.view(-1)[0] = float("nan")
+    return dy, act, poisoned
+
+
+# the smallest shapes that reach the fp32 arm with a mask: N = 32 is below the bf16 GEMM's k-tile (fp32 arm under either grad_dtype);
+# N = 64 with a bf16 act is the box head under train_dtype="bf16", grad_dtype="f32"
+@pytest.mark.parametrize("N,grad_dtype,act_dtype", [(32, "f32", torch.float32), (32, "bf16", torch.float32), (64, "f32", BF)])
+def test_linear_bwd_fp32_arm_masks_by_multiplication(N, grad_dtype, act_dtype):
+    M, K = 3, 64
+    dy, act, poisoned = _masked(70, M, N, dtype=act_dtype)
+    x, w = _rand(72, M, K).to(DEV), _rand(73, N, K, scale=0.1).to(DEV)
+    got = linear_bwd(dy, x, w, True, True, True, grad_dtype, act=act)
+    want = linear_bwd(dy * (act > 0), x, w, True, True, True, grad_dtype)
+    assert all(torch.equal(g, t) for g, t in zip(got, want))
+    g_b = linear_bwd(poisoned, x, w, True, True, True, grad_dtype, act=act)[2]
+    assert not bool(torch.isfinite(g_b).all())                    # NaN * 0: what the default configuration has always given
+    if N == 64:                                                   # the fused launch of the bf16 arm selects: the same input stays finite
+        assert all(bool(torch.isfinite(t).all()) for t in linear_bwd(poisoned, x, w, True, True, True, "bf16", act=act))
+
+
+@pytest.mark.parametrize("grad_dtype", ["f32", "bf16"])
+def test_conv3x3_bwd_fp32_arm_masks_by_multiplication(grad_dtype):
+    B, h, w, Cout, Cin = 1, 2, 3, 32, 64                          # Cout = 32: below the k-tile, the fp32 arm under either grad_dtype
+    dy, act, poisoned = _masked(74, B, h, w, Cout)
+    x, wt = _rand(76, B, h, w, Cin).to(DEV), _rand(77, Cout, Cin, 3, 3, scale=0.05).to(DEV)
+    got = conv3x3_bwd(dy, x, wt, True, True, True, grad_dtype, act=act.view(B * h * w, Cout))      # the stages hand the pixel rows
+    want = conv3x3_bwd(dy * (act > 0), x, wt, True, True, True, grad_dtype)
+    assert all(torch.equal(g, t) for g, t in zip(got, want))
+    assert not bool(torch.isfinite(conv3x3_bwd(poisoned, x, wt, True, True, True, grad_dtype, act=act)[2]).all())

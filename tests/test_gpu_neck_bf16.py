@@ -407,7 +407,7 @@ def test_train_step_invalidates_the_bf16_neck_operands(train_batch):
 
     model.eval().forward_padded(x)                                                                  # fills the bf16 caches with the old weights
     before = neck_out(model)
-    assert all(c.value is not None for c in bb._cache_bf16) and head._packed_bf16.value is not None
+    assert all(bb._operand_cache.filled(("ohwi_bf16", i)) for i in range(4)) and head._operand_cache.filled("bf16")
     model.train()
     step = DetectorTrainStep(model, lr=1e-3, init_scale=1024.0)
     step.step(*train_batch, generator=_seeded(2))

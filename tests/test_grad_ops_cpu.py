@@ -7,8 +7,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from layoutdit_amd import config as cfgs
-from layoutdit_amd.modeling import DiTWithFPN, RPNHead
-from layoutdit_amd.modeling.grad_ops import ParamCache, flip_ihwo, param_key, stack_rows
+from layoutdit_amd.modeling import DiTWithFPN, LayoutDetectionModel, RPNHead
+from layoutdit_amd.modeling.grad_ops import OperandCache, ParamCache, flip_ihwo, param_key, stack_rows
+from layoutdit_amd.modeling.roi_heads import FastRCNNPredictor, TwoMLPHead
 
 
 def _sgd_step(p):
@@ -47,6 +48,72 @@ def test_param_cache_keeps_its_value_until_the_key_changes():
     assert cache.get((param_key(p, q), 7), build) is not again and len(builds) == 4  # whatever else the key carries
     cache.clear()
     assert cache.value is None and cache.get(param_key(p, q), build) is not None and len(builds) == 5
+
+
+def test_operand_cache_keeps_an_entry_until_its_key_changes():
+    p, q = nn.Parameter(torch.zeros(3)), nn.Parameter(torch.zeros(2))
+    cache, builds = OperandCache(), []
+
+    def build():
+        builds.append(1)
+        return torch.cat([p.detach(), q.detach()])
+    assert not cache.filled() and not cache.filled("pq")
+    first = cache.get("pq", (p, q), build)
+    assert cache.get("pq", (p, q), build) is first and len(builds) == 1 and cache.filled() and cache.filled("pq")
+    for i, t in enumerate((p, q)):                                                  # any keyed parameter
+        _sgd_step(t)
+        again = cache.get("pq", (p, q), build)
+        assert again is not first and len(builds) == 2 + i and torch.equal(again, torch.cat([p.detach(), q.detach()]))
+        assert cache.get("pq", (p, q), build) is again
+    assert cache.get("pq", (p, q), build, 7) is not again and len(builds) == 4      # whatever else the key carries
+    cache.clear()
+    assert not cache.filled("pq") and cache.get("pq", (p, q), build) is not None and len(builds) == 5
+
+
+def test_operand_cache_rebuilds_an_entry_alone_and_clear_empties_all():
+    p, q = nn.Parameter(torch.zeros(3)), nn.Parameter(torch.zeros(2))
+    cache, builds = OperandCache(), []
+
+    def builder(name, t):
+        def build():
+            builds.append(name)
+            return t.detach().clone()
+        return build
+    got = {"p": cache.get("p", (p,), builder("p", p)), ("q", 0): cache.get(("q", 0), (q,), builder("q", q), 5)}
+    assert builds == ["p", "q"] and cache.filled("p") and cache.filled(("q", 0)) and not cache.filled("q")
+    _sgd_step(p)                                                                    # p's key alone moves
+    assert cache.get(("q", 0), (q,), builder("q", q), 5) is got[("q", 0)] and builds == ["p", "q"]
+    new_p = cache.get("p", (p,), builder("p", p))
+    assert new_p is not got["p"] and torch.equal(new_p, p.detach()) and builds == ["p", "q", "p"]
+    assert cache.get(("q", 0), (q,), builder("q", q), 5) is got[("q", 0)]           # the other entry keeps its object
+    assert cache.get(("q", 0), (q,), builder("q", q), 6) is not got[("q", 0)] and cache.get("p", (p,), builder("p", p)) is new_p
+    cache.clear()
+    assert not cache.filled() and not cache.filled("p") and not cache.filled(("q", 0))
+
+
+def test_every_stage_keeps_one_cache_that_the_invalidating_loop_finds():
+    """``DetectorTrainStep`` has no CPU path, so this walks the modules as its ``invalidate_caches`` does: by the one attribute and its
+    type, without naming a stage class."""
+    torch.manual_seed(0)
+    model = LayoutDetectionModel(config=cfgs.vit_micro())
+    m = model.model
+    stages = (m.backbone, m.rpn.head, m.roi_heads.box_head, m.roi_heads.box_predictor)
+    assert [type(s) for s in stages] == [DiTWithFPN, RPNHead, TwoMLPHead, FastRCNNPredictor]
+    assert all(isinstance(s._operand_cache, OperandCache) for s in stages)
+    assert len({id(s._operand_cache) for s in stages}) == 4                         # one each
+    owners = [mod for mod in model.modules() if isinstance(getattr(mod, "_operand_cache", None), OperandCache)]
+    assert len(owners) == 4 and all(any(o is s for s in stages) for o in owners)
+    for s in stages:                                                                # and no second cache under another name
+        assert [k for k, v in vars(s).items() if isinstance(v, OperandCache)] == ["_operand_cache"]
+    for i in range(4):
+        m.backbone._ohwi(i)
+    m.rpn.head._operands(), m.roi_heads.box_head.fc6_weight_hwc(256, 7, 7), m.roi_heads.box_predictor._operands()
+    assert all(s._operand_cache.filled() for s in stages)
+    for mod in model.modules():
+        cache = getattr(mod, "_operand_cache", None)
+        if isinstance(cache, OperandCache):
+            cache.clear()
+    assert not any(s._operand_cache.filled() for s in stages)
 
 
 def test_rpn_head_operands_follow_every_parameter():

@@ -84,7 +84,7 @@ def test_train_dtype_option_of_each_stage():
             make(train_dtype="fp16")
     # RoIHeads without the argument keeps what its box head was built with
     assert RoIHeads(pool, TwoMLPHead(64 * 49, 64, train_dtype="bf16"), FastRCNNPredictor(64, 6)).train_dtype == "bf16"
-    assert grad_ops.check_train_dtype("bf16") == "bf16" and grad_ops.TRAIN_DTYPES == ("f32", "bf16")
+    assert grad_ops.check_dtype("train_dtype", "bf16") == "bf16" and grad_ops.DTYPES == ("f32", "bf16")
 
 
 def test_state_dict_does_not_depend_on_train_dtype():
