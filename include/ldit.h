@@ -923,6 +923,20 @@ int ldit_clip_finish(const ldit_opt_state *state, ldit_clip_state *clip, const d
 int ldit_adamw_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyper *hyper, int32_t S, const ldit_opt_state *state,
                                 const ldit_clip_state *clip, double beta1, double beta2, float eps, ldit_stream stream);
 
+/* -- the quantisation-aware mxfp8 encoder under this step (additive): the MX operands of the train mirror, re-made in ONE launch --
+ * cfg->dtype must be LDIT_MXFP8.  `flat_params` is the fp32 master in ldit_flat_param_layout, `mirror` the train mirror of
+ * ldit_train_mirror_bytes(cfg).  For every layer, from the master, exactly what ldit_pack_train makes for the four matrices and the
+ * fused bias: the e4m3 codes and E8M0 scales of wqkv (the q third folded), wo, w1, w2 in the MX section, their dequantised bf16 copies
+ * at the matrices' offsets in the bf16 part, and [fold bq, 0, bv] in the MX section.  NOTHING else of the mirror is written: LayerNorm
+ * vectors, biases, LayerScale, the embeddings and every padding byte keep what the AdamW kernels' bf16 mirror write (or the last pack)
+ * left.  Run behind ldit_adamw_multi_f32 / ldit_adamw_groups_multi_f32 on a mirror that was current before the update, the mirror
+ * equals a fresh ldit_pack_train of the updated master byte for byte.  `state` may be NULL; with state->skip set every workgroup
+ * returns before its first store (the masters did not move, the mirror is current).  One launch whatever the layer count, no LDS, no
+ * atomics, nothing allocated, capturable.  LDIT_EINVAL: null / misaligned pointers (16 bytes; the state block 4), a dtype that is not
+ * LDIT_MXFP8; LDIT_EWORKSPACE: a mirror shorter than ldit_train_mirror_bytes; LDIT_EUNSUPPORTED: a geometry the train step lacks. */
+int ldit_requant_train_mirror(const ldit_cfg *cfg, const void *flat_params, void *mirror, size_t mirror_bytes,
+                              const ldit_opt_state *state, ldit_stream stream);
+
 /* ---- COCO box evaluation: matching, accumulation ----
  * The arithmetic of the reference's Evaluator.score() (ref evaluation/evaluator.py:219-286, which hands a JSON file to a per-image,
  * per-category host loop) on padded device tensors: no host round trip, no allocation, no float atomics, capturable, every output a

@@ -191,6 +191,7 @@ SIGNATURES = {
     "ldit_clip_finish": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "ldit_adamw_groups_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), C.POINTER(LditOptHyper), _i32, _vp, _vp, C.c_double, C.c_double, _f32,
                                               _vp]),
+    "ldit_requant_train_mirror": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _sz, _vp, _vp]),
     # COCO box evaluation
     "ldit_coco_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp]),

@@ -142,6 +142,16 @@ inline size_t mirror_bytes(const Geo &g, int dtype)
     return dtype == LDIT_MXFP8 ? mirror_mx_offset(g) + packed_map(g, LDIT_MXFP8).total : packed_map(g, LDIT_F32).total / 2;
 }
 
+// the four matrices of a layer: where they start in the flat block (elements), their shape and the rows the q fold covers, and where
+// their codes and scales go in the MX section (bytes)
+inline void mx_layer_segs(const PackedLayer &f, const PackedLayer &x, int64_t C, int64_t F, MxRequantSeg *segs)
+{
+    segs[0] = {(int64_t)(f.wqkv / 4), 3 * C * C, (int)C, (int)C, (int64_t)x.wqkv, (int64_t)x.sw_qkv};
+    segs[1] = {(int64_t)(f.wo / 4), C * C, (int)C, 0, (int64_t)x.wo, (int64_t)x.sw_o};
+    segs[2] = {(int64_t)(f.w1 / 4), F * C, (int)C, 0, (int64_t)x.w1, (int64_t)x.sw_1};
+    segs[3] = {(int64_t)(f.w2 / 4), C * F, (int)F, 0, (int64_t)x.w2, (int64_t)x.sw_2};
+}
+
 // mxfp8 mirror from the flat block, per layer (one launch each): update = true fuses the AdamW step on that range (adamw_kernel's
 // arithmetic); the embeddings' range is left to the caller
 int mx_layers(const Geo &g, float *p, const float *gr, float *m, float *v, bool update, float lr, float b1, float b2, float eps, float wd,
@@ -153,14 +163,36 @@ int mx_layers(const Geo &g, float *p, const float *gr, float *m, float *v, bool 
     for (int l = 0; l < g.L; ++l) {
         const PackedLayer &f = fm.layer[l], &x = xm.layer[l];
         const int64_t e0 = (int64_t)(f.ln1_w / 4), e1 = (int64_t)((l + 1 < g.L ? fm.layer[l + 1].ln1_w : fm.total) / 4);
-        const MxRequantSeg segs[4] = {{(int64_t)(f.wqkv / 4), 3 * C * C, (int)C, (int)C, (int64_t)x.wqkv, (int64_t)x.sw_qkv},
-                                      {(int64_t)(f.wo / 4), C * C, (int)C, 0, (int64_t)x.wo, (int64_t)x.sw_o},
-                                      {(int64_t)(f.w1 / 4), F * C, (int)C, 0, (int64_t)x.w1, (int64_t)x.sw_1},
-                                      {(int64_t)(f.w2 / 4), C * F, (int)F, 0, (int64_t)x.w2, (int64_t)x.sw_2}};
+        MxRequantSeg segs[4];
+        mx_layer_segs(f, x, C, F, segs);
         LDIT_TRY(launch_adamw_mx(p, gr, m, v, e0, e1, update, lr, b1, b2, eps, wd, step, grad_scale, mirror, mx, segs, 4,
                                  (int64_t)(f.bqkv / 4), (int64_t)x.bqkv, g.C, qfold_of(g), stream));
     }
     return LDIT_OK;
+}
+
+// The same matrices and bias for ALL layers in one launch, nothing else of the mirror written (ldit_requant_train_mirror).  The layer
+// comes from the grid, so every layer must be layer 0 moved by one stride in the flat block and one in the MX section: packed_map lays
+// equal layers out one after another, which is checked here rather than assumed.
+int mx_requant_all_layers(const Geo &g, const float *p, void *mirror, const ldit_opt_state *state, hipStream_t stream)
+{
+    if (g.L == 0) return LDIT_OK;
+    const PackedMap fm = packed_map(g, LDIT_F32), xm = packed_map(g, LDIT_MXFP8);
+    const PackedLayer &f0 = fm.layer[0], &x0 = xm.layer[0];
+    const size_t fs = g.L > 1 ? fm.layer[1].ln1_w - f0.ln1_w : 0, xs = g.L > 1 ? xm.layer[1].ln1_w - x0.ln1_w : 0;
+    for (int l = 1; l < g.L; ++l) {
+        const PackedLayer &f = fm.layer[l], &x = xm.layer[l];
+        const size_t fo = (size_t)l * fs, xo = (size_t)l * xs;
+        const bool flat = f.wqkv == f0.wqkv + fo && f.bqkv == f0.bqkv + fo && f.wo == f0.wo + fo && f.w1 == f0.w1 + fo && f.w2 == f0.w2 + fo;
+        const bool mx = x.wqkv == x0.wqkv + xo && x.bqkv == x0.bqkv + xo && x.wo == x0.wo + xo && x.w1 == x0.w1 + xo && x.w2 == x0.w2 + xo &&
+                        x.sw_qkv == x0.sw_qkv + xo && x.sw_o == x0.sw_o + xo && x.sw_1 == x0.sw_1 + xo && x.sw_2 == x0.sw_2 + xo;
+        if (!flat || !mx) return fail(LDIT_EUNSUPPORTED, "requant_train_mirror: layer %d is not layer 0 moved by a whole stride", l);
+    }
+    if (fs % 16) return fail(LDIT_EUNSUPPORTED, "requant_train_mirror: layer stride %zu is not a multiple of 16 bytes", fs);
+    MxRequantSeg segs[4];
+    mx_layer_segs(f0, x0, g.C, g.F, segs);
+    return launch_requant_mirror(p, mirror, static_cast<char *>(mirror) + mirror_mx_offset(g), state, segs, (int64_t)(fs / 4), (int64_t)xs,
+                                 (int64_t)(f0.bqkv / 4), (int64_t)x0.bqkv, g.C, g.L, qfold_of(g), stream);
 }
 
 int forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_params, const void *x, int32_t batch,
@@ -490,6 +522,21 @@ int ldit_adamw_step_mxfp8(const ldit_cfg *cfg, void *params, const void *grads, 
     // from the updated master: the codes, scales, folded bias and dequantised copies a fresh ldit_pack_train would make
     LDIT_TRY(launch_adamw(p, gr, m, v, packed_map(g, LDIT_F32).total / 4, lr, beta1, beta2, eps, weight_decay, step, grad_scale, mirror, stream));
     return mx_layers(g, p, nullptr, nullptr, nullptr, false, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 1.0f, mirror, stream);
+}
+
+int ldit_requant_train_mirror(const ldit_cfg *cfg, const void *flat_params, void *mirror, size_t mirror_bytes, const ldit_opt_state *state,
+                              ldit_stream stream)
+{
+    Geo g;
+    LDIT_TRY(train_geometry(cfg, g));
+    if (cfg->dtype != LDIT_MXFP8) return fail(LDIT_EINVAL, "requant_train_mirror: cfg.dtype must be LDIT_MXFP8");
+    if (!flat_params || !mirror) return fail(LDIT_EINVAL, "requant_train_mirror: null pointer");
+    if (!aligned16(flat_params) || !aligned16(mirror)) return fail(LDIT_EINVAL, "requant_train_mirror: pointers must be 16-byte aligned");
+    if (state && (reinterpret_cast<uintptr_t>(state) & 3u)) return fail(LDIT_EINVAL, "requant_train_mirror: state block must be 4-byte aligned");
+    if (mirror_bytes < ldit::mirror_bytes(g, LDIT_MXFP8))
+        return fail(LDIT_EWORKSPACE, "train mirror %zu bytes < required %zu", mirror_bytes, ldit::mirror_bytes(g, LDIT_MXFP8));
+    // one launch for every layer's matrices and fused bias; the rest of the mirror is the AdamW kernels' (or the last pack's)
+    return mx_requant_all_layers(g, static_cast<const float *>(flat_params), mirror, state, static_cast<hipStream_t>(stream));
 }
 
 int ldit_vit_forward_train(const ldit_cfg *cfg, const void *packed, const void *flat_params, const void *x, int32_t batch,

@@ -339,6 +339,10 @@ struct MxRequantSeg { int64_t start, n; int cols; int fold_rows; int64_t codes, 
 int launch_adamw_mx(float *p, const float *g, float *m, float *v, int64_t e0, int64_t e1, bool update, float lr, float b1, float b2,
                     float eps, float wd, int step, float grad_scale, void *mirror16, void *mx, const MxRequantSeg *segs, int nseg,
                     int64_t bias_start, int64_t bias_dst, int C, float fold, hipStream_t stream);
+// ldit_requant_train_mirror: layer 0's four matrix segments and bias, the strides from one layer to the next (flat elements / MX-section
+// bytes), L layers in one launch; state (device, may be null): skip set = nothing is stored
+int launch_requant_mirror(const float *p, void *mirror16, void *mx, const ldit_opt_state *state, const MxRequantSeg *segs, int64_t layer_elems,
+                          int64_t layer_mx, int64_t bias_start, int64_t bias_dst, int C, int L, float fold, hipStream_t stream);
 int launch_layernorm_mxout(const float *X, const float *g, const float *b, void *Y, void *Ys, int64_t rows, int C, float eps,
                            hipStream_t stream);
 int launch_quant_rows_fp8(const float *W, void *dst, float *scales, int N, int K, hipStream_t stream, float mul = 1.0f);

@@ -662,6 +662,41 @@ struct AdamwMxArgs {
     int C;
 };
 
+// The 32-element MX block of a quad: the amax bit pattern of its own four, then the 8-lane exchange (every matrix segment starts at
+// a multiple of 32 elements and a thread holds 4, so 8 neighbouring lanes hold one block).  Every lane of the wave must arrive.
+__device__ __forceinline__ unsigned mx_block_amax(const f32x4 &q)
+{
+    unsigned amax = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) amax = umax32(amax, __float_as_uint(q[e]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) amax = umax32(amax, (unsigned)__shfl_xor((int)amax, o, 64));
+    return amax;
+}
+
+// The quad at element `rel` of a matrix, as quant_mx (ldit_pack_weights) makes it: four e4m3 codes at codes + rel, the block's E8M0
+// scale at scales + rel / 32 (the block's first lane writes it), and the dequantised codes as bf16 at mirror_at (the dgrad's operand).
+// The one quantiser of the train mirror: ldit_pack_train, ldit_adamw_step_mxfp8 and ldit_requant_train_mirror all end here.
+__device__ __forceinline__ void mx_store_quad(const f32x4 &q, unsigned amax, unsigned char *mx, int64_t codes, int64_t scales, int64_t rel,
+                                              bf16_t *mirror_at)
+{
+    const unsigned sb = mx_scale_byte(amax);
+    const float inv = mx_inv_scale(sb);
+    const unsigned pk = pack_fp8x4(q[0] * inv, q[1] * inv, q[2] * inv, q[3] * inv);
+    *reinterpret_cast<unsigned *>(mx + codes + rel) = pk;
+    if ((rel & 31) == 0) mx[scales + (rel >> 5)] = (unsigned char)sb;
+    *reinterpret_cast<mx_bf16x4 *>(mirror_at) = mx_dequant_bf16x4(pk, sb);
+}
+
+// The fused q|k|v bias quad at element r of its 3 C: [fold bq, 0, bv] as fp32, as qkv_bias packs it.
+__device__ __forceinline__ void mx_store_bias_quad(const f32x4 &P, int64_t r, int C, float fold, unsigned char *dst)
+{
+    f32x4 b;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b[e] = r < C ? P[e] * fold : (r < 2 * C ? 0.0f : P[e]);
+    *reinterpret_cast<f32x4 *>(dst + 4 * r) = b;
+}
+
 __global__ void __launch_bounds__(256) adamw_mx_kernel(const AdamwMxArgs a)
 {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -680,29 +715,65 @@ __global__ void __launch_bounds__(256) adamw_mx_kernel(const AdamwMxArgs a)
 #pragma unroll
         for (int e = 0; e < 4; ++e) q[e] *= mul;
     }
-    unsigned amax = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) amax = umax32(amax, __float_as_uint(q[e]) & 0x7fffffffu);
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) amax = umax32(amax, (unsigned)__shfl_xor((int)amax, o, 64));
+    const unsigned amax = mx_block_amax(q);
     if (!ok) return;
     if (s >= 0) {
-        const unsigned sb = mx_scale_byte(amax);
-        const float inv = mx_inv_scale(sb);
-        const unsigned pk = pack_fp8x4(q[0] * inv, q[1] * inv, q[2] * inv, q[3] * inv);
-        *reinterpret_cast<unsigned *>(a.mx + a.seg[s].codes + rel) = pk;
-        if ((rel & 31) == 0) a.mx[a.seg[s].scales + (rel >> 5)] = (unsigned char)sb;
-        *reinterpret_cast<mx_bf16x4 *>(a.mirror + i) = mx_dequant_bf16x4(pk, sb);
+        mx_store_quad(q, amax, a.mx, a.seg[s].codes, a.seg[s].scales, rel, a.mirror + i);
         return;
     }
     *reinterpret_cast<bf16x4 *>(a.mirror + i) = bf16x4{(bf16_t)P[0], (bf16_t)P[1], (bf16_t)P[2], (bf16_t)P[3]};
-    if (i >= a.bias_start && i < a.bias_start + 3 * (int64_t)a.C) {
-        const int64_t r = i - a.bias_start;
-        f32x4 b;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) b[e] = r < a.C ? P[e] * a.fold : (r < 2 * a.C ? 0.0f : P[e]);
-        *reinterpret_cast<f32x4 *>(a.mx + a.bias_dst + 4 * r) = b;
+    if (i >= a.bias_start && i < a.bias_start + 3 * (int64_t)a.C) mx_store_bias_quad(P, i - a.bias_start, a.C, a.fold, a.mx + a.bias_dst);
+}
+
+// ---- the MX operands of the train mirror re-made for ALL layers in one launch (ldit_requant_train_mirror) --------------------------
+// Behind the multi-tensor AdamW of the detector's step (optim_multi.hip), which wrote bf16(p) beside every p: grid.y = the layer,
+// grid.x walks one layer's four matrices and then its fused bias, one quad per thread.  The layers of a geometry are laid out alike,
+// so layer l is layer 0 moved by l * layer_elems in the flat block and by l * layer_mx in the MX section (the host checks it).
+// quad_end[k] = the threads of a layer up to the end of matrix k, each a multiple of 256: a workgroup never straddles two segments, and
+// 8 neighbouring lanes hold one 32-element block.  Matrix quads go through mx_block_amax / mx_store_quad, bias quads through
+// mx_store_bias_quad - adamw_mx_kernel's own, so the bits are ldit_pack_train's.  Nothing else of the mirror is touched: LayerNorm
+// vectors, biases, LayerScale, embeddings and padding keep what the AdamW write left.  A skipped step (state->skip) stores nothing.
+struct RequantMirrorArgs {
+    const float *p;
+    bf16_t *mirror;
+    unsigned char *mx;
+    const ldit_opt_state *state;
+    MxRequantSeg seg[4];            // layer 0's
+    int64_t quad_end[4];
+    int64_t layer_elems, layer_mx;
+    int64_t bias_start, bias_dst;   // layer 0's
+    int C;
+    float fold;
+};
+
+__global__ void __launch_bounds__(256) requant_mirror_kernel(const RequantMirrorArgs a)
+{
+    if (a.state && a.state->skip) return;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const float *p = a.p + (int64_t)blockIdx.y * a.layer_elems;
+    bf16_t *mirror = a.mirror + (int64_t)blockIdx.y * a.layer_elems;
+    unsigned char *mx = a.mx + (int64_t)blockIdx.y * a.layer_mx;
+    if (t >= a.quad_end[3]) {                                  // whole workgroups: quad_end[3] is a multiple of 256
+        const int64_t r = 4 * (t - a.quad_end[3]);
+        if (r >= 3 * (int64_t)a.C) return;
+        mx_store_bias_quad(*reinterpret_cast<const f32x4 *>(p + a.bias_start + r), r, a.C, a.fold, mx + a.bias_dst);
+        return;
     }
+    int64_t start = 0, codes = 0, scales = 0, rel = 0, lo = 0;
+    int cols = 1, fold_rows = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                              // selects, not an indexed read of the arguments
+        if (t >= lo && t < a.quad_end[k]) {
+            start = a.seg[k].start; codes = a.seg[k].codes; scales = a.seg[k].scales; cols = a.seg[k].cols; fold_rows = a.seg[k].fold_rows;
+            rel = 4 * (t - lo);
+        }
+        lo = a.quad_end[k];
+    }
+    f32x4 q = *reinterpret_cast<const f32x4 *>(p + start + rel);
+    const float mul = rel / cols < fold_rows ? a.fold : 1.0f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] *= mul;
+    mx_store_quad(q, mx_block_amax(q), mx, codes, scales, rel, mirror + start + rel);
 }
 
 }  // namespace
@@ -919,6 +990,30 @@ int launch_adamw_mx(float *p, const float *g, float *m, float *v, int64_t e0, in
     a.nseg = nseg; a.bias_start = bias_start; a.bias_dst = bias_dst; a.C = C;
     const int64_t threads = (e1 - e0) / 4;
     LAUNCH_CHECKED(adamw_mx_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
+    return LDIT_OK;
+}
+
+int launch_requant_mirror(const float *p, void *mirror16, void *mx, const ldit_opt_state *state, const MxRequantSeg *segs, int64_t layer_elems,
+                          int64_t layer_mx, int64_t bias_start, int64_t bias_dst, int C, int L, float fold, hipStream_t stream)
+{
+    if (L <= 0) return LDIT_OK;
+    if (L > 65535) return fail(LDIT_EUNSUPPORTED, "requant_mirror: %d layers exceed the grid", L);
+    if (C <= 0 || C % 32 || (layer_elems | bias_start) & 3) return fail(LDIT_EINVAL, "requant_mirror: bad layer geometry");
+    RequantMirrorArgs a{};
+    a.p = p; a.mirror = static_cast<bf16_t *>(mirror16); a.mx = static_cast<unsigned char *>(mx); a.state = state;
+    int64_t quads = 0;
+    for (int k = 0; k < 4; ++k) {
+        // whole workgroups per matrix (so whole 32-element blocks per 8 lanes), whole blocks per row
+        if ((segs[k].start & 31) || segs[k].n <= 0 || segs[k].n % 1024 || segs[k].cols <= 0 || segs[k].cols % 32)
+            return fail(LDIT_EINVAL, "requant_mirror: matrix %d is not whole 1024-element workgroups of 32-element blocks", k);
+        a.seg[k] = segs[k];
+        quads += segs[k].n / 4;
+        a.quad_end[k] = quads;
+    }
+    a.layer_elems = layer_elems; a.layer_mx = layer_mx; a.bias_start = bias_start; a.bias_dst = bias_dst; a.C = C; a.fold = fold;
+    const int64_t blocks = (quads + (3 * (int64_t)C / 4 + 255)) / 256;
+    if (blocks >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "requant_mirror: layer too large for the grid");
+    LAUNCH_CHECKED(requant_mirror_kernel, dim3((unsigned)blocks, (unsigned)L), dim3(256), 0, stream, a);
     return LDIT_OK;
 }
 

@@ -16,6 +16,10 @@ Optional, and with the same property: ``max_grad_norm`` clip
 ``warmup_iters`` ramps the rate up linearly.  The norm, the clip coefficient and the count of clipped steps live in a second,
 16-byte device block (``ldit_clip_state``); one more small launch, one pass over the gradients as before.
 
+The encoder may be the quantisation-aware mxfp8 build (``LayoutDetectionModel(compute_dtype="mxfp8", qat=True)``):
+the same launches, then ONE that re-quantises every layer's MX operands from the updated masters (``ldit_requant_train_mirror``),
+reading the same device block - a skipped step stores nothing there either.
+
 No data parallelism.  PyTorch is plumbing: it owns the memory, the stream and autograd's graph; the arithmetic of
 the update is the library's.
 """
@@ -115,10 +119,10 @@ class DetectorTrainStep:
             raise TypeError("DetectorTrainStep: expected a LayoutDetectionModel (the encoder alone trains with TrainStep)")
         self.model = model
         self.encoder = model.model.backbone.backbone.dit
-        if self.encoder.compute_dtype in ("fp8", "mxfp8"):
+        if self.encoder.compute_dtype == "fp8" or (self.encoder.compute_dtype == "mxfp8" and not getattr(self.encoder, "qat", False)):
             raise NotImplementedError(f"DetectorTrainStep: the {self.encoder.compute_dtype} encoder is not covered - 'fp8' and 'mxfp8' are inference "
-                                      "builds, and the quantisation-aware 'mxfp8' build (qat=True) needs the update that re-quantises its MX "
-                                      "operands, which is TrainStep's (ldit_adamw_step_mxfp8); build the detector with compute_dtype 'f32' or 'bf16'")
+                                      "builds with no training forward (TrainStep refuses them too); build the detector with compute_dtype "
+                                      "'f32' or 'bf16', or with compute_dtype 'mxfp8' and qat=True (quantisation-aware training)")
         self._require_train_mode()
         params = list(model.named_parameters())
         if not params:
@@ -180,7 +184,11 @@ class DetectorTrainStep:
     def apply(self) -> None:
         """The optimizer half alone, on the gradients the parameters hold now (made with the current loss scale): non-finite check,
         state machine, AdamW - or nothing, if the check fired.  No synchronisation; capturable once every moment exists (after one
-        eager call).  A replayed graph moves the weights behind this object's back: call :meth:`invalidate_caches` after replays."""
+        eager call).  A replayed graph moves the weights behind this object's back: call :meth:`invalidate_caches` after replays.
+
+        Under the quantisation-aware mxfp8 encoder (``qat=True``) one launch follows, with the same state block: the MX operands of
+        the encoder's training mirror re-made from the updated masters (``ops.requant_train_mirror``), so that the mirror is a fresh
+        ``ldit_pack_train`` of them - where the mirror was current before the update; otherwise the next forward packs, as ever."""
         self._require_train_mode()
         params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current, hyper = self._segments()
         if not self._grouped:
@@ -210,6 +218,10 @@ class DetectorTrainStep:
             if params:
                 ops.adamw_groups_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, [h[0] for h in hyper], [h[1] for h in hyper],
                                        self._clip, self.betas, self.eps, mirrors)
+        if st is not None and st.mx and current and st.native:
+            # quantisation-aware mxfp8 encoder: the AdamW launches wrote bf16(p) over the whole mirror; one more launch re-makes every
+            # layer's MX operands (codes, scales, dequantised copies, folded bias) from the updated masters - or nothing, on a skipped step
+            ops.requant_train_mirror(st, self._state)
         self.invalidate_caches(_mirror_current=current)
 
     def invalidate_caches(self, _mirror_current: bool = False) -> None:

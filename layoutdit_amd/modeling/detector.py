@@ -49,7 +49,7 @@ class LayoutDetectionModel(nn.Module):
     def __init__(self, num_classes: int = 5, anchor_sizes=((32,), (64,), (128,), (256,), (512,)),
                  aspect_ratios=((0.5, 1.0, 2.0),) * 5, config: Optional[DiTConfig] = None, compute_dtype: str = "f32",
                  fixed_size: Tuple[int, int] = (224, 224), head_dtype: str = "f32", neck_dtype: str = "f32", grad_dtype: str = "f32",
-                 train_dtype: str = "f32"):
+                 train_dtype: str = "f32", qat: bool = False):
         """``num_classes`` counts the foreground classes (the reference adds the background itself, ref model.py:47); the anchor
         defaults are the reference's ``ModelConfig``.  ``compute_dtype`` selects the encoder build; the box head is fp32 in every build
         unless ``head_dtype="bf16"`` (eval mode only: bf16 pooled rows and bf16 GEMMs with fp32 accumulation behind the fp32 maps; the
@@ -64,14 +64,17 @@ class LayoutDetectionModel(nn.Module):
         gradient is wanted - ``losses`` / ``rpn_losses`` in train mode: the FPN's and the RPN head's 3x3 convolutions, the RPN head's
         1x1 pair, fc6, fc7 and the box predictor run as ``neck_dtype`` / ``head_dtype="bf16"`` run them in eval mode (bf16 operand
         rounding, fp32 accumulation), and the backward reads the bf16 tensors that forward saved; eval mode and ``no_grad`` never read
-        it, and it is independent of the other three options."""
+        it, and it is independent of the other three options.  ``qat=True`` (``compute_dtype="mxfp8"`` only; anything else is the
+        encoder's ``ValueError``): the encoder is the quantisation-aware training build of the mxfp8 inference build - ``losses`` runs
+        the inference arithmetic in the forward and a straight-through backward against fp32 masters, and ``DetectorTrainStep`` trains
+        it.  The parameters and ``state_dict`` keys are those of every other build."""
         super().__init__()
         for option, value in (("head_dtype", head_dtype), ("neck_dtype", neck_dtype), ("grad_dtype", grad_dtype), ("train_dtype", train_dtype)):
             check_dtype(option, value)
         if len(set(len(s) * len(r) for s, r in zip(anchor_sizes, aspect_ratios))) != 1:
             raise ValueError("LayoutDetectionModel: every level must have the same number of anchors per location (one RPN head)")
-        backbone = DiTWithFPN(pretrained=False, config=config, compute_dtype=compute_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype,
-                              train_dtype=train_dtype)
+        backbone = DiTWithFPN(pretrained=False, config=config, compute_dtype=compute_dtype, qat=qat, neck_dtype=neck_dtype,
+                              grad_dtype=grad_dtype, train_dtype=train_dtype)
         self.model = _FasterRCNN(backbone, int(num_classes) + 1, AnchorGenerator(sizes=anchor_sizes, aspect_ratios=aspect_ratios),
                                  fixed_size=fixed_size, head_dtype=head_dtype, neck_dtype=neck_dtype, grad_dtype=grad_dtype,
                                  train_dtype=train_dtype)
@@ -81,6 +84,11 @@ class LayoutDetectionModel(nn.Module):
         for stage in stages:
             getattr(stage, "set_" + option)(value)
         return self
+
+    @property
+    def qat(self) -> bool:
+        """Whether the encoder is the quantisation-aware training build of ``compute_dtype="mxfp8"`` (fixed at construction)."""
+        return self.model.backbone.backbone.dit.qat
 
     @property
     def head_dtype(self) -> str:

@@ -1342,6 +1342,21 @@ def adamw_groups_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Ten
             float(betas[1]), float(eps))
 
 
+def requant_train_mirror(flat_state, opt_state: Optional[torch.Tensor] = None) -> None:
+    """The MX operands of a quantisation-aware encoder's training mirror re-made from its fp32 master in ONE launch
+    (``ldit_requant_train_mirror``): every layer's four matrices (codes, scales, dequantised bf16 copies) and fused bias, nothing else.
+    ``flat_state``: the encoder's :class:`~layoutdit_amd.training.FlatState` (mxfp8 with ``qat=True``).  ``opt_state``: the step's
+    ``ldit_opt_state`` block; with its ``skip`` set nothing is written.  No synchronisation."""
+    lib = _lib.load()
+    if not getattr(flat_state, "mx", False):
+        raise ValueError("requant_train_mirror: the flat state is not the quantisation-aware mxfp8 build's (DiTEncoder(compute_dtype='mxfp8', qat=True))")
+    if opt_state is not None:
+        opt_state = _req_opt_state(opt_state)
+    params, mirror = _req(flat_state.params, "flat_state.params"), flat_state.packed
+    _launch(_device(params, mirror, opt_state), lib.ldit_requant_train_mirror, C.byref(flat_state.lcfg), _ptr(params), _ptr(mirror),
+            mirror.numel(), _ptr(opt_state))
+
+
 # ---- COCO box evaluation (include/ldit.h "COCO box evaluation"; csrc/coco_eval.hip) -----------------------------------------------------
 COCO_MAX_DETS, COCO_MAX_GT, COCO_MAX_CLASSES = 128, 128, 64      # per image: detection slots, GT boxes; categories
 COCO_MAX_SLOTS = 1 << 24                                         # capacity * slots per image the total-order key has room for

@@ -7,8 +7,13 @@ scripts/roi_bench.py.  The loss scale is 1 on both sides, so the repeated in-pla
 With --clip the same four-way comparison with global-norm clipping and parameter groups: (a) the default
 apply(), (b) max_grad_norm set, one group, (c) detector_param_groups(layer_decay=0.75) + clipping, (d) clip_grad_norm_(foreach=True)
 + AdamW with the same groups + GradScaler; (b) and (c) are reported beside (d) as ratios of this one run.
+With --qat nothing of the above runs; instead, alternating in one process: apply() of the detector on the bf16
+encoder against apply() of the detector on the quantisation-aware mxfp8 encoder (the same launches plus ldit_requant_train_mirror),
+and that one launch alone against ldit_pack_train on the same master (the cast pass plus one launch per layer: what mark_dirty()
+would cost at the next forward), --inner calls per timed window; the file is profiles/detector_step_bench_qat.json.
 Writes one JSON object (--out, default profiles/detector_step_bench.json)."""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -17,7 +22,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from layoutdit_amd import config as cfgs, synth  # noqa: E402
+from layoutdit_amd import _lib, config as cfgs, ops, synth  # noqa: E402
 from layoutdit_amd.modeling import LayoutDetectionModel  # noqa: E402
 from layoutdit_amd import training  # noqa: E402
 from layoutdit_amd.training import DetectorTrainStep  # noqa: E402
@@ -27,17 +32,21 @@ ap.add_argument("--config", default="vit_base", choices=["vit_micro", "vit_tiny"
 ap.add_argument("--runs", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--clip", action="store_true", help="also time clipping and parameter groups against clip_grad_norm_ + AdamW(groups)")
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "detector_step_bench.json"))
+ap.add_argument("--qat", action="store_true", help="time the qat detector's apply() beside the bf16-encoder detector's, and the re-quantise launch beside ldit_pack_train")
+ap.add_argument("--inner", type=int, default=20, help="--qat: calls of the launch / the pack per timed window")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                    "detector_step_bench_qat.json" if args.qat else "detector_step_bench.json")
 
 dev = "cuda:0"
 cfg = getattr(cfgs, args.config)()
 cfg.drop_path_rate = 0.0
 
 
-def build():
+def build(compute_dtype="f32"):
     torch.manual_seed(0)
-    model = LayoutDetectionModel(config=cfg)
+    model = LayoutDetectionModel(config=cfg, compute_dtype=compute_dtype, qat=compute_dtype == "mxfp8")
     model.model.backbone.backbone.dit.load_numpy(synth.synth_weights(cfg, seed=4))
     return model.to(dev).train()
 
@@ -53,6 +62,69 @@ def with_grads(model):
     sum(model.losses(images, targets, generator=gen).values()).backward()
     return model
 
+
+def window(fn, inner=1):
+    """Milliseconds per call of `inner` back-to-back calls between two HIP events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner
+
+
+def spread(v, digits=4):
+    return {"median_ms": round(statistics.median(v), digits), "min_ms": round(min(v), digits), "max_ms": round(max(v), digits)}
+
+
+if args.qat:
+    m_bf16, m_qat = with_grads(build("bf16")), with_grads(build("mxfp8"))
+    s_bf16 = DetectorTrainStep(m_bf16, lr=1e-6, weight_decay=0.01, loss_scaling=False)
+    s_qat = DetectorTrainStep(m_qat, lr=1e-6, weight_decay=0.01, loss_scaling=False)
+    st = m_qat.model.backbone.backbone.dit._flat_state
+    pairs = {"apply": (("bf16_encoder", s_bf16.apply, 1), ("qat_mxfp8_encoder", s_qat.apply, 1)),
+             "requantise": (("requant_train_mirror_one_launch", lambda: ops.requant_train_mirror(st), args.inner),
+                            ("pack_train_cast_plus_launch_per_layer", lambda: st.repack(force=True), args.inner))}
+    ms = {}
+    for what, pair in pairs.items():
+        for _ in range(args.warmup):
+            for _, fn, _ in pair:
+                fn()
+        torch.cuda.synchronize()
+        samples = {name: [] for name, _, _ in pair}
+        for _ in range(args.runs):                             # alternating: one window of each in turn
+            for name, fn, inner in pair:
+                samples[name].append(window(fn, inner))
+        ms[what] = {name: spread(v, 5) for name, v in samples.items()}
+    L, Cc, F = cfg.num_hidden_layers, cfg.hidden_size, cfg.intermediate_size
+    matrix = L * (4 * Cc * Cc + 2 * Cc * F)
+    a, q = ms["apply"]["bf16_encoder"], ms["apply"]["qat_mxfp8_encoder"]
+    r, p = ms["requantise"]["requant_train_mirror_one_launch"], ms["requantise"]["pack_train_cast_plus_launch_per_layer"]
+    res = {
+        "workload": {"config": args.config, "encoder_elements": int(st.numel), "matrix_elements": int(matrix),
+                     "requantise_bytes": {"read": 4 * matrix, "written": matrix + matrix // 32 + 2 * matrix},
+                     "mirror_bytes": int(_lib.load().ldit_train_mirror_bytes(ctypes.byref(st.lcfg))),
+                     "segments": {"bf16_encoder": len(s_bf16._segments()[0]), "qat_mxfp8_encoder": len(s_qat._segments()[0])},
+                     "launches_per_apply": {"bf16_encoder": 1 + 2 * -(-len(s_bf16._segments()[0]) // 64),
+                                            "qat_mxfp8_encoder": 2 + 2 * -(-len(s_qat._segments()[0]) // 64)},
+                     "launches": {"requant_train_mirror": 1, "pack_train": 1 + L}, "weight_decay": 0.01, "loss_scale": 1.0},
+        "runs": args.runs, "warmup": args.warmup, "inner_calls_per_window": args.inner,
+        "order": "alternating, one window of each of a pair in turn, one process",
+        "timer": "HIP events around each window, host work of the calls included",
+        "ms": ms,
+        "apply_difference": {"median_ms": round(q["median_ms"] - a["median_ms"], 5), "ratio": round(q["median_ms"] / a["median_ms"], 3),
+                             "separated": bool(a["max_ms"] < q["min_ms"] or q["max_ms"] < a["min_ms"])},
+        "one_launch_over_pack_train": {"ratio": round(r["median_ms"] / p["median_ms"], 3),
+                                       "separated": bool(r["max_ms"] < p["min_ms"] or p["max_ms"] < r["min_ms"])},
+        "steps_taken": {"bf16_encoder": s_bf16.steps, "qat_mxfp8_encoder": s_qat.steps},
+        "device": torch.cuda.get_device_name(0), "box": "one MI355X box", "repeats": "one run",
+    }
+    print(json.dumps(res))
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 
 ours, theirs = with_grads(build()), with_grads(build())
 step = DetectorTrainStep(ours, lr=1e-4, weight_decay=0.01, loss_scaling=False)

@@ -8,6 +8,9 @@ iterations per setting.  The weights move by one AdamW step per timed iteration 
 kernel trace of the process from outside: launches per call are differences between two such traces (scripts/README.md).
 --train-dtype f32,bf16: the settings that alternate are train_dtype's instead, under one --grad-dtype (default
 bf16); peak allocated memory of an iteration is recorded per setting, and the file is profiles/detector_train_bench_train_bf16.json.
+--compute-dtype bf16,mxfp8: the settings that alternate are ENCODER builds - "mxfp8" is the quantisation-aware
+build (qat=True), whose apply() ends with the one re-quantise launch - each a detector of its own from the same initial weights,
+under one --grad-dtype; the file is profiles/detector_train_bench_qat.json.
 Needs a GPU: without one it fails.  Writes one JSON object (--out, default profiles/detector_train_bench.json)."""
 import argparse
 import json
@@ -33,27 +36,41 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--settings", default="f32,bf16", help="comma-separated grad_dtype settings, timed alternately in this order")
 ap.add_argument("--train-dtype", default=None, help="comma-separated train_dtype settings: these alternate instead, under --grad-dtype")
-ap.add_argument("--grad-dtype", default="bf16", help="the one grad_dtype of a --train-dtype run")
+ap.add_argument("--compute-dtype", default=None, help="comma-separated encoder builds (bf16, mxfp8 = qat): these alternate instead, under --grad-dtype")
+ap.add_argument("--grad-dtype", default="bf16", help="the one grad_dtype of a --train-dtype or --compute-dtype run")
 ap.add_argument("--count", type=int, default=0, help="no timing, nothing written: this many iterations of --phases in the first setting")
 ap.add_argument("--phases", default="iteration", choices=["losses", "iteration"])
 ap.add_argument("--commit", default=None, help="recorded as the tree's commit (default: git rev-parse of the checkout, if it is one)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-args.out = args.out or os.path.join(ROOT, "profiles", "detector_train_bench_train_bf16.json" if args.train_dtype else "detector_train_bench.json")
+if args.train_dtype and args.compute_dtype:
+    ap.error("--train-dtype and --compute-dtype: one option alternates per run")
+args.out = args.out or os.path.join(ROOT, "profiles", "detector_train_bench_qat.json" if args.compute_dtype else
+                                    "detector_train_bench_train_bf16.json" if args.train_dtype else "detector_train_bench.json")
 if args.runs < 20 and not args.count:
     ap.error("--runs: at least 20 iterations per setting")
 if not torch.cuda.is_available():
     sys.exit("detector_train_bench: no GPU found (the detector has no CPU path)")
 
 dev = "cuda:0"
-settings = (args.train_dtype or args.settings).split(",")
+settings = (args.compute_dtype or args.train_dtype or args.settings).split(",")
+if args.compute_dtype and any(s not in ("bf16", "mxfp8") for s in settings):
+    ap.error("--compute-dtype: bf16 and mxfp8 (the quantisation-aware build) are the encoders this comparison covers")
 cfg = getattr(cfgs, args.config)()
 cfg.drop_path_rate = 0.0
-torch.manual_seed(0)
-model = LayoutDetectionModel(config=cfg, compute_dtype="bf16")
-model.model.backbone.backbone.dit.load_numpy(synth.synth_weights(cfg, seed=4))
-model = model.to(dev).train()
-step = DetectorTrainStep(model, lr=1e-6)
+
+
+def build(compute_dtype: str):
+    torch.manual_seed(0)
+    m = LayoutDetectionModel(config=cfg, compute_dtype=compute_dtype, qat=compute_dtype == "mxfp8")
+    m.model.backbone.backbone.dit.load_numpy(synth.synth_weights(cfg, seed=4))
+    m = m.to(dev).train()
+    return m, DetectorTrainStep(m, lr=1e-6)
+
+
+# one detector whose options alternate, or (--compute-dtype) one detector per encoder build
+built = {s: build(s) for s in settings} if args.compute_dtype else {None: build("bf16")}
+model, step = next(iter(built.values()))
 
 pages = synth.synth_images(args.batch, 224, 224, seed=args.seed, kind="doc")
 images = [torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in pages]
@@ -68,7 +85,10 @@ for _ in range(args.batch):
 
 
 def iteration(setting: str, timed: bool, losses_only: bool = False):
-    if args.train_dtype:
+    model, step = built[setting] if args.compute_dtype else built[None]
+    if args.compute_dtype:
+        model.set_grad_dtype(args.grad_dtype)
+    elif args.train_dtype:
         model.set_grad_dtype(args.grad_dtype).set_train_dtype(setting)
     else:
         model.set_grad_dtype(setting)
@@ -110,7 +130,7 @@ peak = {s: 0 for s in settings}
 finite = True
 for _ in range(args.runs):
     for s in settings:
-        if args.train_dtype:
+        if args.train_dtype or args.compute_dtype:
             torch.cuda.reset_peak_memory_stats()
         t, total = iteration(s, True)
         peak[s] = max(peak[s], torch.cuda.max_memory_allocated())
@@ -130,12 +150,15 @@ try:
 except (OSError, subprocess.SubprocessError):
     pass
 res = {
-    "workload": {"config": args.config, "encoder": "bf16", "batch": args.batch, "image": [224, 224], "seed": args.seed, "drop_path_rate": 0.0,
+    "workload": {"config": args.config, "encoder": "per setting (mxfp8 = qat)" if args.compute_dtype else "bf16", "batch": args.batch, "image": [224, 224], "seed": args.seed, "drop_path_rate": 0.0,
                  "gt_boxes": int(sum(len(t["labels"]) for t in targets)), "sampled_rows_per_image": model.model.roi_heads.batch_size_per_image,
                  "optimizer": "DetectorTrainStep(lr=1e-6), one step per timed iteration"},
-    "settings": settings, "order": "alternating, one iteration of each setting in turn, one process, one set of weights",
+    "settings": settings, "order": "alternating, one iteration of each setting in turn, one process, " +
+                                   ("one detector per encoder build, equal initial weights" if args.compute_dtype else "one set of weights"),
     "runs": args.runs, "warmup": args.warmup, "timer": "HIP events around each call, host work of the call included",
-    "ms": ms, "all_losses_finite": finite, "steps": step.steps, "skipped_steps": step.skipped_steps,
+    "ms": ms, "all_losses_finite": finite,
+    "steps": {s: b[1].steps for s, b in built.items()} if args.compute_dtype else step.steps,
+    "skipped_steps": {s: b[1].skipped_steps for s, b in built.items()} if args.compute_dtype else step.skipped_steps,
     "launches": None,                                  # from kernel traces of --count runs, where they were made (scripts/README.md)
     "device": torch.cuda.get_device_name(0), "commit": commit, "box": "one MI355X box", "repeats": "one run",
 }
@@ -144,6 +167,16 @@ if len(settings) == 2:
     res["backward_difference"] = {"median_ms": round(a["median_ms"] - b["median_ms"], 3),
                                   "spread_ms": {s: round(ms[s]["backward"]["max_ms"] - ms[s]["backward"]["min_ms"], 3) for s in settings},
                                   "separated": bool(b["max_ms"] < a["min_ms"])}
+if args.compute_dtype:
+    res["option"], res["grad_dtype"] = "compute_dtype", args.grad_dtype
+    res["peak_allocated_mb"] = {s: round(peak[s] / 2 ** 20, 1) for s in settings}
+    res["apply_launches"] = "the bf16 encoder's, plus one for mxfp8 (ldit_requant_train_mirror)"
+    if len(settings) == 2:
+        for phase in ("losses", "apply"):
+            a, b = (ms[s][phase] for s in settings)
+            res[phase + "_difference"] = {"median_ms": round(a["median_ms"] - b["median_ms"], 3),
+                                          "spread_ms": {s: round(ms[s][phase]["max_ms"] - ms[s][phase]["min_ms"], 3) for s in settings},
+                                          "separated": bool(b["max_ms"] < a["min_ms"] or a["max_ms"] < b["min_ms"])}
 if args.train_dtype:
     res["option"], res["grad_dtype"] = "train_dtype", args.grad_dtype
     res["peak_allocated_mb"] = {s: round(peak[s] / 2 ** 20, 1) for s in settings}
