@@ -937,6 +937,25 @@ int ldit_adamw_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyp
 int ldit_requant_train_mirror(const ldit_cfg *cfg, const void *flat_params, void *mirror, size_t mirror_bytes,
                               const ldit_opt_state *state, ldit_stream stream);
 
+/* -- gradient accumulation and data-parallel ranks under this step (additive): the fold into one flat gradient bucket --
+ * One segment: n fp32 elements of a gradient tensor g and of its slice acc of the bucket, unrelated allocations of any 4-byte
+ * alignment (n == 0 allowed: its pointers are not looked at).  `segs` is a HOST array: the segments travel in the kernel arguments,
+ * 127 per launch, so nothing is copied to the device and nothing is allocated (capturable).  A workgroup owns 1 024 consecutive
+ * elements of one segment; 16-byte accesses where both pointers of a segment allow them, single elements elsewhere and for the last
+ * n % 4. */
+typedef struct ldit_acc_segment {
+    void *acc;
+    const void *g;
+    int64_t n;
+} ldit_acc_segment;
+
+/* overwrite != 0: acc[i] = g[i] as a copy of the bits (-0.0, NaN payloads and infinities survive; acc is never read, so whatever it
+ * held is legal).  overwrite == 0: acc[i] = acc[i] + g[i], one fp32 addition per element - no atomics and nothing reordered, so equal
+ * inputs give equal bits.  acc and g of a segment must not overlap.  ceil(S' / 127) launches, S' the non-empty segments.
+ * Refused before any launch, with a message: a null array with S > 0, a negative S or n, a null or misaligned pointer in a non-empty
+ * segment (LDIT_EINVAL); a segment of more than 2^41 elements, whose grid would pass 2^31 - 1 blocks (LDIT_EUNSUPPORTED). */
+int ldit_grads_accumulate_multi_f32(const ldit_acc_segment *segs, int32_t S, int32_t overwrite, ldit_stream stream);
+
 /* ---- COCO box evaluation: matching, accumulation ----
  * The arithmetic of the reference's Evaluator.score() (ref evaluation/evaluator.py:219-286, which hands a JSON file to a per-image,
  * per-category host loop) on padded device tensors: no host round trip, no allocation, no float atomics, capturable, every output a

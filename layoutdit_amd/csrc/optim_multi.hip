@@ -14,6 +14,10 @@
 // With global-norm clipping and parameter groups the sequence is check + sum of squares (one pass, one double
 // partial per workgroup), the state machine, ldit_clip_finish (one workgroup: the norm and the clip coefficient into the 16-byte
 // ldit_clip_state) and adamw_groups_multi_kernel: adamw_multi_kernel with a per-segment {lr_scale, weight_decay} beside the table.
+//
+// Gradient accumulation and data-parallel ranks put one launch in front of all that: grads_accumulate_kernel folds
+// the gradient tensors into the slices of one flat bucket (acc = g, or acc = acc + g), 127 {acc, g, n} segments per launch by the
+// same scheme, and the launches above then read the bucket's slices as their gradients.
 #include "api_internal.h"
 
 namespace ldit {
@@ -43,9 +47,18 @@ struct GroupLaunch {
 };
 static_assert(sizeof(GroupLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
 
+constexpr int ACC_SEGS = 127;             // the fold into the bucket: 127 x 24 bytes + the prefix table, under the same 3584
+struct AccLaunch {
+    ldit_acc_segment seg[ACC_SEGS];
+    int first_block[ACC_SEGS + 1];
+    int n;
+};
+static_assert(sizeof(AccLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
+
 template <typename T> struct launch_cap;
 template <> struct launch_cap<OptLaunch> { static constexpr int value = OPT_SEGS; };
 template <> struct launch_cap<GroupLaunch> { static constexpr int value = GROUP_SEGS; };
+template <> struct launch_cap<AccLaunch> { static constexpr int value = ACC_SEGS; };
 
 // the segment of this block: the last j with first_block[j] <= blk (every segment in a launch has at least one block)
 template <typename T>
@@ -314,6 +327,48 @@ __global__ void __launch_bounds__(256) clip_finish_kernel(const ldit_opt_state *
     if (coef < 1.0f) clip->clipped_steps = clip->clipped_steps + 1;
 }
 
+// ---- 0. the fold into the bucket: acc = g (the bits, acc never read) or acc = acc + g (one fp32 addition per element) --------------
+// Every element is read and written by exactly one thread: no atomics, nothing to reorder, equal inputs give equal bits.  The copy
+// moves integers, so -0.0, NaN payloads and infinities arrive as they left.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <bool OVERWRITE>
+__device__ __forceinline__ void fold_element(float *acc, const float *g, const int64_t e)
+{
+    if (OVERWRITE) reinterpret_cast<uint32_t *>(acc)[e] = reinterpret_cast<const uint32_t *>(g)[e];
+    else acc[e] = acc[e] + g[e];
+}
+
+template <bool OVERWRITE>
+__global__ void __launch_bounds__(256) grads_accumulate_kernel(const AccLaunch a)
+{
+    const int tid = threadIdx.x;
+    const int j = find_segment(a, (int)blockIdx.x);
+    float *acc = static_cast<float *>(a.seg[j].acc);
+    const float *g = static_cast<const float *>(a.seg[j].g);
+    const int64_t n = a.seg[j].n;
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    if (quad_aligned(acc) && quad_aligned(g)) {
+        const int64_t i = base + 4 * tid;
+        if (i + 4 <= n) {
+            if (OVERWRITE) {
+                *reinterpret_cast<u32x4 *>(acc + i) = *reinterpret_cast<const u32x4 *>(g + i);
+            } else {
+                const f32x4 A = *reinterpret_cast<const f32x4 *>(acc + i), G = *reinterpret_cast<const f32x4 *>(g + i);
+                *reinterpret_cast<f32x4 *>(acc + i) = f32x4{A[0] + G[0], A[1] + G[1], A[2] + G[2], A[3] + G[3]};
+            }
+        } else {
+            for (int64_t e = i; e < n; ++e) fold_element<OVERWRITE>(acc, g, e);      // the last n % 4 elements of the segment
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t e = base + tid + 256 * k;
+            if (e < n) fold_element<OVERWRITE>(acc, g, e);
+        }
+    }
+}
+
 #define LAUNCH_CHECKED(...)              \
     do {                                 \
         hipLaunchKernelGGL(__VA_ARGS__); \
@@ -344,8 +399,8 @@ int validate(const char *what, const ldit_opt_segment *segs, int32_t S, const vo
 
 // the launches of one entry point: segments in order, the table's capacity of non-empty ones (and at most 2^31 - 1 blocks) per
 // launch.  launch(a, blocks, first) - `first` the host array's index of every slot of `a`, for what rides beside the segments.
-template <typename T, typename F>
-int for_each_launch(const ldit_opt_segment *segs, int32_t S, F &&launch)
+template <typename T, typename Seg, typename F>
+int for_each_launch(const Seg *segs, int32_t S, F &&launch)
 {
     constexpr int CAP = launch_cap<T>::value;
     T a;
@@ -432,6 +487,29 @@ int ldit_adamw_multi_f32(const ldit_opt_segment *segs, int32_t S, const ldit_opt
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     return for_each_launch<OptLaunch>(segs, S, [&](const OptLaunch &a, unsigned blocks, const int32_t *) -> int {
         LAUNCH_CHECKED(adamw_multi_kernel, dim3(blocks), dim3(256), 0, stream, a, state, b1, omb1, b2, omb2, eps, weight_decay, grad_mul);
+        return LDIT_OK;
+    });
+}
+
+int ldit_grads_accumulate_multi_f32(const ldit_acc_segment *segs, int32_t S, int32_t overwrite, ldit_stream stream_)
+{
+    const char *what = "grads_accumulate_multi";
+    if (S < 0) return fail(LDIT_EINVAL, "%s: negative segment count %d", what, S);
+    if (S > 0 && !segs) return fail(LDIT_EINVAL, "%s: null segment array", what);
+    for (int32_t s = 0; s < S; ++s) {
+        const ldit_acc_segment &q = segs[s];
+        if (q.n < 0) return fail(LDIT_EINVAL, "%s: segment %d has negative length %lld", what, s, (long long)q.n);
+        if (q.n == 0) continue;
+        if (q.n > OPT_MAX_BLOCKS * (int64_t)OPT_BLOCK_ELEMS)
+            return fail(LDIT_EUNSUPPORTED, "%s: segment %d longer than 2^41 elements: its grid exceeds 2^31 - 1 blocks", what, s);
+        if (!q.acc || !q.g) return fail(LDIT_EINVAL, "%s: segment %d has a null pointer", what, s);
+        if (!aligned4(q.acc) || !aligned4(q.g)) return fail(LDIT_EINVAL, "%s: segment %d: fp32 pointers must be 4-byte aligned", what, s);
+    }
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return for_each_launch<AccLaunch>(segs, S, [&](const AccLaunch &a, unsigned blocks, const int32_t *) -> int {
+        if (overwrite) LAUNCH_CHECKED(grads_accumulate_kernel<true>, dim3(blocks), dim3(256), 0, stream, a);
+        else LAUNCH_CHECKED(grads_accumulate_kernel<false>, dim3(blocks), dim3(256), 0, stream, a);
         return LDIT_OK;
     });
 }

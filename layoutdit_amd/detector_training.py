@@ -20,7 +20,13 @@ The encoder may be the quantisation-aware mxfp8 build (``LayoutDetectionModel(co
 the same launches, then ONE that re-quantises every layer's MX operands from the updated masters (``ldit_requant_train_mirror``),
 reading the same device block - a skipped step stores nothing there either.
 
-No data parallelism.  PyTorch is plumbing: it owns the memory, the stream and autograd's graph; the arithmetic of
+Gradient accumulation and data-parallel ranks: ``accumulate=A`` makes every ``A``-th ``step()`` the update, on the
+mean gradient of the ``A`` micro-batches; ``rank=`` (a ``dp.Rank`` of an initialised process group) sums over the ranks before the
+update.  Both go through one flat fp32 bucket that one multi-tensor launch folds the gradients into (``ldit_grads_accumulate_multi_f32``)
+and that the launches above read instead of ``p.grad``; the mean's ``1 / (A * world)`` rides in the loss multiplier, so no kernel of the
+update changes.  Every rank decides from the same reduced bits, hence alike, without exchanging a flag.
+
+PyTorch is plumbing: it owns the memory, the stream and autograd's graph; the arithmetic of
 the update is the library's.
 """
 from __future__ import annotations
@@ -28,14 +34,38 @@ from __future__ import annotations
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
+import torch.distributed as dist
 
 from . import _lib, ops
+from .dp import Rank, all_reduce_sum, broadcast_from_main
 
 _FIELD = {n: i for i, n in enumerate(_lib.OPT_STATE_FIELDS)}
 _INT_FIELDS = ("found_inf", "skip", "step", "growth_tracker", "skipped_steps")
 _FLOAT_FIELDS = ("scale", "inv_scale_used", "lr", "bc1", "bc2_sqrt")
 _CLIP = {n: i for i, n in enumerate(_lib.CLIP_STATE_FIELDS)}
 _ENCODER = "model.backbone.backbone.dit."
+BUCKET_ALIGN = 64                                                    # fp32 elements: every slice of the bucket starts on 256 bytes
+
+
+def bucket_layout(lengths: Sequence[int]) -> Tuple[Tuple[int, ...], int]:
+    """Where the slices of the gradient bucket lie: ``(offsets, total)`` in fp32 elements for segments of these lengths, in their
+    order - every offset a multiple of ``BUCKET_ALIGN`` (256 bytes), slices disjoint, ``total`` covering the last one.  A segment of
+    length 0 takes no room.  A pure function of the tuple of lengths."""
+    offsets, at = [], 0
+    for n in lengths:
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"bucket_layout: negative segment length {n}")
+        offsets.append(at)
+        at += -(-n // BUCKET_ALIGN) * BUCKET_ALIGN
+    return tuple(offsets), at
+
+
+def _numel(shape) -> int:
+    n = 1
+    for v in shape:
+        n *= int(v)
+    return n
 
 
 def warmup_lr(lr: float, it: int, warmup_iters: int, warmup_factor: float) -> float:
@@ -108,15 +138,32 @@ class DetectorTrainStep:
     gradients (of the parameters' own elements; nothing else of the encoder's flat block enters).  ``param_groups``: a list of
     ``{"params": names or parameters, "lr_scale": float, "weight_decay": float}``; a parameter no group names has ``lr_scale`` 1 and
     the constructor's ``weight_decay``.  ``warmup_iters``: for that many first calls of :meth:`step` the learning rate is
-    :func:`warmup_lr`.  With all four left alone the step is the three launches it always was."""
+    :func:`warmup_lr`.  With all four left alone the step is the three launches it always was.
+
+    ``accumulate``: micro-batches per update.  Every :meth:`step` is one micro-batch; its gradients are folded into one flat fp32
+    bucket (:meth:`accumulate_grads`) and the ``accumulate``-th call updates from the bucket: the mean gradient, since the loss was
+    multiplied by ``scale / (accumulate * world)``.  ``rank``: this process's :class:`~layoutdit_amd.dp.Rank`; with ``world > 1`` the
+    bucket is summed over the ranks (one collective) before the update, and ``broadcast_parameters`` makes rank 0's weights everybody's
+    at construction.  ``iters``, the warmup and :attr:`steps` count updates, not micro-batches.  With ``accumulate == 1`` and one rank
+    there is no bucket and nothing changes."""
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 0.0, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  step_size: Optional[int] = None, gamma: float = 0.1, init_scale: float = 65536.0, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, loss_scaling: bool = True, max_grad_norm: Optional[float] = None,
-                 param_groups: Optional[Sequence[dict]] = None, warmup_iters: int = 0, warmup_factor: float = 1e-3):
+                 param_groups: Optional[Sequence[dict]] = None, warmup_iters: int = 0, warmup_factor: float = 1e-3, accumulate: int = 1,
+                 rank: Optional[Rank] = None, broadcast_parameters: bool = True):
         from .modeling.detector import LayoutDetectionModel
         if not isinstance(model, LayoutDetectionModel):
             raise TypeError("DetectorTrainStep: expected a LayoutDetectionModel (the encoder alone trains with TrainStep)")
+        if int(accumulate) < 1:
+            raise ValueError("DetectorTrainStep: accumulate must be at least 1 (micro-batches per update)")
+        if rank is not None and not isinstance(rank, Rank):
+            raise TypeError("DetectorTrainStep: rank must be a layoutdit_amd.dp.Rank (dp.init() returns one)")
+        if rank is not None and rank.world > 1:
+            if not (dist.is_available() and dist.is_initialized()):
+                raise RuntimeError(f"DetectorTrainStep: rank {rank.rank} of {rank.world} without an initialised process group - call dp.init() first")
+            if dist.get_world_size() != rank.world:
+                raise RuntimeError(f"DetectorTrainStep: rank.world = {rank.world}, the process group has {dist.get_world_size()} ranks")
         self.model = model
         self.encoder = model.model.backbone.backbone.dit
         if self.encoder.compute_dtype == "fp8" or (self.encoder.compute_dtype == "mxfp8" and not getattr(self.encoder, "qat", False)):
@@ -156,6 +203,19 @@ class DetectorTrainStep:
         self._partials: Optional[torch.Tensor] = None                        # one float64 per 1 024 gradient elements, made with the moments
         self._partials_key = None
         self._grouped = self._hyper is not None or self._clip is not None
+        self.accumulate, self.rank, self.world = int(accumulate), rank, 1 if rank is None else int(rank.world)
+        self._use_bucket = self.accumulate > 1 or self.world > 1
+        self._loss_mul = 1.0 / (self.accumulate * self.world)
+        self.pending_micro_batches = 0                                       # folds since the last apply()
+        self._bucket: Optional[torch.Tensor] = None                          # made at the first fold, never re-made
+        self._bucket_key: Optional[tuple] = None                             # ((first parameter of the segment, its length), ...)
+        self._bucket_slices: List[torch.Tensor] = []
+        self._bucket_members: List[list] = []                                # per slice: (parameter name, offset in the slice, shape)
+        self._members: List[list] = []                                       # the same, of the last _segments() call
+        self._layout_agreed = False
+        if self.world > 1 and broadcast_parameters:
+            broadcast_from_main(rank, list(model.parameters()) + list(model.buffers()))
+            self.invalidate_caches()
 
     def _hyper_of(self, name: str) -> Tuple[float, float]:
         return (1.0, self.weight_decay) if self._hyper is None else self._hyper.get(name, (1.0, self.weight_decay))
@@ -165,20 +225,84 @@ class DetectorTrainStep:
              generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
         """One iteration: gradients cleared, ``model.losses``, backward on the scaled sum, check / advance / update.  Returns the four
         unscaled, detached losses.  From the backward on there is no host synchronisation; the loss scale enters the graph as a device
-        tensor.  (The input transform's host bookkeeping is ``model.losses``'s own.)"""
+        tensor.  (The input transform's host bookkeeping is ``model.losses``'s own.)
+
+        With ``accumulate`` or ranks every call is one micro-batch: the loss is multiplied by ``scale * (1 / (accumulate * world))`` -
+        one fp32 product of the block's scale and a constant, on the device -, the gradients are folded into the bucket, and only the
+        ``accumulate``-th call goes on to :meth:`apply`.  The losses returned are this call's, of this rank."""
         self._require_train_mode()
-        if self.warmup_iters and self.iters <= self.warmup_iters:           # the last of these fills writes the full rate
+        if self.pending_micro_batches == 0 and self.warmup_iters and self.iters <= self.warmup_iters:   # the last of these fills writes the full rate
             self._write_lr()
-        self.iters += 1
         for p in self.model.parameters():
             p.grad = None
         losses = self.model.losses(images, targets, generator=generator)
         total = sum(losses.values())
-        if self.loss_scaling:
+        if self._use_bucket:
+            total = total * (self._state_f[_FIELD["scale"]] * self._loss_mul if self.loss_scaling else self._loss_mul)
+        elif self.loss_scaling:
             total = total * self._state_f[_FIELD["scale"]]
         total.backward()
-        self.apply()
+        if self._use_bucket:
+            self.accumulate_grads()
+        if self.pending_micro_batches >= self.accumulate or not self._use_bucket:
+            self.iters += 1
+            self.apply()
         return {k: v.detach() for k, v in losses.items()}
+
+    # ---- the gradient bucket ------------------------------------------------------------------------------------------------------------
+    @property
+    def bucket(self) -> Optional[torch.Tensor]:
+        """The flat fp32 gradient bucket, or None: before the first fold, and always with ``accumulate == 1`` on one rank."""
+        return self._bucket
+
+    def accumulated_grads(self) -> Dict[str, torch.Tensor]:
+        """Parameter name -> its gradient in the bucket (a view): ``scale / (accumulate * world)`` times the sum over the micro-batches
+        folded since the last update, and over the ranks once :meth:`apply` reduced it."""
+        return {name: self._bucket_slices[i][off: off + _numel(shape)].view(shape)
+                for i, members in enumerate(self._bucket_members) for name, off, shape in members}
+
+    def _bind_bucket(self, grads: List[torch.Tensor]) -> List[torch.Tensor]:
+        """The bucket's slices for the segments ``_segments()`` just returned.  The layout is fixed by the first fold; segments that do
+        not repeat it (a parameter that got no gradient this time, another input grid) are refused."""
+        key = tuple((members[0][0], g.numel()) for members, g in zip(self._members, grads))
+        if self._bucket is None:
+            offsets, total = bucket_layout([n for _, n in key])
+            flat = torch.zeros(total + BUCKET_ALIGN, dtype=torch.float32, device=self.device)
+            first = (-flat.data_ptr() % (4 * BUCKET_ALIGN)) // 4              # the allocator's blocks are aligned already: 0
+            self._bucket = flat[first: first + total]
+            self._bucket_key, self._bucket_members = key, [list(m) for m in self._members]
+            self._bucket_slices = [self._bucket[o: o + n] for o, (_, n) in zip(offsets, key)]
+        elif key != self._bucket_key:
+            i = next((i for i, (a, b) in enumerate(zip(key, self._bucket_key)) if a != b), min(len(key), len(self._bucket_key)))
+            now = "no segment" if i >= len(key) else f"{key[i][0]} ({key[i][1]} elements)"
+            was = "no segment" if i >= len(self._bucket_key) else f"{self._bucket_key[i][0]} ({self._bucket_key[i][1]} elements)"
+            raise RuntimeError(f"DetectorTrainStep: the gradients do not repeat the bucket's layout, fixed at the first fold: segment {i} is "
+                               f"{now}, the bucket has {was} there (a parameter without a gradient in this micro-batch, or another input grid)")
+        return self._bucket_slices
+
+    @torch.no_grad()
+    def accumulate_grads(self) -> None:
+        """Fold the gradients the parameters hold now into the bucket: the first fold since the last :meth:`apply` overwrites it (bit
+        for bit), later ones add (one fp32 addition per element).  ``ceil(S / ops.ACC_MAX_SEGMENTS)`` launches, no synchronisation."""
+        if not self._use_bucket:
+            raise RuntimeError("DetectorTrainStep.accumulate_grads: built with accumulate=1 on one rank, there is no bucket - apply() reads p.grad")
+        self._require_train_mode()
+        grads = self._segments()[1]
+        ops.grads_accumulate_multi(self._bind_bucket(grads), grads, overwrite=self.pending_micro_batches == 0)
+        self.pending_micro_batches += 1
+
+    def _reduce_bucket(self) -> None:
+        """The bucket summed over the ranks: one collective.  Every rank receives the same bits."""
+        if not self._layout_agreed:                                           # once, host side: better than a mis-sized collective
+            keys = [None] * self.world
+            dist.all_gather_object(keys, self._bucket_key)
+            if any(k != keys[0] for k in keys):
+                bad = next(r for r, k in enumerate(keys) if k != keys[0])
+                raise RuntimeError(f"DetectorTrainStep: the ranks' gradient buckets differ in layout (rank {bad} against rank 0): "
+                                   "every rank must give the same parameters a gradient")
+            self._layout_agreed = True
+        if self._bucket.numel():
+            all_reduce_sum(self.rank, self._bucket)
 
     @torch.no_grad()
     def apply(self) -> None:
@@ -188,9 +312,20 @@ class DetectorTrainStep:
 
         Under the quantisation-aware mxfp8 encoder (``qat=True``) one launch follows, with the same state block: the MX operands of
         the encoder's training mirror re-made from the updated masters (``ops.requant_train_mirror``), so that the mirror is a fresh
-        ``ldit_pack_train`` of them - where the mirror was current before the update; otherwise the next forward packs, as ever."""
+        ``ldit_pack_train`` of them - where the mirror was current before the update; otherwise the next forward packs, as ever.
+
+        With a bucket in use (``accumulate > 1`` or ranks) the gradients are the bucket's slices, as :meth:`accumulate_grads` left
+        them, after their sum over the ranks - ordered on the current stream under RCCL, no host wait; the launches are the same."""
         self._require_train_mode()
         params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current, hyper = self._segments()
+        if self._use_bucket:
+            if self.pending_micro_batches == 0:
+                raise RuntimeError("DetectorTrainStep.apply: nothing was folded into the bucket since the last update - call "
+                                   "accumulate_grads() after each backward (step() does)")
+            grads = self._bind_bucket(grads)
+            if self.world > 1:
+                self._reduce_bucket()
+            self.pending_micro_batches = 0
         if not self._grouped:
             if params:
                 ops.grads_check_multi(grads, self._state)
@@ -307,6 +442,8 @@ class DetectorTrainStep:
         covers the parameters' own elements and nothing else."""
         params, grads, exp_avgs, exp_avg_sqs, mirrors = [], [], [], [], []
         hyper = [] if self._grouped else None
+        members = self._members = []                      # per segment: (parameter name, offset in the segment, shape); for the bucket only
+        track = self._use_bucket
         st = getattr(self.encoder, "_flat_state", None)
         if st is not None and not st.intact():
             st = None                                     # re-homed since (.to() / assign): plain parameters until the next forward
@@ -321,6 +458,8 @@ class DetectorTrainStep:
                 p.grad is not None and p.grad.dtype == torch.float32 and p.grad.data_ptr() == g.data_ptr() + 4 * off for off, p in in_flat.values())
             if whole:
                 params.append(st.params), grads.append(g), exp_avgs.append(self._enc[1]), exp_avg_sqs.append(self._enc[2]), mirrors.append(mirror)
+                if track:
+                    members.append([(self._names[id(p)], off, shape) for _, p, off, shape in st.named])
             elif self._grouped and g.dtype == torch.float32 and g.is_contiguous():
                 runs = []                                 # [first offset, end offset, (lr_scale, weight_decay)] over slots whose gradient is autograd's view
                 for off, p in sorted(in_flat.values(), key=lambda e: e[0]):
@@ -330,9 +469,12 @@ class DetectorTrainStep:
                     if runs and runs[-1][1] == off and runs[-1][2] == h:
                         runs[-1][1] = off + p.numel()
                     else:
-                        runs.append([off, off + p.numel(), h])
+                        runs.append([off, off + p.numel(), h, []])
+                    runs[-1][3].append((self._names[id(p)], off - runs[-1][0], tuple(p.shape)))
                     taken.add(id(p))
-                for a, b, h in runs:
+                for a, b, h, inside in runs:
+                    if track:
+                        members.append(inside)
                     params.append(st.params[a:b]), grads.append(g[a:b]), exp_avgs.append(self._enc[1][a:b]), exp_avg_sqs.append(self._enc[2][a:b])
                     mirrors.append(mirror[a:b]), hyper.append(h)
         else:
@@ -345,6 +487,8 @@ class DetectorTrainStep:
                 raise ValueError(f"DetectorTrainStep: the gradient of {name} is {g.dtype} on {g.device}; expected float32 beside its parameter")
             m, v = self._moments(name, p)
             params.append(p.detach()), grads.append(g.contiguous()), exp_avgs.append(m), exp_avg_sqs.append(v)
+            if track:
+                members.append([(name, 0, tuple(p.shape))])
             if id(p) in in_flat:
                 off = in_flat[id(p)][0]
                 mirrors.append(mirror[off: off + p.numel()])
@@ -394,7 +538,10 @@ class DetectorTrainStep:
 
     def state_dict(self) -> dict:
         """Everything a resumed run needs: the device block's fields, both moments keyed by the model's parameter names, the host-side
-        schedule.  Synchronises."""
+        schedule.  Synchronises.  Refused in the middle of an accumulation: the bucket is not part of it."""
+        if self.pending_micro_batches:
+            raise RuntimeError(f"DetectorTrainStep.state_dict: {self.pending_micro_batches} of {self.accumulate} micro-batches are folded into the "
+                               "gradient bucket, which no state dictionary holds - save after the update")
         moments = {n: (m.detach().clone(), v.detach().clone()) for n, (m, v) in self._mom.items()}
         moments.update({n: (m.clone(), v.clone()) for n, (m, v) in self._pending.items() if n not in moments})
         out = {"state": self._read_state(), "exp_avg": {n: mv[0] for n, mv in moments.items()},

@@ -140,6 +140,30 @@ def gather_over_ranks(r: Rank, values) -> list:
     return [t.cpu().tolist() for t in out]
 
 
+def all_reduce_sum(r: Rank, t: torch.Tensor, async_op: bool = False):
+    """``t`` summed over the ranks, in place (the data plane of both train steps).  RCCL (backend nccl): on RCCL's own stream,
+    ordered after the kernels already enqueued on the current stream; ``async_op`` returns the work to ``wait()`` on, otherwise the
+    current stream is made to wait for the result - the host never does.  gloo (the tests): through a host copy, synchronous."""
+    if r.backend == "nccl":
+        return dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=async_op)
+    host = t.cpu()
+    dist.all_reduce(host, op=dist.ReduceOp.SUM)
+    t.copy_(host)
+    return None
+
+
+def broadcast_from_main(r: Rank, tensors) -> None:
+    """Every tensor of ``tensors`` overwritten, in place, by rank 0's (gloo: through host copies)."""
+    with torch.no_grad():
+        for t in tensors:
+            if r.backend == "nccl":
+                dist.broadcast(t, src=0)
+            else:
+                host = t.detach().cpu()
+                dist.broadcast(host, src=0)
+                t.copy_(host)
+
+
 def finalize(r: Rank) -> None:
     if dist.is_initialized():
         dist.destroy_process_group()

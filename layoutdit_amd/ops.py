@@ -1342,6 +1342,29 @@ def adamw_groups_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Ten
             float(betas[1]), float(eps))
 
 
+# -- gradient accumulation and data-parallel ranks: the fold into one flat gradient bucket, in front of the launches above --
+ACC_MAX_SEGMENTS = _lib.ACC_MAX_SEGMENTS
+
+
+def grads_accumulate_multi(accs: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], overwrite: bool) -> None:
+    """``accs[i] = grads[i]`` bit for bit (``overwrite``: ``accs`` is never read) or ``accs[i] += grads[i]``, one fp32 addition per
+    element, over the lists in ``ceil(S / ACC_MAX_SEGMENTS)`` launches.  Tensors may be views at any element offset; a pair must not
+    overlap.  No synchronisation, nothing allocated."""
+    lib = _lib.load()
+    grads = list(grads)
+    grads = _req_list(grads, "grads", len(grads))
+    S = len(grads)
+    accs = _req_list(accs, "accs", S)
+    segs = (_lib.LditAccSegment * max(S, 1))()
+    for i, (s, a, g) in enumerate(zip(segs, accs, grads)):
+        if a.numel() != g.numel():
+            raise ValueError(f"segment {i}: accs and grads differ in length ({a.numel()} and {g.numel()})")
+        s.acc, s.g, s.n = a.data_ptr(), g.data_ptr(), g.numel()
+    if S == 0:
+        return
+    _launch(_device(*accs, *grads), lib.ldit_grads_accumulate_multi_f32, segs, S, 1 if overwrite else 0)
+
+
 def requant_train_mirror(flat_state, opt_state: Optional[torch.Tensor] = None) -> None:
     """The MX operands of a quantisation-aware encoder's training mirror re-made from its fp32 master in ONE launch
     (``ldit_requant_train_mirror``): every layer's four matrices (codes, scales, dequantised bf16 copies) and fused bias, nothing else.

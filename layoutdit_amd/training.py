@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .dp import Rank
+from .dp import Rank, all_reduce_sum
 
 _LAYER_SLOTS = ("ln1_w", "ln1_b", "wqkv", "bqkv", "wo", "bo", "lam1", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2", "lam2")
 
@@ -395,12 +395,7 @@ class TrainStep:
     def _all_reduce(self, t: torch.Tensor):
         """Sum over ranks.  RCCL (backend nccl): asynchronous on RCCL's own stream, ordered after the kernels already enqueued
         on the current stream - the remaining backward overlaps it.  gloo (CPU tests): through a host copy, synchronous."""
-        if self.rank.backend == "nccl":
-            return dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=True)
-        host = t.cpu()
-        dist.all_reduce(host, op=dist.ReduceOp.SUM)
-        t.copy_(host)
-        return None
+        return all_reduce_sum(self.rank, t, async_op=True)
 
     @torch.no_grad()
     def step(self, x: torch.Tensor, _timing: Optional[dict] = None, drop_scales: Optional[torch.Tensor] = None,

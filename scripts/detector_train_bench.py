@@ -11,6 +11,11 @@ bf16); peak allocated memory of an iteration is recorded per setting, and the fi
 --compute-dtype bf16,mxfp8: the settings that alternate are ENCODER builds - "mxfp8" is the quantisation-aware
 build (qat=True), whose apply() ends with the one re-quantise launch - each a detector of its own from the same initial weights,
 under one --grad-dtype; the file is profiles/detector_train_bench_qat.json.
+--accumulate A: one detector under DetectorTrainStep(accumulate=A), --grad-dtype as given.  Timed per call of
+step(): the A - 1 calls of an update that only fold their gradients into the bucket, and the one that also applies it.  Then, on
+the gradients and the bucket's slices the last call left, the fold launches alone in both modes (ops.grads_accumulate_multi) beside
+torch._foreach_copy_ / torch._foreach_add_ over the same tensor lists, the four alternating; the file is
+profiles/detector_train_bench_accum.json.
 Needs a GPU: without one it fails.  Writes one JSON object (--out, default profiles/detector_train_bench.json)."""
 import argparse
 import json
@@ -38,6 +43,7 @@ ap.add_argument("--settings", default="f32,bf16", help="comma-separated grad_dty
 ap.add_argument("--train-dtype", default=None, help="comma-separated train_dtype settings: these alternate instead, under --grad-dtype")
 ap.add_argument("--compute-dtype", default=None, help="comma-separated encoder builds (bf16, mxfp8 = qat): these alternate instead, under --grad-dtype")
 ap.add_argument("--grad-dtype", default="bf16", help="the one grad_dtype of a --train-dtype or --compute-dtype run")
+ap.add_argument("--accumulate", type=int, default=0, help="micro-batches per update: time step() per call and the fold launches (see above)")
 ap.add_argument("--count", type=int, default=0, help="no timing, nothing written: this many iterations of --phases in the first setting")
 ap.add_argument("--phases", default="iteration", choices=["losses", "iteration"])
 ap.add_argument("--commit", default=None, help="recorded as the tree's commit (default: git rev-parse of the checkout, if it is one)")
@@ -45,7 +51,10 @@ ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.train_dtype and args.compute_dtype:
     ap.error("--train-dtype and --compute-dtype: one option alternates per run")
-args.out = args.out or os.path.join(ROOT, "profiles", "detector_train_bench_qat.json" if args.compute_dtype else
+if args.accumulate and (args.train_dtype or args.compute_dtype or args.count or args.accumulate < 2):
+    ap.error("--accumulate: at least 2, and on its own (no --train-dtype, --compute-dtype or --count)")
+args.out = args.out or os.path.join(ROOT, "profiles", "detector_train_bench_accum.json" if args.accumulate else
+                                    "detector_train_bench_qat.json" if args.compute_dtype else
                                     "detector_train_bench_train_bf16.json" if args.train_dtype else "detector_train_bench.json")
 if args.runs < 20 and not args.count:
     ap.error("--runs: at least 20 iterations per setting")
@@ -65,7 +74,7 @@ def build(compute_dtype: str):
     m = LayoutDetectionModel(config=cfg, compute_dtype=compute_dtype, qat=compute_dtype == "mxfp8")
     m.model.backbone.backbone.dit.load_numpy(synth.synth_weights(cfg, seed=4))
     m = m.to(dev).train()
-    return m, DetectorTrainStep(m, lr=1e-6)
+    return m, DetectorTrainStep(m, lr=1e-6, accumulate=max(args.accumulate, 1))
 
 
 # one detector whose options alternate, or (--compute-dtype) one detector per encoder build
@@ -116,6 +125,84 @@ def iteration(setting: str, timed: bool, losses_only: bool = False):
     return None, float(total.detach())
 
 
+def stats(v):
+    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+
+
+def head_commit():
+    try:
+        return args.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True, timeout=10).stdout.strip() or None
+    except (OSError, subprocess.SubprocessError):
+        return args.commit
+
+
+def timed_call(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+if args.accumulate:
+    from layoutdit_amd import ops  # noqa: E402
+    model.set_grad_dtype(args.grad_dtype)
+    A = args.accumulate
+
+    def micro_batch():
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(2)
+        return step.step(images, targets, generator=gen)
+
+    for _ in range(args.warmup * A):                # whole updates: every shape, every cache, every moment and the bucket
+        micro_batch()
+    torch.cuda.synchronize()
+    calls = {"fold_only": [], "fold_and_apply": []}
+    finite = True
+    for _ in range(args.runs):                      # the two kinds of call alternate by construction: A - 1 folds, then the update
+        for k in range(A):
+            t, losses = timed_call(micro_batch)
+            calls["fold_and_apply" if k == A - 1 else "fold_only"].append(t)
+            finite = finite and all(bool(torch.isfinite(v)) for v in losses.values())
+    assert step.pending_micro_batches == 0
+    # the fold alone, on what the last call left: the parameters' gradients and the bucket's slices (rewritten by the next fold)
+    grads, slices = [g.reshape(-1) for g in step._segments()[1]], step._bucket_slices
+    assert len(grads) == len(slices) and all(g.numel() == s.numel() for g, s in zip(grads, slices))
+    folds = {"ldit_overwrite": lambda: ops.grads_accumulate_multi(slices, grads, True),
+             "ldit_add": lambda: ops.grads_accumulate_multi(slices, grads, False),
+             "torch_foreach_copy_": lambda: torch._foreach_copy_(slices, grads),
+             "torch_foreach_add_": lambda: torch._foreach_add_(slices, grads)}
+    step.bucket.zero_()                             # finite sums whatever the folds above left
+    for _ in range(args.warmup):
+        for fn in folds.values():
+            fn()
+    torch.cuda.synchronize()
+    fold_ms = {k: [] for k in folds}
+    for _ in range(args.runs):
+        for k, fn in folds.items():
+            fold_ms[k].append(timed_call(fn)[0])
+    elements = int(sum(g.numel() for g in grads))
+    res = {
+        "workload": {"config": args.config, "encoder": "bf16", "batch": args.batch, "image": [224, 224], "seed": args.seed, "drop_path_rate": 0.0,
+                     "grad_dtype": args.grad_dtype, "optimizer": f"DetectorTrainStep(lr=1e-6, accumulate={A}), every call one micro-batch of the whole batch"},
+        "accumulate": A, "order": "alternating in one process: the calls of an update in turn; the four folds in turn",
+        "runs": args.runs, "warmup": args.warmup, "timer": "HIP events around each call, host work of the call included",
+        "step_call_ms": {k: stats(v) for k, v in calls.items()},
+        "apply_share_ms": round(statistics.median(calls["fold_and_apply"]) - statistics.median(calls["fold_only"]), 3),
+        "fold": {"segments": len(grads), "elements": elements, "launches": -(-sum(1 for g in grads if g.numel()) // ops.ACC_MAX_SEGMENTS),
+                 "bytes_moved": {"overwrite": 8 * elements, "add": 12 * elements}, "ms": {k: stats(v) for k, v in fold_ms.items()}},
+        "all_losses_finite": finite, "steps": step.steps, "skipped_steps": step.skipped_steps,
+        "device": torch.cuda.get_device_name(0), "commit": head_commit(), "box": "one MI355X box", "repeats": "one run",
+    }
+    for mode, nbytes in (("overwrite", 8), ("add", 12)):
+        res["fold"]["ldit_" + mode + "_gb_per_s"] = round(nbytes * elements / (res["fold"]["ms"]["ldit_" + mode]["median_ms"] * 1e-3) / 1e9, 1)
+    print(json.dumps(res))
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
+
 if args.count:
     for _ in range(args.count):
         iteration(settings[0], False, losses_only=args.phases == "losses")
@@ -139,16 +226,8 @@ for _ in range(args.runs):
 torch.cuda.synchronize()
 
 
-def stats(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-
-
 ms = {s: {name: stats([t[i] for t in samples[s]]) for i, name in enumerate(("losses", "backward", "apply"))} for s in settings}
-commit = args.commit
-try:
-    commit = commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True, timeout=10).stdout.strip() or None
-except (OSError, subprocess.SubprocessError):
-    pass
+commit = head_commit()
 res = {
     "workload": {"config": args.config, "encoder": "per setting (mxfp8 = qat)" if args.compute_dtype else "bf16", "batch": args.batch, "image": [224, 224], "seed": args.seed, "drop_path_rate": 0.0,
                  "gt_boxes": int(sum(len(t["labels"]) for t in targets)), "sampled_rows_per_image": model.model.roi_heads.batch_size_per_image,
