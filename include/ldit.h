@@ -523,8 +523,8 @@ int ldit_adamw_step(void *params, const void *grads, void *exp_avg, void *exp_av
                     float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *bf16_mirror,
                     ldit_stream stream);
 
-/* mxfp8 build: ldit_adamw_step's update of the whole flat block (same bits for master and moments), fused per layer with the
- * re-quantisation of the forward's operands: afterwards `mirror` (ldit_train_mirror_bytes(cfg) bytes) equals ldit_pack_train of
+/* mxfp8 build: ldit_adamw_step's update of the whole flat block (same bits for master and moments), followed by one launch that
+ * re-quantises the forward's operands of every layer (the launch of ldit_requant_train_mirror): afterwards `mirror` (ldit_train_mirror_bytes(cfg) bytes) equals ldit_pack_train of
  * the updated master bit for bit.  cfg->dtype == LDIT_MXFP8. */
 int ldit_adamw_step_mxfp8(const ldit_cfg *cfg, void *params, const void *grads, void *exp_avg, void *exp_avg_sq, float lr, float beta1,
                           float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *mirror, size_t mirror_bytes,

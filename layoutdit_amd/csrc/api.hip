@@ -59,15 +59,12 @@ DiagSwitches read_switches()
     auto is = [](const char *name, char c) { const char *e = getenv(name); return e && e[0] == c; };
     d.gemm_tile = digit("LDIT_GEMM_TILE", 0, 7);
     if (const char *e = getenv("LDIT_GEMM_THIN_TILES")) d.thin_tiles = atol(e);
-    d.panel_r16_vec = is("LDIT_PANEL_R16", 'v');
     d.panel_persist = is("LDIT_GEMM_PERSIST", '1');
     d.bf16_tile = digit("LDIT_GEMM_BF16_TILE", 2, 7);
     d.bf16_tile_env = getenv("LDIT_GEMM_BF16_TILE") != nullptr;
     d.bf16_tr_tile = digit("LDIT_GEMM_BF16_TR_TILE", 0, 9);
     d.bf16_tail_launch = is("LDIT_GEMM_BF16_TAIL_LAUNCH", '1');
     d.fp8_tile = digit("LDIT_GEMM_FP8_TILE", 0, 6);
-    d.fp8_k16 = is("LDIT_GEMM_FP8_K16", '1');
-    d.fp8_noskinny = is("LDIT_GEMM_FP8_NOSKINNY", '1');
     d.direct_epi = is("LDIT_GEMM_DIRECT_EPILOGUE", '1');
     d.seg_order = digit("LDIT_GEMM_SEG_ORDER", 0, 1);
     if (const char *e = getenv("LDIT_PLANES_TAIL_WAVES")) d.planes_tail_waves = atol(e);

@@ -152,28 +152,12 @@ inline void mx_layer_segs(const PackedLayer &f, const PackedLayer &x, int64_t C,
     segs[3] = {(int64_t)(f.w2 / 4), C * F, (int)F, 0, (int64_t)x.w2, (int64_t)x.sw_2};
 }
 
-// mxfp8 mirror from the flat block, per layer (one launch each): update = true fuses the AdamW step on that range (adamw_kernel's
-// arithmetic); the embeddings' range is left to the caller
-int mx_layers(const Geo &g, float *p, const float *gr, float *m, float *v, bool update, float lr, float b1, float b2, float eps, float wd,
-              int step, float grad_scale, void *mirror, hipStream_t stream)
-{
-    const PackedMap fm = packed_map(g, LDIT_F32), xm = packed_map(g, LDIT_MXFP8);
-    char *mx = static_cast<char *>(mirror) + mirror_mx_offset(g);
-    const int64_t C = g.C, F = g.F;
-    for (int l = 0; l < g.L; ++l) {
-        const PackedLayer &f = fm.layer[l], &x = xm.layer[l];
-        const int64_t e0 = (int64_t)(f.ln1_w / 4), e1 = (int64_t)((l + 1 < g.L ? fm.layer[l + 1].ln1_w : fm.total) / 4);
-        MxRequantSeg segs[4];
-        mx_layer_segs(f, x, C, F, segs);
-        LDIT_TRY(launch_adamw_mx(p, gr, m, v, e0, e1, update, lr, b1, b2, eps, wd, step, grad_scale, mirror, mx, segs, 4,
-                                 (int64_t)(f.bqkv / 4), (int64_t)x.bqkv, g.C, qfold_of(g), stream));
-    }
-    return LDIT_OK;
-}
-
-// The same matrices and bias for ALL layers in one launch, nothing else of the mirror written (ldit_requant_train_mirror).  The layer
-// comes from the grid, so every layer must be layer 0 moved by one stride in the flat block and one in the MX section: packed_map lays
-// equal layers out one after another, which is checked here rather than assumed.
+// The MX part of the mirror from the flat block: the matrices and the fused bias of ALL layers in one launch, nothing else of the
+// mirror written - the bf16 part is the caller's launch before (ldit_pack_train: the convert pass, ldit_adamw_step_mxfp8: adamw_kernel,
+// ldit_requant_train_mirror: the multi-tensor AdamW).  The layer comes from the grid, so every layer must be layer 0 moved by one stride
+// in the flat block and one in the MX section: packed_map lays equal layers out one after another, which is checked here rather than
+// assumed.  (mxfp8 geometries have hidden and mlp multiples of 128: every matrix is whole 16 384-element pieces, far inside
+// launch_requant_mirror's 1024-element rule.)
 int mx_requant_all_layers(const Geo &g, const float *p, void *mirror, const ldit_opt_state *state, hipStream_t stream)
 {
     if (g.L == 0) return LDIT_OK;
@@ -497,9 +481,8 @@ int ldit_pack_train(const ldit_cfg *cfg, const void *flat_params, void *mirror, 
     LDIT_TRY(launch_cvt_bf16(static_cast<const float *>(flat_params), mirror, n, static_cast<hipStream_t>(stream)));
     if (cfg->dtype != LDIT_MXFP8) return LDIT_OK;
     // mxfp8: each layer's matrices re-made as ldit_pack_weights(LDIT_MXFP8) makes them (codes + scales, q third folded) with their
-    // dequantised codes in the bf16 part, and the folded q|k|v bias - the AdamW-MX pass without the update
-    return mx_layers(g, const_cast<float *>(static_cast<const float *>(flat_params)), nullptr, nullptr, nullptr, false, 0.f, 0.f, 0.f,
-                     0.f, 0.f, 0, 1.0f, mirror, static_cast<hipStream_t>(stream));
+    // dequantised codes in the bf16 part, and the folded q|k|v bias - one launch for all layers
+    return mx_requant_all_layers(g, static_cast<const float *>(flat_params), mirror, /*state*/ nullptr, static_cast<hipStream_t>(stream));
 }
 
 int ldit_adamw_step_mxfp8(const ldit_cfg *cfg, void *params, const void *grads, void *exp_avg, void *exp_avg_sq, float lr, float beta1,
@@ -521,7 +504,7 @@ int ldit_adamw_step_mxfp8(const ldit_cfg *cfg, void *params, const void *grads, 
     // ldit_adamw_step over the whole block (its bf16 mirror = the embeddings' operands), then every layer's matrices re-quantised
     // from the updated master: the codes, scales, folded bias and dequantised copies a fresh ldit_pack_train would make
     LDIT_TRY(launch_adamw(p, gr, m, v, packed_map(g, LDIT_F32).total / 4, lr, beta1, beta2, eps, weight_decay, step, grad_scale, mirror, stream));
-    return mx_layers(g, p, nullptr, nullptr, nullptr, false, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 1.0f, mirror, stream);
+    return mx_requant_all_layers(g, p, mirror, /*state*/ nullptr, stream);
 }
 
 int ldit_requant_train_mirror(const ldit_cfg *cfg, const void *flat_params, void *mirror, size_t mirror_bytes, const ldit_opt_state *state,

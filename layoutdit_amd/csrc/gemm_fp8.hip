@@ -2,10 +2,9 @@
 // A8, W8 fp8 e4m3 (K-contiguous), fp32 accumulate.  Groundwork for BASELINE configs[4] (fp8 forward).
 //
 // Same skeleton as gemm_bf16.hip: K-contiguous operands -> LDS by LDS-DMA, 128-B LDS rows (128 fp8), 16-B chunk
-// XOR-swizzled with (row>>1)&7, two stages, 2 x 4 waves (two per SIMD) on a 256 x 256 tile.  A lane's b128 fragment read
-// holds 16 consecutive fp8 of its row: the low 8 bytes feed one v_mfma_f32_32x32x16_fp8_fp8, the high 8 bytes the next
-// (a permutation of the k order applied identically to both operands), so each LDS read pays for two MFMAs.
-// The non-scaled fp8 MFMA issues at the bf16 rate; what fp8 buys here is half the DMA / LDS bytes per FLOP.
+// XOR-swizzled with (row>>1)&7, two stages, 2 x 4 waves (two per SIMD) on a 256 x 256 tile.  The MFMA is
+// v_mfma_f32_32x32x64_f8f6f4 with e4m3 operands (2x the bf16 rate, half the DMA / LDS bytes per FLOP): a lane's operand is 32
+// consecutive fp8 of its row, two b128 fragment reads, two chunk steps per 128-deep k-tile.
 // Epilogues: bias -> bf16 ; bias + erf-GELU -> fp8 (times out_inv_scale, saturated to +-448) ; R + lam (.) (.) -> fp32.
 #include <cstdlib>
 #include <type_traits>
@@ -18,7 +17,6 @@ namespace ldit {
 
 namespace {
 
-typedef long i64x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_8 __attribute__((ext_vector_type(4)));
@@ -206,10 +204,9 @@ __device__ __forceinline__ void store_q(const PA &p, const f32x16 (&acc)[TM][TN]
     }
 }
 
-// K64 = false: v_mfma_f32_32x32x16_fp8_fp8 (bf16 rate), two per b128 fragment read, four chunk steps per k-tile.
-// K64 = true : v_mfma_f32_32x32x64_f8f6f4 with e4m3 operands and unit block scales (2x the bf16 rate): a lane's operand is
+// MX = false: v_mfma_f32_32x32x64_f8f6f4 with e4m3 operands and unit block scales (2x the bf16 rate): a lane's operand is
 //              32 consecutive fp8 of its row (two b128 reads), two chunk steps per k-tile.
-// MX = true (K64 only): the same MFMA with VGPR block scales (v_mfma_scale_f32_32x32x64_f8f6f4 ..., vS, vT).  The instruction's
+// MX = true : the same MFMA with VGPR block scales (v_mfma_scale_f32_32x32x64_f8f6f4 ..., vS, vT).  The instruction's
 //              scale block b of a 64-deep step is the b-th 16 bytes of BOTH lane halves, and lane half b supplies its scale: a lane
 //              therefore takes 16-B chunks h and 2 + h of the step (not 2 h, 2 h + 1), block b is then the row's 32 consecutive
 //              bytes 64 c + 32 b, and lane half h's scale is byte 2 c + h of the row's k-tile dword - the dword shifted right by
@@ -217,10 +214,10 @@ __device__ __forceinline__ void store_q(const PA &p, const f32x16 (&acc)[TM][TN]
 //              barrier one iteration ahead (asm loads in front of that iteration's DMA pieces, so that the counted wait at the end
 //              of the iteration lets the DMA stay in flight), the per-tensor instantiations are unchanged.
 // TR = true (MX only): the mxfp8 train step's epilogues; such an instantiation takes GemmArgs8T, every other one GemmArgs8.
-template <int WM, int WN, int TM, int TN, int EPI, bool K64, bool MX = false, bool TR = false>
+template <int WM, int WN, int TM, int TN, int EPI, bool MX = false, bool TR = false>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(const std::conditional_t<TR, GemmArgs8T, GemmArgs8> p)
 {
-    static_assert(!TR || (MX && K64), "the train epilogues exist on the MX kernels only");
+    static_assert(!TR || MX, "the train epilogues exist on the MX kernels only");
     constexpr int NWAVES = WM * WN;
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, ROWS = BM + BN, NLD = ROWS / (8 * NWAVES);
     static_assert(ROWS % (8 * NWAVES) == 0 && BM % 8 == 0, "DMA pieces must split evenly over the waves");
@@ -280,203 +277,154 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
     const int nk = p.K / BKE;
     const int a_row = (wm * TM * 32 + c32) * ROW8, b_row = (BM + wn * TN * 32 + c32) * ROW8;
 
-    if constexpr (!K64) {
-        auto load_frags = [&](int stage, int c, i64x2(&xa)[TM], i64x2(&wb)[TN]) {
-            const char *base = smem + stage * (ROWS * ROW8) + ((c * 2 + h) ^ sw) * 16;
+    // MX: sx / sw = the scale dwords of tile kt (shifted: byte 0 = block h, byte 2 = block 2 + h), nx / nw_ = tile kt + 1 in flight
+    unsigned xo[MX ? TM : 1], wo[MX ? TN : 1], sx[MX ? TM : 1], sw_[MX ? TN : 1], nx[MX ? TM : 1], nw_[MX ? TN : 1];
+    const unsigned sh = 8u * (unsigned)h;
+    if constexpr (MX) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) xa[i] = *reinterpret_cast<const i64x2 *>(base + a_row + i * 32 * ROW8);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) wb[j] = *reinterpret_cast<const i64x2 *>(base + b_row + j * 32 * ROW8);
-        };
-        auto mfma_chunk = [&](const i64x2(&xa)[TM], const i64x2(&wb)[TN]) {
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(wb[j][half], xa[i][half], acc[i][j], 0, 0, 0);
-        };
-        i64x2 xa0[TM], wb0[TN], xa1[TM], wb1[TN];
-        issue(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // explicit: the first tile has landed before anybody reads it
-        __syncthreads();
-        load_frags(0, 0, xa0, wb0);
-        // (round 4: the order reads | MFMAs is pinned with sched_barrier - left alone, the scheduler sinks a chunk's reads behind its
-        //  MFMAs, right in front of the wait that needs them: profiles/r04_tr_pinned_order_ab.txt, same finding as gemm_bf16_tr)
-        for (int kt = 0; kt < nk; ++kt) {
-            const int cur = kt & 1;
-            const int knext = (kt + 1 < nk ? kt + 1 : nk - 1) * BKE;
-            load_frags(cur, 1, xa1, wb1);
-            __builtin_amdgcn_sched_barrier(0);
-            issue(cur ^ 1, knext);
-            mfma_chunk(xa0, wb0);
-            __builtin_amdgcn_sched_barrier(0);
-            load_frags(cur, 2, xa0, wb0);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(xa1, wb1);
-            __builtin_amdgcn_sched_barrier(0);
-            load_frags(cur, 3, xa1, wb1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(xa0, wb0);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // explicit: do not rely on hipcc to drain the LDS-DMA in front of the barrier
-            __syncthreads();   // hand-over: tile kt+1 landed in every wave, stage cur released
-            load_frags(cur ^ 1, 0, xa0, wb0);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_chunk(xa1, wb1);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int i = 0; i < TM; ++i) {
+            const int r = m0 + wm * TM * 32 + i * 32 + c32;
+            xo[i] = (unsigned)(r < p.M ? r : p.M - 1) * (unsigned)p.ldas;
         }
-    } else {
-        // MX: sx / sw = the scale dwords of tile kt (shifted: byte 0 = block h, byte 2 = block 2 + h), nx / nw_ = tile kt + 1 in flight
-        unsigned xo[MX ? TM : 1], wo[MX ? TN : 1], sx[MX ? TM : 1], sw_[MX ? TN : 1], nx[MX ? TM : 1], nw_[MX ? TN : 1];
-        const unsigned sh = 8u * (unsigned)h;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int r = n0 + wn * TN * 32 + j * 32 + c32;
+            wo[j] = (unsigned)(r < p.N ? r : p.N - 1) * (unsigned)p.ldws;
+        }
+    }
+    // (hand-counted like the DMA: hipcc cannot see these loads, the registers are read only behind an explicit vmcnt wait
+    //  that names them - `landed`)
+    auto fetch_scales = [&](unsigned(&dx)[MX ? TM : 1], unsigned(&dw)[MX ? TN : 1], int kt) {
+        if constexpr (MX) {
+            const unsigned char *xb = p.As + 4 * kt, *wbs = p.Ws + 4 * kt;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) asm volatile("global_load_dword %0, %1, %2" : "=v"(dx[i]) : "v"(xo[i]), "s"(xb) : "memory");
+#pragma unroll
+            for (int j = 0; j < TN; ++j) asm volatile("global_load_dword %0, %1, %2" : "=v"(dw[j]) : "v"(wo[j]), "s"(wbs) : "memory");
+        }
+    };
+    auto landed = [&](unsigned(&dx)[MX ? TM : 1], unsigned(&dw)[MX ? TN : 1]) {   // behind a vmcnt that covers them
         if constexpr (MX) {
 #pragma unroll
+            for (int i = 0; i < TM; ++i) { asm volatile("" : "+v"(dx[i])); sx[i] = dx[i] >> sh; }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) { asm volatile("" : "+v"(dw[j])); sw_[j] = dw[j] >> sh; }
+        }
+    };
+    auto mfma_chunk = [&](const i32x8(&xa)[TM], const i32x8(&wb)[TN], auto chunk) {
+        constexpr int OPS = 2 * decltype(chunk)::value;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                if constexpr (MX)
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, OPS, (int)sw_[j], OPS, (int)sx[i]);
+                else
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, 0, 0, 0);
+            }
+    };
+    const std::integral_constant<int, 0> chunk0{};
+    const std::integral_constant<int, 1> chunk1{};
+    i32x8 xa0[TM], wb0[TN], xa1[TM], wb1[TN];
+    // Round 3: the DMA of tile kt+2 is issued right BEHIND the hand-over barrier of iteration kt (stage `cur` is free there:
+    // every wave's last fragments of tile kt are in registers) and waited for at the NEXT hand-over - a whole k-tile of MFMA
+    // time (2048 cycles per SIMD) to land.  Rounds 1-2 issued tile kt+1 at the top of iteration kt and waited for it half a
+    // k-tile later: shorter than an L2 / Infinity-Cache round trip under load, so every k-tile stalled on its own DMA.
+    // Round 4: the order reads | DMA pieces | MFMAs | wait is PINNED (sched_barrier), and for that every fragment read is an asm
+    // statement waited for by hand.  Left to hipcc, a chunk's reads sank behind its MFMAs - right in front of the wait that needs
+    // them, so the wait in front of the hand-over barrier and the first MFMA of the next chunk each sat out an LDS latency - and
+    // its own counted waits degenerated to lgkmcnt(0) right behind freshly issued reads (it cannot see across the asm DMA).
+    // The 320-row tile keeps hipcc's order: both fragment sets live at once (112 registers beside 160 of accumulators) do not
+    // fit, which is why the reads were sunk there in the first place.
+    constexpr bool PIN = TM < 5;
+    // fragment of rows r: chunks (4 c + 2 h) ^ sw and (4 c + 2 h + 1) ^ sw of the 128-byte row - the chunk index is an XOR of
+    // address bits 6 (c) and 4 (second half); every other term is a multiple of 128 bytes (aligned(128) stage memory)
+    // MX: the fragment of chunk c is 16-B chunks (4 c + h) ^ sw and (4 c + 2 + h) ^ sw instead - the instruction's block b of a
+    // 64-deep step is the b-th 16 bytes of BOTH lane halves, so that block b = the row's 32 consecutive bytes 64 c + 32 b
+    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)smem);
+    constexpr unsigned HI = MX ? 32u : 16u;
+    const int hc = MX ? h : 2 * h;
+    const unsigned fa0 = lds0 + a_row + ((hc ^ sw) << 4), fb0 = lds0 + b_row + ((hc ^ sw) << 4);
+    auto load_frags = [&](int stage, int c, i32x8(&xa)[TM], i32x8(&wb)[TN]) {
+        if constexpr (PIN) {
+            const unsigned so = (unsigned)(stage * (ROWS * ROW8));
+            const unsigned a_lo = (fa0 + so) ^ (unsigned)(c << 6), a_hi = a_lo ^ HI, b_lo = (fb0 + so) ^ (unsigned)(c << 6), b_hi = b_lo ^ HI;
+#pragma unroll
             for (int i = 0; i < TM; ++i) {
-                const int r = m0 + wm * TM * 32 + i * 32 + c32;
-                xo[i] = (unsigned)(r < p.M ? r : p.M - 1) * (unsigned)p.ldas;
+                union { i32x4 v[2]; i32x8 f; } u;
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[0]) : "v"(a_lo), "n"(i * 32 * ROW8));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[1]) : "v"(a_hi), "n"(i * 32 * ROW8));
+                xa[i] = u.f;
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const int r = n0 + wn * TN * 32 + j * 32 + c32;
-                wo[j] = (unsigned)(r < p.N ? r : p.N - 1) * (unsigned)p.ldws;
+                union { i32x4 v[2]; i32x8 f; } u;
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[0]) : "v"(b_lo), "n"(j * 32 * ROW8));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[1]) : "v"(b_hi), "n"(j * 32 * ROW8));
+                wb[j] = u.f;
+            }
+        } else {
+            const char *base = smem + stage * (ROWS * ROW8);
+            const int o0 = MX ? ((4 * c + h) ^ sw) * 16 : ((4 * c + 2 * h) ^ sw) * 16;
+            const int o1 = MX ? ((4 * c + 2 + h) ^ sw) * 16 : ((4 * c + 2 * h + 1) ^ sw) * 16;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const i32x4 lo = *reinterpret_cast<const i32x4 *>(base + a_row + i * 32 * ROW8 + o0);
+                const i32x4 hi = *reinterpret_cast<const i32x4 *>(base + a_row + i * 32 * ROW8 + o1);
+                xa[i] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const i32x4 lo = *reinterpret_cast<const i32x4 *>(base + b_row + j * 32 * ROW8 + o0);
+                const i32x4 hi = *reinterpret_cast<const i32x4 *>(base + b_row + j * 32 * ROW8 + o1);
+                wb[j] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
         }
-        // (hand-counted like the DMA: hipcc cannot see these loads, the registers are read only behind an explicit vmcnt wait
-        //  that names them - `landed`)
-        auto fetch_scales = [&](unsigned(&dx)[MX ? TM : 1], unsigned(&dw)[MX ? TN : 1], int kt) {
-            if constexpr (MX) {
-                const unsigned char *xb = p.As + 4 * kt, *wbs = p.Ws + 4 * kt;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) asm volatile("global_load_dword %0, %1, %2" : "=v"(dx[i]) : "v"(xo[i]), "s"(xb) : "memory");
-#pragma unroll
-                for (int j = 0; j < TN; ++j) asm volatile("global_load_dword %0, %1, %2" : "=v"(dw[j]) : "v"(wo[j]), "s"(wbs) : "memory");
-            }
-        };
-        auto landed = [&](unsigned(&dx)[MX ? TM : 1], unsigned(&dw)[MX ? TN : 1]) {   // behind a vmcnt that covers them
-            if constexpr (MX) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) { asm volatile("" : "+v"(dx[i])); sx[i] = dx[i] >> sh; }
-#pragma unroll
-                for (int j = 0; j < TN; ++j) { asm volatile("" : "+v"(dw[j])); sw_[j] = dw[j] >> sh; }
-            }
-        };
-        auto mfma_chunk = [&](const i32x8(&xa)[TM], const i32x8(&wb)[TN], auto chunk) {
-            constexpr int OPS = 2 * decltype(chunk)::value;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if constexpr (MX)
-                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, OPS, (int)sw_[j], OPS, (int)sx[i]);
-                    else
-                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wb[j], xa[i], acc[i][j], 0, 0, 0, 0, 0, 0);
-                }
-        };
-        const std::integral_constant<int, 0> chunk0{};
-        const std::integral_constant<int, 1> chunk1{};
-        i32x8 xa0[TM], wb0[TN], xa1[TM], wb1[TN];
-        // Round 3: the DMA of tile kt+2 is issued right BEHIND the hand-over barrier of iteration kt (stage `cur` is free there:
-        // every wave's last fragments of tile kt are in registers) and waited for at the NEXT hand-over - a whole k-tile of MFMA
-        // time (2048 cycles per SIMD) to land.  Rounds 1-2 issued tile kt+1 at the top of iteration kt and waited for it half a
-        // k-tile later: shorter than an L2 / Infinity-Cache round trip under load, so every k-tile stalled on its own DMA.
-        // Round 4: the order reads | DMA pieces | MFMAs | wait is PINNED (sched_barrier), and for that every fragment read is an asm
-        // statement waited for by hand.  Left to hipcc, a chunk's reads sank behind its MFMAs - right in front of the wait that needs
-        // them, so the wait in front of the hand-over barrier and the first MFMA of the next chunk each sat out an LDS latency - and
-        // its own counted waits degenerated to lgkmcnt(0) right behind freshly issued reads (it cannot see across the asm DMA).
-        // The 320-row tile keeps hipcc's order: both fragment sets live at once (112 registers beside 160 of accumulators) do not
-        // fit, which is why the reads were sunk there in the first place.
-        constexpr bool PIN = TM < 5;
-        // fragment of rows r: chunks (4 c + 2 h) ^ sw and (4 c + 2 h + 1) ^ sw of the 128-byte row - the chunk index is an XOR of
-        // address bits 6 (c) and 4 (second half); every other term is a multiple of 128 bytes (aligned(128) stage memory)
-        // MX: the fragment of chunk c is 16-B chunks (4 c + h) ^ sw and (4 c + 2 + h) ^ sw instead - the instruction's block b of a
-        // 64-deep step is the b-th 16 bytes of BOTH lane halves, so that block b = the row's 32 consecutive bytes 64 c + 32 b
-        const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)smem);
-        constexpr unsigned HI = MX ? 32u : 16u;
-        const int hc = MX ? h : 2 * h;
-        const unsigned fa0 = lds0 + a_row + ((hc ^ sw) << 4), fb0 = lds0 + b_row + ((hc ^ sw) << 4);
-        auto load_frags = [&](int stage, int c, i32x8(&xa)[TM], i32x8(&wb)[TN]) {
-            if constexpr (PIN) {
-                const unsigned so = (unsigned)(stage * (ROWS * ROW8));
-                const unsigned a_lo = (fa0 + so) ^ (unsigned)(c << 6), a_hi = a_lo ^ HI, b_lo = (fb0 + so) ^ (unsigned)(c << 6), b_hi = b_lo ^ HI;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    union { i32x4 v[2]; i32x8 f; } u;
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[0]) : "v"(a_lo), "n"(i * 32 * ROW8));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[1]) : "v"(a_hi), "n"(i * 32 * ROW8));
-                    xa[i] = u.f;
-                }
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    union { i32x4 v[2]; i32x8 f; } u;
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[0]) : "v"(b_lo), "n"(j * 32 * ROW8));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(u.v[1]) : "v"(b_hi), "n"(j * 32 * ROW8));
-                    wb[j] = u.f;
-                }
-            } else {
-                const char *base = smem + stage * (ROWS * ROW8);
-                const int o0 = MX ? ((4 * c + h) ^ sw) * 16 : ((4 * c + 2 * h) ^ sw) * 16;
-                const int o1 = MX ? ((4 * c + 2 + h) ^ sw) * 16 : ((4 * c + 2 * h + 1) ^ sw) * 16;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const i32x4 lo = *reinterpret_cast<const i32x4 *>(base + a_row + i * 32 * ROW8 + o0);
-                    const i32x4 hi = *reinterpret_cast<const i32x4 *>(base + a_row + i * 32 * ROW8 + o1);
-                    xa[i] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const i32x4 lo = *reinterpret_cast<const i32x4 *>(base + b_row + j * 32 * ROW8 + o0);
-                    const i32x4 hi = *reinterpret_cast<const i32x4 *>(base + b_row + j * 32 * ROW8 + o1);
-                    wb[j] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-            }
-        };
-        // (PIN: every group below is fenced; else the fences and hand waits for the reads drop out and hipcc orders / waits as before)
-        auto fence = [&]() { if constexpr (PIN) __builtin_amdgcn_sched_barrier(0); };
-        auto reads_done = [&]() { if constexpr (PIN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-        if constexpr (MX) fetch_scales(nx, nw_, 0);
-        issue(0, 0);
-        issue(1, (nk > 1 ? 1 : 0) * BKE);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");      // tile 0 landed; tile 1's NLD pieces stay in flight
-        landed(nx, nw_);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        load_frags(0, 0, xa0, wb0);
-        reads_done();
+    };
+    // (PIN: every group below is fenced; else the fences and hand waits for the reads drop out and hipcc orders / waits as before)
+    auto fence = [&]() { if constexpr (PIN) __builtin_amdgcn_sched_barrier(0); };
+    auto reads_done = [&]() { if constexpr (PIN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
+    if constexpr (MX) fetch_scales(nx, nw_, 0);
+    issue(0, 0);
+    issue(1, (nk > 1 ? 1 : 0) * BKE);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");      // tile 0 landed; tile 1's NLD pieces stay in flight
+    landed(nx, nw_);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    load_frags(0, 0, xa0, wb0);
+    reads_done();
+    fence();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int cur = kt & 1;
+        const int k2 = (kt + 2 < nk ? kt + 2 : nk - 1) * BKE;
+        load_frags(cur, 1, xa1, wb1);
         fence();
-        for (int kt = 0; kt < nk; ++kt) {
-            const int cur = kt & 1;
-            const int k2 = (kt + 2 < nk ? kt + 2 : nk - 1) * BKE;
-            load_frags(cur, 1, xa1, wb1);
+        mfma_chunk(xa0, wb0, chunk0);
+        fence();
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // tile kt+1 landed; own reads of stage cur retired
+        __builtin_amdgcn_s_barrier();   // hand-over: tile kt+1 visible to every wave, stage cur released
+        asm volatile("" ::: "memory");
+        fence();
+        if constexpr (PIN) {
+            load_frags(cur ^ 1, 0, xa0, wb0);
             fence();
-            mfma_chunk(xa0, wb0, chunk0);
-            fence();
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // tile kt+1 landed; own reads of stage cur retired
-            __builtin_amdgcn_s_barrier();   // hand-over: tile kt+1 visible to every wave, stage cur released
-            asm volatile("" ::: "memory");
-            fence();
-            if constexpr (PIN) {
-                load_frags(cur ^ 1, 0, xa0, wb0);
-                fence();
-                if constexpr (MX) fetch_scales(nx, nw_, kt + 1 < nk ? kt + 1 : nk - 1);
-                issue(cur, k2);             // tile kt+2 -> stage cur (a clamped re-fetch on the last two iterations, never read)
-            } else {
-                if constexpr (MX) fetch_scales(nx, nw_, kt + 1 < nk ? kt + 1 : nk - 1);
-                issue(cur, k2);
-                load_frags(cur ^ 1, 0, xa0, wb0);
-            }
-            mfma_chunk(xa1, wb1, chunk1);
-            fence();
-            reads_done();
-            if constexpr (MX) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");   // tile kt+1's scales; tile kt+2's pieces stay in flight
-                landed(nx, nw_);
-            }
-            fence();
+            if constexpr (MX) fetch_scales(nx, nw_, kt + 1 < nk ? kt + 1 : nk - 1);
+            issue(cur, k2);             // tile kt+2 -> stage cur (a clamped re-fetch on the last two iterations, never read)
+        } else {
+            if constexpr (MX) fetch_scales(nx, nw_, kt + 1 < nk ? kt + 1 : nk - 1);
+            issue(cur, k2);
+            load_frags(cur ^ 1, 0, xa0, wb0);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-fetches must not outlive the LDS allocation
+        mfma_chunk(xa1, wb1, chunk1);
+        fence();
+        reads_done();
+        if constexpr (MX) {
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");   // tile kt+1's scales; tile kt+2's pieces stay in flight
+            landed(nx, nw_);
+        }
+        fence();
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-fetches must not outlive the LDS allocation
 
     const bool cols_in = (n0 + BN <= p.N) && ((p.ldy & 3) == 0);
     const int mw = m0 + wm * TM * 32, nw = n0 + wn * TN * 32;
@@ -494,13 +442,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN) / 4) gemm_fp8_mfma(con
     else store_q<TM, TN, EPI, 2, MX>(p, acc, mw, nw, lane);
 }
 
-template <int WM, int WN, int TM, int TN, int EPI, bool K64, bool MX, typename PA>
+template <int WM, int WN, int TM, int TN, int EPI, bool MX, typename PA>
 int launch_q(const PA &a, hipStream_t stream)
 {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int lds = 2 * (BM + BN) * ROW8;
     const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    auto kern = gemm_fp8_mfma<WM, WN, TM, TN, EPI, K64, MX, is_train_v<PA>>;
+    auto kern = gemm_fp8_mfma<WM, WN, TM, TN, EPI, MX, is_train_v<PA>>;
     LDIT_DYN_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(64 * WM * WN), lds, stream, a);
     LDIT_HIP_CHECK(hipGetLastError());
@@ -587,10 +535,7 @@ int launch_qtail(const PA &a, hipStream_t stream)
 template <int EPI, bool MX, typename PA>
 int launch_q_tiled(const PA &a, hipStream_t stream)
 {
-    // LDIT_GEMM_FP8_K16=1 selects the K = 16 MFMA, LDIT_GEMM_FP8_TILE=0..2 forces a tile (both for experiments / tests)
-    // (MX: the K = 16 MFMA has no block scales - the switch does not apply)
-    const bool k16 = !MX && diag().fp8_k16, noskinny = diag().fp8_noskinny;
-    if (a.M <= 64 && !noskinny && !k16) return launch_qtail<EPI, MX>(a, stream);     // peeled tail / tiny batch (bit-identical to the K = 64 tiles)
+    if (a.M <= 64) return launch_qtail<EPI, MX>(a, stream);     // peeled tail / tiny batch (bit-identical to the tiles)
     // Time model fitted to scripts/gemm_fp8_bench.py on ViT-B / ViT-L shapes, M = 3 k .. 25 k (profiles/README.md), in us:
     //   256 x 256 (one workgroup per CU):  strict rounds of 256 tiles, each  a[epi] + 11.3e-3 K
     //   128 x 128 (two per CU, they overlap each other's prologue / epilogue):  rounds of 256 tiles, each  r[epi] + 4.25e-3 K,
@@ -610,23 +555,14 @@ int launch_q_tiled(const PA &a, hipStream_t stream)
         const double c = (double)((t + 255) / 256) * per256 * (bm / 256.0) * 1.03;
         if (c < best) { best = c; pick = bm == 192 ? 3 : 4; }
     }
-    if (const int force = diag().fp8_tile; force >= 0 && force <= 4) pick = force;
-    // pick -> tile.  The 192- and 320-row tiles exist for the K = 64 MFMA only, the 320-row one not with the residual epilogue (above):
-    // where a tile does not exist, 256 x 256 stands in.
-    auto launch = [&](auto k64) {
-        constexpr bool K64 = decltype(k64)::value;
-        if constexpr (K64) {
-            if (pick == 3) return launch_q<2, 4, 3, 2, EPI, K64, MX>(a, stream);       // 192 x 256
-            if constexpr (EPI != EPI_SCALE_RESID)
-                if (pick == 4) return launch_q<2, 4, 5, 2, EPI, K64, MX>(a, stream);   // 320 x 256
-        }
-        if (pick == 1) return launch_q<2, 2, 4, 2, EPI, K64, MX>(a, stream);           // 256 x 128, 4 waves
-        if (pick == 2) return launch_q<2, 2, 2, 2, EPI, K64, MX>(a, stream);           // 128 x 128, 4 waves
-        return launch_q<2, 4, 4, 2, EPI, K64, MX>(a, stream);                          // 256 x 256, 8 waves
-    };
-    if constexpr (!MX)
-        if (k16) return launch(std::false_type{});
-    return launch(std::true_type{});
+    if (const int force = diag().fp8_tile; force >= 0 && force <= 4) pick = force;      // LDIT_GEMM_FP8_TILE=0..4 (experiments / tests)
+    // pick -> tile.  The 320-row tile does not exist with the residual epilogue (above): 256 x 256 stands in.
+    if (pick == 3) return launch_q<2, 4, 3, 2, EPI, MX>(a, stream);       // 192 x 256
+    if constexpr (EPI != EPI_SCALE_RESID)
+        if (pick == 4) return launch_q<2, 4, 5, 2, EPI, MX>(a, stream);   // 320 x 256
+    if (pick == 1) return launch_q<2, 2, 4, 2, EPI, MX>(a, stream);       // 256 x 128, 4 waves
+    if (pick == 2) return launch_q<2, 2, 2, 2, EPI, MX>(a, stream);       // 128 x 128, 4 waves
+    return launch_q<2, 4, 4, 2, EPI, MX>(a, stream);                      // 256 x 256, 8 waves
 }
 
 // ---- host side of the three launchers (at the end of the file) ------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// fp32 MFMA GEMM, "panel" tiling:  Y[M,N] = epi( A[M,K] . W[N,K]^T ), block tile (32*T32 + 16*HALF) x 128,
+// fp32 MFMA GEMM, "panel" tiling:  Y[M,N] = epi( A[M,K] . W[N,K]^T ), block tile (32*T32 + 16) x 128,
 // four waves side by side along N, each owning the full block height x 32 columns.
 //
 // Why a second kernel next to gemm_f32.hip: there every SIMD owns whole 32x32 output tiles and the block height is a
@@ -15,8 +15,7 @@
 //     position add) runs on float4 and stores 16 B per lane - 4x fewer memory instructions than gemm_f32.hip.
 //   * K-contiguous operands -> LDS by LDS-DMA, 128-B rows, 16-B chunk XOR-swizzled with (row>>1)&7 on the source address
 //     and on the read: the b128 reads of the nine 32-row tiles are conflict-free; the scalar reads of the 16-row remainder
-//     are 4-way conflicted (41 % of the LDS-active cycles) but off the critical path - see load_frags for the measured
-//     conflict-free alternative and why it is not the default.
+//     are 4-way conflicted (41 % of the LDS-active cycles) but off the critical path - see load_frags.
 //   * 8-deep chunks: a 32-row tile lane (r, h) reads k = 8c+4h..+3 (b128), MFMA step s uses k-pair {s, 4+s};
 //     a 16-row tile lane (r, q) reads k = 8c+4(q&1)+(q>>1) and +2, so its two 16x16x4 steps add k0,k4,k1,k5 | k2,k6,k3,k7:
 //     the same product order as the 32x32x2 steps - results are bit-identical across the two shapes.
@@ -32,8 +31,6 @@
 //     turns into stragglers.  Kept selectable as evidence.
 //   * exact fp32: every output element is one fma chain over k in one fixed order, the same for both MFMA shapes, so a
 //     row's result does not depend on where in a block or batch it sits (tests/test_gpu_forward.py checks bit equality).
-#include <cstdlib>
-
 #include "ldit_common.h"
 #include "lds_dma.h"
 
@@ -88,7 +85,7 @@ __device__ __forceinline__ void emit4(const GemmArgs &p, int m, int n, f32x4 acc
 }
 
 template <int MODE>
-__device__ __forceinline__ f32x4 load4(const GemmArgs &p, const float *base, int m, int n, bool row_major_out)
+__device__ __forceinline__ f32x4 load4(const GemmArgs &p, const float *base, int m, int n)
 {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (MODE == 1 || (MODE == 2 && m < p.M)) return *reinterpret_cast<const f32x4 *>(base + ((unsigned)m * (unsigned)p.ldy + (unsigned)n));
@@ -97,7 +94,6 @@ __device__ __forceinline__ f32x4 load4(const GemmArgs &p, const float *base, int
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             if (n + r < p.N) v[r] = base[(unsigned)m * (unsigned)p.ldy + (unsigned)(n + r)];
-    (void)row_major_out;
     return v;
 }
 
@@ -117,7 +113,7 @@ __device__ __forceinline__ f32x4 vec4(const float *v, int n, int N)
 // nw + 8g + 4h .. +3.  16-row remainder, lane (c = lane&15, q = lane>>4): row m0+32*T32+c, tile it holds nw+16it+4q..+3.
 // The residual quads of the next tile are fetched before the current tile is stored (R may alias Y: fenced so that
 // hipcc neither hoists all loads to the top nor serialises them - see gemm_f32.hip).
-template <int T32, bool HALF, int EPI, int VEC, bool DUAL>
+template <int T32, int EPI, int VEC, bool DUAL>
 __device__ __forceinline__ void store_panel(const GemmArgs &p, const f32x16 (&acc32)[T32], const f32x4 (&acc16)[2], int m0,
                                             int nw, int lane)
 {
@@ -133,9 +129,9 @@ __device__ __forceinline__ void store_panel(const GemmArgs &p, const f32x16 (&ac
     }
     auto fetch = [&](int t, f32x4(&dst)[4]) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) dst[g] = load4<VEC>(p, p.R, m0 + 32 * t + c32, nw + 8 * g + 4 * h, true);
+        for (int g = 0; g < 4; ++g) dst[g] = load4<VEC>(p, p.R, m0 + 32 * t + c32, nw + 8 * g + 4 * h);
     };
-    if constexpr (EPI == EPI_SCALE_RESID && VEC == 1 && T32 > 0) {
+    if constexpr (EPI == EPI_SCALE_RESID && VEC == 1) {
         // Interior tile (round 4): EVERY residual quad of the wave tile is fetched before the first store, waited for once, and the
         // stores then go out back to back.  The tile-ahead pipeline below left an s_waitcnt vmcnt(0) in front of every 32-row tile's
         // stores (nine per wave tile) - and vmcnt counts stores: each of them sat out the acknowledgement of the previous tile's
@@ -145,19 +141,17 @@ __device__ __forceinline__ void store_panel(const GemmArgs &p, const f32x16 (&ac
         f32x4 ra[T32][4], rh[2], bh[2], lh[2];
 #pragma unroll
         for (int t = 0; t < T32; ++t) fetch(t, ra[t]);
-        if (HALF) {
 #pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                rh[it] = load4<VEC>(p, p.R, m0 + 32 * T32 + c16, nw + 16 * it + 4 * q, true);
-                bh[it] = vec4<VEC>(p.bias, nw + 16 * it + 4 * q, p.N);      // (the remainder's bias / lambda quads too: a load behind the
-                lh[it] = vec4<VEC>(p.lam, nw + 16 * it + 4 * q, p.N);       //  stores would wait for every one of them)
-            }
+        for (int it = 0; it < 2; ++it) {
+            rh[it] = load4<VEC>(p, p.R, m0 + 32 * T32 + c16, nw + 16 * it + 4 * q);
+            bh[it] = vec4<VEC>(p.bias, nw + 16 * it + 4 * q, p.N);      // (the remainder's bias / lambda quads too: a load behind the
+            lh[it] = vec4<VEC>(p.lam, nw + 16 * it + 4 * q, p.N);       //  stores would wait for every one of them)
         }
 #pragma unroll
         for (int t = 0; t < T32; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(ra[t][g]));      // hipcc waits here, once, and knows of no pending load below
-        if (HALF) asm volatile("" : "+v"(rh[0]), "+v"(rh[1]), "+v"(bh[0]), "+v"(bh[1]), "+v"(lh[0]), "+v"(lh[1]));
+        asm volatile("" : "+v"(rh[0]), "+v"(rh[1]), "+v"(bh[0]), "+v"(bh[1]), "+v"(lh[0]), "+v"(lh[1]));
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int t = 0; t < T32; ++t)
@@ -166,17 +160,15 @@ __device__ __forceinline__ void store_panel(const GemmArgs &p, const f32x16 (&ac
                 const f32x4 a = {acc32[t][4 * g + 0], acc32[t][4 * g + 1], acc32[t][4 * g + 2], acc32[t][4 * g + 3]};
                 emit4<EPI, VEC, DUAL>(p, m0 + 32 * t + c32, nw + 8 * g + 4 * h, a, bias32[g], lam32[g], ra[t][g]);
             }
-        if (HALF) {
-            const int m = m0 + 32 * T32 + c16;
+        const int m = m0 + 32 * T32 + c16;
 #pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int n = nw + 16 * it + 4 * q;
-                emit4<EPI, VEC, DUAL>(p, m, n, acc16[it], bh[it], lh[it], rh[it]);
-            }
+        for (int it = 0; it < 2; ++it) {
+            const int n = nw + 16 * it + 4 * q;
+            emit4<EPI, VEC, DUAL>(p, m, n, acc16[it], bh[it], lh[it], rh[it]);
         }
         return;
     }
-    if (EPI == EPI_SCALE_RESID && T32 > 0) fetch(0, res[0]);
+    if (EPI == EPI_SCALE_RESID) fetch(0, res[0]);
 #pragma unroll
     for (int t = 0; t < T32; ++t) {
         if (EPI == EPI_SCALE_RESID) {
@@ -190,22 +182,20 @@ __device__ __forceinline__ void store_panel(const GemmArgs &p, const f32x16 (&ac
         }
         if (EPI == EPI_SCALE_RESID) asm volatile("" ::: "memory");
     }
-    if (HALF) {
-        const int m = m0 + 32 * T32 + c16;
+    const int m = m0 + 32 * T32 + c16;
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int n = nw + 16 * it + 4 * q;
-            const f32x4 r = EPI == EPI_SCALE_RESID ? load4<VEC>(p, p.R, m, n, true) : zero;
-            const f32x4 l = EPI == EPI_SCALE_RESID ? vec4<VEC>(p.lam, n, p.N) : zero;
-            emit4<EPI, VEC, DUAL>(p, m, n, acc16[it], vec4<VEC>(p.bias, n, p.N), l, r);
-        }
+    for (int it = 0; it < 2; ++it) {
+        const int n = nw + 16 * it + 4 * q;
+        const f32x4 r = EPI == EPI_SCALE_RESID ? load4<VEC>(p, p.R, m, n) : zero;
+        const f32x4 l = EPI == EPI_SCALE_RESID ? vec4<VEC>(p.lam, n, p.N) : zero;
+        emit4<EPI, VEC, DUAL>(p, m, n, acc16[it], vec4<VEC>(p.bias, n, p.N), l, r);
     }
 }
 
-template <int T32, bool HALF, int EPI, int AMODE, bool R16VEC = true>
+template <int T32, int EPI, int AMODE>
 __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
 {
-    constexpr int BM = 32 * T32 + (HALF ? 16 : 0), BN = BNP, PIECES = (BM + BN) / 8, NLD = (PIECES + 3) / 4;
+    constexpr int BM = 32 * T32 + 16, BN = BNP, PIECES = (BM + BN) / 8, NLD = (PIECES + 3) / 4;
     constexpr int STAGE_BYTES = NLD * 4 * 1024;     // pieces past PIECES land in slack rows nobody reads
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -283,7 +273,7 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
         }
     };
 
-    f32x16 acc32[T32 > 0 ? T32 : 1];
+    f32x16 acc32[T32];
     f32x4 acc16[2];
 
     const int nk = p.K / BK;
@@ -293,7 +283,7 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
     const bool odd16 = (q >> 1) != 0;     // which two of the four k of its 16-B half-chunk this lane multiplies
 
     struct Frags {
-        f32x4 x32[T32 > 0 ? T32 : 1];
+        f32x4 x32[T32];
         f32x4 w32;
         f32x2 x16;
         f32x2 w16[2];
@@ -304,38 +294,21 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
 #pragma unroll
         for (int t = 0; t < T32; ++t) f.x32[t] = *reinterpret_cast<const f32x4 *>(b32 + x32_row + t * 32 * ROW_BYTES);
         f.w32 = *reinterpret_cast<const f32x4 *>(b32 + w32_row);
-        if (HALF) {
-            // lane (r, q), element s <- k = 8c + 4(q&1) + (q>>1) + 2s: the 16x16x4 steps then add the products in the
-            // order k0,k4,k1,k5 | k2,k6,k3,k7 - the order of the 32x32x2 steps above - so a row's result is bit-identical
-            // whichever tile shape it falls into (rows keep their values when the batch composition changes)
-            // Two ways to fetch the lane's two floats of its 16-B half-chunk:
-            //  * scalar ds_read_b32 (default): the 32 lanes of a half-wave land on 8 banks (every lane reads the same offset
-            //    inside its chunk) - a 4-way conflict on three reads per chunk, 41 % of SQ_LDS_IDX_ACTIVE in the PMC pass
-            //    (profiles/r01_final_pmc_summary.txt).  The LDS is idle ~85 % of a chunk's 2.4 k MFMA cycles, the reads are
-            //    issued a whole chunk ahead, so the conflict costs nothing measurable;
-            //  * R16VEC: whole half-chunk by ds_read_b128 (conflict-free under the (row>>1)&7 swizzle, like the 32-row reads:
-            //    SQ_LDS_BANK_CONFLICT = 0, profiles/r02_cfg1_vec_pmc_summary.txt) + a register select.  1.7 % SLOWER per layer
-            //    (12 more VGPRs live per chunk, 6 selects, 3x the LDS bytes) - kept selectable as evidence, not shipped.
-            const char *b16 = st + (((c * 2 + (q & 1)) ^ sw16) * 16);
-            if (R16VEC) {
-                const f32x4 xv = *reinterpret_cast<const f32x4 *>(b16 + x16_row);
-                const f32x4 w0 = *reinterpret_cast<const f32x4 *>(b16 + w16_row);
-                const f32x4 w1 = *reinterpret_cast<const f32x4 *>(b16 + w16_row + 16 * ROW_BYTES);
+        // The 16-row remainder.  Lane (r, q), element s <- k = 8c + 4(q&1) + (q>>1) + 2s: the 16x16x4 steps then add the products in
+        // the order k0,k4,k1,k5 | k2,k6,k3,k7 - the order of the 32x32x2 steps above - so a row's result is bit-identical whichever
+        // tile shape it falls into (rows keep their values when the batch composition changes).  The lane's two floats of its 16-B
+        // half-chunk are read by scalar ds_read_b32: the 32 lanes of a half-wave land on 8 banks (every lane reads the same offset
+        // inside its chunk) - a 4-way conflict on three reads per chunk, 41 % of SQ_LDS_IDX_ACTIVE (profiles/r01_final_pmc_summary.txt).
+        // It is off the critical path: the LDS is idle ~85 % of a chunk's 2.4 k MFMA cycles and the reads are issued a whole chunk
+        // ahead.  The conflict-free form (the whole half-chunk by ds_read_b128 + a register select) measured 1.7 % slower per layer
+        // (profiles/r02_cfg1_vec_pmc_summary.txt) and is retired.
+        const char *b16 = st + (((c * 2 + (q & 1)) ^ sw16) * 16);
+        const int o16 = odd16 ? 4 : 0;
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    f.x16[s] = odd16 ? xv[2 * s + 1] : xv[2 * s];
-                    f.w16[0][s] = odd16 ? w0[2 * s + 1] : w0[2 * s];
-                    f.w16[1][s] = odd16 ? w1[2 * s + 1] : w1[2 * s];
-                }
-            } else {        // LDIT_PANEL_R16=scalar: the round-1 scalar reads (4-way bank conflict), kept for A/B timing only
-                const int o16 = odd16 ? 4 : 0;
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    f.x16[s] = *reinterpret_cast<const float *>(b16 + x16_row + o16 + 8 * s);
-                    f.w16[0][s] = *reinterpret_cast<const float *>(b16 + w16_row + o16 + 8 * s);
-                    f.w16[1][s] = *reinterpret_cast<const float *>(b16 + w16_row + 16 * ROW_BYTES + o16 + 8 * s);
-                }
-            }
+        for (int s = 0; s < 2; ++s) {
+            f.x16[s] = *reinterpret_cast<const float *>(b16 + x16_row + o16 + 8 * s);
+            f.w16[0][s] = *reinterpret_cast<const float *>(b16 + w16_row + o16 + 8 * s);
+            f.w16[1][s] = *reinterpret_cast<const float *>(b16 + w16_row + 16 * ROW_BYTES + o16 + 8 * s);
         }
     };
     auto mfma_chunk = [&](const Frags &f) {
@@ -344,7 +317,7 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
 #pragma unroll
             for (int t = 0; t < T32; ++t)
                 acc32[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w32[s], f.x32[t][s], acc32[t], 0, 0, 0);
-            if (HALF && s < 2) {
+            if (s < 2) {
                 acc16[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w16[0][s], f.x16[s], acc16[0], 0, 0, 0);
                 acc16[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w16[1][s], f.x16[s], acc16[1], 0, 0, 0);
             }
@@ -352,8 +325,8 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
     };
 
     constexpr int SG_MFMA = 0x8, SG_VMEM = 0x20, SG_DSR = 0x100;
-    constexpr int NM = 4 * T32 + (HALF ? 4 : 0);          // MFMAs per 8-deep chunk
-    constexpr int NF = T32 + 1 + (HALF ? 3 : 0);          // LDS fragment reads per chunk (three b128 for the 16-row remainder)
+    constexpr int NM = 4 * T32 + 4;                       // MFMAs per 8-deep chunk
+    constexpr int NF = T32 + 1 + 3;                       // LDS fragment reads per chunk (three for the 16-row remainder)
     constexpr int MPD = (NM - NF) / NLD;                  // MFMAs per DMA piece in chunk 0 (0: tile too small)
     static_assert(NF <= NM, "fewer MFMAs than fragment reads in a chunk");
 
@@ -452,21 +425,21 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
     const int nw = en0 + wave * 32;
     const bool interior = cols_in && em0 + BM <= p.M;
     if (interior) {
-        if (p.Y2) store_panel<T32, HALF, EPI, 1, true>(p, acc32, acc16, em0, nw, lane);
-        else store_panel<T32, HALF, EPI, 1, false>(p, acc32, acc16, em0, nw, lane);
+        if (p.Y2) store_panel<T32, EPI, 1, true>(p, acc32, acc16, em0, nw, lane);
+        else store_panel<T32, EPI, 1, false>(p, acc32, acc16, em0, nw, lane);
     } else if (cols_in) {
-        if (p.Y2) store_panel<T32, HALF, EPI, 2, true>(p, acc32, acc16, em0, nw, lane);
-        else store_panel<T32, HALF, EPI, 2, false>(p, acc32, acc16, em0, nw, lane);
+        if (p.Y2) store_panel<T32, EPI, 2, true>(p, acc32, acc16, em0, nw, lane);
+        else store_panel<T32, EPI, 2, false>(p, acc32, acc16, em0, nw, lane);
     } else {
-        if (p.Y2) store_panel<T32, HALF, EPI, 0, true>(p, acc32, acc16, em0, nw, lane);
-        else store_panel<T32, HALF, EPI, 0, false>(p, acc32, acc16, em0, nw, lane);
+        if (p.Y2) store_panel<T32, EPI, 0, true>(p, acc32, acc16, em0, nw, lane);
+        else store_panel<T32, EPI, 0, false>(p, acc32, acc16, em0, nw, lane);
     }
     if (!more) break;
     // The next k-tile 0 must have landed before anybody reads it.  Vector-memory operations retire in issue order, and this wave
     // issued at least 4 T32 store instructions (one 16-B store per accumulator quad of the 32-row tiles; global stores cannot be
     // moved above the DMA, which reads global memory) AFTER its DMA pieces: "all but the youngest 4 T32 done" therefore covers every
     // piece while the tail of the stores stays in flight under the next k-loop.  Any other epilogue shape drains everything.
-    if (interior && !p.Y2 && T32 > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * T32) : "memory");
+    if (interior && !p.Y2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * T32) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -487,25 +460,13 @@ __global__ void __launch_bounds__(256) gemm_panel_f32(const GemmArgs p)
 #endif
 }
 
-template <int T32, bool HALF, int EPI, int AMODE, bool R16VEC>
-int launch_panel_v(const GemmArgs &a, hipStream_t stream);
-
-template <int T32, bool HALF, int EPI, int AMODE>
+template <int T32, int EPI, int AMODE>
 int launch_panel(const GemmArgs &a, hipStream_t stream)
 {
-    // LDIT_PANEL_R16=vec selects the conflict-free b128 remainder reads (see load_frags); the default scalar reads measured
-    // 1.7 % faster (profiles/README.md, round 2: three interleaved A/B pairs on one device)
-    const bool vec = diag().panel_r16_vec;
-    return vec ? launch_panel_v<T32, HALF, EPI, AMODE, true>(a, stream) : launch_panel_v<T32, HALF, EPI, AMODE, false>(a, stream);
-}
-
-template <int T32, bool HALF, int EPI, int AMODE, bool R16VEC>
-int launch_panel_v(const GemmArgs &a, hipStream_t stream)
-{
-    constexpr int BM = 32 * T32 + (HALF ? 16 : 0), PIECES = (BM + BNP) / 8, NLD = (PIECES + 3) / 4;
+    constexpr int BM = 32 * T32 + 16, PIECES = (BM + BNP) / 8, NLD = (PIECES + 3) / 4;
     constexpr int lds = 2 * NLD * 4 * 1024;
     const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BNP - 1) / BNP);
-    auto kern = gemm_panel_f32<T32, HALF, EPI, AMODE, R16VEC>;
+    auto kern = gemm_panel_f32<T32, EPI, AMODE>;
     LDIT_DYN_LDS(kern, lds);
     // LDIT_GEMM_PERSIST=1: as many workgroups as fit the chip at once (one per CU at > 80 KB of LDS each, two below), each walking its tiles
     const int resident = (lds > 80 * 1024 ? 1 : 2) * compute_units();
@@ -525,15 +486,15 @@ template <int T32>
 static int launch_panel_epi(const GemmArgs &a, int epi, hipStream_t stream)
 {
     switch (epi) {
-        case EPI_BIAS: return launch_panel<T32, true, EPI_BIAS, A_ROWMAJOR>(a, stream);
-        case EPI_BIAS_GELU: return launch_panel<T32, true, EPI_BIAS_GELU, A_ROWMAJOR>(a, stream);
-        default: return launch_panel<T32, true, EPI_SCALE_RESID, A_ROWMAJOR>(a, stream);
+        case EPI_BIAS: return launch_panel<T32, EPI_BIAS, A_ROWMAJOR>(a, stream);
+        case EPI_BIAS_GELU: return launch_panel<T32, EPI_BIAS_GELU, A_ROWMAJOR>(a, stream);
+        default: return launch_panel<T32, EPI_SCALE_RESID, A_ROWMAJOR>(a, stream);
     }
 }
 
 int launch_gemm_panel(const GemmArgs &a, int epi, int amode, hipStream_t stream, int height)
 {
-    if (amode == A_PATCH) return launch_panel<9, true, EPI_EMBED, A_PATCH>(a, stream);
+    if (amode == A_PATCH) return launch_panel<9, EPI_EMBED, A_PATCH>(a, stream);
     switch (height) {
         case 48: return launch_panel_epi<1>(a, epi, stream);
         case 80: return launch_panel_epi<2>(a, epi, stream);

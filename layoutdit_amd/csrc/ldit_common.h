@@ -49,14 +49,12 @@ int compute_units();
 struct DiagSwitches {
     int gemm_tile = -1;          // LDIT_GEMM_TILE 0..7 (fp32 GEMM tiling)
     long thin_tiles = 192;       // LDIT_GEMM_THIN_TILES
-    bool panel_r16_vec = false;  // LDIT_PANEL_R16=vec
     bool panel_persist = false;  // LDIT_GEMM_PERSIST=1: persistent tile loop of the fp32 panel GEMM (measured equal: off by default)
     int bf16_tile = -1;          // LDIT_GEMM_BF16_TILE 2..5 (-1 = picker; any value also disables the small-M kernel)
     bool bf16_tile_env = false;  //   the variable is present at all
     int bf16_tr_tile = -1;       // LDIT_GEMM_BF16_TR_TILE
     bool bf16_tail_launch = false;   // LDIT_GEMM_BF16_TAIL_LAUNCH=1: the peeled tail of a bf16 GEMM as its own launch (round 3) instead of riding in the main one
     int fp8_tile = -1;           // LDIT_GEMM_FP8_TILE 0..4
-    bool fp8_k16 = false, fp8_noskinny = false;   // LDIT_GEMM_FP8_K16, LDIT_GEMM_FP8_NOSKINNY
     bool direct_epi = false;     // LDIT_GEMM_DIRECT_EPILOGUE=1
     int attn_bf16_nw = -1;       // LDIT_ATTN_BF16_NW=8: eight query tiles per workgroup (one staging of a chunk per 256 queries)
     long planes_tail_waves = 700;    // LDIT_PLANES_TAIL_WAVES: split-fp32 GEMMs of at most this many 32 x 32 output tiles run on the one-wave-per-tile kernel
@@ -336,10 +334,7 @@ int launch_gemm_mxfp8_train(const void *A, int lda, const void *As, const void *
                             const float *rowscale, void *Yd, hipStream_t stream);
 int launch_scale_inplace(float *x, size_t n, float mul, hipStream_t stream);
 struct MxRequantSeg { int64_t start, n; int cols; int fold_rows; int64_t codes, scales; };
-int launch_adamw_mx(float *p, const float *g, float *m, float *v, int64_t e0, int64_t e1, bool update, float lr, float b1, float b2,
-                    float eps, float wd, int step, float grad_scale, void *mirror16, void *mx, const MxRequantSeg *segs, int nseg,
-                    int64_t bias_start, int64_t bias_dst, int C, float fold, hipStream_t stream);
-// ldit_requant_train_mirror: layer 0's four matrix segments and bias, the strides from one layer to the next (flat elements / MX-section
+// the MX pass of the train mirror (ldit_pack_train, ldit_adamw_step_mxfp8, ldit_requant_train_mirror): layer 0's four matrix segments and bias, the strides from one layer to the next (flat elements / MX-section
 // bytes), L layers in one launch; state (device, may be null): skip set = nothing is stored
 int launch_requant_mirror(const float *p, void *mirror16, void *mx, const ldit_opt_state *state, const MxRequantSeg *segs, int64_t layer_elems,
                           int64_t layer_mx, int64_t bias_start, int64_t bias_dst, int C, int L, float fold, hipStream_t stream);

@@ -640,28 +640,6 @@ __global__ void __launch_bounds__(256) scale_inplace(float *__restrict__ x, size
 }
 
 // ---- mxfp8 train step: re-quantisation of the forward's MX operands from the fp32 master (pack and after each update) -------------
-// One thread per 4 consecutive elements of [e0, e1) of the flat block, 8 lanes per 32-element block (every segment starts at a
-// multiple of 32 elements); the master is only read (ldit_pack_train; ldit_adamw_step_mxfp8 runs it right behind adamw_kernel,
-// whose update it then re-quantises - the update's bits are adamw_kernel's by construction).  From the master:
-//   matrix segments (a.seg): the row block times `fold` on the first fold_rows rows (the q third of W_qkv) -> MX codes + E8M0
-//     scale exactly as quant_mx (ldit_pack_weights) makes them, into the MX section `mx`; the bf16 mirror gets the dequantised
-//     codes (the dgrad's operand);
-//   the fused q|k|v bias (a.bias_start, 3 C elements): [fold bq, 0, bv] into the MX section as fp32, as qkv_bias packs it;
-//   everything else: the bf16 mirror gets bf16(master), as adamw_kernel / ldit_pack_train write it.
-struct AdamwMxArgs {
-    float *p, *m, *v;
-    const float *g;
-    int64_t e0, e1;
-    int update;
-    float lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, fold;
-    bf16_t *mirror;
-    unsigned char *mx;
-    MxRequantSeg seg[4];
-    int nseg;
-    int64_t bias_start, bias_dst;
-    int C;
-};
-
 // The 32-element MX block of a quad: the amax bit pattern of its own four, then the 8-lane exchange (every matrix segment starts at
 // a multiple of 32 elements and a thread holds 4, so 8 neighbouring lanes hold one block).  Every lane of the wave must arrive.
 __device__ __forceinline__ unsigned mx_block_amax(const f32x4 &q)
@@ -697,42 +675,21 @@ __device__ __forceinline__ void mx_store_bias_quad(const f32x4 &P, int64_t r, in
     *reinterpret_cast<f32x4 *>(dst + 4 * r) = b;
 }
 
-__global__ void __launch_bounds__(256) adamw_mx_kernel(const AdamwMxArgs a)
-{
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t i0 = a.e0 + 4 * gid;
-    const bool ok = i0 < a.e1;
-    const int64_t i = ok ? i0 : a.e1 - 4;
-    f32x4 P = *reinterpret_cast<const f32x4 *>(a.p + i);
-    int s = -1;
-    for (int k = 0; k < a.nseg; ++k)
-        if (i >= a.seg[k].start && i < a.seg[k].start + a.seg[k].n) s = k;
-    f32x4 q = P;
-    int64_t rel = 0;
-    if (s >= 0) {
-        rel = i - a.seg[s].start;
-        const float mul = rel / a.seg[s].cols < a.seg[s].fold_rows ? a.fold : 1.0f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q[e] *= mul;
-    }
-    const unsigned amax = mx_block_amax(q);
-    if (!ok) return;
-    if (s >= 0) {
-        mx_store_quad(q, amax, a.mx, a.seg[s].codes, a.seg[s].scales, rel, a.mirror + i);
-        return;
-    }
-    *reinterpret_cast<bf16x4 *>(a.mirror + i) = bf16x4{(bf16_t)P[0], (bf16_t)P[1], (bf16_t)P[2], (bf16_t)P[3]};
-    if (i >= a.bias_start && i < a.bias_start + 3 * (int64_t)a.C) mx_store_bias_quad(P, i - a.bias_start, a.C, a.fold, a.mx + a.bias_dst);
-}
-
-// ---- the MX operands of the train mirror re-made for ALL layers in one launch (ldit_requant_train_mirror) --------------------------
-// Behind the multi-tensor AdamW of the detector's step (optim_multi.hip), which wrote bf16(p) beside every p: grid.y = the layer,
-// grid.x walks one layer's four matrices and then its fused bias, one quad per thread.  The layers of a geometry are laid out alike,
-// so layer l is layer 0 moved by l * layer_elems in the flat block and by l * layer_mx in the MX section (the host checks it).
-// quad_end[k] = the threads of a layer up to the end of matrix k, each a multiple of 256: a workgroup never straddles two segments, and
-// 8 neighbouring lanes hold one 32-element block.  Matrix quads go through mx_block_amax / mx_store_quad, bias quads through
-// mx_store_bias_quad - adamw_mx_kernel's own, so the bits are ldit_pack_train's.  Nothing else of the mirror is touched: LayerNorm
-// vectors, biases, LayerScale, embeddings and padding keep what the AdamW write left.  A skipped step (state->skip) stores nothing.
+// ---- the MX operands of the train mirror re-made for ALL layers in one launch -------------------------------------------------------
+// The one MX pass of ldit_pack_train, ldit_adamw_step_mxfp8 and ldit_requant_train_mirror.  It runs behind a launch that wrote
+// bf16(p) beside every p of the flat block - cvt_f32_bf16 (pack), adamw_kernel (step) or the multi-tensor AdamW of the detector's
+// step (optim_multi.hip) - and only reads the master.  From the master, per layer:
+//   the four matrices (a.seg): the row block times `fold` on the first fold_rows rows (the q third of W_qkv) -> MX codes + E8M0
+//     scale exactly as quant_mx (ldit_pack_weights) makes them, into the MX section `mx`; the bf16 mirror gets the dequantised
+//     codes (the dgrad's operand) over the bf16(master) of the launch before;
+//   the fused q|k|v bias (a.bias_start, 3 C elements): [fold bq, 0, bv] into the MX section as fp32, as qkv_bias packs it;
+//   everything else - LayerNorm vectors, biases, LayerScale, embeddings, padding - is not touched: the mirror keeps the bf16(master)
+//     of the launch before.
+// grid.y = the layer, grid.x walks one layer's four matrices and then its fused bias, one quad per thread.  The layers of a geometry
+// are laid out alike, so layer l is layer 0 moved by l * layer_elems in the flat block and by l * layer_mx in the MX section (the host
+// checks it).  quad_end[k] = the threads of a layer up to the end of matrix k, each a multiple of 256: a workgroup never straddles two
+// segments, and 8 neighbouring lanes hold one 32-element block.  A skipped step (state->skip) stores nothing; state == nullptr never
+// skips.
 struct RequantMirrorArgs {
     const float *p;
     bf16_t *mirror;
@@ -964,32 +921,6 @@ int launch_adamw(float *p, const float *g, float *m, float *v, size_t n, float l
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     LAUNCH_CHECKED(adamw_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p, g, m, v, n / 4, lr, b1, b2, eps, wd,
                    (float)bc1, (float)sqrt(bc2), grad_scale, static_cast<bf16_t *>(mirror));
-    return LDIT_OK;
-}
-
-int launch_adamw_mx(float *p, const float *g, float *m, float *v, int64_t e0, int64_t e1, bool update, float lr, float b1, float b2,
-                    float eps, float wd, int step, float grad_scale, void *mirror16, void *mx, const MxRequantSeg *segs, int nseg,
-                    int64_t bias_start, int64_t bias_dst, int C, float fold, hipStream_t stream)
-{
-    if (e1 <= e0) return LDIT_OK;
-    if ((e0 | e1) & 31) return fail(LDIT_EINVAL, "adamw_mx: range must be whole 32-element blocks");
-    if (nseg < 0 || nseg > 4) return fail(LDIT_EINVAL, "adamw_mx: at most 4 matrix segments per launch");
-    if (update && (!g || !m || !v || step < 1)) return fail(LDIT_EINVAL, "adamw_mx: update needs grads, moments and step >= 1");
-    AdamwMxArgs a{};
-    a.p = p; a.g = g; a.m = m; a.v = v; a.e0 = e0; a.e1 = e1; a.update = update ? 1 : 0;
-    if (update) {
-        const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-        a.bc1 = (float)bc1; a.bc2_sqrt = (float)sqrt(bc2);
-    }
-    a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd; a.grad_scale = grad_scale; a.fold = fold;
-    a.mirror = static_cast<bf16_t *>(mirror16); a.mx = static_cast<unsigned char *>(mx);
-    for (int k = 0; k < nseg; ++k) {
-        if ((segs[k].start | segs[k].n) & 31 || segs[k].cols % 32) return fail(LDIT_EINVAL, "adamw_mx: segment not block aligned");
-        a.seg[k] = segs[k];
-    }
-    a.nseg = nseg; a.bias_start = bias_start; a.bias_dst = bias_dst; a.C = C;
-    const int64_t threads = (e1 - e0) / 4;
-    LAUNCH_CHECKED(adamw_mx_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);
     return LDIT_OK;
 }
 

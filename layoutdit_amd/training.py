@@ -342,7 +342,7 @@ class TrainStep:
     """Fused train step on the flat state: forward, staged backward with overlapped per-layer gradient all-reduce,
     AdamW, re-pack.  ``dtaps`` stands in for the detector head: fixed synthetic upstream gradients, one per tap - this is the
     ENCODER's step, the one ``bench.py --config 2`` measures; on the quantisation-aware mxfp8 build its update re-quantises the MX
-    operands layer by layer (``ldit_adamw_step_mxfp8``).  The whole detector (FPN, RPN and box head behind the encoder, real losses,
+    operands in one launch behind it (``ldit_adamw_step_mxfp8``).  The whole detector (FPN, RPN and box head behind the encoder, real losses,
     loss scaling) trains with :class:`DetectorTrainStep`, which drives that build on a task loss too (``qat=True``)."""
 
     def __init__(self, encoder, rank: Optional[Rank] = None, lr: float = 1e-4, weight_decay: float = 0.0,

@@ -5,7 +5,8 @@ LDS, kernel-argument size, ...) differ, and every kernel without a partner; exit
 "this change leaves the kernels' instruction streams untouched".
     python scripts/isa_diff.py old.s new.s [map.txt]
 map.txt renames kernels of old.s, one `<regex> <replacement>` (re.sub on the mangled name) per line.  A kernel's own name inside its
-labels / symbol references and the function number of local labels (.LBB<n>_) are neutralised before comparing.
+labels / symbol references, the function number of local labels (.LBB<n>_) and the file-wide counter of a long branch's
+.Lpost_getpc<n> label (it moves when a kernel in front of it leaves the file) are neutralised before comparing.
 A changed parameter type renames EVERY instantiation, not only a renamed kernel.  Example: gemm_fp8.hip, when gemm_fp8_mfma_tr /
 gemm_fp8_tail_tr became the TR instantiations of gemm_fp8_mfma / gemm_fp8_tail (argument std::conditional_t<TR, GemmArgs8T, GemmArgs8>):
     16gemm_fp8_mfma_trI(\w+?E)EEvNS0_10GemmArgs8TE$ 13gemm_fp8_mfmaI\1Lb1ELb1ELb1EEEvNSt11conditionalIXT6_ENS0_10GemmArgs8TENS0_9GemmArgs8EE4typeE
@@ -27,7 +28,7 @@ def load(path):
         name = f.split(":")[0]
         meta = [re.sub(r"\s+", " ", l).strip() for l in f.splitlines()]
         meta = [l for l in meta if l.startswith(".amdhsa_") or re.match(r"; [\w:]+ ?: ", l)]
-        neutral = lambda l: re.sub(r"\.L(BB|JTI|tmp)\d+_", r".L\1_", l.replace(name, "<self>"))
+        neutral = lambda l: re.sub(r"\.L(BB|JTI|tmp)\d+_|\.L(post_getpc)\d+", r".L\1\2_", l.replace(name, "<self>"))
         out[name] = ([neutral(l) for l in code[name]], [neutral(l) for l in meta])
     return out
 

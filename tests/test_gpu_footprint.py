@@ -108,7 +108,7 @@ the whole path in tests/test_gpu_fresh_memory.py; "exempt": with the reason (7 o
   ldit_set_fp8_act_scales        exempt  a memcpy of HOST floats into the packed block
   ldit_pack_train                here    the bf16 mirror of ViT-micro's flat block
   ldit_adamw_step                here    n 4 / 1028; parameters and moments in place, the bf16 mirror an output
-  ldit_adamw_step_mxfp8          exempt  ldit_adamw_step fused with ldit_pack_train's mxfp8 form; tests/test_gpu_mxfp8_qat.py compares master,
+  ldit_adamw_step_mxfp8          exempt  ldit_adamw_step, then the MX launch of ldit_pack_train's mxfp8 form; tests/test_gpu_mxfp8_qat.py compares master,
                                          moments and mirror with those two bit for bit
   ldit_grads_check_multi_f32     exempt  tests/test_gpu_detector_step.py already surrounds its segments with sentinels
   ldit_opt_advance               exempt  the same

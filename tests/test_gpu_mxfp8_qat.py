@@ -64,6 +64,33 @@ def _pack_train(st):
     return fresh
 
 
+@pytest.mark.parametrize("layers", [1, 3])
+def test_pack_train_leaves_nothing_the_forward_reads_to_the_mirrors_old_bytes(layers):
+    """ldit_pack_train (mxfp8) = the convert pass over the whole flat block + ONE launch that re-makes the matrices and the fused
+    bias of every layer (one layer: the zero-stride branch of the host side).  Everything the training forward reads must come from
+    those two: the pack into a mirror of 0x00 bytes and into one of 0xFF bytes gives bit-equal taps, and they are the eval
+    forward's (which reads ldit_pack_weights' block: codes, scales and folded bias made by another kernel)."""
+    from layoutdit_amd.training import flat_state
+    cfg = dataclasses.replace(cfgs.vit_micro(), drop_path_rate=0.0, num_hidden_layers=layers, taps=[])
+    taps = list(range(layers + 1))
+    m = _enc(cfg, synth.synth_weights(cfg, 7))
+    x = torch.from_numpy(synth.synth_images(2, 64, 64, seed=5)).to(DEV)
+    st = flat_state(m, 64, 64)
+    st.repack(force=True)
+    outs = []
+    with torch.no_grad():
+        for fill in (0x00, 0xFF):
+            st.packed.fill_(fill)
+            st.repack(force=True)
+            outs.append([t.clone() for t in st.forward(x, taps, None, st.new_saved(2))])
+        m.eval()
+        ev = [t for t in m(x, taps=taps).hidden_states if t is not None]
+    assert len(outs[0]) == len(outs[1]) == len(ev) == layers + 1
+    for t, a, b, e in zip(taps, outs[0], outs[1], ev):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), t
+        assert torch.equal(a.view(torch.int32), e.view(torch.int32)), t
+
+
 def _trainstep_run(cfg, w, x, steps=3):
     from layoutdit_amd.training import TrainStep
     m = _enc(cfg, w)

@@ -86,7 +86,7 @@ def test_residual_epilogues_do_not_wait_for_their_own_stores(tmp_path):
     behind a slab's first store there is no vmcnt wait until the next slab's accumulators enter LDS."""
     iso = _isa_order()
     import re
-    lines = [l for n, l in iso.kernels(_device_asm("gemm_panel_f32.hip", tmp_path)).items() if "gemm_panel_f32ILi9ELb1ELi2ELi0ELb0" in n]
+    lines = [l for n, l in iso.kernels(_device_asm("gemm_panel_f32.hip", tmp_path)).items() if "gemm_panel_f32ILi9ELi2ELi0EE" in n]
     assert len(lines) == 1
     tail = lines[0][max(i for i, l in enumerate(lines[0]) if "v_mfma" in l):]
     o = iso.order(tail, valu=False)

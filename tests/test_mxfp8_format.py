@@ -195,7 +195,7 @@ def test_mx_gemm_instantiations_issue_the_vgpr_scaled_mfma(tmp_path):
     assert len(mx) + len(plain) + len(train) == sum("gemm_fp8_" in n for n in ks), sorted(ks)
     # three epilogues x (five tiles + the tail)
     assert len(mx) == 3 * 6 - 1, sorted(mx)        # (the scale+residual epilogue has no 320-row tile)
-    assert len(plain) >= 3 * 9 - 1, sorted(plain)
+    assert len(plain) == 3 * 6 - 1, sorted(plain)
     # the two train epilogues x (five tiles + the tail), no 320-row scale+residual tile
     assert len(train) == 2 * 6 - 1, sorted(train)
     for n, t in plain.items():
