@@ -366,6 +366,44 @@ int ldit_preprocess_f16(const void *const *images, const int32_t *heights, const
 int ldit_preprocess_u8(const void *const *images, const int32_t *heights, const int32_t *widths, int32_t interleaved, int32_t B,
                        int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream);
 
+/* ---- train-time augmentation: crop, scale jitter and flip inside the input transform -----------------------
+ * A WINDOW of image i is five host integers (x0, y0, cw, ch, flip): the cw x ch pixels whose top-left one is column x0 of row y0 of
+ * the page, mirrored left-right where flip == 1.  cw >= 1, ch >= 1, x0 >= 0, y0 >= 0, x0 + cw <= w_i, y0 + ch <= h_i, flip 0 or 1;
+ * anything else is LDIT_EINVAL with a message that names the image, before any launch.  `windows` is a HOST array [B][5].
+ *
+ * ldit_preprocess_win_f32 / _f16 / _u8: ldit_preprocess_f32 / _f16 / _u8 on the windows instead of the whole pages.  With
+ *   crop_i = images[i][:, y0 : y0 + ch, x0 : x0 + cw] (and .flip(-1) where flip is set), row i of `out` EQUALS, bit for bit, what the
+ *   sibling without `_win` gives for a contiguous copy of crop_i: the same statement (csrc/image_blend.h) on the window's extent, the
+ *   source row y0 + y, the source column x0 + x or, flipped, x0 + cw - 1 - x.  No copy is made, and no byte of a page outside its
+ *   window is read.  Every other argument, the four image formats, the alignment rules and "one launch per 48 images" are the
+ *   sibling's: the windows travel in the kernel arguments beside the image descriptors (no device-side table, no copy to the
+ *   device).  windows == NULL: whole pages, no flip - the sibling itself.
+ *
+ * ldit_augment_targets_f32: the boxes of the same batch through the same windows, as the padded targets ldit_rpn_targets_f32 and
+ *   ldit_roi_targets_f32 read.  gt_boxes fp32 [B, Gmax, 4] (x1, y1, x2, y2 in the page's pixels), gt_labels int32 [B, Gmax] or NULL,
+ *   gt_count int32 [B] (clamped to [0, Gmax]); Gmax <= 512.  For each row g < gt_count[i], in fp32, every operation rounded once:
+ *       X0 = (float)x0, Y0 = (float)y0, X1 = (float)(x0 + cw), Y1 = (float)(y0 + ch), CW = (float)cw
+ *       ax1 = min(max(x1, X0), X1), ax2 = min(max(x2, X0), X1), ay1 / ay2 alike;  iw = ax2 - ax1, ih = ay2 - ay1
+ *       keep = iw > 0 && ih > 0 && iw * ih >= min_visibility * ((x2 - x1) * (y2 - y1))
+ *       lx1 = ax1 - X0, lx2 = ax2 - X0;  flip: (lx1, lx2) = (CW - lx2, CW - lx1);  ly1 = ay1 - Y0, ly2 = ay2 - Y0
+ *       b = (lx1 * rw, ly1 * rh, lx2 * rw, ly2 * rh),  rw = (float)((double)out_w / cw), rh = (float)((double)out_h / ch)
+ *       keep = keep && b.x2 - b.x1 >= min_size && b.y2 - b.y1 >= min_size
+ *   The kept rows of image i are written to out_boxes [B, Gmax, 4] / out_labels int32 [B, Gmax] in their original order, out_count[i]
+ *   (int32 [B]) is their number, and every row at or beyond it is zero.  gt_labels == NULL: out_labels, if given, is all zero.  Rows of
+ *   the inputs at or beyond gt_count[i] are never read (they may hold NaN).  The pages' sizes are not known here: only cw, ch >= 1,
+ *   x0, y0 >= 0 and flip are checked.  The outputs must not alias the inputs; boxes 16-byte aligned.  One launch per 48 images, one
+ *   wave per image, no atomics, no synchronisation: capturable, and the output is a pure function of the input. */
+int ldit_preprocess_win_f32(const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows, int32_t B,
+                            int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream);
+int ldit_preprocess_win_f16(const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows, int32_t B,
+                            int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream);
+int ldit_preprocess_win_u8(const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows,
+                           int32_t interleaved, int32_t B, int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out,
+                           ldit_stream stream);
+int ldit_augment_targets_f32(const void *gt_boxes, const void *gt_labels, const void *gt_count, const int32_t *windows, int32_t B,
+                             int32_t Gmax, int32_t out_h, int32_t out_w, float min_visibility, float min_size, void *out_boxes,
+                             void *out_labels, void *out_count, ldit_stream stream);
+
 /* fp16 <-> fp32 conversion of a pixel batch / of the returned taps for an fp16 caller (round to nearest even), n elements;
  * the fp16 side 8-byte aligned, the fp32 side 16-byte aligned. */
 int ldit_cast_f16_f32(const void *src, void *dst, int64_t n, ldit_stream stream);

@@ -323,6 +323,23 @@ int preprocess(ImgFmt fmt, const void *const *images, const int32_t *heights, co
                              static_cast<hipStream_t>(stream));
 }
 
+// the *_win siblings: the same checks, then the windowed kernels - or, without windows, the entry above itself
+int preprocess_win(ImgFmt fmt, const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows, int32_t B,
+                   int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
+{
+    if (!windows) return preprocess(fmt, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
+    if (!images || !heights || !widths || !out) return fail(LDIT_EINVAL, "preprocess: null argument");
+    if (B <= 0 || B > 65535 || in_ch <= 0 || out_h <= 0 || out_w <= 0) return fail(LDIT_EINVAL, "preprocess: bad geometry");
+    if (!(std > 0.0f)) return fail(LDIT_EINVAL, "preprocess: std must be positive");
+    if ((int64_t)B * in_ch * out_h * out_w >= (1ll << 31)) return fail(LDIT_EUNSUPPORTED, "preprocess: batch exceeds 2^31 elements");
+    for (int i = 0; i < B; ++i) {                                   // every window before the first launch
+        if (!images[i] || heights[i] <= 0 || widths[i] <= 0) return fail(LDIT_EINVAL, "image %d is null or empty", i);
+        LDIT_TRY(check_window(windows + (size_t)i * 5, i, heights[i], widths[i]));
+    }
+    return launch_preprocess_windows(images, fmt, heights, widths, windows, B, in_ch, mean, std, out_h, out_w, static_cast<float *>(out),
+                                     static_cast<hipStream_t>(stream));
+}
+
 // The side stream of the two-lane forward: one non-blocking stream per device ordinal, created on first use and kept for the life
 // of the process (with the dynamic-LDS bits and the CU count, the library's only per-device state).  Null: ordinal out of range.
 int side_stream(hipStream_t &out)
@@ -883,6 +900,27 @@ int ldit_preprocess_u8(const void *const *images, const int32_t *heights, const 
     ImgFmt fmt;
     LDIT_TRY(u8_format("preprocess_u8", interleaved, fmt));
     return preprocess(fmt, images, heights, widths, B, in_ch, mean, std, out_h, out_w, out, stream);
+}
+
+int ldit_preprocess_win_f32(const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows, int32_t B,
+                            int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
+{
+    return preprocess_win(IMG_F32, images, heights, widths, windows, B, in_ch, mean, std, out_h, out_w, out, stream);
+}
+
+int ldit_preprocess_win_f16(const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows, int32_t B,
+                            int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out, ldit_stream stream)
+{
+    return preprocess_win(IMG_F16, images, heights, widths, windows, B, in_ch, mean, std, out_h, out_w, out, stream);
+}
+
+int ldit_preprocess_win_u8(const void *const *images, const int32_t *heights, const int32_t *widths, const int32_t *windows,
+                           int32_t interleaved, int32_t B, int32_t in_ch, float mean, float std, int32_t out_h, int32_t out_w, void *out,
+                           ldit_stream stream)
+{
+    ImgFmt fmt;
+    LDIT_TRY(u8_format("preprocess_win_u8", interleaved, fmt));
+    return preprocess_win(fmt, images, heights, widths, windows, B, in_ch, mean, std, out_h, out_w, out, stream);
 }
 
 int ldit_fpn_merge_f32(const void *lat, const void *top, void *out, int64_t B, int64_t Gh, int64_t Gw, int64_t Ch, float scale,

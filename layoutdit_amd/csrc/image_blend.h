@@ -67,6 +67,24 @@ __device__ __forceinline__ BlendCol blend_col(int ox, int w, int out_w)
     return c;
 }
 
+// Train-time windows: image i of a windowed launch is the cw x ch window of its page whose top-left pixel ImageList
+// img[i] points AT (the host adds the offset; h[i] / w[i] stay the page's, i.e. the plane and row strides), mirrored left-right
+// where bit i of `flip` is set.  The descriptors travel in the kernel arguments beside the ImageList.
+struct WindowList {
+    int cw[PRE_MAX], ch[PRE_MAX];
+    uint64_t flip;
+};
+static_assert(PRE_MAX <= 64, "one flip bit per image of a launch");
+
+// blend_col on a window's extent; under flip window column x is source column cw - 1 - x (the weights stay with their columns, so
+// blend_at evaluates the statement it evaluates on the mirrored copy)
+__device__ __forceinline__ BlendCol blend_col_win(int ox, int cw, int out_w, bool flip)
+{
+    BlendCol c = blend_col(ox, cw, out_w);
+    if (flip) { c.x0 = cw - 1 - c.x0; c.x1 = cw - 1 - c.x1; }
+    return c;
+}
+
 // the normalised blend of the four samples at columns bc.x0 / bc.x1 of the source rows r0 / r1; `xs`: elements from one pixel of a
 // row to the next (1 planar; in_ch interleaved, r0 / r1 then pointing at the channel wanted of the row's first pixel)
 template <typename IN>

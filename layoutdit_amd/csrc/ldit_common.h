@@ -277,6 +277,11 @@ int launch_tap_to_map_bwd(const float *dmap, float *dtap, int B, int Gh, int Gw,
 enum ImgFmt { IMG_F32 = 0, IMG_F16 = 1, IMG_U8 = 2, IMG_U8_HWC = 3 };
 int launch_preprocess(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, int B, int in_ch, float mean,
                       float std, int out_h, int out_w, float *out, hipStream_t stream);
+// the same transform on windows of the pages (train-time crop / flip): `windows` host [B][5] = (x0, y0, cw, ch, flip), never null
+int launch_preprocess_windows(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, const int *windows, int B,
+                              int in_ch, float mean, float std, int out_h, int out_w, float *out, hipStream_t stream);
+// one window of `image` against its h x w page (w < 0: page unknown); LDIT_EINVAL with a message that names the image
+int check_window(const int *win, int image, int h, int w);
 struct ImageList;
 int fill_image_list(ImageList &l, const void *const *images, const int *heights, const int *widths, int B, int first, float mean, float std);
 // the bf16 (or plane) im2col rows of the patch embedding straight from a ragged image list: the input transform fused into the load

@@ -165,6 +165,63 @@ __global__ void __launch_bounds__(256) preprocess_images_hwc(const PreArgs a)
     }
 }
 
+// The same two kernels on WINDOWS of the pages (train-time crop and flip, image_blend.h: WindowList): a.l.img[i] points at the
+// window's top-left pixel, a.l.h[i] / a.l.w[i] are still the page's (plane and row strides), the blend runs on the window's extent
+// cw x ch and a flipped window reflects its column indices.  Output pixel for output pixel the statements of the kernels above on
+// a contiguous copy of the (mirrored) window, so the bits are those; no byte of the page outside the window is addressed.
+struct PreWinArgs {
+    ImageList l;
+    WindowList win;
+    float *out;
+    int in_ch, out_h, out_w;
+};
+static_assert(sizeof(PreWinArgs) <= 4096, "the descriptors of one launch must fit the kernel-argument segment");
+
+template <typename IN>
+__global__ void __launch_bounds__(256) preprocess_windows(const PreWinArgs a)
+{
+    const int owv = (a.out_w + 3) / 4;
+    const int per_img = a.in_ch * a.out_h * owv;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.y;
+    if (idx >= per_img) return;
+    const int ch = idx / (a.out_h * owv), rem = idx - ch * (a.out_h * owv), oy = rem / owv, ox0 = (rem - oy * owv) * 4;
+    const int h = a.l.h[i], w = a.l.w[i], cw = a.win.cw[i];
+    const bool flip = (a.win.flip >> i) & 1;
+    const IN *src = static_cast<const IN *>(a.l.img[i]) + (size_t)ch * h * w;
+    const BlendRow br = blend_row(oy, a.win.ch[i], a.out_h);
+    const IN *r0 = src + (size_t)br.y0 * w, *r1 = src + (size_t)br.y1 * w;
+    float *dst = a.out + (((size_t)(a.l.first + i) * a.in_ch + ch) * a.out_h + oy) * a.out_w + ox0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (ox0 + e >= a.out_w) break;
+        dst[e] = blend_at(r0, r1, blend_col_win(ox0 + e, cw, a.out_w, flip), 1, br, a.l.mean, a.l.inv_std);
+    }
+}
+
+__global__ void __launch_bounds__(256) preprocess_windows_hwc(const PreWinArgs a)
+{
+    const int owv = (a.out_w + 3) / 4;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.y;
+    if (idx >= a.out_h * owv) return;
+    const int oy = idx / owv, ox0 = (idx - oy * owv) * 4;
+    const int w = a.l.w[i], cw = a.win.cw[i];
+    const bool flip = (a.win.flip >> i) & 1;
+    const uint8_t *src = static_cast<const uint8_t *>(a.l.img[i]);
+    const BlendRow br = blend_row(oy, a.win.ch[i], a.out_h);
+    const uint8_t *r0 = src + (size_t)br.y0 * w * a.in_ch, *r1 = src + (size_t)br.y1 * w * a.in_ch;
+    const size_t plane = (size_t)a.out_h * a.out_w;
+    float *dst = a.out + ((size_t)(a.l.first + i) * a.in_ch * a.out_h + oy) * a.out_w + ox0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (ox0 + e >= a.out_w) break;
+        const BlendCol bc = blend_col_win(ox0 + e, cw, a.out_w, flip);
+        for (int ch = 0; ch < a.in_ch; ++ch)
+            dst[ch * plane + e] = blend_at(r0 + ch, r1 + ch, bc, a.in_ch, br, a.l.mean, a.l.inv_std);
+    }
+}
+
 template <int CB>
 int launch_tiled_maps(const float *tap, float *out, int B, int Gh, int Gw, int C, int Oh, int Ow, float scale,
                       hipStream_t stream)
@@ -247,6 +304,47 @@ int launch_preprocess(const void *const *images, ImgFmt fmt, const int *heights,
         else if (fmt == IMG_U8) hipLaunchKernelGGL(preprocess_images<uint8_t>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
         else if (fmt == IMG_U8_HWC) hipLaunchKernelGGL(preprocess_images_hwc, dim3((per_row + 255) / 256, a.l.n), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(preprocess_images<float>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        LDIT_HIP_CHECK(hipGetLastError());
+    }
+    return LDIT_OK;
+}
+
+// one window (x0, y0, cw, ch, flip) of `image` against its h x w page; w < 0: the page is not known to the caller (the target kernel)
+int check_window(const int *win, int image, int h, int w)
+{
+    const int x0 = win[0], y0 = win[1], cw = win[2], ch = win[3], flip = win[4];
+    if (cw < 1 || ch < 1) return fail(LDIT_EINVAL, "image %d: window extent %d x %d (width x height) must be at least 1 x 1", image, cw, ch);
+    if (x0 < 0 || y0 < 0) return fail(LDIT_EINVAL, "image %d: window origin (%d, %d) is negative", image, x0, y0);
+    if ((int64_t)x0 + cw > INT32_MAX || (int64_t)y0 + ch > INT32_MAX) return fail(LDIT_EINVAL, "image %d: window exceeds 2^31 pixels a side", image);
+    if (w >= 0 && ((int64_t)x0 + cw > w || (int64_t)y0 + ch > h))
+        return fail(LDIT_EINVAL, "image %d: window x [%d, %lld) y [%d, %lld) leaves the %d x %d page (width x height)", image, x0,
+                    (long long)x0 + cw, y0, (long long)y0 + ch, w, h);
+    if (flip != 0 && flip != 1) return fail(LDIT_EINVAL, "image %d: flip = %d (0 or 1)", image, flip);
+    return LDIT_OK;
+}
+
+// `windows`: host [B][5] = (x0, y0, cw, ch, flip) per image, validated here against the pages; never null (the caller's whole-page
+// case is launch_preprocess itself)
+int launch_preprocess_windows(const void *const *images, ImgFmt fmt, const int *heights, const int *widths, const int *windows, int B,
+                              int in_ch, float mean, float std, int out_h, int out_w, float *out, hipStream_t stream)
+{
+    const size_t pixel = fmt == IMG_F32 ? 4 : fmt == IMG_F16 ? 2 : fmt == IMG_U8_HWC ? (size_t)in_ch : 1;   // bytes from a pixel to its right neighbour
+    for (int first = 0; first < B; first += PRE_MAX) {
+        PreWinArgs a{};
+        if (int rc = fill_image_list(a.l, images, heights, widths, B, first, mean, std)) return rc;
+        for (int i = 0; i < a.l.n; ++i) {
+            const int *win = windows + (size_t)(first + i) * 5;
+            if (int rc = check_window(win, first + i, a.l.h[i], a.l.w[i])) return rc;
+            a.l.img[i] = static_cast<const unsigned char *>(a.l.img[i]) + ((size_t)win[1] * a.l.w[i] + win[0]) * pixel;
+            a.win.cw[i] = win[2]; a.win.ch[i] = win[3];
+            a.win.flip |= (uint64_t)win[4] << i;
+        }
+        a.out = out; a.in_ch = in_ch; a.out_h = out_h; a.out_w = out_w;
+        const int per_row = out_h * ((out_w + 3) / 4), per_img = in_ch * per_row;
+        if (fmt == IMG_F16) hipLaunchKernelGGL(preprocess_windows<_Float16>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        else if (fmt == IMG_U8) hipLaunchKernelGGL(preprocess_windows<uint8_t>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        else if (fmt == IMG_U8_HWC) hipLaunchKernelGGL(preprocess_windows_hwc, dim3((per_row + 255) / 256, a.l.n), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(preprocess_windows<float>, dim3((per_img + 255) / 256, a.l.n), dim3(256), 0, stream, a);
         LDIT_HIP_CHECK(hipGetLastError());
     }
     return LDIT_OK;

@@ -37,6 +37,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, ops
+from .augment import DetectorAugment
 from .dp import Rank, all_reduce_sum, broadcast_from_main
 
 _FIELD = {n: i for i, n in enumerate(_lib.OPT_STATE_FIELDS)}
@@ -145,13 +146,17 @@ class DetectorTrainStep:
     multiplied by ``scale / (accumulate * world)``.  ``rank``: this process's :class:`~layoutdit_amd.dp.Rank`; with ``world > 1`` the
     bucket is summed over the ranks (one collective) before the update, and ``broadcast_parameters`` makes rank 0's weights everybody's
     at construction.  ``iters``, the warmup and :attr:`steps` count updates, not micro-batches.  With ``accumulate == 1`` and one rank
-    there is no bucket and nothing changes."""
+    there is no bucket and nothing changes.
+
+    ``augment``: a :class:`~layoutdit_amd.augment.DetectorAugment`; every :meth:`step` then trains on windows of its pages - random
+    crop, scale jitter and flip - drawn on the host from the augment's own generator: the windowed input transform
+    and one launch for the targets, no copy of a page and no synchronisation.  Without it the step launches what it always did."""
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 0.0, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  step_size: Optional[int] = None, gamma: float = 0.1, init_scale: float = 65536.0, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, loss_scaling: bool = True, max_grad_norm: Optional[float] = None,
                  param_groups: Optional[Sequence[dict]] = None, warmup_iters: int = 0, warmup_factor: float = 1e-3, accumulate: int = 1,
-                 rank: Optional[Rank] = None, broadcast_parameters: bool = True):
+                 rank: Optional[Rank] = None, broadcast_parameters: bool = True, augment: Optional[DetectorAugment] = None):
         from .modeling.detector import LayoutDetectionModel
         if not isinstance(model, LayoutDetectionModel):
             raise TypeError("DetectorTrainStep: expected a LayoutDetectionModel (the encoder alone trains with TrainStep)")
@@ -164,7 +169,12 @@ class DetectorTrainStep:
                 raise RuntimeError(f"DetectorTrainStep: rank {rank.rank} of {rank.world} without an initialised process group - call dp.init() first")
             if dist.get_world_size() != rank.world:
                 raise RuntimeError(f"DetectorTrainStep: rank.world = {rank.world}, the process group has {dist.get_world_size()} ranks")
+        if augment is not None and not isinstance(augment, DetectorAugment):
+            raise TypeError("DetectorTrainStep: augment must be a layoutdit_amd.augment.DetectorAugment")
         self.model = model
+        self.augment = augment
+        if augment is not None:                                              # what keeps a box under a window is the augment's to say
+            model.model.transform.min_visibility, model.model.transform.min_size = augment.min_visibility, augment.min_size
         self.encoder = model.model.backbone.backbone.dit
         if self.encoder.compute_dtype == "fp8" or (self.encoder.compute_dtype == "mxfp8" and not getattr(self.encoder, "qat", False)):
             raise NotImplementedError(f"DetectorTrainStep: the {self.encoder.compute_dtype} encoder is not covered - 'fp8' and 'mxfp8' are inference "
@@ -222,20 +232,27 @@ class DetectorTrainStep:
 
     # ---- the iteration ----------------------------------------------------------------------------------------------------------------
     def step(self, images: List[torch.Tensor], targets: List[Dict[str, torch.Tensor]],
-             generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+             generator: Optional[torch.Generator] = None, windows=None) -> Dict[str, torch.Tensor]:
         """One iteration: gradients cleared, ``model.losses``, backward on the scaled sum, check / advance / update.  Returns the four
         unscaled, detached losses.  From the backward on there is no host synchronisation; the loss scale enters the graph as a device
         tensor.  (The input transform's host bookkeeping is ``model.losses``'s own.)
 
         With ``accumulate`` or ranks every call is one micro-batch: the loss is multiplied by ``scale * (1 / (accumulate * world))`` -
         one fp32 product of the block's scale and a constant, on the device -, the gradients are folded into the bucket, and only the
-        ``accumulate``-th call goes on to :meth:`apply`.  The losses returned are this call's, of this rank."""
+        ``accumulate``-th call goes on to :meth:`apply`.  The losses returned are this call's, of this rank.
+
+        ``windows``: this call's windows (``LayoutDetectionModel.losses``); left out, an ``augment`` draws them - one draw per call."""
         self._require_train_mode()
+        if windows is None and self.augment is not None:
+            windows = self.augment.sample([img.shape[-2:] for img in images])
         if self.pending_micro_batches == 0 and self.warmup_iters and self.iters <= self.warmup_iters:   # the last of these fills writes the full rate
             self._write_lr()
         for p in self.model.parameters():
             p.grad = None
-        losses = self.model.losses(images, targets, generator=generator)
+        if windows is None:
+            losses = self.model.losses(images, targets, generator=generator)
+        else:
+            losses = self.model.losses(images, targets, generator=generator, windows=windows)
         total = sum(losses.values())
         if self._use_bucket:
             total = total * (self._state_f[_FIELD["scale"]] * self._loss_mul if self.loss_scaling else self._loss_mul)
@@ -549,6 +566,8 @@ class DetectorTrainStep:
         if self._clip is not None:
             host = self._clip.cpu()
             out["clip"] = {n: (int(host.view(torch.int32)[i]) if n == "clipped_steps" else float(host[i])) for n, i in _CLIP.items()}
+        if self.augment is not None:
+            out["augment"] = self.augment.state_dict()
         return out
 
     def load_state_dict(self, sd: dict) -> None:
@@ -574,6 +593,8 @@ class DetectorTrainStep:
                 else:
                     host[i] = float(sd["clip"][n])
             self._clip.copy_(host)
+        if self.augment is not None and "augment" in sd:
+            self.augment.load_state_dict(sd["augment"])
         self._pending = {n: (sd["exp_avg"][n].detach().to(self.device, torch.float32), sd["exp_avg_sq"][n].detach().to(self.device, torch.float32))
                          for n in sd["exp_avg"]}
         with torch.no_grad():

@@ -140,40 +140,48 @@ class LayoutDetectionModel(nn.Module):
             return m.roi_heads(feats, proposals, count, image_size, padded=True)
 
     def rpn_losses(self, images: List[torch.Tensor], targets: List[Dict[str, torch.Tensor]],
-                   generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+                   generator: Optional[torch.Generator] = None, windows=None) -> Dict[str, torch.Tensor]:
         """The RPN half of the reference's loss dict: ``{"loss_objectness", "loss_rpn_box_reg"}`` for a list of ``[3, h, w]`` images
         and the reference's targets (``{"boxes": [G, 4] in the image's own coordinates, ...}`` per image).  Train mode only.  The
         transform rescales the boxes with the images, the backbone runs with gradients, the RPN in train mode; ``backward()`` on
         the losses reaches ``rpn.head``, the FPN and the encoder.  :meth:`losses` adds the box head's two.  ``generator`` seeds the
-        sampler's keys."""
+        sampler's keys.  ``windows``: as for :meth:`losses`."""
         if not self.training:
             raise RuntimeError("LayoutDetectionModel.rpn_losses: train mode only - call .train() first")
         if targets is None:
             raise ValueError("LayoutDetectionModel.rpn_losses: targets are required")
         m = self.model
-        image_list, targets = m.transform(images, targets)
+        image_list, targets = m.transform(images, targets, windows=windows)
+        if windows is not None:
+            targets = (targets[0], targets[2])                       # the RPN's pair of the padded triple
         batch = image_list.tensors
         feats = {k: _nhwc_f32(v) for k, v in m.backbone(batch).items()}
         _, losses = m.rpn(feats, tuple(batch.shape[-2:]), targets=targets, padded=True, generator=generator)
         return losses
 
     def losses(self, images: List[torch.Tensor], targets: List[Dict[str, torch.Tensor]],
-               generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+               generator: Optional[torch.Generator] = None, windows=None) -> Dict[str, torch.Tensor]:
         """The reference's ``loss_dict = model(images, targets)``: ``{"loss_classifier", "loss_box_reg", "loss_objectness",
         "loss_rpn_box_reg"}`` for a list of ``[3, h, w]`` images and targets ``{"boxes": [G, 4] in the image's own coordinates,
         "labels": [G] in [1, num_classes]}``.  Train mode only.  The transform and the backbone run once; the RPN in train mode gives
         its two losses and its proposals (detached), the box head samples from them and gives the other two.  ``backward()`` on the
-        sum reaches the box head, ``rpn.head``, the FPN and the encoder.  ``generator`` seeds both samplers' keys."""
+        sum reaches the box head, ``rpn.head``, the FPN and the encoder.  ``generator`` seeds both samplers' keys.
+
+        ``windows`` (train-time crop, scale jitter and flip; one ``(x0, y0, cw, ch, flip)`` per image, e.g. from
+        ``augment.DetectorAugment.sample``): the losses of the cropped (mirrored) pages and of the targets those still show - bit for
+        bit ``losses(crops, crop_targets)`` where the padded width of the targets is the same - without copying a page and without a
+        synchronisation.  None: nothing changes."""
         if not self.training:
             raise RuntimeError("LayoutDetectionModel.losses: train mode only - call .train() first")
         if targets is None:
             raise ValueError("LayoutDetectionModel.losses: targets are required")
         m = self.model
-        image_list, targets = m.transform(images, targets)
+        image_list, targets = m.transform(images, targets, windows=windows)
         batch = image_list.tensors
         image_size = tuple(batch.shape[-2:])
         feats = {k: _nhwc_f32(v) for k, v in m.backbone(batch).items()}
-        (proposals, _, count), rpn_losses = m.rpn(feats, image_size, targets=targets, padded=True, generator=generator)
+        rpn_targets = targets if windows is None else (targets[0], targets[2])    # the RPN takes the pair, the box head the triple
+        (proposals, _, count), rpn_losses = m.rpn(feats, image_size, targets=rpn_targets, padded=True, generator=generator)
         out = m.roi_heads(feats, proposals.detach(), count, image_size, targets=targets, padded=True, generator=generator)
         out.update(rpn_losses)
         return out

@@ -55,6 +55,8 @@ class DetectorInputTransform(nn.Module):
             raise NotImplementedError(f"fixed size {self.out_h}x{self.out_w} is not a multiple of {size_divisible}: batching "
                                       "would pad (LayoutDiT's 224x224 does not)")
         self.mean, self.std = float(image_mean[0]), float(image_std[0])
+        # what a box must keep under a window to stay a target (ops.augment_targets); read by the windowed forward only
+        self.min_visibility, self.min_size = 0.3, 1.0
 
     @staticmethod
     def _operands(images: List[torch.Tensor]) -> List[torch.Tensor]:
@@ -62,7 +64,13 @@ class DetectorInputTransform(nn.Module):
         ``[h, w, C]`` page under ``permute(2, 0, 1)`` is read in place (``ops.image_list_args``) and a copy would undo that."""
         return [img if img.dtype == torch.uint8 else img.contiguous() for img in images]
 
-    def forward(self, images: List[torch.Tensor], targets: Optional[List[Dict[str, torch.Tensor]]] = None):
+    def forward(self, images: List[torch.Tensor], targets: Optional[List[Dict[str, torch.Tensor]]] = None, windows=None):
+        """``windows`` (train-time crop / flip, ``ops.window_args``; one ``(x0, y0, cw, ch, flip)`` per image): the batch is resized from
+        the windows instead of the whole pages (``ops.preprocess(..., windows=)``: no cropped copy) and the targets come back as the
+        padded triple ``(gt_boxes [B, Gmax, 4], gt_labels int32 [B, Gmax] or None, gt_count int32 [B])`` in the batch's coordinates -
+        the host-shaped padding of ``RoIHeads.pad_targets`` (of ``RegionProposalNetwork.pad_targets`` where the targets carry no
+        labels), then ``ops.augment_targets`` with ``self.min_visibility`` / ``self.min_size``: boxes a window no longer shows are gone,
+        without a synchronisation.  Without ``windows`` nothing changes."""
         if len(images) == 0:
             raise ValueError("empty image list")
         for img in images:
@@ -70,6 +78,8 @@ class DetectorInputTransform(nn.Module):
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(img.shape)}")
         if targets is not None and len(targets) != len(images):
             raise ValueError("one target per image")
+        if windows is not None:
+            return self._forward_windows(images, targets, windows)
         batch = ops.preprocess(self._operands(images), size=(self.out_h, self.out_w), mean=self.mean, std=self.std)
         out_targets = None
         if targets is not None:
@@ -80,6 +90,22 @@ class DetectorInputTransform(nn.Module):
                     t["boxes"] = resize_boxes(t["boxes"], img.shape[-2:], (self.out_h, self.out_w))
                 out_targets.append(t)
         return ImageList(batch, [(self.out_h, self.out_w)] * len(images)), out_targets
+
+    def _forward_windows(self, images, targets, windows):
+        from .roi_heads import RoIHeads
+        from .rpn import RegionProposalNetwork
+        size = (self.out_h, self.out_w)
+        batch = ops.preprocess(self._operands(images), size=size, mean=self.mean, std=self.std, windows=windows)
+        out_targets = None
+        if targets is not None:
+            device = images[0].device
+            if isinstance(targets, (tuple, list)) and len(targets) == 3 and isinstance(targets[0], torch.Tensor) or \
+                    all("labels" in t for t in targets):
+                gt_boxes, gt_labels, gt_count = RoIHeads.pad_targets(targets, device)
+            else:
+                (gt_boxes, gt_count), gt_labels = RegionProposalNetwork.pad_targets(targets, device), None
+            out_targets = ops.augment_targets(gt_boxes, gt_labels, gt_count, windows, size, self.min_visibility, self.min_size)
+        return ImageList(batch, [size] * len(images)), out_targets
 
     def encode(self, encoder, images: List[torch.Tensor], taps: Optional[Sequence[int]] = None):
         """``encoder(self(images)[0].tensors)`` in eval mode with the transform FUSED into the encoder's patch-embedding load

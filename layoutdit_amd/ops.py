@@ -6,6 +6,7 @@ Every function requires CUDA(=HIP) fp32 contiguous tensors and raises otherwise 
 from __future__ import annotations
 
 import ctypes as C
+import operator
 from typing import Optional, Sequence
 
 import torch
@@ -183,17 +184,73 @@ def tap_to_map_autograd(tap: torch.Tensor, gh: int, gw: int, scale: float) -> to
     return _TapToMapFn.apply(tap, gh, gw, scale)
 
 
-def preprocess(images: Sequence[torch.Tensor], size=224, mean: float = 0.5, std: float = 0.5) -> torch.Tensor:
+def window_args(windows, count: int, sizes: Optional[Sequence[Sequence[int]]] = None):
+    """Train-time windows as the C ABI takes them: the HOST int32 array ``[count][5]`` of ``(x0, y0, cw, ch, flip)`` per image, from
+    a sequence of five-integer rows or a CPU int32 tensor ``[count, 5]``, checked on the host before anything is launched: ``cw, ch >=
+    1``, ``x0, y0 >= 0``, ``flip`` 0 or 1 and, where ``sizes`` gives the pages' ``(h, w)``, ``x0 + cw <= w`` and ``y0 + ch <= h``.
+    A ``ValueError`` names the image."""
+    if isinstance(windows, torch.Tensor):
+        if windows.is_cuda or windows.dtype != torch.int32:
+            raise ValueError(f"windows: a tensor of windows must be int32 on the CPU (host descriptors), got {windows.dtype} on {windows.device}")
+        if windows.dim() != 2:
+            raise ValueError(f"windows: expected shape [{count}, 5], got {tuple(windows.shape)}")
+        rows = windows.tolist()
+    else:
+        rows = list(windows)
+    if len(rows) != count:
+        raise ValueError(f"windows: {len(rows)} windows for {count} images (expected shape [{count}, 5])")
+    flat = []
+    for i, r in enumerate(rows):
+        try:
+            r = [operator.index(v) for v in r]           # integers only: a fractional window is not silently truncated
+        except TypeError:
+            r = None
+        if r is None or len(r) != 5:
+            raise ValueError(f"windows[{i}]: the window of images[{i}] must be five integers (x0, y0, cw, ch, flip), got {rows[i]!r}")
+        x0, y0, cw, ch, flip = r
+        if cw < 1 or ch < 1:
+            raise ValueError(f"windows[{i}]: the window of images[{i}] has extent {cw} x {ch} (width x height); both must be at least 1")
+        if x0 < 0 or y0 < 0:
+            raise ValueError(f"windows[{i}]: the window of images[{i}] starts at ({x0}, {y0}); the origin must not be negative")
+        if max(x0 + cw, y0 + ch) >= 2 ** 31:
+            raise ValueError(f"windows[{i}]: the window of images[{i}] does not fit 32-bit pixel coordinates")
+        if sizes is not None:
+            h, w = int(sizes[i][0]), int(sizes[i][1])
+            if x0 + cw > w or y0 + ch > h:
+                raise ValueError(f"windows[{i}]: x [{x0}, {x0 + cw}) y [{y0}, {y0 + ch}) leaves images[{i}], a {w} x {h} page (width x height)")
+        if flip not in (0, 1):
+            raise ValueError(f"windows[{i}]: flip = {flip} for images[{i}]; it must be 0 or 1")
+        flat.extend(r)
+    return (C.c_int32 * (5 * count))(*flat)
+
+
+def preprocess(images: Sequence[torch.Tensor], size=224, mean: float = 0.5, std: float = 0.5, windows=None) -> torch.Tensor:
     """The detector's input transform in one kernel (ref src/layoutdit/modeling/model.py:50-54: fixed_size 224,
     mean = std = 0.5): list of ``[3, h, w]`` images in [0, 1] (all fp32 or all fp16) -> normalised, bilinearly resized
     fp32 ``[B, 3, size, size]``.  A uint8 list (codes ``c`` standing for ``c / 255``, planar or interleaved: ``image_list_args``)
-    gives, bit for bit, what the fp32 list ``img.float().div(255)`` gives (``ldit_preprocess_u8``)."""
+    gives, bit for bit, what the fp32 list ``img.float().div(255)`` gives (``ldit_preprocess_u8``).
+
+    ``windows`` (train-time crop and flip; :func:`window_args`): per image ``(x0, y0, cw, ch, flip)``.  Row ``i`` is then, bit for bit,
+    what this function gives for a contiguous copy of ``images[i][:, y0:y0 + ch, x0:x0 + cw]`` (``.flip(-1)`` where ``flip`` is 1) -
+    without the copy, and without reading the page outside the window (``ldit_preprocess_win_*``)."""
     lib = _lib.load()
+    wins = None
+    if windows is not None:                              # host checks first: they need no GPU
+        if any(not isinstance(t, torch.Tensor) or t.dim() != 3 for t in images):
+            raise ValueError("every image must be [C, h, w] with the same C")
+        wins = window_args(windows, len(images), [t.shape[-2:] for t in images])
     imgs, ptrs, hs, ws, fmt, ch = image_list_args(images)
     B = len(imgs)
     out_h, out_w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
     out = torch.empty((B, ch, out_h, out_w), device=imgs[0].device, dtype=torch.float32)
-    if fmt in (IMG_U8, IMG_U8_HWC):
+    if wins is not None:
+        if fmt in (IMG_U8, IMG_U8_HWC):
+            _launch(_device(*imgs), lib.ldit_preprocess_win_u8, ptrs, hs, ws, wins, int(fmt == IMG_U8_HWC), B, ch, mean, std, out_h, out_w, _ptr(out))
+        elif fmt == IMG_F16:
+            _launch(_device(*imgs), lib.ldit_preprocess_win_f16, ptrs, hs, ws, wins, B, ch, mean, std, out_h, out_w, _ptr(out))
+        else:
+            _launch(_device(*imgs), lib.ldit_preprocess_win_f32, ptrs, hs, ws, wins, B, ch, mean, std, out_h, out_w, _ptr(out))
+    elif fmt in (IMG_U8, IMG_U8_HWC):
         _launch(_device(*imgs), lib.ldit_preprocess_u8, ptrs, hs, ws, int(fmt == IMG_U8_HWC), B, ch, mean, std, out_h, out_w, _ptr(out))
     elif fmt == IMG_F16:
         _launch(_device(*imgs), lib.ldit_preprocess_f16, ptrs, hs, ws, B, ch, mean, std, out_h, out_w, _ptr(out))
@@ -1491,3 +1548,41 @@ def coco_accumulate(code: torch.Tensor, rank: torch.Tensor, npig: torch.Tensor, 
     _launch(_device(code, rank, npig, precision, recall, keys, index), lib.ldit_coco_accumulate, _ptr(keys), _ptr(index), _ptr(code), _ptr(rank),
             _ptr(npig), n, Ds, K, (C.c_double * 101)(*rec), (C.c_int32 * 3)(*md), _ptr(precision), _ptr(recall))
     return precision, recall
+
+
+# ---- train-time augmentation of the targets (include/ldit.h "train-time augmentation"; csrc/augment.hip) ------------------------------
+def augment_targets(gt_boxes: torch.Tensor, gt_labels: Optional[torch.Tensor], gt_count: torch.Tensor, windows, size,
+                    min_visibility: float = 0.3, min_size: float = 1.0):
+    """The padded targets of a batch through the windows :func:`preprocess` cut from its pages: ``gt_boxes`` [B, Gmax, 4] in the pages'
+    pixels, ``gt_labels`` int32 [B, Gmax] or None, ``gt_count`` int32 [B], ``windows`` as for :func:`window_args`, ``size`` the batch's
+    ``(out_h, out_w)`` (or one int).  A box is clipped to its window and kept if its clipped area is positive and at least
+    ``min_visibility`` of its own; it is shifted to the window, mirrored under ``flip`` and scaled to the batch, and kept if both sides
+    are then at least ``min_size``.  Returns ``(out_boxes [B, Gmax, 4], out_labels int32 [B, Gmax] or None, out_count int32 [B])``: the
+    kept rows in their original order, zeros behind them - the triple ``RoIHeads`` takes, its first and last member the pair of the
+    RPN.  Rows at or beyond ``gt_count`` are never read.  ``Gmax <= RPN_TARGETS_MAX_GT``.  One launch per 48 images, no
+    synchronisation."""
+    lib = _lib.load()
+    if not isinstance(gt_boxes, torch.Tensor) or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise ValueError(f"augment_targets: gt_boxes {tuple(getattr(gt_boxes, 'shape', ()))} is not [B, Gmax, 4]")
+    B, Gmax = gt_boxes.shape[:2]
+    wins = window_args(windows, B)                       # host checks first: they need no GPU
+    out_h, out_w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if out_h <= 0 or out_w <= 0 or not float(min_visibility) >= 0.0 or not float(min_size) >= 0.0:
+        raise ValueError("augment_targets: need a positive size and non-negative min_visibility and min_size")
+    gt_boxes, gt_count = _req(gt_boxes, "gt_boxes"), _req_i32(gt_count, "gt_count")
+    if gt_labels is not None:
+        gt_labels = _req_i32(gt_labels, "gt_labels")
+    if tuple(gt_count.shape) != (B,) or (gt_labels is not None and tuple(gt_labels.shape) != (B, Gmax)):
+        raise ValueError(f"augment_targets: gt_count {tuple(gt_count.shape)} / gt_labels "
+                         f"{None if gt_labels is None else tuple(gt_labels.shape)} are not [{B}] / [{B}, {Gmax}]")
+    if B == 0 or Gmax == 0:
+        raise ValueError("augment_targets: empty problem (pad gt_boxes to at least one row)")
+    if Gmax > RPN_TARGETS_MAX_GT:
+        raise ValueError(f"augment_targets: Gmax = {Gmax}, at most {RPN_TARGETS_MAX_GT} boxes per image are handled")
+    dev = gt_boxes.device
+    out_boxes = torch.empty((B, Gmax, 4), device=dev, dtype=torch.float32)
+    out_labels = None if gt_labels is None else torch.empty((B, Gmax), device=dev, dtype=torch.int32)
+    out_count = torch.empty((B,), device=dev, dtype=torch.int32)
+    _launch(_device(gt_boxes, gt_labels, gt_count), lib.ldit_augment_targets_f32, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_count), wins, B,
+            Gmax, out_h, out_w, float(min_visibility), float(min_size), _ptr(out_boxes), _ptr(out_labels), _ptr(out_count))
+    return out_boxes, out_labels, out_count
