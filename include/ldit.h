@@ -994,6 +994,38 @@ typedef struct ldit_acc_segment {
  * segment (LDIT_EINVAL); a segment of more than 2^41 elements, whose grid would pass 2^31 - 1 blocks (LDIT_EUNSUPPORTED). */
 int ldit_grads_accumulate_multi_f32(const ldit_acc_segment *segs, int32_t S, int32_t overwrite, ldit_stream stream);
 
+/* -- an exponential moving average of the weights inside the update, and the exchange that evaluates on it (additive) --
+ * ldit_adamw_groups_multi_f32 and, in the same launch, for every segment s with a shadow ema[s] (n fp32 elements, 4-byte aligned,
+ * overlapping nothing else of the segment; NULL: the segment has none, and `ema` itself NULL: no segment has one)
+ *     E = E + w * (P - E)          one fp32 multiply-add on the P the update just formed, still in registers,
+ * stored beside p, m, v and the mirror.  w is formed in the kernel from the device block, in double, rounded to float once:
+ *     d = ema_warmup ? min(ema_decay, (1 + step) / (10 + step)) : ema_decay ,   w = float(1 - d) ,
+ * step = state->step after ldit_opt_advance: the steps TAKEN, this one included - a skipped step neither moves a shadow (state->skip
+ * set: nothing at all is written) nor ages the warmup.  p, m, v and the mirror receive ldit_adamw_groups_multi_f32's bits: with
+ * lr_scale == 1, one weight_decay and no clip block those of ldit_adamw_multi_f32(grad_mul = 1).  The shadow joins the alignment
+ * test of the 16-byte path.  `ema` is a HOST array parallel to `segs`; the shadow pointers ride beside the segments and their
+ * hyper-parameters in the kernel arguments, 52 segments per launch.  0 <= ema_decay < 1.  Refused before any launch like the call
+ * above, and: ema_decay outside [0, 1), a misaligned shadow (LDIT_EINVAL). */
+int ldit_adamw_ema_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyper *hyper, void *const *ema, int32_t S,
+                                    const ldit_opt_state *state, const ldit_clip_state *clip, double beta1, double beta2, float eps,
+                                    double ema_decay, int32_t ema_warmup, ldit_stream stream);
+
+/* One pair of the exchange: n fp32 elements at a and at b (4-byte aligned, disjoint; n == 0 allowed: its pointers are not looked at)
+ * and an optional bf16 copy of a (n bf16 elements, 2-byte aligned; 8-byte for the 16-byte path). */
+typedef struct ldit_swap_segment {
+    void *a;
+    void *b;
+    int64_t n;
+    void *bf16_mirror;
+} ldit_swap_segment;
+
+/* a[i] <-> b[i] for every element of every segment, moved as integers: -0.0, NaN payloads and infinities survive, and two calls
+ * are the identity bit for bit.  Where a mirror is given it receives bf16(new a).  Every element is read and written by exactly one
+ * thread: no atomics.  `segs` is a HOST array, 99 segments per launch in the kernel arguments; nothing is allocated (capturable).
+ * Refused before any launch: a null array with S > 0, a negative S or n, a null or misaligned pointer in a non-empty segment, an odd
+ * mirror address (LDIT_EINVAL); a segment of more than 2^41 elements (LDIT_EUNSUPPORTED). */
+int ldit_swap_multi_f32(const ldit_swap_segment *segs, int32_t S, ldit_stream stream);
+
 /* ---- COCO box evaluation: matching, accumulation ----
  * The arithmetic of the reference's Evaluator.score() (ref evaluation/evaluator.py:219-286, which hands a JSON file to a per-image,
  * per-category host loop) on padded device tensors: no host round trip, no allocation, no float atomics, capturable, every output a

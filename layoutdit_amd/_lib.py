@@ -71,11 +71,18 @@ class LditAccSegment(C.Structure):
     _fields_ = [("acc", C.c_void_p), ("g", C.c_void_p), ("n", C.c_int64)]
 
 
+class LditSwapSegment(C.Structure):
+    """One pair of the weight / shadow exchange and the optional bf16 copy of ``a`` (``ldit_swap_segment``, 32 bytes)."""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("n", C.c_int64), ("bf16_mirror", C.c_void_p)]
+
+
 OPT_STATE_FIELDS = tuple(n for n, _ in LditOptState._fields_)       # index of a field = its 4-byte slot in the block
 CLIP_STATE_FIELDS = tuple(n for n, _ in LditClipState._fields_)
 OPT_MAX_SEGMENTS = 64                                               # segments per launch (csrc/optim_multi.hip)
 OPT_GROUP_SEGMENTS = 48                                             # of the grouped update, whose hyper-parameters ride beside them
 ACC_MAX_SEGMENTS = 127                                              # of the fold into the gradient bucket: 24 bytes a segment
+EMA_MAX_SEGMENTS = 52                                               # of the grouped update with an EMA: a shadow pointer rides along too
+SWAP_MAX_SEGMENTS = 99                                              # of the weight / shadow exchange: 32 bytes a segment
 
 # name -> (restype, argtypes); every symbol include/ldit.h declares
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
@@ -206,6 +213,9 @@ SIGNATURES = {
                                               _vp]),
     "ldit_requant_train_mirror": (C.c_int, [C.POINTER(LditCfg), _vp, _vp, _sz, _vp, _vp]),
     "ldit_grads_accumulate_multi_f32": (C.c_int, [C.POINTER(LditAccSegment), _i32, _i32, _vp]),
+    "ldit_adamw_ema_groups_multi_f32": (C.c_int, [C.POINTER(LditOptSegment), C.POINTER(LditOptHyper), C.POINTER(_vp), _i32, _vp, _vp, C.c_double,
+                                                  C.c_double, _f32, C.c_double, _i32, _vp]),
+    "ldit_swap_multi_f32": (C.c_int, [C.POINTER(LditSwapSegment), _i32, _vp]),
     # COCO box evaluation
     "ldit_coco_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp]),

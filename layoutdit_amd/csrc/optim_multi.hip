@@ -18,6 +18,10 @@
 // Gradient accumulation and data-parallel ranks put one launch in front of all that: grads_accumulate_kernel folds
 // the gradient tensors into the slices of one flat bucket (acc = g, or acc = acc + g), 127 {acc, g, n} segments per launch by the
 // same scheme, and the launches above then read the bucket's slices as their gradients.
+//
+// An exponential moving average of the weights is the grouped update's launch with one more fp32 pointer per
+// segment beside the table: adamw_ema_groups_multi_kernel reads and writes the shadow element next to the p it just formed.
+// swap_multi_kernel exchanges weights and shadows (99 {a, b, n, mirror} segments per launch) for an evaluation on the average.
 #include "api_internal.h"
 
 namespace ldit {
@@ -55,10 +59,30 @@ struct AccLaunch {
 };
 static_assert(sizeof(AccLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
 
+constexpr int EMA_SEGS = 52;              // the update with an EMA: 52 x (48 + 8 + 8) bytes + the prefix table, under the same 3584
+struct EmaLaunch {
+    ldit_opt_segment seg[EMA_SEGS];
+    float *ema[EMA_SEGS];                 // the segment's fp32 shadow, or null: it has none
+    ldit_opt_hyper hyper[EMA_SEGS];
+    int first_block[EMA_SEGS + 1];
+    int n;
+};
+static_assert(sizeof(EmaLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
+
+constexpr int SWAP_SEGS = 99;             // the exchange: 99 x 32 bytes + the prefix table, under the same 3584
+struct SwapLaunch {
+    ldit_swap_segment seg[SWAP_SEGS];
+    int first_block[SWAP_SEGS + 1];
+    int n;
+};
+static_assert(sizeof(SwapLaunch) <= 3584, "the segment table must fit the kernel-argument block beside the scalars");
+
 template <typename T> struct launch_cap;
 template <> struct launch_cap<OptLaunch> { static constexpr int value = OPT_SEGS; };
 template <> struct launch_cap<GroupLaunch> { static constexpr int value = GROUP_SEGS; };
 template <> struct launch_cap<AccLaunch> { static constexpr int value = ACC_SEGS; };
+template <> struct launch_cap<EmaLaunch> { static constexpr int value = EMA_SEGS; };
+template <> struct launch_cap<SwapLaunch> { static constexpr int value = SWAP_SEGS; };
 
 // the segment of this block: the last j with first_block[j] <= blk (every segment in a launch has at least one block)
 template <typename T>
@@ -231,15 +255,21 @@ __device__ __forceinline__ AdamwConsts adamw_consts(const ldit_opt_state *__rest
     return c;
 }
 
-// this workgroup's 1024 elements of one segment, from element `base` on
-__device__ __forceinline__ void adamw_block(const ldit_opt_segment &sg, const int64_t base, const int tid, const AdamwConsts &c)
+// the moving average of the weights, on the P the update just formed: one fp32 multiply-add, E + w (P - E)
+__device__ __forceinline__ float ema_element(const float E, const float P, const float w) { return E + w * (P - E); }
+
+// this workgroup's 1024 elements of one segment, from element `base` on.  EMA: `shadow` (null: this segment has none) moves towards
+// the new p by the weight w in the same pass; without EMA neither is looked at and the code is the update's alone.
+template <bool EMA>
+__device__ __forceinline__ void adamw_block(const ldit_opt_segment &sg, const int64_t base, const int tid, const AdamwConsts &c,
+                                            float *shadow = nullptr, const float w = 0.0f)
 {
     float *p = static_cast<float *>(sg.p), *m = static_cast<float *>(sg.m), *v = static_cast<float *>(sg.v);
     const float *g = static_cast<const float *>(sg.g);
     bf16_t *mirror = static_cast<bf16_t *>(sg.bf16_mirror);
     const int64_t n = sg.n;
     const bool vec = quad_aligned(p) && quad_aligned(g) && quad_aligned(m) && quad_aligned(v) &&
-                     (reinterpret_cast<uintptr_t>(mirror) & 7u) == 0;
+                     (reinterpret_cast<uintptr_t>(mirror) & 7u) == 0 && (!EMA || quad_aligned(shadow));
     if (vec) {
         const int64_t i = base + 4 * tid;
         if (i + 4 <= n) {
@@ -255,12 +285,19 @@ __device__ __forceinline__ void adamw_block(const ldit_opt_segment &sg, const in
             if (mirror) *reinterpret_cast<bf16x4 *>(mirror + i) = bf16x4{(bf16_t)P[0], (bf16_t)P[1], (bf16_t)P[2], (bf16_t)P[3]};
             *reinterpret_cast<f32x4 *>(m + i) = Mo;
             *reinterpret_cast<f32x4 *>(v + i) = Vo;
+            if (EMA && shadow) {
+                f32x4 E = *reinterpret_cast<f32x4 *>(shadow + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) E[e] = ema_element(E[e], P[e], w);
+                *reinterpret_cast<f32x4 *>(shadow + i) = E;
+            }
         } else {
             for (int64_t e = i; e < n; ++e) {        // the last n % 4 elements of the segment
                 float P = p[e], Mo = m[e], Vo = v[e];
                 adamw_element(P, g[e], Mo, Vo, c);
                 p[e] = P; m[e] = Mo; v[e] = Vo;
                 if (mirror) mirror[e] = (bf16_t)P;
+                if (EMA && shadow) shadow[e] = ema_element(shadow[e], P, w);
             }
         }
     } else {
@@ -272,6 +309,7 @@ __device__ __forceinline__ void adamw_block(const ldit_opt_segment &sg, const in
                 adamw_element(P, g[e], Mo, Vo, c);
                 p[e] = P; m[e] = Mo; v[e] = Vo;
                 if (mirror) mirror[e] = (bf16_t)P;
+                if (EMA && shadow) shadow[e] = ema_element(shadow[e], P, w);
             }
         }
     }
@@ -284,7 +322,7 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const OptLaunch a, con
     const int j = find_segment(a, (int)blockIdx.x);
     const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
     const AdamwConsts c = adamw_consts(st, (double)st->lr, wd, grad_mul * st->inv_scale_used, b1, omb1, b2, omb2, eps);
-    adamw_block(a.seg[j], base, threadIdx.x, c);
+    adamw_block<false>(a.seg[j], base, threadIdx.x, c);
 }
 
 // ---- 3b. the same update with the segment's own {lr_scale, weight_decay} and the clip coefficient in the gradient multiplier -------
@@ -299,7 +337,25 @@ __global__ void __launch_bounds__(256) adamw_groups_multi_kernel(const GroupLaun
     const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
     const float gs = clip ? clip->clip_coef * st->inv_scale_used : st->inv_scale_used;
     const AdamwConsts c = adamw_consts(st, (double)st->lr * (double)a.hyper[j].lr_scale, a.hyper[j].weight_decay, gs, b1, omb1, b2, omb2, eps);
-    adamw_block(a.seg[j], base, threadIdx.x, c);
+    adamw_block<false>(a.seg[j], base, threadIdx.x, c);
+}
+
+// ---- 3c. the grouped update with an exponential moving average of the weights in the same launch ----------------
+// The weight of this step from the block: decay, or min(decay, (1 + step) / (10 + step)) under warmup, step the count of steps TAKEN
+// (opt_advance ran: this one included), so a skipped step does not age the warmup and the host needs no count.  In double, 1 - d
+// rounded to float once.  Everything else is adamw_groups_multi_kernel's.
+__global__ void __launch_bounds__(256) adamw_ema_groups_multi_kernel(const EmaLaunch a, const ldit_opt_state *__restrict__ st,
+                                                                     const ldit_clip_state *__restrict__ clip, float b1, float omb1, float b2,
+                                                                     float omb2, float eps, double ema_decay, int ema_warmup)
+{
+    if (st->skip) return;                            // a skipped step writes nothing at all: no shadow moves either
+    const int j = find_segment(a, (int)blockIdx.x);
+    const int64_t base = (int64_t)((int)blockIdx.x - a.first_block[j]) * OPT_BLOCK_ELEMS;
+    const float gs = clip ? clip->clip_coef * st->inv_scale_used : st->inv_scale_used;
+    const AdamwConsts c = adamw_consts(st, (double)st->lr * (double)a.hyper[j].lr_scale, a.hyper[j].weight_decay, gs, b1, omb1, b2, omb2, eps);
+    const double step = (double)st->step;
+    const double d = ema_warmup ? fmin(ema_decay, (1.0 + step) / (10.0 + step)) : ema_decay;
+    adamw_block<true>(a.seg[j], base, threadIdx.x, c, a.ema[j], (float)(1.0 - d));
 }
 
 // ---- 2b. the global norm and the clip coefficient, one workgroup, after the state machine ------------------------------------------
@@ -365,6 +421,45 @@ __global__ void __launch_bounds__(256) grads_accumulate_kernel(const AccLaunch a
         for (int k = 0; k < 4; ++k) {
             const int64_t e = base + tid + 256 * k;
             if (e < n) fold_element<OVERWRITE>(acc, g, e);
+        }
+    }
+}
+
+// ---- the exchange of the weights with their averages: a <-> b as integers, bf16(new a) into the mirror ---------------------------------
+// Every element is read and written by exactly one thread, so two launches are the identity bit for bit.
+__device__ __forceinline__ void swap_element(uint32_t *a, uint32_t *b, bf16_t *mirror, const int64_t e)
+{
+    const uint32_t A = a[e], B = b[e];
+    a[e] = B;
+    b[e] = A;
+    if (mirror) mirror[e] = (bf16_t)__uint_as_float(B);
+}
+
+__global__ void __launch_bounds__(256) swap_multi_kernel(const SwapLaunch s)
+{
+    const int tid = threadIdx.x;
+    const int j = find_segment(s, (int)blockIdx.x);
+    uint32_t *a = static_cast<uint32_t *>(s.seg[j].a), *b = static_cast<uint32_t *>(s.seg[j].b);
+    bf16_t *mirror = static_cast<bf16_t *>(s.seg[j].bf16_mirror);
+    const int64_t n = s.seg[j].n;
+    const int64_t base = (int64_t)((int)blockIdx.x - s.first_block[j]) * OPT_BLOCK_ELEMS;
+    if (quad_aligned(a) && quad_aligned(b) && (reinterpret_cast<uintptr_t>(mirror) & 7u) == 0) {
+        const int64_t i = base + 4 * tid;
+        if (i + 4 <= n) {
+            const u32x4 A = *reinterpret_cast<const u32x4 *>(a + i), B = *reinterpret_cast<const u32x4 *>(b + i);
+            *reinterpret_cast<u32x4 *>(a + i) = B;
+            *reinterpret_cast<u32x4 *>(b + i) = A;
+            if (mirror)
+                *reinterpret_cast<bf16x4 *>(mirror + i) = bf16x4{(bf16_t)__uint_as_float(B[0]), (bf16_t)__uint_as_float(B[1]),
+                                                                 (bf16_t)__uint_as_float(B[2]), (bf16_t)__uint_as_float(B[3])};
+        } else {
+            for (int64_t e = i; e < n; ++e) swap_element(a, b, mirror, e);      // the last n % 4 elements of the segment
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t e = base + tid + 256 * k;
+            if (e < n) swap_element(a, b, mirror, e);
         }
     }
 }
@@ -572,6 +667,58 @@ int ldit_adamw_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyp
         for (int k = 0; k < a.n; ++k) a.hyper[k] = hyper[index[k]];
         for (int k = a.n; k < GROUP_SEGS; ++k) a.hyper[k] = ldit_opt_hyper{0.0f, 0.0f};
         LAUNCH_CHECKED(adamw_groups_multi_kernel, dim3(blocks), dim3(256), 0, stream, a, state, clip, b1, omb1, b2, omb2, eps);
+        return LDIT_OK;
+    });
+}
+
+int ldit_adamw_ema_groups_multi_f32(const ldit_opt_segment *segs, const ldit_opt_hyper *hyper, void *const *ema, int32_t S,
+                                    const ldit_opt_state *state, const ldit_clip_state *clip, double beta1, double beta2, float eps,
+                                    double ema_decay, int32_t ema_warmup, ldit_stream stream_)
+{
+    const char *what = "adamw_ema_groups_multi";
+    LDIT_TRY(validate(what, segs, S, state, true));
+    if (S > 0 && !hyper) return fail(LDIT_EINVAL, "%s: null hyper-parameter array", what);
+    for (int32_t s = 0; s < S; ++s) {
+        if (!(hyper[s].lr_scale >= 0.0f) || !(hyper[s].weight_decay >= 0.0f))
+            return fail(LDIT_EINVAL, "%s: segment %d: lr_scale and weight_decay must be >= 0", what, s);
+        if (ema && segs[s].n > 0 && !aligned4(ema[s])) return fail(LDIT_EINVAL, "%s: segment %d: the shadow must be 4-byte aligned", what, s);
+    }
+    if (clip && !aligned4(clip)) return fail(LDIT_EINVAL, "%s: clip block must be 4-byte aligned", what);
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LDIT_EINVAL, "%s: betas must lie in [0, 1)", what);
+    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return fail(LDIT_EINVAL, "%s: ema_decay must lie in [0, 1)", what);
+    const float b1 = (float)beta1, omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return for_each_launch<EmaLaunch>(segs, S, [&](EmaLaunch &a, unsigned blocks, const int32_t *index) -> int {
+        for (int k = 0; k < EMA_SEGS; ++k) {
+            a.hyper[k] = k < a.n ? hyper[index[k]] : ldit_opt_hyper{0.0f, 0.0f};
+            a.ema[k] = k < a.n && ema ? static_cast<float *>(ema[index[k]]) : nullptr;
+        }
+        LAUNCH_CHECKED(adamw_ema_groups_multi_kernel, dim3(blocks), dim3(256), 0, stream, a, state, clip, b1, omb1, b2, omb2, eps, ema_decay,
+                       (int)(ema_warmup != 0));
+        return LDIT_OK;
+    });
+}
+
+int ldit_swap_multi_f32(const ldit_swap_segment *segs, int32_t S, ldit_stream stream_)
+{
+    const char *what = "swap_multi";
+    if (S < 0) return fail(LDIT_EINVAL, "%s: negative segment count %d", what, S);
+    if (S > 0 && !segs) return fail(LDIT_EINVAL, "%s: null segment array", what);
+    for (int32_t s = 0; s < S; ++s) {
+        const ldit_swap_segment &q = segs[s];
+        if (q.n < 0) return fail(LDIT_EINVAL, "%s: segment %d has negative length %lld", what, s, (long long)q.n);
+        if (q.n == 0) continue;
+        if (q.n > OPT_MAX_BLOCKS * (int64_t)OPT_BLOCK_ELEMS)
+            return fail(LDIT_EUNSUPPORTED, "%s: segment %d longer than 2^41 elements: its grid exceeds 2^31 - 1 blocks", what, s);
+        if (!q.a || !q.b) return fail(LDIT_EINVAL, "%s: segment %d has a null pointer", what, s);
+        if (!aligned4(q.a) || !aligned4(q.b)) return fail(LDIT_EINVAL, "%s: segment %d: fp32 pointers must be 4-byte aligned", what, s);
+        if (reinterpret_cast<uintptr_t>(q.bf16_mirror) & 1u) return fail(LDIT_EINVAL, "%s: segment %d: bf16 mirror must be 2-byte aligned", what, s);
+    }
+    LDIT_TRY(need_device());
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return for_each_launch<SwapLaunch>(segs, S, [&](const SwapLaunch &a, unsigned blocks, const int32_t *) -> int {
+        LAUNCH_CHECKED(swap_multi_kernel, dim3(blocks), dim3(256), 0, stream, a);
         return LDIT_OK;
     });
 }

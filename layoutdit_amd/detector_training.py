@@ -26,11 +26,16 @@ update.  Both go through one flat fp32 bucket that one multi-tensor launch folds
 and that the launches above read instead of ``p.grad``; the mean's ``1 / (A * world)`` rides in the loss multiplier, so no kernel of the
 update changes.  Every rank decides from the same reduced bits, hence alike, without exchanging a flag.
 
+An exponential moving average of the weights: with ``ema_decay`` the update's launch also moves an fp32 shadow of
+every parameter it touches towards the new value (``ldit_adamw_ema_groups_multi_f32``: one more read and write per element, the same
+skip decision, no further launch), and ``with step.ema_weights():`` exchanges weights and shadows in one launch to evaluate on the average.
+
 PyTorch is plumbing: it owns the memory, the stream and autograd's graph; the arithmetic of
 the update is the library's.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -150,13 +155,18 @@ class DetectorTrainStep:
 
     ``augment``: a :class:`~layoutdit_amd.augment.DetectorAugment`; every :meth:`step` then trains on windows of its pages - random
     crop, scale jitter and flip - drawn on the host from the augment's own generator: the windowed input transform
-    and one launch for the targets, no copy of a page and no synchronisation.  Without it the step launches what it always did."""
+    and one launch for the targets, no copy of a page and no synchronisation.  Without it the step launches what it always did.
+
+    ``ema_decay``: keep an exponential moving average of every updated parameter, ``e += (1 - d) * (p - e)`` inside the update's own
+    launch, with ``d = min(ema_decay, (1 + n) / (10 + n))`` after ``n`` taken steps (``ema_warmup=False``: ``d = ema_decay``);
+    :meth:`ema_state_dict` returns it, ``with step.ema_weights():`` evaluates on it.  With ``None`` no launch and no bit changes."""
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 0.0, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  step_size: Optional[int] = None, gamma: float = 0.1, init_scale: float = 65536.0, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, loss_scaling: bool = True, max_grad_norm: Optional[float] = None,
                  param_groups: Optional[Sequence[dict]] = None, warmup_iters: int = 0, warmup_factor: float = 1e-3, accumulate: int = 1,
-                 rank: Optional[Rank] = None, broadcast_parameters: bool = True, augment: Optional[DetectorAugment] = None):
+                 rank: Optional[Rank] = None, broadcast_parameters: bool = True, augment: Optional[DetectorAugment] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         from .modeling.detector import LayoutDetectionModel
         if not isinstance(model, LayoutDetectionModel):
             raise TypeError("DetectorTrainStep: expected a LayoutDetectionModel (the encoder alone trains with TrainStep)")
@@ -171,6 +181,8 @@ class DetectorTrainStep:
                 raise RuntimeError(f"DetectorTrainStep: rank.world = {rank.world}, the process group has {dist.get_world_size()} ranks")
         if augment is not None and not isinstance(augment, DetectorAugment):
             raise TypeError("DetectorTrainStep: augment must be a layoutdit_amd.augment.DetectorAugment")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"DetectorTrainStep: ema_decay must lie in [0, 1) (None: no moving average), got {ema_decay}")
         self.model = model
         self.augment = augment
         if augment is not None:                                              # what keeps a box under a window is the augment's to say
@@ -206,6 +218,12 @@ class DetectorTrainStep:
         self._mom: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}        # parameter name -> (exp_avg, exp_avg_sq)
         self._pending: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}    # loaded moments of parameters not seen yet
         self._enc = None                                                     # (FlatState, flat exp_avg, flat exp_avg_sq)
+        self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
+        self._ema: Dict[str, torch.Tensor] = {}                              # parameter name -> its fp32 shadow (the moving average)
+        self._ema_pending: Dict[str, torch.Tensor] = {}                      # loaded shadows of parameters not seen yet
+        self._enc_ema = None                                                 # (FlatState, the encoder's shadows as one flat block)
+        self._shadows: List[Optional[torch.Tensor]] = []                     # per segment of the last _segments() call
+        self._averaged = None                                                # inside ema_weights(): what its exit swaps back
         # parameter name -> (lr_scale, weight_decay), or None: one group, the three launches of section 21
         self._hyper = None if param_groups is None else resolve_param_groups(model, param_groups, self.weight_decay)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -242,6 +260,7 @@ class DetectorTrainStep:
         ``accumulate``-th call goes on to :meth:`apply`.  The losses returned are this call's, of this rank.
 
         ``windows``: this call's windows (``LayoutDetectionModel.losses``); left out, an ``augment`` draws them - one draw per call."""
+        self._require_own_weights("step")
         self._require_train_mode()
         if windows is None and self.augment is not None:
             windows = self.augment.sample([img.shape[-2:] for img in images])
@@ -303,6 +322,7 @@ class DetectorTrainStep:
         for bit), later ones add (one fp32 addition per element).  ``ceil(S / ops.ACC_MAX_SEGMENTS)`` launches, no synchronisation."""
         if not self._use_bucket:
             raise RuntimeError("DetectorTrainStep.accumulate_grads: built with accumulate=1 on one rank, there is no bucket - apply() reads p.grad")
+        self._require_own_weights("accumulate_grads")
         self._require_train_mode()
         grads = self._segments()[1]
         ops.grads_accumulate_multi(self._bind_bucket(grads), grads, overwrite=self.pending_micro_batches == 0)
@@ -332,9 +352,14 @@ class DetectorTrainStep:
         ``ldit_pack_train`` of them - where the mirror was current before the update; otherwise the next forward packs, as ever.
 
         With a bucket in use (``accumulate > 1`` or ranks) the gradients are the bucket's slices, as :meth:`accumulate_grads` left
-        them, after their sum over the ranks - ordered on the current stream under RCCL, no host wait; the launches are the same."""
+        them, after their sum over the ranks - ordered on the current stream under RCCL, no host wait; the launches are the same.
+
+        With ``ema_decay`` the update is ``ops.adamw_ema_groups_multi`` in place of ``adamw_multi`` / ``adamw_groups_multi``: the same
+        bits in the parameters, the moments and the mirror, and every segment's shadow moved in the same launch."""
+        self._require_own_weights("apply")
         self._require_train_mode()
         params, grads, exp_avgs, exp_avg_sqs, mirrors, st, current, hyper = self._segments()
+        shadows = self._shadows
         if self._use_bucket:
             if self.pending_micro_batches == 0:
                 raise RuntimeError("DetectorTrainStep.apply: nothing was folded into the bucket since the last update - call "
@@ -347,7 +372,11 @@ class DetectorTrainStep:
             if params:
                 ops.grads_check_multi(grads, self._state)
             ops.opt_advance(self._state, self.betas, self.growth_factor, self.backoff_factor, self.growth_interval)
-            if params:
+            if params and self.ema_decay is not None:
+                # lr_scale 1, one weight decay and no clip block: adamw_multi's bits (csrc/optim_multi.hip), and the shadows beside them
+                ops.adamw_ema_groups_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, [1.0] * len(params), [self.weight_decay] * len(params),
+                                           shadows, self.ema_decay, self.ema_warmup, None, self.betas, self.eps, mirrors)
+            elif params:
                 ops.adamw_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, self.betas, self.eps, self.weight_decay, 1.0, mirrors)
         else:
             # check (+ sum of squares) -> state machine -> (norm, clip coefficient) -> update: each needs its predecessor complete
@@ -367,7 +396,10 @@ class DetectorTrainStep:
             ops.opt_advance(self._state, self.betas, self.growth_factor, self.backoff_factor, self.growth_interval)
             if self._clip is not None:
                 ops.clip_finish(self._state, self._clip, self._partials, n)
-            if params:
+            if params and self.ema_decay is not None:
+                ops.adamw_ema_groups_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, [h[0] for h in hyper], [h[1] for h in hyper],
+                                           shadows, self.ema_decay, self.ema_warmup, self._clip, self.betas, self.eps, mirrors)
+            elif params:
                 ops.adamw_groups_multi(params, grads, exp_avgs, exp_avg_sqs, self._state, [h[0] for h in hyper], [h[1] for h in hyper],
                                        self._clip, self.betas, self.eps, mirrors)
         if st is not None and st.mx and current and st.native:
@@ -412,6 +444,46 @@ class DetectorTrainStep:
     def _require_train_mode(self) -> None:
         if not self.model.training:
             raise RuntimeError("DetectorTrainStep: the model is in eval mode - call .train() first")
+
+    def _require_own_weights(self, what: str) -> None:
+        if self._averaged is not None:
+            raise RuntimeError(f"DetectorTrainStep.{what}: inside ema_weights() the parameters hold the moving average and the shadows "
+                               "hold the trained weights - leave the block first")
+
+    def _restore_shadow(self, name: str, view: torch.Tensor) -> None:
+        loaded = self._ema_pending.pop(name, None)
+        if loaded is not None:
+            if tuple(view.shape) != tuple(loaded.shape):
+                raise ValueError(f"DetectorTrainStep: loaded moving average of {name} has shape {tuple(loaded.shape)}, the parameter {tuple(view.shape)}")
+            view.copy_(loaded)
+
+    def _shadow(self, name: str, p: torch.Tensor) -> Optional[torch.Tensor]:
+        """The parameter's moving average: an fp32 clone of it at first sight - before its first update - or what was loaded."""
+        if self.ema_decay is None:
+            return None
+        e = self._ema.get(name)
+        if e is None:
+            e = p.detach().clone(memory_format=torch.contiguous_format)
+            self._restore_shadow(name, e)
+            self._ema[name] = e
+        return e
+
+    def _bind_encoder_ema(self, st) -> None:
+        """The encoder's shadows as one flat block in the layout of its parameter block, like its moments: a clone of that block at
+        first sight; re-made, the averages carried over, when the encoder re-homed its parameters."""
+        if self.ema_decay is None or (self._enc_ema is not None and self._enc_ema[0] is st):
+            return
+        flat = st.params.detach().clone()
+        for _, p, off, shape in st.named:
+            name = self._names[id(p)]
+            view = flat[off: off + p.numel()].view(shape)
+            old = self._ema.get(name)
+            if old is not None:
+                view.copy_(old)
+            else:
+                self._restore_shadow(name, view)
+            self._ema[name] = view
+        self._enc_ema = (st, flat)
 
     def _restore(self, name: str, views: Tuple[torch.Tensor, torch.Tensor]) -> None:
         loaded = self._pending.pop(name, None)
@@ -460,6 +532,7 @@ class DetectorTrainStep:
         params, grads, exp_avgs, exp_avg_sqs, mirrors = [], [], [], [], []
         hyper = [] if self._grouped else None
         members = self._members = []                      # per segment: (parameter name, offset in the segment, shape); for the bucket only
+        shadows = self._shadows = []                      # per segment: its moving average (ema_decay), else None
         track = self._use_bucket
         st = getattr(self.encoder, "_flat_state", None)
         if st is not None and not st.intact():
@@ -467,6 +540,8 @@ class DetectorTrainStep:
         in_flat, current, taken = {}, False, set()
         if st is not None:
             self._bind_encoder(st)
+            self._bind_encoder_ema(st)
+            flat_ema = None if self._enc_ema is None else self._enc_ema[1]
             in_flat = {id(p): (off, p) for _, p, off, _ in st.named}
             current = not st._dirty and st._packed_version == st.version()
             mirror = st.packed[: 2 * st.numel].view(torch.bfloat16)
@@ -475,6 +550,7 @@ class DetectorTrainStep:
                 p.grad is not None and p.grad.dtype == torch.float32 and p.grad.data_ptr() == g.data_ptr() + 4 * off for off, p in in_flat.values())
             if whole:
                 params.append(st.params), grads.append(g), exp_avgs.append(self._enc[1]), exp_avg_sqs.append(self._enc[2]), mirrors.append(mirror)
+                shadows.append(flat_ema)
                 if track:
                     members.append([(self._names[id(p)], off, shape) for _, p, off, shape in st.named])
             elif self._grouped and g.dtype == torch.float32 and g.is_contiguous():
@@ -494,6 +570,7 @@ class DetectorTrainStep:
                         members.append(inside)
                     params.append(st.params[a:b]), grads.append(g[a:b]), exp_avgs.append(self._enc[1][a:b]), exp_avg_sqs.append(self._enc[2][a:b])
                     mirrors.append(mirror[a:b]), hyper.append(h)
+                    shadows.append(None if flat_ema is None else flat_ema[a:b])
         else:
             whole = False
         for name, p in self.model.named_parameters():
@@ -504,6 +581,7 @@ class DetectorTrainStep:
                 raise ValueError(f"DetectorTrainStep: the gradient of {name} is {g.dtype} on {g.device}; expected float32 beside its parameter")
             m, v = self._moments(name, p)
             params.append(p.detach()), grads.append(g.contiguous()), exp_avgs.append(m), exp_avg_sqs.append(v)
+            shadows.append(self._shadow(name, p))
             if track:
                 members.append([(name, 0, tuple(p.shape))])
             if id(p) in in_flat:
@@ -553,9 +631,85 @@ class DetectorTrainStep:
             raise RuntimeError("DetectorTrainStep.clipped_steps: built without max_grad_norm")
         return int(self._clip.cpu().view(torch.int32)[_CLIP["clipped_steps"]])
 
+    # ---- the moving average ----------------------------------------------------------------------------------------------------------------
+    def _require_ema(self, what: str) -> None:
+        if self.ema_decay is None:
+            raise RuntimeError(f"DetectorTrainStep.{what}: built without ema_decay, no moving average is kept")
+
+    @torch.no_grad()
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The model's ``state_dict()`` with every parameter that has a shadow replaced by a clone of it: what a fresh
+        ``LayoutDetectionModel`` of the same construction loads to evaluate on the average.  Parameters that never had a gradient, and
+        buffers, are the model's own entries."""
+        self._require_ema("ema_state_dict")
+        out = dict(self.model.state_dict())
+        if self._averaged is not None:                    # inside ema_weights() the model holds the average already
+            return {k: (v.detach().clone() if k in self._ema else v) for k, v in out.items()}
+        for name in self._names.values():
+            e = self._ema.get(name, self._ema_pending.get(name))
+            if e is not None and name in out:
+                out[name] = e.detach().clone().view(out[name].shape)
+        return out
+
+    def _swap_lists(self):
+        """(parameters, shadows, mirrors) of one ``ops.swap_multi``: at the encoder's own grid its flat block against its flat shadow,
+        the bf16 mirror attached; every other parameter that has a shadow on its own."""
+        a, b, mirrors, in_flat = [], [], [], set()
+        st = getattr(self.encoder, "_flat_state", None)
+        if st is not None and not st.intact():
+            st = None
+        if st is not None and st.native and self._enc_ema is not None and self._enc_ema[0] is st:
+            a.append(st.params), b.append(self._enc_ema[1]), mirrors.append(st.packed[: 2 * st.numel].view(torch.bfloat16))
+            in_flat = {id(p) for _, p, _, _ in st.named}
+        for name, p in self.model.named_parameters():
+            e = self._ema.get(name)
+            if e is None or id(p) in in_flat:
+                continue
+            if not p.is_contiguous():
+                raise ValueError(f"DetectorTrainStep.ema_weights: parameter {name} is not contiguous")
+            a.append(p.detach()), b.append(e), mirrors.append(None)
+        return a, b, mirrors, st
+
+    @contextmanager
+    def ema_weights(self):
+        """``with step.ema_weights():`` - the model holds the moving average and is in eval mode: ONE ``ops.swap_multi`` exchanges
+        every parameter with its shadow (the elements move as integers; parameters without a shadow stay), every derived copy of the
+        weights is dropped (:meth:`invalidate_caches`), and ``evaluate(model, batches)`` / ``forward_padded`` see the average with no
+        further change - under the quantisation-aware mxfp8 encoder, the mxfp8 inference build of the averaged masters.  On exit the
+        same launch swaps back bit for bit, the caches are dropped again, the encoder's training mirror is re-packed from the restored
+        masters where it was current before, and the mode the model was in returns.  Inside, :meth:`step`, :meth:`apply`,
+        :meth:`accumulate_grads` and :meth:`state_dict` are refused: weights and shadows have changed places."""
+        self._require_ema("ema_weights")
+        self._require_own_weights("ema_weights")
+        if self.pending_micro_batches:
+            raise RuntimeError(f"DetectorTrainStep.ema_weights: {self.pending_micro_batches} of {self.accumulate} micro-batches are folded into "
+                               "the gradient bucket - evaluate after the update")
+        with torch.no_grad():
+            for name, p in self.model.named_parameters():     # loaded averages of parameters no update has bound yet
+                if name in self._ema_pending and name not in self._ema:
+                    self._shadow(name, p)
+        a, b, mirrors, st = self._swap_lists()
+        current = st is not None and not st._dirty and st._packed_version == st.version()
+        was_training = self.model.training
+        ops.swap_multi(a, b, mirrors)
+        self._averaged = (a, b, mirrors)
+        self.invalidate_caches()
+        self.model.eval()
+        try:
+            yield self.model
+        finally:
+            ops.swap_multi(a, b, mirrors)
+            self._averaged = None
+            self.invalidate_caches()
+            if current and st.intact():
+                st.repack(force=True)                     # the swaps wrote bf16 of whole blocks: the training mirror is a fresh pack again
+            self.model.train(was_training)
+
     def state_dict(self) -> dict:
         """Everything a resumed run needs: the device block's fields, both moments keyed by the model's parameter names, the host-side
-        schedule.  Synchronises.  Refused in the middle of an accumulation: the bucket is not part of it."""
+        schedule - and, with ``ema_decay``, the shadows under ``"ema"``.  Synchronises.  Refused in the middle of an accumulation: the
+        bucket is not part of it."""
+        self._require_own_weights("state_dict")
         if self.pending_micro_batches:
             raise RuntimeError(f"DetectorTrainStep.state_dict: {self.pending_micro_batches} of {self.accumulate} micro-batches are folded into the "
                                "gradient bucket, which no state dictionary holds - save after the update")
@@ -568,13 +722,23 @@ class DetectorTrainStep:
             out["clip"] = {n: (int(host.view(torch.int32)[i]) if n == "clipped_steps" else float(host[i])) for n, i in _CLIP.items()}
         if self.augment is not None:
             out["augment"] = self.augment.state_dict()
+        if self.ema_decay is not None:
+            shadow = {n: e.detach().clone() for n, e in self._ema.items()}
+            shadow.update({n: e.clone() for n, e in self._ema_pending.items() if n not in shadow})
+            out["ema"] = {"shadow": shadow, "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup}
         return out
 
     def load_state_dict(self, sd: dict) -> None:
+        self._require_own_weights("load_state_dict")
         names = set(self._names.values())
         unknown = [n for n in sd["exp_avg"] if n not in names]
         if unknown or set(sd["exp_avg"]) != set(sd["exp_avg_sq"]):
             raise KeyError(f"DetectorTrainStep.load_state_dict: moments do not match the model's parameter names (e.g. {unknown[:3]})")
+        ema = sd.get("ema") if self.ema_decay is not None else None      # a step built without ema_decay keeps none
+        if ema:
+            unknown = [n for n in ema["shadow"] if n not in names]
+            if unknown:
+                raise KeyError(f"DetectorTrainStep.load_state_dict: moving averages do not match the model's parameter names (e.g. {unknown[:3]})")
         host = torch.zeros(len(_FIELD), dtype=torch.int32)
         hf = host.view(torch.float32)
         for n in _INT_FIELDS:
@@ -604,3 +768,10 @@ class DetectorTrainStep:
                 else:
                     views[0].zero_()
                     views[1].zero_()
+        if self.ema_decay is not None:
+            # every shadow is dropped and re-made when first needed: a clone of the parameter as it is then, overwritten by the loaded
+            # average where the dictionary holds one (one written without ema_decay holds none: the average restarts at the weights)
+            self._ema, self._enc_ema = {}, None
+            self._ema_pending = {n: t.detach().to(self.device, torch.float32).clone() for n, t in ema["shadow"].items()} if ema else {}
+            if ema:
+                self.ema_decay, self.ema_warmup = float(ema["ema_decay"]), bool(ema["ema_warmup"])

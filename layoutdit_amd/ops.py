@@ -1422,6 +1422,75 @@ def grads_accumulate_multi(accs: Sequence[torch.Tensor], grads: Sequence[torch.T
     _launch(_device(*accs, *grads), lib.ldit_grads_accumulate_multi_f32, segs, S, 1 if overwrite else 0)
 
 
+# -- an exponential moving average of the weights inside the update's launch, and the exchange that evaluates on it --
+EMA_MAX_SEGMENTS = _lib.EMA_MAX_SEGMENTS
+SWAP_MAX_SEGMENTS = _lib.SWAP_MAX_SEGMENTS
+
+
+def adamw_ema_groups_multi(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+                           exp_avg_sqs: Sequence[torch.Tensor], state: torch.Tensor, lr_scales: Sequence[float], weight_decays: Sequence[float],
+                           shadows: Sequence[Optional[torch.Tensor]], ema_decay: float, ema_warmup: bool = True,
+                           clip: Optional[torch.Tensor] = None, betas=(0.9, 0.999), eps: float = 1e-8,
+                           mirrors: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """``adamw_groups_multi`` and, in the same launches, ``shadows[i] += w * (params[i] - shadows[i])`` on the updated parameter for
+    every ``i`` whose shadow is not None (float32, the parameter's length, overlapping nothing).  ``w = 1 - d`` with ``d = ema_decay``,
+    or ``min(ema_decay, (1 + step) / (10 + step))`` under ``ema_warmup``, ``step`` the count of steps taken in ``state`` - formed on the
+    device; a skipped step moves no shadow.  ``ceil(S / EMA_MAX_SEGMENTS)`` launches.  No synchronisation."""
+    lib = _lib.load()
+    state = _req_opt_state(state)
+    if clip is not None:
+        clip = _req_clip_state(clip)
+    segs, S, used = _opt_segments(params, grads, exp_avgs, exp_avg_sqs, mirrors)
+    lr_scales, weight_decays = [float(x) for x in lr_scales], [float(x) for x in weight_decays]
+    if len(lr_scales) != S or len(weight_decays) != S:
+        raise ValueError(f"lr_scales / weight_decays: {len(lr_scales)} / {len(weight_decays)} entries for {S} segments")
+    hyper = (_lib.LditOptHyper * max(S, 1))()
+    for i, (h, s, w) in enumerate(zip(hyper, lr_scales, weight_decays)):
+        if not s >= 0.0 or not w >= 0.0:
+            raise ValueError(f"segment {i}: lr_scale and weight_decay must be >= 0")
+        h.lr_scale, h.weight_decay = s, w
+    ema_decay = float(ema_decay)
+    if not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+    shadows = list(shadows)
+    if len(shadows) != S:
+        raise ValueError(f"shadows: {len(shadows)} entries for {S} segments")
+    ema = (C.c_void_p * max(S, 1))()
+    given = _req_list([e for e in shadows if e is not None], "shadows", sum(e is not None for e in shadows))
+    for i, e in enumerate(shadows):
+        if e is not None:
+            if e.numel() != segs[i].n:
+                raise ValueError(f"shadows[{i}]: {e.numel()} elements beside a parameter of {segs[i].n}")
+            ema[i] = e.data_ptr()
+    _launch(_device(state, clip, *used, *given), lib.ldit_adamw_ema_groups_multi_f32, segs, hyper, ema, S, _ptr(state), _ptr(clip),
+            float(betas[0]), float(betas[1]), float(eps), ema_decay, 1 if ema_warmup else 0)
+
+
+def swap_multi(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor], mirrors: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """``a[i] <-> b[i]`` bit for bit (the elements move as integers) over the lists in ``ceil(S / SWAP_MAX_SEGMENTS)`` launches;
+    ``mirrors[i]`` (bfloat16, optional) receives the rounded new ``a[i]``.  Calling it twice restores every bit.  Tensors may be views
+    at any element offset; a pair must not overlap.  No synchronisation, nothing allocated."""
+    lib = _lib.load()
+    a = list(a)
+    S = len(a)
+    a, b = _req_list(a, "a", S), _req_list(b, "b", S)
+    mirrors = [None] * S if mirrors is None else list(mirrors)
+    if len(mirrors) != S:
+        raise ValueError(f"mirrors: {len(mirrors)} entries for {S} segments")
+    segs = (_lib.LditSwapSegment * max(S, 1))()
+    for i, (s, x, y, mi) in enumerate(zip(segs, a, b, mirrors)):
+        if x.numel() != y.numel():
+            raise ValueError(f"segment {i}: a and b differ in length ({x.numel()} and {y.numel()})")
+        if mi is not None:
+            if not isinstance(mi, torch.Tensor) or not mi.is_cuda or mi.dtype != torch.bfloat16 or not mi.is_contiguous() or mi.numel() != x.numel():
+                raise ValueError(f"mirrors[{i}]: expected a contiguous bfloat16 GPU tensor of the segment's length")
+            s.bf16_mirror = mi.data_ptr()
+        s.a, s.b, s.n = x.data_ptr(), y.data_ptr(), x.numel()
+    if S == 0:
+        return
+    _launch(_device(*a, *b, *[mi for mi in mirrors if mi is not None]), lib.ldit_swap_multi_f32, segs, S)
+
+
 def requant_train_mirror(flat_state, opt_state: Optional[torch.Tensor] = None) -> None:
     """The MX operands of a quantisation-aware encoder's training mirror re-made from its fp32 master in ONE launch
     (``ldit_requant_train_mirror``): every layer's four matrices (codes, scales, dequantised bf16 copies) and fused bias, nothing else.

@@ -11,6 +11,10 @@ With --qat nothing of the above runs; instead, alternating i
 encoder against apply() of the detector on the quantisation-aware mxfp8 encoder (the same launches plus ldit_requant_train_mirror),
 and that one launch alone against ldit_pack_train on the same master (the cast pass plus one launch per layer: what mark_dirty()
 would cost at the next forward), --inner calls per timed window; the file is profiles/detector_step_bench_qat.json.
+With --ema nothing of the above runs either; instead, alternating in one process on the detector with the bf16
+encoder: apply() without a moving average, apply() with ema_decay (the same launches, the update's one reading and writing a shadow
+element as well), and apply() without followed by torch._foreach_lerp_ over the same tensors; then ops.swap_multi (weights <-> shadows,
+one launch) against three torch._foreach_copy_ through a temporary, --inner calls per timed window; profiles/detector_step_bench_ema.json.
 Writes one JSON object (--out, default profiles/detector_step_bench.json)."""
 import argparse
 import ctypes
@@ -33,11 +37,14 @@ ap.add_argument("--runs", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--clip", action="store_true", help="also time clipping and parameter groups against clip_grad_norm_ + AdamW(groups)")
 ap.add_argument("--qat", action="store_true", help="time the qat detector's apply() beside the bf16-encoder detector's, and the re-quantise launch beside ldit_pack_train")
-ap.add_argument("--inner", type=int, default=20, help="--qat: calls of the launch / the pack per timed window")
+ap.add_argument("--ema", action="store_true", help="time apply() with the moving average beside apply() and apply() + torch._foreach_lerp_, and the swap launch")
+ap.add_argument("--inner", type=int, default=20, help="--qat / --ema: calls of the launch / the pack / the exchange per timed window")
+ap.add_argument("--commit", default=None, help="--ema: recorded as the commit the tree was measured at")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                    "detector_step_bench_qat.json" if args.qat else "detector_step_bench.json")
+                                    "detector_step_bench_qat.json" if args.qat else "detector_step_bench_ema.json" if args.ema else
+                                    "detector_step_bench.json")
 
 dev = "cuda:0"
 cfg = getattr(cfgs, args.config)()
@@ -119,6 +126,79 @@ if args.qat:
                                        "separated": bool(r["max_ms"] < p["min_ms"] or p["max_ms"] < r["min_ms"])},
         "steps_taken": {"bf16_encoder": s_bf16.steps, "qat_mxfp8_encoder": s_qat.steps},
         "device": torch.cuda.get_device_name(0), "box": "one MI355X box", "repeats": "one run",
+    }
+    print(json.dumps(res))
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
+
+if args.ema:
+    m_plain, m_ema, m_lerp = with_grads(build("bf16")), with_grads(build("bf16")), with_grads(build("bf16"))
+    s_plain = DetectorTrainStep(m_plain, lr=1e-6, weight_decay=0.01, loss_scaling=False)
+    s_ema = DetectorTrainStep(m_ema, lr=1e-6, weight_decay=0.01, loss_scaling=False, ema_decay=0.9999)
+    s_lerp = DetectorTrainStep(m_lerp, lr=1e-6, weight_decay=0.01, loss_scaling=False)
+    # what a user without the option runs after every step(): torch._foreach_lerp_ over the tensors the update touched (the encoder's
+    # flat block as the one tensor it is to the update - 238 separate parameters would only add launches on that side)
+    lerp_params = [p.detach() for p in s_lerp._segments()[0]]
+    lerp_shadows = [p.clone() for p in lerp_params]
+
+    def apply_then_lerp():
+        s_lerp.apply()
+        torch._foreach_lerp_(lerp_shadows, lerp_params, 1.0 - 0.9999)
+
+    s_ema.apply()                                              # makes the shadows the swap exchanges
+    swap_a, swap_b, swap_mirrors, _ = s_ema._swap_lists()
+    copy_a, copy_b = [t.clone() for t in swap_a], [t.clone() for t in swap_b]
+    copy_tmp = [torch.empty_like(t) for t in copy_a]
+
+    def copy_swap():
+        torch._foreach_copy_(copy_tmp, copy_a)
+        torch._foreach_copy_(copy_a, copy_b)
+        torch._foreach_copy_(copy_b, copy_tmp)
+
+    pairs = {"apply": (("apply_without_ema", s_plain.apply, 1), ("apply_with_ema", s_ema.apply, 1), ("apply_without_ema_then_foreach_lerp", apply_then_lerp, 1)),
+             "swap": (("swap_multi_one_exchange", lambda: ops.swap_multi(swap_a, swap_b, swap_mirrors), args.inner),
+                      ("foreach_copy_through_a_temporary", copy_swap, args.inner))}
+    ms = {}
+    for what, group in pairs.items():
+        for _ in range(args.warmup):
+            for _, fn, _ in group:
+                fn()
+        torch.cuda.synchronize()
+        samples = {name: [] for name, _, _ in group}
+        for _ in range(args.runs):                             # alternating: one window of each in turn
+            for name, fn, inner in group:
+                samples[name].append(window(fn, inner))
+        ms[what] = {name: spread(v, 5) for name, v in samples.items()}
+    if (args.warmup + args.runs * args.inner) % 2:
+        ops.swap_multi(swap_a, swap_b, swap_mirrors)           # an even number of exchanges: the weights are where they were
+    segs = s_ema._segments()[0]
+    elements = int(sum(p.numel() for p in segs))
+
+    def apart(x, y):
+        return bool(x["max_ms"] < y["min_ms"] or y["max_ms"] < x["min_ms"])
+
+    plain, fused, lerp = (ms["apply"][k] for k in ("apply_without_ema", "apply_with_ema", "apply_without_ema_then_foreach_lerp"))
+    sw, cp = ms["swap"]["swap_multi_one_exchange"], ms["swap"]["foreach_copy_through_a_temporary"]
+    res = {
+        "workload": {"config": args.config, "encoder": "bf16", "elements": elements, "segments": len(segs),
+                     "launches_per_apply": {"without_ema": 1 + 2 * -(-len(segs) // ops.OPT_MAX_SEGMENTS),
+                                            "with_ema": 1 + -(-len(segs) // ops.OPT_MAX_SEGMENTS) + -(-len(segs) // ops.EMA_MAX_SEGMENTS)},
+                     "update_bytes_per_element": {"without_ema": 4 * 7 + 2, "with_ema": 4 * 9 + 2},
+                     "swap": {"pairs": len(swap_a), "elements": int(sum(t.numel() for t in swap_a)),
+                              "launches": -(-len(swap_a) // ops.SWAP_MAX_SEGMENTS), "foreach_copies": 3},
+                     "ema_decay": 0.9999, "weight_decay": 0.01, "loss_scale": 1.0},
+        "runs": args.runs, "warmup": args.warmup, "inner_calls_per_window": {"apply": 1, "swap": args.inner},
+        "order": "alternating, one window of each of a group in turn, one process",
+        "timer": "HIP events around each window, host work of the calls included",
+        "ms": ms,
+        "ema_over_plain": {"median_ms": round(fused["median_ms"] - plain["median_ms"], 5), "ratio": round(fused["median_ms"] / plain["median_ms"], 3),
+                           "separated": apart(plain, fused)},
+        "ema_over_apply_then_lerp": {"ratio": round(fused["median_ms"] / lerp["median_ms"], 3), "separated": apart(fused, lerp)},
+        "swap_over_foreach_copy": {"ratio": round(sw["median_ms"] / cp["median_ms"], 3), "separated": apart(sw, cp)},
+        "steps_taken": {"without_ema": s_plain.steps, "with_ema": s_ema.steps, "then_lerp": s_lerp.steps},
+        "device": torch.cuda.get_device_name(0), "commit": args.commit, "box": "one MI355X box", "repeats": "one run",
     }
     print(json.dumps(res))
     with open(args.out, "w") as f:
