@@ -404,6 +404,38 @@ int ldit_augment_targets_f32(const void *gt_boxes, const void *gt_labels, const 
                              int32_t Gmax, int32_t out_h, int32_t out_w, float min_visibility, float min_size, void *out_boxes,
                              void *out_labels, void *out_count, ldit_stream stream);
 
+/* ---- test-time augmentation: the views of a page merged on the device ---------------------------------------------
+ * A VIEW is the batch at another size and / or mirrored left-right; its padded detections (boxes fp32 [B, D, 4], scores fp32 [B, D],
+ * labels int32 [B, D], count int32 [B], as ldit_box_detections leaves them) are in the view's coordinates.  The merge is
+ * ldit_tta_pool_f32 -> ldit_nms_batched_f32 (groups = the pooled labels) -> ldit_box_vote_f32: three launches, no synchronisation,
+ * no atomics, capturable.  Both entries are additive (the ABI number did not move).
+ *
+ * ldit_tta_pool_f32: `boxes`, `scores`, `labels`, `count` are HOST arrays of V device pointers (the views by value: no stacked copy),
+ *   `view_specs` a HOST array [V][3] = (W_v, H_v, flip_v), `page_sizes` a HOST array [B][2] = (ow_b, oh_b).  1 <= V <= 16,
+ *   V * D <= 8192 (what the NMS takes per problem).  Pool entry v * D + d of image b, for d < count_v[b] (clamped to [0, D]), in fp32,
+ *   every operation rounded once:
+ *       (x1, x2) = flip_v ? ((float)W_v - x2, (float)W_v - x1) : (x1, x2)
+ *       box = (x1 * rw, y1 * rh, x2 * rw, y2 * rh),  rw = (float)((double)ow_b / W_v), rh = (float)((double)oh_b / H_v)
+ *   with the view's score and label beside it - an unmirrored view's boxes are those of resize_boxes bit for bit.  For
+ *   d >= count_v[b] the entry is (zero box, score -inf, label 0) and the input row is never read (it may hold NaN).  Outputs:
+ *   pool_boxes fp32 [B, V * D, 4] (16-byte aligned, like every view's boxes), pool_scores fp32 [B, V * D], pool_labels int32
+ *   [B, V * D]; they must not alias the inputs.  One launch per 256 images (the descriptors travel in the kernel arguments).
+ *
+ * ldit_box_vote_f32: behind the NMS of the pool (N = V * D entries per image; keep int32 [B, D_out] = the kept pool indices, kept
+ *   int32 [B] their number).  Row k < kept[b] with i = keep[b][k]: out_labels[b][k] = pool_labels[b][i], and out_boxes[b][k] is the
+ *   score-weighted mean of the VOTING SET of i - every entry j of image b with pool_labels[j] == pool_labels[i], pool_scores[j] > -inf
+ *   and inter / uni >= vote_thresh, the IoU formed in fp32 exactly as ldit_nms_batched_f32 forms it (area = (x2 - x1) * (y2 - y1),
+ *   iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih alike, inter = iw * ih, uni = (area_a + area_b) - inter); i itself is always a
+ *   member, even where its own IoU is NaN.  Per coordinate sum(s_j * b_j) / sum(s_j) with products, sums and the quotient in double
+ *   and ONE rounding to fp32; the sum runs in a fixed order (per lane ascending j, then a fixed butterfly), so the result is a pure
+ *   function of the input.  Rows k >= kept[b] (and rows whose index is no pool index) are zero in both outputs.  out_boxes == NULL:
+ *   only the labels are gathered (the NMS's own boxes stand).  0 <= vote_thresh <= 1; boxes 16-byte aligned; one wave per row. */
+int ldit_tta_pool_f32(const void *const *boxes, const void *const *scores, const void *const *labels, const void *const *count,
+                      const int32_t *view_specs, const int32_t *page_sizes, int32_t V, int32_t B, int32_t D, void *pool_boxes,
+                      void *pool_scores, void *pool_labels, ldit_stream stream);
+int ldit_box_vote_f32(const void *pool_boxes, const void *pool_scores, const void *pool_labels, const void *keep, const void *kept,
+                      int32_t B, int32_t N, int32_t D_out, float vote_thresh, void *out_boxes, void *out_labels, ldit_stream stream);
+
 /* fp16 <-> fp32 conversion of a pixel batch / of the returned taps for an fp16 caller (round to nearest even), n elements;
  * the fp16 side 8-byte aligned, the fp32 side 16-byte aligned. */
 int ldit_cast_f16_f32(const void *src, void *dst, int64_t n, ldit_stream stream);

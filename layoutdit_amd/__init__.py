@@ -24,6 +24,9 @@ def __getattr__(name):
     if name in ("CocoBoxEvaluator", "evaluate"):
         from . import evaluation
         return getattr(evaluation, name)
+    if name == "TestTimeAugment":
+        from .tta import TestTimeAugment
+        return TestTimeAugment
     if name in ("stage_images", "StagingBuffer"):
         from . import data
         return getattr(data, name)

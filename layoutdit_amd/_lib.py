@@ -140,6 +140,10 @@ SIGNATURES = {
     "ldit_preprocess_win_u8": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _f32, _f32,
                                          _i32, _i32, _vp, _vp]),
     "ldit_augment_targets_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    # test-time augmentation
+    "ldit_tta_pool_f32": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32,
+                                    _i32, _vp, _vp, _vp, _vp]),
+    "ldit_box_vote_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "ldit_cast_f16_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
     "ldit_cast_f32_f16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "ldit_fpn_merge_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _i64, _i64, _vp]),

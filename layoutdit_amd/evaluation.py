@@ -131,25 +131,36 @@ def _to_device(host: torch.Tensor, device: torch.device) -> torch.Tensor:
 
 
 def evaluate(model, batches: Iterable[Tuple[List[torch.Tensor], List[Dict[str, torch.Tensor]]]], capacity: Optional[int] = None,
-             max_gt: int = 128, evaluator: Optional[CocoBoxEvaluator] = None) -> Dict[str, float]:
+             max_gt: int = 128, evaluator: Optional[CocoBoxEvaluator] = None, tta=None) -> Dict[str, float]:
     """The loop of the reference's ``Evaluator.score()``: ``batches`` yields ``(images, targets)`` - a list of ``[3, h, w]`` images and
     the reference's target dicts in the ORIGINAL images' coordinates.  Per batch: the input transform, ``forward_padded``, the boxes
     times each image's ``(rw, rh, rw, rh)`` (formed on the host from the shapes exactly as ``resize_boxes`` forms them, so the boxes
     scored are bit for bit those of ``model.forward(images)``), then ``CocoBoxEvaluator.update``.  Nothing is read back before the
-    end; returns the 12 numbers as a dict.  ``capacity``: the number of images (``None``: ``batches`` is listed first and counted)."""
+    end; returns the 12 numbers as a dict.  ``capacity``: the number of images (``None``: ``batches`` is listed first and counted).
+
+    ``tta`` (a ``layoutdit_amd.TestTimeAugment``): per batch ``model.forward_padded_tta(images, tta)`` instead - its
+    detections are already in the pages' coordinates and go to ``CocoBoxEvaluator.update`` as they are, still without a
+    synchronisation.  ``head_dtype``, ``neck_dtype`` and ``compute_dtype`` need nothing, and under ``with step.ema_weights():`` the
+    averaged weights are evaluated either way.  None: nothing changes."""
     if model.training:
         raise RuntimeError("evaluate: inference only - call .eval() first")
     m = model.model
     dev = next(model.parameters()).device
+    d_out = m.roi_heads.detections_per_img if tta is None else tta.merge_args(model)[1]
     if evaluator is None:
         if capacity is None:
             batches = list(batches)
             capacity = sum(len(images) for images, _ in batches)
-        evaluator = CocoBoxEvaluator(m.roi_heads.box_predictor.num_classes - 1, max(int(capacity), 1), m.roi_heads.detections_per_img,
-                                     max_gt, device=dev)
+        evaluator = CocoBoxEvaluator(m.roi_heads.box_predictor.num_classes - 1, max(int(capacity), 1), d_out, max_gt, device=dev)
+    elif tta is not None and evaluator.max_dets < d_out:
+        raise ValueError(f"evaluate: the evaluator's max_dets = {evaluator.max_dets} does not cover the {d_out} detections per image of tta")
     for images, targets in batches:
         if len(images) != len(targets):
             raise ValueError("evaluate: one target per image")
+        if tta is not None:
+            boxes, scores, labels, count = model.forward_padded_tta(images, tta)
+            evaluator.update(boxes, scores, labels, count, *_pad_targets(targets, evaluator.max_gt, boxes.device))
+            continue
         image_list, _ = m.transform(images)
         boxes, scores, labels, count = model.forward_padded(image_list.tensors)
         ratios = []

@@ -186,10 +186,47 @@ class LayoutDetectionModel(nn.Module):
         out.update(rpn_losses)
         return out
 
-    def forward(self, images: List[torch.Tensor], targets=None) -> List[Dict[str, torch.Tensor]]:
+    def forward_padded_tta(self, images: List[torch.Tensor], tta) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Test-time augmentation (``tta``: a ``layoutdit_amd.TestTimeAugment``): a list of ``[3, h, w]`` pages ->
+        ``(boxes [B, D_out, 4], scores [B, D_out], labels int32 [B, D_out], count int32 [B])`` in the PAGES' coordinates, zero padding, no
+        synchronisation.  Per view of ``tta.views(self)`` one ``ops.preprocess`` of the list at the view's size - a mirrored view through
+        the whole-page window ``(0, 0, w, h, 1)``: no mirrored or resized copy, every image format the transform takes, uint8
+        included - then :meth:`forward_padded`; ``ops.tta_merge`` maps every view back to its page, pools them, runs one class-wise NMS
+        and, where ``tta.vote_thresh`` is set, box voting.  ``head_dtype``, ``neck_dtype`` and ``compute_dtype`` act through
+        :meth:`forward_padded` as they stand, and under ``with step.ema_weights():`` the views are those of the averaged weights."""
+        if self.training:
+            raise RuntimeError("LayoutDetectionModel: forward_padded_tta is inference only (the four losses are losses(images, targets)) - "
+                               "call .eval() first")
+        from .. import ops
+        t = self.model.transform
+        if len(images) == 0:
+            raise ValueError("empty image list")
+        for img in images:
+            if img.dim() != 3:
+                raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(img.shape)}")
+        views = tta.views(self)
+        nms_thresh, detections_per_img, vote_thresh = tta.merge_args(self)
+        original = [tuple(img.shape[-2:]) for img in images]
+        operands = t._operands(images)
+        mirror = [(0, 0, w, h, 1) for h, w in original]
+        outs = []
+        for view in views:
+            batch = ops.preprocess(operands, size=(view.height, view.width), mean=t.mean, std=t.std, windows=mirror if view.flip else None)
+            outs.append(self.forward_padded(batch))
+        return ops.tta_merge(outs, views, original, nms_thresh, detections_per_img, vote_thresh)
+
+    def forward(self, images: List[torch.Tensor], targets=None, tta=None) -> List[Dict[str, torch.Tensor]]:
+        """``tta`` (a ``layoutdit_amd.TestTimeAugment``): the detections of :meth:`forward_padded_tta` as the list of dicts - they are
+        already in the pages' coordinates, so ``transform.postprocess`` is not applied to them.  ``head_dtype``, ``neck_dtype`` and
+        ``compute_dtype`` need nothing, and ``with step.ema_weights():`` evaluates the averaged weights either way.  None: nothing
+        changes."""
         if self.training or targets is not None:
             raise RuntimeError("LayoutDetectionModel: forward is inference only (the four losses are losses(images, targets)) - call "
                                ".eval() first and pass no targets")
+        if tta is not None:
+            boxes, scores, labels, count = self.forward_padded_tta(images, tta)
+            return [{"boxes": boxes[i, :n], "labels": labels[i, :n].to(torch.int64), "scores": scores[i, :n]}
+                    for i, n in enumerate(count.tolist())]
         m = self.model
         original = [tuple(img.shape[-2:]) for img in images]
         image_list, _ = m.transform(images)

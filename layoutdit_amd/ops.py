@@ -1655,3 +1655,117 @@ def augment_targets(gt_boxes: torch.Tensor, gt_labels: Optional[torch.Tensor], g
     _launch(_device(gt_boxes, gt_labels, gt_count), lib.ldit_augment_targets_f32, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_count), wins, B,
             Gmax, out_h, out_w, float(min_visibility), float(min_size), _ptr(out_boxes), _ptr(out_labels), _ptr(out_count))
     return out_boxes, out_labels, out_count
+
+
+# ---- test-time augmentation, the merge (include/ldit.h "test-time augmentation"; csrc/tta_merge.hip) ----------------------------------
+TTA_MAX_VIEWS = 16
+
+
+def _tta_views(views, view_specs, original_sizes, who: str):
+    """Host checks of the merge's arguments (they need no GPU): ``(V, B, D, specs, pages)`` with the two HOST int32 arrays of the C ABI."""
+    views, specs_in = list(views), list(view_specs)
+    V = len(views)
+    if V < 1 or V > TTA_MAX_VIEWS:
+        raise ValueError(f"{who}: {V} views, between 1 and {TTA_MAX_VIEWS} are handled")
+    if len(specs_in) != V:
+        raise ValueError(f"{who}: {len(specs_in)} view specs for {V} views")
+    if any(not isinstance(v, (tuple, list)) or len(v) != 4 for v in views):
+        raise ValueError(f"{who}: every view is the tuple (boxes, scores, labels, count) of forward_padded")
+    if not isinstance(views[0][1], torch.Tensor) or views[0][1].dim() != 2:
+        raise ValueError(f"{who}: views[0]: scores: expected a [B, D] tensor")
+    B, D = views[0][1].shape
+    if B < 1 or D < 1:
+        raise ValueError(f"{who}: empty problem (B={B}, D={D})")
+    if V * D > NMS_MAX_CANDIDATES:
+        raise ValueError(f"{who}: {V} views x {D} detections = {V * D} pool entries per image, at most NMS_MAX_CANDIDATES = "
+                         f"{NMS_MAX_CANDIDATES} are handled (fewer views, or a smaller detections_per_img)")
+    for v, (boxes, scores, labels, count) in enumerate(views):
+        _req_form(boxes, f"views[{v}]: boxes", torch.float32, (B, D, 4)), _req_form(scores, f"views[{v}]: scores", torch.float32, (B, D))
+        _req_form(labels, f"views[{v}]: labels", torch.int32, (B, D)), _req_form(count, f"views[{v}]: count", torch.int32, (B,))
+    flat = []
+    for v, s in enumerate(specs_in):
+        try:
+            s = [operator.index(x) for x in s]
+        except TypeError:
+            s = None
+        if s is None or len(s) != 3 or s[0] < 1 or s[1] < 1 or s[2] not in (0, 1) or max(s[:2]) >= 2 ** 31:
+            raise ValueError(f"{who}: view_specs[{v}] must be (width >= 1, height >= 1, flip 0 or 1), got {specs_in[v]!r}")
+        flat.extend(s)
+    pages = [(operator.index(hw[0]), operator.index(hw[1])) for hw in original_sizes]
+    if len(pages) != B:
+        raise ValueError(f"{who}: {len(pages)} original sizes for {B} images")
+    if any(h < 1 or w < 1 or max(h, w) >= 2 ** 31 for h, w in pages):
+        raise ValueError(f"{who}: original_sizes are the pages' (height, width), each at least 1")
+    return V, B, D, (C.c_int32 * (3 * V))(*flat), (C.c_int32 * (2 * B))(*[x for h, w in pages for x in (w, h)])
+
+
+def tta_pool(views, view_specs, original_sizes):
+    """The padded detections of ``V`` views of one batch as one pool per image, in the pages' coordinates (``ldit_tta_pool_f32``).
+    ``views``: ``V`` tuples ``(boxes [B, D, 4], scores [B, D], labels int32 [B, D], count int32 [B])`` as ``forward_padded`` returns
+    them, each in its view's coordinates; ``view_specs``: ``V`` triples ``(width, height, flip)``; ``original_sizes``: the pages'
+    ``(height, width)`` as ``img.shape[-2:]`` gives them.  Returns ``(pool_boxes [B, V * D, 4], pool_scores [B, V * D], pool_labels int32
+    [B, V * D])``, entry ``v * D + d`` from detection ``d`` of view ``v``: unmirrored where ``flip`` is 1, then times ``(rw, rh, rw, rh)``
+    formed as ``resize_boxes`` forms them; an entry at or beyond its view's count has score ``-inf``, label 0 and a zero box, whatever
+    the input's padding row holds.  The host integers travel in the kernel arguments: no copy, no synchronisation."""
+    lib = _lib.load()
+    V, B, D, specs, pages = _tta_views(views, view_specs, original_sizes, "tta_pool")
+    tensors = [t for view in views for t in view]
+    dev = _device(*tensors)
+    pool_boxes = torch.empty((B, V * D, 4), device=dev, dtype=torch.float32)
+    pool_scores = torch.empty((B, V * D), device=dev, dtype=torch.float32)
+    pool_labels = torch.empty((B, V * D), device=dev, dtype=torch.int32)
+    ptrs = [(C.c_void_p * V)(*[view[m].data_ptr() for view in views]) for m in range(4)]
+    _launch(_device(*tensors), lib.ldit_tta_pool_f32, ptrs[0], ptrs[1], ptrs[2], ptrs[3], specs, pages, V, B, D, _ptr(pool_boxes),
+            _ptr(pool_scores), _ptr(pool_labels))
+    return pool_boxes, pool_scores, pool_labels
+
+
+def box_vote(pool_boxes: torch.Tensor, pool_scores: torch.Tensor, pool_labels: torch.Tensor, keep: torch.Tensor, kept: torch.Tensor,
+             vote_thresh: Optional[float] = None):
+    """Behind :func:`batched_nms_padded` on a pool (``keep`` int32 [B, D_out], ``kept`` int32 [B]): ``(boxes [B, D_out, 4] or None, labels
+    int32 [B, D_out])`` (``ldit_box_vote_f32``).  The labels are the kept entries' own.  The box of a kept entry is the score-weighted
+    mean of every pool entry of its image with its label, a score ``> -inf`` and an IoU with it ``>= vote_thresh`` (the NMS's fp32
+    IoU; the entry itself always) - sums and quotient in double, rounded to fp32 once, in a fixed order, so two runs agree bit for
+    bit.  Rows at or beyond ``kept`` are zero.  ``vote_thresh=None``: no arithmetic, boxes ``None`` (the NMS's own stand), only the
+    labels are gathered.  One launch, no synchronisation."""
+    lib = _lib.load()
+    if not isinstance(pool_scores, torch.Tensor) or pool_scores.dim() != 2 or not isinstance(keep, torch.Tensor) or keep.dim() != 2:
+        raise ValueError("box_vote: pool_scores / keep: expected [B, N] / [B, D_out] tensors")
+    (B, N), Dout = pool_scores.shape, keep.shape[1]
+    if B < 1 or N < 1 or Dout < 1:
+        raise ValueError("box_vote: empty problem")
+    if N > NMS_MAX_CANDIDATES:
+        raise ValueError(f"box_vote: {N} pool entries per image, at most NMS_MAX_CANDIDATES = {NMS_MAX_CANDIDATES} are handled")
+    if vote_thresh is not None and not 0.0 <= float(vote_thresh) <= 1.0:
+        raise ValueError(f"box_vote: vote_thresh = {vote_thresh} is outside [0, 1]")
+    _req_form(pool_boxes, "pool_boxes", torch.float32, (B, N, 4)), _req_form(pool_scores, "pool_scores", torch.float32, (B, N))
+    _req_form(pool_labels, "pool_labels", torch.int32, (B, N)), _req_form(keep, "keep", torch.int32, (B, Dout))
+    _req_form(kept, "kept", torch.int32, (B,))
+    dev = _device(pool_boxes, pool_scores, pool_labels, keep, kept)
+    boxes = None if vote_thresh is None else torch.empty((B, Dout, 4), device=dev, dtype=torch.float32)
+    labels = torch.empty((B, Dout), device=dev, dtype=torch.int32)
+    _launch(_device(pool_boxes, pool_scores, pool_labels, keep, kept), lib.ldit_box_vote_f32, _ptr(pool_boxes), _ptr(pool_scores),
+            _ptr(pool_labels), _ptr(keep), _ptr(kept), B, N, Dout, 0.0 if vote_thresh is None else float(vote_thresh), _ptr(boxes), _ptr(labels))
+    return boxes, labels
+
+
+def tta_merge(views, view_specs, original_sizes, nms_thresh: float = 0.5, detections_per_img: int = 100,
+              vote_thresh: Optional[float] = None):
+    """Test-time augmentation's merge: :func:`tta_pool`, one class-wise :func:`batched_nms_padded` over each image's pool (the NMS
+    of the box head: same kernel, same IoU arithmetic), :func:`box_vote`.  Arguments as for :func:`tta_pool`; ``V * D`` must not
+    exceed ``NMS_MAX_CANDIDATES``.  Returns ``(boxes [B, D_out, 4] in page coordinates, scores [B, D_out], labels int32 [B, D_out], count
+    int32 [B])`` with ``D_out = detections_per_img``, zero padding, in the NMS's order: descending score, ties by pool index (plain
+    views first, in the order given).  ``vote_thresh=None``: the boxes are the kept pool entries' own bits.  Three launches, no
+    synchronisation, capturable."""
+    Dout = int(detections_per_img)
+    if Dout < 1:
+        raise ValueError("tta_merge: detections_per_img must be positive")
+    if not 0.0 <= float(nms_thresh) <= 1.0:
+        raise ValueError(f"tta_merge: nms_thresh = {nms_thresh} is outside [0, 1]")
+    if vote_thresh is not None and not 0.0 <= float(vote_thresh) <= 1.0:
+        raise ValueError(f"tta_merge: vote_thresh = {vote_thresh} is outside [0, 1]")
+    _tta_views(views, view_specs, original_sizes, "tta_merge")         # every host check before the first launch
+    pool_boxes, pool_scores, pool_labels = tta_pool(views, view_specs, original_sizes)
+    keep, count, boxes, scores = batched_nms_padded(pool_boxes, pool_scores, pool_labels, float(nms_thresh), Dout)
+    voted, labels = box_vote(pool_boxes, pool_scores, pool_labels, keep, count, vote_thresh)
+    return (boxes if voted is None else voted), scores, labels, count
